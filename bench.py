@@ -2,6 +2,7 @@
 """Benchmark of the PNN intra-prediction hot path on MI355X (contract: see DESIGN.md "Measurement").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fc8|conv16|...] [--batch B] [--arithmetic f32|split]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (L-context gather -> PNN -> +mean/clamp/round -> int32 Pel) over one
 batch of synthetic transform blocks per GPU, inputs (reconstructed planes + TB descriptors) resident in
@@ -9,12 +10,16 @@ HBM.  Default workload = BASELINE.json configs[1]: 8x8 fully-connected PNN, batc
 For N > 1 (launched by torch.distributed.run, one rank per GPU) every rank processes its own batch
 (independent blocks: no data-path collective, weak scaling) and the time is the max over ranks.
 
-Rank 0 prints ONE JSON line of < 4 KB (build_line; tests/test_host.py checks the size on canned results).  Its top level
--- value, dtype, roofline, cpu_baseline -- is the workload on the REFERENCE's arithmetic, IEEE float32 (`precision` = 0,
-pnn/components.py:169-176); `fast_arithmetic` is the same workload on the library's split-f16 mode, and `per_width` the
-table BASELINE.json's metric asks for ("blocks/s (per width)": FC 4, FC 8, conv 16 / 32 / 64, both arithmetics, each checked
-against the oracle).  Everything else -- every region's time, the CPU legs, the other kernels of the pass -- goes to
-`bench_detail.json` (--detail-file).  The HM campaigns (configs[3] / [4]) run only under `--workload hm_kodak | hm_bsds`.
+A plain run sets up, warms up, times exactly K steps (ONE region), writes the last step's predictions if `--dump-outputs DIR` is
+given (DIR/pred_pel.npy, float32) and prints ONE JSON line of < 4 KB (build_line; tests/test_host.py checks the size on canned
+results): `value` (blocks/s), `ms_per_step`, `dtype` -- the workload on the REFERENCE's arithmetic, IEEE float32 (`precision` = 0,
+pnn/components.py:169-176) -- and nothing it did not measure.  `--full` adds everything else, as every run did before the option
+existed: five regions of K steps (value = the median one), the oracle check and pred-PSNR of the timed steps, `roofline`,
+`cpu_baseline`, `fast_arithmetic` (the same workload on the library's split-f16 mode), `per_width` (the table BASELINE.json's
+metric asks for: "blocks/s (per width)", FC 4, FC 8, conv 16 / 32 / 64, both arithmetics, each checked against the oracle),
+single-block calls, natural-picture pred-PSNR, this run's own counter passes -- and `bench_detail.json` (--detail-file) with every
+region's time, the CPU legs and the other kernels of the pass.
+The HM campaigns (configs[3] / [4]) run only under `--workload hm_kodak | hm_bsds`.
 `--gpus N` without a launcher (WORLD_SIZE unset) starts its own ranks: `python -m torch.distributed.run` as a CHILD process.
 """
 import argparse
@@ -36,6 +41,7 @@ PEAK_F16_MFMA_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense f16/bf16 matrix p
 PEAK_HBM_GBPS = 8000.0            # MI355X_MICROARCH.md: HBM3E peak (the roof a single-block call's parameter stream is priced against)
 SUSTAIN_SECONDS = 2.0       # --sustained: one region of back-to-back steps per (workload, arithmetic), clocks sampled meanwhile
 LINE_LIMIT = 4096           # the driver keeps the tail of stdout: the line must fit with room to spare
+DUMP_LIMIT_BYTES = 64 << 20 # --dump-outputs: at most this much in all (a larger output is sampled: rows drawn with a fixed seed)
 DTYPE = {0: "f32",
          1: "f32-class split: 2 x f16 per operand, 3 f16-MFMA products, f32 accumulate"}
 DTYPE_LONG = {1: "f32 emulated: 2 x f16 per operand (hi + lo, 22-bit significand), 3 of the 4 partial products on f16 MFMA "
@@ -141,9 +147,10 @@ def stagger(dist, fn):
         dist.barrier()
 
 
-def measure(wl, precision, steps, warmup, dist, repeats=REPEATS, check=True, sustain_s=0.0, ramp_s=RAMP_SECONDS, global_batch=None):
+def measure(wl, precision, steps, warmup, dist, repeats=REPEATS, check=True, sustain_s=0.0, ramp_s=RAMP_SECONDS, global_batch=None, full=True):
     """Times the hot path of workload `wl` on arithmetic `precision` (1: split products on f16 MFMA, 0: exact-f32 MFMA)
-    and derives the dominant kernel's roofline from HIP events attached to every tap-GEMM launch."""
+    and, with `full`, derives the dominant kernel's roofline from HIP events attached to every tap-GEMM launch.  Without `full`:
+    set-up, ramp, warm-up and the timed regions only (no clock sampling, sustained region, roofline or oracle check)."""
     import torch
     from context_adaptive_neural_network_based_prediction_amd import PredictionNeuralNetwork, sharding
     L, w, n = wl.L, wl.width, wl.batch
@@ -167,14 +174,20 @@ def measure(wl, precision, steps, warmup, dist, repeats=REPEATS, check=True, sus
     t_ramp = time.perf_counter()
     # ... and the shader clock the chip HOLDS under exactly this load is sampled meanwhile (sysfs, second half of the ramp): the split-f16
     # kernels run into the power cap and hold ~1.9 of the nominal 2.4 GHz, so their roof is quoted at both clocks
-    smp = sharding.GpuClockSampler(wl.local_rank, period_s=0.01)
-    with smp:
+    def ramp():
         while time.perf_counter() - t_ramp < ramp_s:
             for _ in range(20):
                 step()
             torch.cuda.synchronize()
-    held = sorted(smp.mhz[len(smp.mhz) // 2:])
-    held_mhz = held[len(held) // 2] if held else None
+    held_mhz = None
+    if full:
+        smp = sharding.GpuClockSampler(wl.local_rank, period_s=0.01)
+        with smp:
+            ramp()
+        held = sorted(smp.mhz[len(smp.mhz) // 2:])
+        held_mhz = held[len(held) // 2] if held else None
+    else:
+        ramp()
     for _ in range(warmup):
         step()
     regions = [sharding.timed_steps(step, steps, torch.cuda.synchronize, dist, None if os.environ.get("PNN_BENCH_SHARE_GPU") == "1" else "cuda") for _ in range(repeats)]
@@ -192,8 +205,11 @@ def measure(wl, precision, steps, warmup, dist, repeats=REPEATS, check=True, sus
         "repeats": {"n": repeats, "regions_of_steps": steps, "value_is": "median region",
                     "blocks_per_s_min": job_blocks * steps / max(regions), "blocks_per_s_max": job_blocks * steps / min(regions),
                     "ms_per_step_all": [round(1e3 * r / steps, 5) for r in regions]},
-        "launches_per_step": stats["launches"], "held_sclk_mhz": held_mhz,
+        "launches_per_step": stats["launches"], "held_sclk_mhz": held_mhz, "roofline": None,
     }
+    if not full:
+        net.close()
+        return res
     gpu_pred = wl.d_dst.cpu().numpy()
     if sustain_s > 0:
         # ---- sustained: ONE region of back-to-back steps lasting >= sustain_s, clocks sampled from sysfs meanwhile
@@ -505,11 +521,12 @@ def self_launch(args):
     raise SystemExit(r.returncode if r.returncode or line else 1)
 
 
-def hm_campaigns(which, devices, quick=False, pictures="synthetic", cpu_leg=True, arithmetic="f32"):
+def hm_campaigns(which, devices, quick=False, pictures="synthetic", cpu_leg=True, arithmetic="f32", yardstick=True):
     """BASELINE.json configs[3] / configs[4] at their stated picture counts through the reference's own HM binaries
     (tools/hm/campaign.py; built by __graft_entry__.build() where /root/reference exists, they travel with the tree), and -- the
     cpu_baseline leg -- the first pictures of the same campaign with the PNN answered on HOST CORES (the reference's route: inference
     on the CPU; here the CPU oracle behind the same batching service, tools/hm/cpu_pnn_service.py), beside the same pictures on the GPU.
+    `yardstick`: hm_16_15_regular (no PNN) timed on the same pictures as well.
     Returns {name: record}; a missing binary or a failed run is recorded, never raised."""
     import shutil
     import tempfile
@@ -520,11 +537,12 @@ def hm_campaigns(which, devices, quick=False, pictures="synthetic", cpu_leg=True
     except Exception as e:                            # noqa: BLE001
         return {"error": "tools/hm/campaign.py not importable: %r" % (e,)}
     if not campaign.binaries_present():
-        return {"error": "tools/hm/_build/*/TApp{Encoder,Decoder}Static are missing (built where /root/reference exists: `make -C tools/hm`)"}
+        return {"error": "oracle/_ref/hm/*/TApp{Encoder,Decoder}Static are missing (built from the reference checkout: `make -C oracle hm`)"}
     for name in which:
         work = tempfile.mkdtemp(prefix="pnn_bench_hm_")
         try:
-            rec = campaign.run_campaign(name, work, devices, pictures=(4 if quick else None), timeout=300, picture_set=pictures, arithmetic=arithmetic)   # per codec process: a wedged service must not hold the line for long
+            rec = campaign.run_campaign(name, work, devices, pictures=(4 if quick else None), timeout=300, picture_set=pictures, arithmetic=arithmetic,
+                                        yardstick=yardstick)   # per codec process: a wedged service must not hold the line for long
             if cpu_leg:
                 k = 2
                 small = campaign.run_campaign(name, os.path.join(work, "gpu_small"), devices[:1], pictures=k, timeout=300, picture_set=pictures, yardstick=False, arithmetic=arithmetic)
@@ -549,12 +567,12 @@ def hm_campaigns(which, devices, quick=False, pictures="synthetic", cpu_leg=True
 
 def natural_pred_psnr(device):
     """BASELINE.json's "pred-PSNR delta vs ref" where it means something: the reference's two TRAINED checkpoints (convolutional 4x4 / 8x8,
-    tests/golden/conv{4,8}_single.pnnw) on 2500 natural contexts per width (tests/golden/natural_luma.npz), prediction PSNR
+    tests/golden/conv{4,8}_single.pnnw) on 2500 natural contexts per width (oracle/_ref/natural_luma.npz), prediction PSNR
     (tools/tools.py:364-401) against the blocks they predict -- the HIP path on both arithmetics beside the oracle."""
     from context_adaptive_neural_network_based_prediction_amd import PredictionNeuralNetwork, weights as wts
     from oracle import pnn_oracle as O
     from tests import test_natural as tn, util
-    if not os.path.exists(os.path.join(ROOT, "tests", "golden", "natural_luma.npz")):     # generated by __graft_entry__.build() where the reference checkout exists
+    if not os.path.exists(tn.NATURAL):     # generated by __graft_entry__.build() where the reference checkout exists
         return None
     out = {}
     for w in (4, 8):
@@ -573,6 +591,24 @@ def natural_pred_psnr(device):
             rec[arith + "_max_abs_lsb_vs_oracle"] = int(np.abs(got.astype(np.int64) - want).max())
         out[str(w)] = rec
     return out
+
+
+def dump_outputs(wl, out_dir, rank, world=1):
+    """--dump-outputs: what the timed path handed its caller in the last step -- the Pel predictions of the batch, [n, w, w] --
+    as float32 (exact: values 0..255) in out_dir/pred_pel.npy (rank r > 0: pred_pel_rank<r>.npy).  Above its share of
+    DUMP_LIMIT_BYTES (1 / world of it per rank) a fixed seeded sample of blocks is written instead, its block indices beside it
+    (pred_pel_index.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    pred = wl.d_dst.cpu().numpy().astype(np.float32)
+    tag = "" if rank == 0 else "_rank%d" % rank
+    per_block = pred[0].nbytes
+    limit = DUMP_LIMIT_BYTES // world
+    if pred.nbytes > limit:
+        keep = max(1, (limit - 8 * pred.shape[0]) // per_block)
+        idx = np.sort(np.random.RandomState(0).choice(pred.shape[0], keep, replace=False))
+        pred = pred[idx]
+        np.save(os.path.join(out_dir, "pred_pel%s_index.npy" % tag), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "pred_pel%s.npy" % tag), np.ascontiguousarray(pred))
 
 
 def _r(x, nd=4):
@@ -601,20 +637,21 @@ def build_line(main_res, world, steps, warmup, cfg_name, fast=None, per_width=No
                rccl_ranks_seen=None, natural=None, single=None):
     """The ONE JSON line of rank 0 (< LINE_LIMIT bytes).  `main_res` / `fast` / `per_width[name][arith]` are measure() results;
     `single` = single_block_calls() results by workload name (exact f32)."""
-    rf = main_res["roofline"]
+    rf = main_res.get("roofline")
+    n_regions = main_res["repeats"]["n"]
     out = {
         "metric": "pnn_intra_pred_blocks_per_s", "value": _r(main_res["value"], 6), "unit": "blocks/s", "n_gpus": world, "steps": steps, "warmup": warmup,
         "ms_per_step": _r(main_res["ms_per_step"], 6), "higher_is_better": True, "scaling": main_res.get("scaling", "weak"), "vs_baseline": None,
         "dtype": DTYPE[main_res["precision"]], "data": "synthetic",
         "config": {"workload": cfg_name, "batch_per_gpu": main_res["batch_per_gpu"], "global_batch": main_res.get("global_batch"), "path": "gather + net + HM epilogue (pnn_predict_tbs_device)",
                    "weights": "seeded random init (reference initialisers' statistics)", "parallelism": "independent blocks sharded over ranks, no collective",
-                   "timing": "%d regions of K steps, median" % main_res["repeats"]["n"]},
+                   "timing": "one region of K steps" if n_regions == 1 else "%d regions of K steps, median" % n_regions},
         "max_abs_lsb_vs_oracle": main_res.get("max_abs_lsb_vs_oracle"),
         "pred_psnr_delta_db": _r((main_res.get("pred_psnr") or {}).get("delta_db"), 3),
         "roofline": {"bound": "mfma", "kernel": rf["kernel"].split(" (")[0], "achieved": _r(rf["achieved"]), "peak": _r(rf["peak"]), "unit": "TFLOP/s",
                      "frac": _r(rf["frac"], 3), "traffic": _r(rf["traffic"]), "traffic_source": (rf.get("traffic_source") or "")[:60] or None,
                      "flops_per_launch": _r(rf["flops_per_launch"]), "avg_launch_us": _r(rf["avg_launch_us"]), "launches_timed": rf["launches_timed"],
-                     "whole_pass_frac": _r(rf["whole_pass"]["frac_of_peak"], 3)},
+                     "whole_pass_frac": _r(rf["whole_pass"]["frac_of_peak"], 3)} if rf else None,
         "cpu_baseline": None,
     }
     if extra_config:
@@ -677,7 +714,7 @@ def main():
     ap.add_argument("--workload", default="fc8", choices=sorted(WORKLOADS) + ["hm_kodak", "hm_bsds"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="--gpus N > 1: weak = every rank its own batch of the workload's size (the contract's default); strong = ONE batch of that "
-                         "size split over the ranks (sharding.shard_bounds), at least 200 steps per region")
+                         "size split over the ranks (sharding.shard_bounds); with --full at least 200 steps per region")
     ap.add_argument("--force-dist", default=None, choices=["nccl", "gloo"],
                     help="--gpus 1 only: join a ONE-rank process group anyway and run the barrier, the max-over-ranks clock, the device census and a "
                          "gather of the predictions through it -- with nccl the only execution of the RCCL branch a one-GPU box allows")
@@ -685,12 +722,17 @@ def main():
     ap.add_argument("--hm-quick", action="store_true", help=argparse.SUPPRESS)   # 4 pictures per campaign (plumbing tests)
     ap.add_argument("--hm-pictures", default="synthetic", choices=["synthetic", "natural"], help="hm_* workloads: picture set")
     ap.add_argument("--batch", type=int, default=0, help="blocks per GPU per step (0 = the workload's default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's predictions (float32 .npy, <= 64 MB) to DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: 5 regions (median), oracle check, roofline, CPU baseline, split arithmetic, "
+                         "per-width table, single-block calls, natural pictures, counter passes, the detail file (the options below act on it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-legs-full", action="store_true", help="CPU legs at every candidate thread count (slower)")
     ap.add_argument("--no-extras", action="store_true", help="only the top-level measurement (no fast_arithmetic / per_width / live traffic)")
     ap.add_argument("--no-per-width", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from profiles/pmc_traffic.json instead of this run's own counter passes")
-    ap.add_argument("--sustained", action="store_true", help="add a >= %.0f s region per measurement (detail file)" % SUSTAIN_SECONDS)
+    ap.add_argument("--sustained", action="store_true", help="with --full: add a >= %.0f s region per measurement (detail file)" % SUSTAIN_SECONDS)
     ap.add_argument("--no-sustained", action="store_true", help=argparse.SUPPRESS)   # accepted, ignored (the default since round 4)
     ap.add_argument("--no-hm", action="store_true", help=argparse.SUPPRESS)          # accepted, ignored (campaigns run only under --workload hm_*)
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"))
@@ -708,11 +750,14 @@ def main():
 
     from context_adaptive_neural_network_based_prediction_amd import sharding
     if args.workload.startswith("hm_"):
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the hm_* workloads time whole campaigns, not a step with outputs")
         # configs[3] / configs[4]: whole encodes through the reference's HM binaries, one batching service per device; this
         # process never touches the GPU (the services and the codecs are child processes)
         name = args.workload[3:]
-        rec = hm_campaigns([name], list(range(args.gpus)), args.hm_quick, args.hm_pictures, cpu_leg=not args.no_cpu_baseline,
-                           arithmetic="f32" if precision == 0 else "split")
+        # the CPU leg and the hm_16_15_regular yardstick are extras of --full, like every figure beside the headline
+        rec = hm_campaigns([name], list(range(args.gpus)), args.hm_quick, args.hm_pictures, cpu_leg=args.full and not args.no_cpu_baseline,
+                           arithmetic="f32" if precision == 0 else "split", yardstick=args.full)
         r = rec.get(name, rec)
         ok = "error" not in r
         with open(args.detail_file, "w") as f:
@@ -775,22 +820,27 @@ def main():
     if strong:
         # ONE batch split over the ranks: rank r takes the contiguous shard shard_bounds(global_batch, r, world); a step of the job is
         # still one pass over the whole batch, so `value` = global_batch * steps / (slowest rank's time).  Shards of a bench batch are
-        # short (FC 8x8: 512 blocks at N = 8, ~60 us of device time), so regions are at least 200 steps
+        # short (FC 8x8: 512 blocks at N = 8, ~60 us of device time), so --full makes regions at least 200 steps; a plain run times
+        # exactly --steps steps
         _, mine = sharding.strong_shard(global_batch, rank, world)
-        args.steps = max(args.steps, 200)
+        if args.full:
+            args.steps = max(args.steps, 200)
         wl = Workload(args.workload, mine, rank, local_rank)
     else:
         wl = Workload(args.workload, args.batch, rank, local_rank)
     single = world == 1
-    sustain = SUSTAIN_SECONDS if args.sustained else 0.0
-    main_res = measure(wl, precision, args.steps, args.warmup, dist, check=(rank == 0 and single), sustain_s=sustain,
-                       global_batch=global_batch if strong else None)
+    full = args.full
+    sustain = SUSTAIN_SECONDS if args.sustained and full else 0.0
+    main_res = measure(wl, precision, args.steps, args.warmup, dist, repeats=REPEATS if full else 1, check=(rank == 0 and single), sustain_s=sustain,
+                       global_batch=global_batch if strong else None, full=full)
+    if args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, rank, world)
     detail = {"cmd": " ".join(sys.argv), "n_gpus": world, "main": main_res,
               "config": {"rank_placement": ("rank 0 bound to cpus %s (its GPU's NUMA node)" % bound) if bound else "no NUMA binding (one node / not exposed)",
                          "tile_autotune": "split kernels: on first use, before the warm-up steps; f32 kernels: rule-based",
                          "device_ramp_s": RAMP_SECONDS, "share_gpu_plumbing_check": share}}
     fast, per_width, cpu, cpu16 = None, None, None, None
-    if single and not args.no_extras:
+    if full and single and not args.no_extras:
         k_pw = min(args.steps, 20)
         per_width = {args.workload: {("f32" if precision == 0 else "split"): main_res}} if args.workload in PER_WIDTH else {}
         fast = measure(wl, 1 - precision, args.steps, args.warmup, None, sustain_s=sustain)
@@ -809,40 +859,41 @@ def main():
         detail["per_width"] = per_width
         detail["fast_arithmetic"] = fast
     single_res = None
-    if rank == 0 and single and not args.no_extras:
+    if full and rank == 0 and single and not args.no_extras:
         try:
             single_res = single_block_calls(PER_WIDTH, local_rank)
         except Exception as e:                        # noqa: BLE001 -- an extra of the line must never cost the measurement
             detail["single_block_error"] = repr(e)[:500]
         detail["single_block"] = single_res
     natural = None
-    if rank == 0 and single and not args.no_extras:
+    if full and rank == 0 and single and not args.no_extras:
         try:
             natural = natural_pred_psnr(local_rank)
         except Exception as e:                        # noqa: BLE001 -- fixtures absent / anything else: the kernel line must survive
             natural = None
             detail["natural_pred_psnr_error"] = repr(e)[:500]
         detail["natural_pred_psnr"] = natural
-    if rank == 0 and single and not args.no_extras and not args.no_live_traffic:
+    if full and rank == 0 and single and not args.no_extras and not args.no_live_traffic:
         lt = live_traffic(args.workload, wl.batch, precision)
         detail["live_traffic"] = lt
         if lt and "bytes_per_launch" in lt:
             main_res["roofline"]["traffic"], main_res["roofline"]["traffic_source"] = lt["bytes_per_launch"], "this run: rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE"
-    if rank == 0 and single and not args.no_cpu_baseline:
+    if full and rank == 0 and single and not args.no_cpu_baseline:
         cpu = cpu_legs(args.workload, full=args.cpu_legs_full)
         detail["cpu_baseline"] = cpu
         if not args.no_extras and args.workload != "conv16":
             cpu16 = cpu_legs("conv16", full=args.cpu_legs_full)
             detail["cpu_baseline_conv16"] = cpu16
     if rank == 0:
-        detail["wall_s"] = time.perf_counter() - t_start
-        try:
-            with open(args.detail_file, "w") as f:
-                json.dump(detail, f, indent=1)
-            dfile = os.path.basename(args.detail_file)
-        except OSError as e:
-            sys.stderr.write("bench.py: cannot write %s: %s\n" % (args.detail_file, e))
-            dfile = None
+        dfile = None
+        if full:
+            detail["wall_s"] = time.perf_counter() - t_start
+            try:
+                with open(args.detail_file, "w") as f:
+                    json.dump(detail, f, indent=1)
+                dfile = os.path.basename(args.detail_file)
+            except OSError as e:
+                sys.stderr.write("bench.py: cannot write %s: %s\n" % (args.detail_file, e))
         print(build_line(main_res, world, args.steps, args.warmup, wl.cfg_name, fast, per_width, cpu, cpu16, dfile,
                          {"plumbing_check": "PNN_BENCH_SHARE_GPU=1: all ranks on ONE device"} if share else None, ranks_seen, natural, single_res))
         sys.stdout.flush()

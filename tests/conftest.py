@@ -1,5 +1,8 @@
 import os
+import pathlib
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -17,3 +20,21 @@ def oracle():
     from oracle import pnn_oracle
     pnn_oracle.build()
     return pnn_oracle
+
+
+# A Unix-domain socket's address holds at most 107 bytes (sockaddr_un.sun_path); pytest's tmp_path under a deep $TMPDIR
+# can be longer than that on its own, and the service refuses such a path (PNN_E_ARG).
+SOCK_DIR_MAX = 64
+
+
+@pytest.fixture
+def sock_dir(tmp_path):
+    """A directory short enough to hold the tests' sockets: tmp_path where it is, else a fresh directory under /tmp."""
+    if len(str(tmp_path)) <= SOCK_DIR_MAX:
+        yield tmp_path
+        return
+    d = tempfile.mkdtemp(prefix="pnn-", dir="/tmp")
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)

@@ -1,6 +1,6 @@
 """Natural-content fixtures from the pictures the reference checkout holds (build container only: needs /root/reference and PIL).
 
-    python tests/golden/make_natural.py          ->  tests/golden/natural_luma.npz
+    python tests/golden/make_natural.py          ->  oracle/_ref/natural_luma.npz
 
 What it records (data only: uint8 luminance planes, no reference source text):
   cactus, kimono, parkscene   768 x 1152 windows of the first-frame luminance PNGs of three HEVC class-B sequences
@@ -9,8 +9,9 @@ What it records (data only: uint8 luminance planes, no reference source text):
                               tools.tools.rgb_to_ycbcr (imported from /root/reference), cropped to 640 x 960
 Provenance: the three PNGs are first frames of JCT-VC class-B test sequences (Cactus, Kimono, ParkScene) as the reference's authors
 published them in their repository; the two JPEGs are the authors' own test photographs.  The fixture is therefore GENERATED where the
-reference checkout exists (__graft_entry__.build() calls this script) and git-ignored: it travels to the GPU box with the working tree
-and is never committed or redistributed; tests and campaigns that need it skip / refuse when it is absent.
+reference checkout exists (__graft_entry__.build() calls this script) into oracle/_ref/, beside the other products of that checkout,
+git-ignored: it travels with the built tree and is never committed or redistributed; tests and campaigns that need it skip / refuse
+when it is absent.
 The trained networks were trained on natural (ImageNet) luminance: these are the only natural pictures the repository holds, and
 what the parity / evidence tests (tests/test_natural.py) and the natural-picture HM campaigns (tools/hm/campaign.py) run on.
 """
@@ -38,7 +39,8 @@ def main():
         rgb = np.asarray(Image.open(os.path.join(REF, "hevc/pseudo_data/rgb_%s.jpg" % name)))
         assert rgb.dtype == np.uint8 and rgb.shape == (641, 960, 3)
         out[name] = np.ascontiguousarray(tls.rgb_to_ycbcr(rgb)[:640, :, 0])
-    path = os.path.join(HERE, "natural_luma.npz")
+    path = os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref", "natural_luma.npz")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), {k: (v.shape, float(v.mean())) for k, v in out.items()})
 

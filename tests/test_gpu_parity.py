@@ -590,7 +590,7 @@ def test_bench_one_rank_through_rccl(precision):
     for k in ("PNN_PRECISION", "WORLD_SIZE", "RANK", "LOCAL_RANK", "PNN_BENCH_SHARE_GPU"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "nccl", "--steps", "10", "--warmup", "2",
-                        "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+                        "--full", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -769,7 +769,7 @@ def test_block_cost_bit_exact_and_fused_entry(pnn, oracle, w, is_fc, n, pel_byte
         assert np.array_equal(d_cost.cpu().numpy().view(np.uint32), oracle.block_costs(org, xs, ys, w, rnd.cpu().numpy(), had))
 
 
-def test_batching_service_on_gpu(pnn, tmp_path):
+def test_batching_service_on_gpu(pnn, sock_dir):
     """include/pnn_service.h end to end: client threads send single-block requests over the socket, the server answers
     them from batched pnn_predict_pel calls on one context; under canonical_order every answer equals the direct
     single-block call bit for bit."""
@@ -782,7 +782,7 @@ def test_batching_service_on_gpu(pnn, tmp_path):
     net = pnn.PredictionNeuralNetwork(1, w, True, params=params)
     net.set_option("canonical_order", 1)
     want = [net.predict_pel(ctxs[i:i + 1])[0].copy() for i in range(n)]
-    sock = str(tmp_path / "pnn.sock")
+    sock = str(sock_dir / "pnn.sock")
     srv = service.serve_in_thread(sock, ctx=net.ctx, max_batch=16, window_us=2000)
     bad = []
 

@@ -92,7 +92,7 @@ def test_service_header_symbols_exported():
         assert hasattr(L, name), "libpnn_hip.so does not export %s" % name
 
 
-def test_batching_service_routes_and_coalesces(tmp_path):
+def test_batching_service_routes_and_coalesces(sock_dir):
     """include/pnn_service.h on the CPU with a stand-in backend (sum of the inputs per block): several client threads,
     mixed widths and both input kinds; every client gets ITS result, and concurrent requests are served in batches."""
     import threading
@@ -103,7 +103,7 @@ def test_batching_service_routes_and_coalesces(tmp_path):
         ramp = np.arange(width * width, dtype=np.int64).reshape(1, width, width)
         return (np.round(s).astype(np.int64)[:, None, None] + ramp).astype(np.int32)
 
-    sock = str(tmp_path / "pnn.sock")
+    sock = str(sock_dir / "pnn.sock")
     srv = service.serve_in_thread(sock, backend=backend, max_batch=8, window_us=3000)
     errors = []
 
@@ -469,7 +469,7 @@ def test_frozen_graphdef_reader(tmp_path):
         wts.params_from_frozen_graph(path, 8, False)       # a width-8 net does not match this file's tensors
 
 
-def test_batching_service_survives_bad_clients(tmp_path):
+def test_batching_service_survives_bad_clients(sock_dir):
     """One client that stops in the middle of a header, one that sends a malformed header and one that never reads its
     reply must not delay or break the others (the server is non-blocking with per-client buffers); a repeated request is
     answered from the client-side cache without reaching the server."""
@@ -483,7 +483,7 @@ def test_batching_service_survives_bad_clients(tmp_path):
             time.sleep(0.15)                                  # the request of the client that is killed meanwhile (below)
         return np.tile(np.round(above.sum(axis=1)).astype(np.int32)[:, None, None], (1, width, width))
 
-    sock = str(tmp_path / "pnn.sock")
+    sock = str(sock_dir / "pnn.sock")
     srv = service.serve_in_thread(sock, backend=backend, max_batch=8, window_us=500)
     good = service.Client(sock)
     stalled = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
@@ -529,7 +529,7 @@ def test_batching_service_survives_bad_clients(tmp_path):
         s.close()
 
 
-def test_arithmetic_tag_travels_through_the_service_and_the_session_checks_it(tmp_path, monkeypatch):
+def test_arithmetic_tag_travels_through_the_service_and_the_session_checks_it(tmp_path, sock_dir, monkeypatch):
     """The arithmetic contract, enforced: the batching service reports the tag of what answers a width
     (pnn_client_arithmetic_tag: a flag in the request header, answered by the I/O thread), and the TensorFlow look-alike's
     Session::Create fails with a clean "arithmetic mismatch" when $PNN_EXPECT_TAG names another one -- instead of a decoder that
@@ -543,7 +543,7 @@ def test_arithmetic_tag_travels_through_the_service_and_the_session_checks_it(tm
         return np.clip(np.round(f32), 0, 255).astype(np.int32), f32
 
     monkeypatch.setenv("PNN_SERVICE_TAG", "stand-in:f32:test order 7")
-    sock = str(tmp_path / "pnn.sock")
+    sock = str(sock_dir / "pnn.sock")
     srv = service.serve_in_thread(sock, backend=backend, max_batch=8, window_us=0)
     cl = service.Client(sock)
     for w in (4, 8, 16, 32, 64):
@@ -577,7 +577,7 @@ def test_arithmetic_tag_travels_through_the_service_and_the_session_checks_it(tm
     assert srv.rc == 0 and stats["requests"] == 1 + 2 * 2                                       # tag requests never reach the backend
 
 
-def test_batching_service_many_clients_over_io_threads(tmp_path, monkeypatch):
+def test_batching_service_many_clients_over_io_threads(sock_dir, monkeypatch):
     """The server's socket side runs on several I/O threads (a connection belongs to one of them for life; the workers hand a
     reply to the owner's queue): 48 clients on 4 I/O threads, 60 requests each over the five widths and both input shapes -- every
     reply must be the answer to ITS request, and clients that vanish in the middle must not disturb the rest."""
@@ -590,7 +590,7 @@ def test_batching_service_many_clients_over_io_threads(tmp_path, monkeypatch):
 
     monkeypatch.setenv("PNN_SERVICE_IO_THREADS", "4")
     monkeypatch.setenv("PNN_CACHE_MB", "0")                  # every request reaches the server
-    sock = str(tmp_path / "pnn.sock")
+    sock = str(sock_dir / "pnn.sock")
     srv = service.serve_in_thread(sock, backend=backend, max_batch=16, window_us=0)
     bad = []
 
@@ -622,26 +622,26 @@ def test_batching_service_many_clients_over_io_threads(tmp_path, monkeypatch):
     assert srv.rc == 0 and stats["clients"] == 48 and stats["requests"] == 44 * 60 + 4 * 21
 
 
-def test_host_code_under_sanitizers(tmp_path):
+def test_host_code_under_sanitizers(sock_dir):
     """the host-only part of the library (context gather, descriptor builder, model-table parser,
     batching server + client incl. misbehaving clients) and the CPU oracle under AddressSanitizer + UBSan
     (`make -C csrc sanitize`, driver tests/sanitize_host.cpp).  Any report aborts the driver."""
     csrc = os.path.join(ROOT, "context_adaptive_neural_network_based_prediction_amd", "csrc")
-    env = dict(os.environ, TMPDIR=str(tmp_path))
+    env = dict(os.environ, TMPDIR=str(sock_dir))
     r = subprocess.run(["make", "-C", csrc, "sanitize"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "sanitize_host: ok" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
 
 
-def test_service_under_thread_sanitizer(tmp_path):
+def test_service_under_thread_sanitizer(sock_dir):
     """`make -C csrc tsan`: the batching service -- server in its production thread layout (five width workers, four I/O
     threads) and client stub -- under ThreadSanitizer, driven by tests/tsan_service.cpp: 32 client threads against a stand-in backend
     with randomised latencies, with and without a batching window, clients that reconnect / vanish mid-request / die with a request in
     flight, tag requests, a server stopped under load.  Any report ends the run with exit code 66.  (3000 requests per client here,
     `make tsan` alone runs 10000: profiles/r06_tsan_service.txt.)  CPU build only."""
     csrc = os.path.join(ROOT, "context_adaptive_neural_network_based_prediction_amd", "csrc")
-    env = dict(os.environ, TMPDIR=str(tmp_path))
+    env = dict(os.environ, TMPDIR=str(sock_dir))
     r = subprocess.run(["make", "-C", csrc, "tsan", "N=3000"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "tsan_service: ok" in r.stdout and "ThreadSanitizer" not in r.stdout + r.stderr
@@ -795,6 +795,47 @@ def test_bench_line_fits_the_driver_tail_buffer():
     # the minimal line (N > 1 ranks: no extras) carries the contract keys too
     d2 = json.loads(bench.build_line(main, 2, 20, 5, "w", rccl_ranks_seen={"backend": "nccl", "world_size": 2, "devices": 2}))
     assert d2["cpu_baseline"] is None and d2["rccl_ranks_seen"]["devices"] == 2 and d2["value"] == d["value"]
+
+
+def test_bench_plain_line_says_what_it_measured():
+    """A plain run (no --full) measures one region of K steps and nothing else: the line keeps the contract keys, and the figures it
+    did not take -- roofline, oracle check, CPU baseline, extras -- are null or absent."""
+    import json
+    import bench
+    main = {"value": 1.76789e7, "ms_per_step": 0.231688, "precision": 0, "batch_per_gpu": 4096, "scaling": "weak", "global_batch": 4096,
+            "repeats": {"n": 1, "ms_per_step_all": [0.231688]}, "roofline": None}
+    d = json.loads(bench.build_line(main, 1, 500, 5, bench.WORKLOADS["fc8"][3]))
+    assert d["metric"] == "pnn_intra_pred_blocks_per_s" and d["unit"] == "blocks/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] == 1.76789e7 and d["ms_per_step"] == 0.231688 and d["steps"] == 500 and d["warmup"] == 5
+    assert d["config"]["timing"] == "one region of K steps"
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["max_abs_lsb_vs_oracle"] is None and d["pred_psnr_delta_db"] is None
+    assert not {"fast_arithmetic", "per_width", "single_block", "natural_pred_psnr_db", "detail_file"} & set(d)
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's Pel blocks as float32 pred_pel.npy, exact; above the cap (shared by the ranks) a sample of
+    blocks drawn with a fixed seed, its indices beside it -- the same sample every run, within the cap in all."""
+    import types
+    import torch
+    import bench
+    pel = np.random.RandomState(3).randint(0, 256, (4096, 8, 8)).astype(np.int32)
+    wl = types.SimpleNamespace(d_dst=torch.from_numpy(pel))
+    bench.dump_outputs(wl, str(tmp_path / "all"), 0)
+    got = np.load(str(tmp_path / "all" / "pred_pel.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, pel) and sorted(os.listdir(str(tmp_path / "all"))) == ["pred_pel.npy"]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200000)
+    for run in ("a", "b"):
+        for rank in (0, 1):
+            bench.dump_outputs(wl, str(tmp_path / run), rank, world=2)
+    total = 0
+    for tag in ("", "_rank1"):
+        got = np.load(str(tmp_path / "a" / ("pred_pel%s.npy" % tag)))
+        idx = np.load(str(tmp_path / "a" / ("pred_pel%s_index.npy" % tag)))
+        assert got.dtype == np.float32 and idx.dtype == np.float64 and 0 < got.shape[0] < pel.shape[0]
+        assert np.array_equal(got, pel[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
+        assert np.array_equal(idx, np.load(str(tmp_path / "b" / ("pred_pel%s_index.npy" % tag))))
+        total += got.nbytes + idx.nbytes
+    assert total <= 200000
 
 
 def test_gpu_placement_helpers(tmp_path):

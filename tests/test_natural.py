@@ -3,7 +3,7 @@
 TensorFlow cannot be run here and the reference checkout holds no output vector of its networks, so the op
 semantics of the restated graphs -- TF's SAME padding rule, the crop of conv2d_transpose, the order of the channel-wise merger,
 the LeakyReLU slope -- are pinned on what IS there: the two trained checkpoints (convolutional 4x4 / 8x8, pnn/results/...,
-converted to tests/golden/conv{4,8}_single.pnnw) and the natural pictures of the checkout (tests/golden/natural_luma.npz,
+converted to tests/golden/conv{4,8}_single.pnnw) and the natural pictures of the checkout (oracle/_ref/natural_luma.npz,
 tests/golden/make_natural.py).  A network trained under semantics S predicts natural blocks well when it is EVALUATED under S
 and worse under anything else: with >= 2000 natural contexts per width the restated semantics must beat a DC predictor by a stated
 margin, and every single perturbation of one restated rule must lose prediction PSNR (tools/tools.py:364-401) -- most of them
@@ -20,6 +20,7 @@ from tests import util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
+NATURAL = os.path.join(ROOT, "oracle", "_ref", "natural_luma.npz")   # made by __graft_entry__.build() from the reference checkout
 N_CONTEXTS = 2500
 # measured with `python -m tests.test_natural` (2500 contexts per width; table in DESIGN.md section 2): restated semantics 24.95 dB
 # (4x4) / 23.21 dB (8x8) against 21.69 / 20.34 for the DC predictor; the mildest perturbation (LeakyReLU -> ReLU on the 8x8 net)
@@ -31,9 +32,9 @@ MIN_DROP_DB = 0.5                                      # every perturbation must
 def natural_contexts(w, n, seed=5):
     """n (above [w, 3w], left [2w, w], target [w, w]) triples of uint8 natural luminance, all context available, blocks on the
     w-grid of the five fixture pictures (the layout of extraction_context.cpp:3-208 / sets/common.py:466-473)."""
-    if not os.path.exists(os.path.join(GOLD, "natural_luma.npz")):
-        pytest.skip("tests/golden/natural_luma.npz is generated from the reference checkout by __graft_entry__.build() (tests/golden/make_natural.py)")
-    pics = np.load(os.path.join(GOLD, "natural_luma.npz"))
+    if not os.path.exists(NATURAL):
+        pytest.skip("oracle/_ref/natural_luma.npz is generated from the reference checkout by __graft_entry__.build() (tests/golden/make_natural.py)")
+    pics = np.load(NATURAL)
     rng = np.random.RandomState(seed)
     names = sorted(pics.files)
     above, left, target = [], [], []

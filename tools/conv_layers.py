@@ -5,7 +5,7 @@ import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for wl in (sys.argv[1:] or ["conv16", "conv32"]):
     env = dict(os.environ, PNN_PROFILE="1", PNN_AUTOTUNE="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--no-cpu-baseline", "--no-extras", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--full", "--no-cpu-baseline", "--no-extras", "--steps", "3", "--warmup", "1"],
                        env=env, capture_output=True, text=True, cwd=ROOT)
     rows = re.findall(r"\[pnn-prof\] M=(\d+) K=(\d+) N=(\d+) ncls=(\d+) f32 cfg=(\d+) rt=(\d+) nt=(\d+) kc=(\d+) mf=\d+ us=([0-9.]+) tflops=([0-9.]+)", r.stderr)
     # the last pass's launches: one row per distinct (M, K, N) in launch order

@@ -269,7 +269,7 @@ def run_campaign(config, work, devices=(0,), pictures=None, in_flight=None, qp=3
         "config": cfg["baseline"], "variant": "hm_16_15_" + variant, "pictures": n, "picture_size": "%dx%d 4:0:0" % (w, h), "qp": qp,
         "picture_set": picture_set, "pnn_backend": backend,
         "arithmetic": "f32 (CPU oracle)" if backend == "cpu" else (arithmetic or {"0": "f32", "1": "split"}.get(os.environ.get("PNN_PRECISION", "0"), "f32")),
-        "data": ("windows of the natural fixtures (tests/golden/natural_luma.npz); widths 4 / 8 on the reference's trained convolutional checkpoints, 16 / 32 / 64 "
+        "data": ("windows of the natural fixtures (oracle/_ref/natural_luma.npz); widths 4 / 8 on the reference's trained convolutional checkpoints, 16 / 32 / 64 "
                  "seeded random init" if natural else "seeded synthetic pictures + seeded random-init models") + " (Kodak / BSDS and the trained production models "
                 "are not in the reference checkout)",
         "devices": list(devices), "services": len(devices), "encodes_in_flight": in_flight, "host_cores": os.cpu_count(), "cpu_budget": _cpu_quota() or os.cpu_count(),

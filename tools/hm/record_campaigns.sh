@@ -10,7 +10,7 @@ for cfg in kodak bsds; do
     for ar in $ariths; do
       extra=""
       [ "$ar" != "f32" ] && extra="--no-cpu-baseline"      # the PNN-on-host-cores leg once per campaign is enough
-      python3 bench.py --workload hm_$cfg --hm-pictures $pics --arithmetic $ar $extra --detail-file $out/hm_${cfg}_${pics}_${ar}_detail.json \
+      python3 bench.py --workload hm_$cfg --full --hm-pictures $pics --arithmetic $ar $extra --detail-file $out/hm_${cfg}_${pics}_${ar}_detail.json \
         > $out/hm_${cfg}_${pics}_${ar}.json 2> $out/hm_${cfg}_${pics}_${ar}.err
       python3 - $out/hm_${cfg}_${pics}_${ar}.json <<'PY'
 import json, sys

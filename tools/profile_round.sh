@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 r=${1:-r06}
 out=gpurun_out/profiles_$r
 mkdir -p $out
-B="--steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+B="--steps 20 --warmup 3 --full --no-cpu-baseline --no-extras"
 for wl in fc8 conv16 fc4 conv32 conv64; do
   for ar in f32 split; do
     # kernel durations with the branches of a conv pass on ONE stream (two kernels side by side share the chip and each one's
@@ -37,7 +37,7 @@ for wl in fc8 conv16; do
 done
 python3 tools/pmc_traffic.py $out/pmc_traffic.json fc8_split conv16_split fc8_f32 conv16_f32 > /dev/null
 python3 tools/f32_sweep.py fc8 conv16 fc4 conv32 conv64 > $out/f32_tile_sweep.txt 2>&1
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 cp bench_detail.json $out/bench_default_detail.json
 # round 5: the single-block path on the reference's arithmetic, the host-array entry points, the width workers side by side
 ( echo "# tools/batch1_latency.py, one MI355X (host call pnn_predict_pel at batch 1: staging + net + epilogue + wait); the library's defaults (plain launches)"; PNN_GRAPHS=0 python3 tools/batch1_latency.py 2>&1 | grep -v amdgpu.ids

@@ -10,7 +10,7 @@ for i in 1 2; do
 for lib in prev new; do
   L=$B/libpnn_hip_prev.so; [ $lib = new ] && L=$PWD/context_adaptive_neural_network_based_prediction_amd/libpnn_hip.so
   for wl in conv16 conv32 conv64; do
-    v=$(PNN_LIB_PATH=$L python3 bench.py --workload $wl --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.4g blocks/s  %.4f ms  frac %.3f' % (d['value'], d['ms_per_step'], d['roofline']['frac']))")
+    v=$(PNN_LIB_PATH=$L python3 bench.py --workload $wl --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.4g blocks/s  %.4f ms  frac %.3f' % (d['value'], d['ms_per_step'], d['roofline']['frac']))")
     echo "$lib $wl: $v"
   done
 done; done > $out/exp10_ab.txt 2>&1

@@ -8,7 +8,7 @@ tail -3 $out/exp9_tests.txt
 for i in 1 2; do
 for wl in conv32 conv64; do
 for mode in 0 1 -1; do
-  v=$(PNN_F32_SEG_MODE=$mode python3 bench.py --workload $wl --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.4g blocks/s  %.4f ms  frac %.3f launches %s' % (d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['launches_timed']))")
+  v=$(PNN_F32_SEG_MODE=$mode python3 bench.py --workload $wl --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.4g blocks/s  %.4f ms  frac %.3f launches %s' % (d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['launches_timed']))")
   echo "$wl f32_seg_mode=$mode: $v"
 done; done; done > $out/exp9_segmode.txt 2>&1
 cat $out/exp9_segmode.txt
