@@ -254,8 +254,14 @@ __device__ __forceinline__ void tconv_cout1_lds_tile(const TConv1Params& p, f32x
             const f32x4* xp = xt + (size_t)li * C4 * NP + ry * TI + rx;
             const f32x4* wp = wl + (ky * K + kx) * C4;
             for (int c4 = 0; c4 < C4; c4++) {
+                // one product and three fmas per channel quad, in THIS order: written out, so that the
+                // bits of the 4x4 net do not hang on how the compiler contracts a sum of four products (what it chose for that sum)
                 const f32x4 xv = xp[c4 * NP], wv = wp[c4];
-                acc += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
+                float q = xv[1] * wv[1];
+                q = __builtin_fmaf(xv[0], wv[0], q);
+                q = __builtin_fmaf(xv[2], wv[2], q);
+                q = __builtin_fmaf(xv[3], wv[3], q);
+                acc += q;
             }
         }
     }

@@ -20,8 +20,8 @@ _u8p = ctypes.POINTER(ctypes.c_uint8)
 def build(force=False):
     """Compile liboracle.so (and oracle/_ref when /root/reference exists)."""
     so = os.path.join(_HERE, "liboracle.so")
-    if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(
-            os.path.join(_HERE, "pnn_oracle.c")):
+    sources = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith(".c") or f == "Makefile"]
+    if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in sources):
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
     if os.path.isdir("/root/reference") and (force or not os.path.exists(
             os.path.join(_HERE, "_ref", "libref_extract.so")) or not os.path.exists(
@@ -58,6 +58,14 @@ def lib():
         L.oracle_predict_tbs.restype = ctypes.c_int
         L.oracle_predict_tbs.argtypes = [_f32p, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, _i32p,
                                          _u8p, ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_float, _i32p]
+        L.order_fc_forward.restype = ctypes.c_int
+        L.order_fc_forward.argtypes = [_f32p, ctypes.c_int, _f32p, ctypes.c_int, _f32p, ctypes.c_uint]
+        L.order_conv_forward.restype = ctypes.c_int
+        L.order_conv_forward.argtypes = [_f32p, ctypes.c_int, _f32p, _f32p, ctypes.c_int, _f32p, ctypes.c_uint]
+        L.order_tag.restype = ctypes.c_char_p
+        L.order_tag.argtypes = []
+        L.order_set_threads.restype = None
+        L.order_set_threads.argtypes = [ctypes.c_int]
         _LIB = L
     return _LIB
 
@@ -140,6 +148,59 @@ def conv_forward(params, w, above, left):
     out = np.empty((above.shape[0], w, w), np.float32)
     rc = lib().oracle_conv_forward(_p(params, _f32p), w, _p(above, _f32p), _p(left, _f32p), above.shape[0],
                                    _p(out, _f32p))
+    assert rc == 0
+    return out
+
+
+# ---- the bit-exact model of the exact-f32 summation order (oracle/pnn_order.c) ----------------
+# Deliberate departures from the order, for the sensitivity test only (pnn_order.c, ORDER_V_*): name -> (bit, applies to FC, conv)
+ORDER_VARIANTS = {
+    "chunk_plain": (0x001, True, True),        # k = 0..15 inside a chunk
+    "no_conv_kseg": (0x002, False, True),      # deep convolution layers as one chain
+    "no_fc_kseg": (0x004, True, False),        # deep FC layers as one chain
+    "fc_out_oneseg": (0x008, True, False),     # FC output layer as one chain
+    "seg_reverse": (0x010, True, True),        # segment sums added last to first
+    "bias_first": (0x020, True, True),         # tap GEMMs: chain starts from the bias
+    "conv1_bias_last": (0x040, False, True),   # first convolution: bias added after the chain
+    "merger_plain": (0x080, False, True),      # merger: one chain over positions 0..79
+    "last_plain": (0x100, False, True),        # last layer: channels in plain order
+    "fc_out_k16": (0x200, True, False),        # FC output layer in the hidden layers' in-chunk order
+}
+
+
+def order_tag():
+    """The arithmetic tag of the order the model implements (pnn_arithmetic_tag of a library on the same order)."""
+    return lib().order_tag().decode()
+
+
+def require_order_tag(tag):
+    """The model knows ONE order: any other tag (a later revision, the split mode) is refused."""
+    if tag != order_tag():
+        raise ValueError("the order model implements %r, not %r" % (order_tag(), tag))
+
+
+def order_set_threads(n):
+    lib().order_set_threads(int(n))
+
+
+def order_fc_forward(params, w, ctx, variant=0):
+    params = _c(params, np.float32)
+    ctx = _c(ctx, np.float32).reshape(-1, 5 * w * w)
+    assert params.size == param_count(w, True)
+    out = np.empty((ctx.shape[0], w, w), np.float32)
+    rc = lib().order_fc_forward(_p(params, _f32p), w, _p(ctx, _f32p), ctx.shape[0], _p(out, _f32p), int(variant))
+    assert rc == 0
+    return out
+
+
+def order_conv_forward(params, w, above, left, variant=0):
+    params = _c(params, np.float32)
+    above = _c(above, np.float32).reshape(-1, w, 3 * w)
+    left = _c(left, np.float32).reshape(-1, 2 * w, w)
+    assert params.size == param_count(w, False) and above.shape[0] == left.shape[0]
+    out = np.empty((above.shape[0], w, w), np.float32)
+    rc = lib().order_conv_forward(_p(params, _f32p), w, _p(above, _f32p), _p(left, _f32p), above.shape[0], _p(out, _f32p),
+                                  int(variant))
     assert rc == 0
     return out
 

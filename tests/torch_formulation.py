@@ -1,6 +1,7 @@
 """Independent PyTorch-CPU formulation of the PNN graphs (SURVEY.md Appendix B.3's cross-check), built on
 torch.nn.functional ops instead of hand-written loops.  Used only to validate the CPU oracle: the two must
-agree to <= 1e-3 absolute on seeded random weights and on the reference's two real checkpoints."""
+agree to <= 1e-3 absolute on seeded random weights and on the reference's two real checkpoints.  `dtype` = np.float64 evaluates
+the same graphs in double precision: the high-precision yardstick of the f32 order model (tests/test_order_model.py)."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -12,6 +13,10 @@ def _leaky(x):
     return torch.maximum(0.1 * x, x)          # pnn/tfutils.py:192
 
 
+def _t(a, dtype):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype))
+
+
 def _conv_same(x, W, b, s):
     """TF conv2d SAME, NHWC weights [k,k,Cin,Cout] -> NCHW torch; asymmetric padding for s = 2 (Appendix B.1)."""
     k = W.shape[0]
@@ -19,7 +24,7 @@ def _conv_same(x, W, b, s):
     oh, ow = -(-H // s), -(-Wd // s)
     pth, ptw = max((oh - 1) * s + k - H, 0), max((ow - 1) * s + k - Wd, 0)
     x = F.pad(x, (ptw // 2, ptw - ptw // 2, pth // 2, pth - pth // 2))
-    return F.conv2d(x, torch.from_numpy(np.ascontiguousarray(W.transpose(3, 2, 0, 1))), torch.from_numpy(b), stride=s)
+    return F.conv2d(x, _t(W.transpose(3, 2, 0, 1), W.dtype), _t(b, b.dtype), stride=s)
 
 
 def _tconv_same(x, W, b, s):
@@ -27,14 +32,19 @@ def _tconv_same(x, W, b, s):
     k = W.shape[0]
     H, Wd = x.shape[2], x.shape[3]
     pb = max((H - 1) * s + k - H * s, 0) // 2
-    y = F.conv_transpose2d(x, torch.from_numpy(np.ascontiguousarray(W.transpose(3, 2, 0, 1))), None, stride=s)
+    y = F.conv_transpose2d(x, _t(W.transpose(3, 2, 0, 1), W.dtype), None, stride=s)
     y = y[:, :, pb:pb + H * s, pb:pb + Wd * s]
-    return y + torch.from_numpy(b).view(1, -1, 1, 1)
+    return y + _t(b, b.dtype).view(1, -1, 1, 1)
 
 
-def fc_forward(flat, w, ctx):
-    t = wts.split_params(np.asarray(flat, np.float32), w, True)
-    x = torch.from_numpy(np.asarray(ctx, np.float32).reshape(-1, 5 * w * w))
+def _params(flat, w, is_fc, dtype):
+    """float32 parameters as given (the nets' values), widened to `dtype` when that is wider"""
+    return {k: v.astype(dtype) for k, v in wts.split_params(np.asarray(flat, np.float32), w, is_fc).items()}
+
+
+def fc_forward(flat, w, ctx, dtype=np.float32):
+    t = _params(flat, w, True, dtype)
+    x = _t(np.asarray(ctx, np.float32).reshape(-1, 5 * w * w), dtype)
     for i in range(4):
         x = x @ torch.from_numpy(t["fully_connected/weights_%d" % i]) + torch.from_numpy(t["fully_connected/biases_%d" % i])
         if i < 3:
@@ -42,12 +52,12 @@ def fc_forward(flat, w, ctx):
     return x.reshape(-1, w, w).numpy()
 
 
-def conv_forward(flat, w, above, left):
-    t = wts.split_params(np.asarray(flat, np.float32), w, False)
+def conv_forward(flat, w, above, left, dtype=np.float32):
+    t = _params(flat, w, False, dtype)
     st = wts.STRIDES_BRANCH[w]
     feats = []
     for name, inp, shape in (("branch_above", above, (w, 3 * w)), ("branch_left", left, (2 * w, w))):
-        x = torch.from_numpy(np.asarray(inp, np.float32).reshape(-1, 1, *shape))
+        x = _t(np.asarray(inp, np.float32).reshape(-1, 1, *shape), dtype)
         for i, s in enumerate(st):
             p = "convolutional/%s/convolution_%d/" % (name, i)
             x = _leaky(_conv_same(x, t[p + "weights"], t[p + "biases"], s))
