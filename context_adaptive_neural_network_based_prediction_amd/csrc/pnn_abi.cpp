@@ -124,16 +124,9 @@ int pending_range_error(pnn_ctx* c)
                                 "kernels (|v| >= 65504): its predictions are invalid; repeat it with pnn_set_option(ctx, \"precision\", 0)");
 }
 
-// End of a synchronous host call: wait for the context's stream.  hipStreamSynchronize parks the thread on the completion
-// signal (an interrupt and a wake-up: several microseconds on a 45 us call); HM's thread has nothing else to do, so it polls.
+// End of a synchronous host call whose last kernel took no completion signal: wait for the context's stream.
 int wait_stream(pnn_ctx* c, hipStream_t s)
 {
-    if (c->opt_spin_wait) {
-        hipError_t e;
-        while ((e = hipStreamQuery(s)) == hipErrorNotReady) {}
-        if (e != hipSuccess) return fail(c, PNN_E_HIP, "hipStreamQuery failed: %s", hipGetErrorString(e));
-        return PNN_OK;
-    }
     HIPCHK(c, hipStreamSynchronize(s));
     return PNN_OK;
 }
@@ -225,6 +218,88 @@ int range_fallback(pnn_ctx* c, long n, Pass pass, hipStream_t s)
 
 struct PnnwHeader { char magic[4]; uint32_t version, width, is_fc; uint64_t n_params, reserved; };
 
+// ---- options (pnn_set_option; their list and meaning: include/pnn_hip.h) ----------------------------------------------------------
+// An option is a number in the context (`field`), optionally read from an environment variable at pnn_create* (`env`).  Setting it
+// stores the value and then, by `effect`, drops the tuner's remembered choices (kRetune: the option changes which configurations
+// are legal or how they perform) or only starts a new tuning generation (kNewTuneGen: pnn_ctx::tune_gen).  An option with a `set`
+// handler is set by that instead of the plain store.  Any successful set drops the cached predictions (pnn_set_option).
+enum OptionEffect { kStore, kRetune, kNewTuneGen };
+
+int set_canonical_order(pnn_ctx* c, long value)   // kept as a name: one summation order at every batch size is the only mode since round 5
+{
+    if (value != 1) return fail(c, PNN_E_ARG, "canonical_order = %ld: the kernels with another summation order were removed; 1 is the only mode", value);
+    return PNN_OK;
+}
+
+int set_stream_priority(pnn_ctx* c, long value)
+{
+    // the context's own stream (the host entry points run on it) at the device's greatest (< 0), default (0) or least (> 0) priority
+    HIPCHK(c, hipSetDevice(c->device));
+    int least = 0, greatest = 0;
+    HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    const int pr = value < 0 ? greatest : value > 0 ? least : (least + greatest) / 2;
+    hipStream_t ns = nullptr;
+    HIPCHK(c, hipStreamCreateWithPriority(&ns, hipStreamNonBlocking, pr));
+    if (c->stream) { (void)hipStreamSynchronize(c->stream); if (c->stream_owned) (void)hipStreamDestroy(c->stream); }
+    c->stream = ns; c->stream_owned = true;
+    return PNN_OK;
+}
+
+int set_stream(pnn_ctx* c, long value)
+{
+    // the host entry points run on the caller's stream (a hipStream_t passed as the value; the caller keeps and destroys it) --
+    // what pnn_streams_on_distinct_queues is for
+    if (!value) return fail(c, PNN_E_ARG, "stream = NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->stream) { (void)hipStreamSynchronize(c->stream); if (c->stream_owned) (void)hipStreamDestroy(c->stream); }
+    c->stream = reinterpret_cast<hipStream_t>(value); c->stream_owned = false;
+    return PNN_OK;
+}
+
+int set_cache_mb(pnn_ctx* c, long value) { c->opt_cache_mb = value; c->cache_hits = c->cache_misses = 0; return PNN_OK; }
+int set_ws_cap_mb(pnn_ctx* c, long value) { c->ws_cap_bytes = (size_t)value << 20; return PNN_OK; }
+
+struct OptionRow { const char* name; long pnn_ctx::*field; const char* env; OptionEffect effect; int (*set)(pnn_ctx*, long); };
+const OptionRow kOptions[] = {
+    // name                  field                              environment variable    effect        handler
+    {"precision",            &pnn_ctx::opt_precision,           "PNN_PRECISION",        kStore,       nullptr},
+    {"canonical_order",      nullptr,                           nullptr,                kStore,       set_canonical_order},
+    {"f32_small",            &pnn_ctx::opt_f32_small,           "PNN_F32_SMALL",        kStore,       nullptr},
+    {"f32_small_max_tiles",  &pnn_ctx::opt_f32_small_tiles,     "PNN_F32_SMALL_TILES",  kStore,       nullptr},
+    {"fc_out_f32",           &pnn_ctx::opt_fc_out_f32,          nullptr,                kStore,       nullptr},
+    {"chain_io",             &pnn_ctx::opt_chain_io,            "PNN_CHAIN_IO",         kStore,       nullptr},
+    {"tails",                &pnn_ctx::opt_tails,               "PNN_TAILS",            kStore,       nullptr},
+    {"f32_cfg",              &pnn_ctx::opt_f32_cfg,             "PNN_F32_CFG",          kStore,       nullptr},
+    {"f32_seg_mode",         &pnn_ctx::opt_f32_seg_mode,        "PNN_F32_SEG_MODE",     kRetune,      nullptr},
+    {"f32_persist",          &pnn_ctx::opt_f32_persist,         "PNN_F32_PERSIST",      kRetune,      nullptr},
+    {"f32_overlap",          &pnn_ctx::opt_f32_overlap,         "PNN_F32_OVERLAP",      kStore,       nullptr},
+    {"fuse_last",            &pnn_ctx::opt_fuse_last,           "PNN_FUSE_LAST",        kStore,       nullptr},
+    {"seg_fold",             &pnn_ctx::opt_seg_fold,            nullptr,                kStore,       nullptr},
+    {"f32_small_deep",       &pnn_ctx::opt_f32_small_deep,      "PNN_F32_SMALL_DEEP",   kStore,       nullptr},
+    {"sp_cfg",               &pnn_ctx::opt_sp_cfg,              nullptr,                kStore,       nullptr},
+    {"ring",                 &pnn_ctx::opt_ring,                "PNN_RING",             kRetune,      nullptr},
+    {"convimg",              &pnn_ctx::opt_convimg,             "PNN_CONVIMG",          kRetune,      nullptr},
+    {"small",                &pnn_ctx::opt_small,               "PNN_SMALL",            kStore,       nullptr},
+    {"small_max_tiles",      &pnn_ctx::opt_small_tiles,         nullptr,                kStore,       nullptr},
+    {"fuse_first",           &pnn_ctx::opt_fuse_first,          "PNN_FUSE_FIRST",       kRetune,      nullptr},
+    {"fuse_tail",            &pnn_ctx::opt_fuse_tail,           "PNN_FUSE_TAIL",        kRetune,      nullptr},
+    {"ring_pm",              &pnn_ctx::opt_ring_pm,             "PNN_RING_PM",          kRetune,      nullptr},
+    {"autotune",             &pnn_ctx::opt_autotune,            "PNN_AUTOTUNE",         kNewTuneGen,  nullptr},
+    {"host_slice",           &pnn_ctx::opt_host_slice,          nullptr,                kStore,       nullptr},
+    {"pair",                 &pnn_ctx::opt_pair,                nullptr,                kStore,       nullptr},
+    {"branch_streams",       &pnn_ctx::opt_branch_streams,      "PNN_BRANCH_STREAMS",   kStore,       nullptr},
+    {"fuse_gather",          &pnn_ctx::opt_fuse_gather,         "PNN_FUSE_GATHER",      kStore,       nullptr},
+    {"cache_mb",             &pnn_ctx::opt_cache_mb,            "PNN_CACHE_MB",         kStore,       set_cache_mb},
+    {"flag_wait",            &pnn_ctx::opt_flag_wait,           "PNN_FLAG_WAIT",        kStore,       nullptr},
+    {"stream_priority",      nullptr,                           nullptr,                kStore,       set_stream_priority},
+    {"stream",               nullptr,                           nullptr,                kStore,       set_stream},
+    {"wait_sleep",           &pnn_ctx::opt_wait_sleep,          "PNN_WAIT_SLEEP",       kStore,       nullptr},
+    {"graphs",               &pnn_ctx::opt_graphs,              "PNN_GRAPHS",           kStore,       nullptr},
+    {"max_chunk",            &pnn_ctx::opt_max_chunk,           "PNN_MAX_CHUNK",        kStore,       nullptr},
+    {"ws_cap_mb",            nullptr,                           nullptr,                kStore,       set_ws_cap_mb},
+    {"time_launches",        &pnn_ctx::opt_time_launches,       nullptr,                kStore,       nullptr},
+};
+
 }  // namespace
 
 extern "C" {
@@ -244,33 +319,9 @@ int pnn_create_empty(pnn_ctx** out, float mean, int device)
         delete c;
         return fail(nullptr, PNN_E_HIP, "cannot initialise HIP device %d", device);
     }
-    if (const char* e = getenv("PNN_MAX_CHUNK")) c->opt_max_chunk = atol(e);
-    if (const char* e = getenv("PNN_PRECISION")) c->opt_precision = atol(e);
-    if (const char* e = getenv("PNN_AUTOTUNE")) c->opt_autotune = atol(e);
-    if (const char* e = getenv("PNN_F32_CFG")) c->opt_f32_cfg = atol(e);
-    if (const char* e = getenv("PNN_F32_OVERLAP")) c->opt_f32_overlap = atol(e);
-    if (const char* e = getenv("PNN_F32_SMALL")) c->opt_f32_small = atol(e);
-    if (const char* e = getenv("PNN_F32_SMALL_TILES")) c->opt_f32_small_tiles = atol(e);
-    if (const char* e = getenv("PNN_CONVIMG")) c->opt_convimg = atol(e);
-    if (const char* e = getenv("PNN_RING")) c->opt_ring = atol(e);
-    if (const char* e = getenv("PNN_SMALL")) c->opt_small = atol(e);
-    if (const char* e = getenv("PNN_FUSE_LAST")) c->opt_fuse_last = atol(e);
-    if (const char* e = getenv("PNN_F32_SEG_MODE")) c->opt_f32_seg_mode = atol(e);
-    if (const char* e = getenv("PNN_F32_PERSIST")) c->opt_f32_persist = atol(e);
-    if (const char* e = getenv("PNN_FUSE_FIRST")) c->opt_fuse_first = atol(e);
-    if (const char* e = getenv("PNN_FUSE_GATHER")) c->opt_fuse_gather = atol(e);
-    if (const char* e = getenv("PNN_FUSE_TAIL")) c->opt_fuse_tail = atol(e);
-    if (const char* e = getenv("PNN_RING_PM")) c->opt_ring_pm = atol(e);
-    if (const char* e = getenv("PNN_BRANCH_STREAMS")) c->opt_branch_streams = atol(e);
-    if (const char* e = getenv("PNN_CACHE_MB")) c->opt_cache_mb = atol(e);
-    if (const char* e = getenv("PNN_FC_OUT")) c->opt_fc_out = atol(e);
-    if (const char* e = getenv("PNN_SPIN_WAIT")) c->opt_spin_wait = atol(e);
-    if (const char* e = getenv("PNN_FLAG_WAIT")) c->opt_flag_wait = atol(e);
-    if (const char* e = getenv("PNN_WAIT_SLEEP")) c->opt_wait_sleep = atol(e);
-    if (const char* e = getenv("PNN_GRAPHS")) c->opt_graphs = atol(e);
-    if (const char* e = getenv("PNN_F32_SMALL_DEEP")) c->opt_f32_small_deep = atol(e);
-    if (const char* e = getenv("PNN_CHAIN_IO")) c->opt_chain_io = atol(e);
-    if (const char* e = getenv("PNN_TAILS")) c->opt_tails = atol(e);
+    for (const OptionRow& o : kOptions)
+        if (o.env)
+            if (const char* e = getenv(o.env)) c->*o.field = atol(e);
     if (hipHostMalloc((void**)&c->h_range, (pnn_ctx::kDoneFlag0 + pnn_ctx::kDoneFlagsMax) * 4, hipHostMallocDefault) != hipSuccess) {
         pnn_destroy(c);
         return fail(nullptr, PNN_E_NOMEM, "hipHostMalloc of the range flag failed");
@@ -429,64 +480,15 @@ int pnn_set_option(pnn_ctx* c, const char* name, long value)
 {
     if (!c || !name) return PNN_E_ARG;
     PNN_UNSAFE_CALLS_GUARD;
-    if (!strcmp(name, "max_chunk")) c->opt_max_chunk = value;
-    else if (!strcmp(name, "canonical_order")) {       // kept as a name: one summation order at every batch size is the only mode since round 5
-        if (value != 1) return fail(c, PNN_E_ARG, "canonical_order = %ld: the kernels with another summation order were removed; 1 is the only mode", value);
+    const OptionRow* o = std::find_if(std::begin(kOptions), std::end(kOptions), [name](const OptionRow& r) { return !strcmp(r.name, name); });
+    if (o == std::end(kOptions)) return fail(c, PNN_E_ARG, "unknown option %s", name);
+    if (o->set) {
+        if (const int rc = o->set(c, value)) return rc;
+    } else {
+        c->*o->field = value;
     }
-    else if (!strcmp(name, "time_launches")) c->opt_time_launches = value;
-    else if (!strcmp(name, "precision")) c->opt_precision = value;
-    else if (!strcmp(name, "autotune")) { c->opt_autotune = value; c->tune_gen++; }
-    else if (!strcmp(name, "convimg")) { c->opt_convimg = value; c->tuned.clear(); c->tune_gen++; }
-    else if (!strcmp(name, "ring")) { c->opt_ring = value; c->tuned.clear(); c->tune_gen++; }
-    else if (!strcmp(name, "small")) c->opt_small = value;
-    else if (!strcmp(name, "small_max_tiles")) c->opt_small_tiles = value;
-    else if (!strcmp(name, "pair")) c->opt_pair = value;
-    else if (!strcmp(name, "fc_out")) c->opt_fc_out = value;
-    else if (!strcmp(name, "spin_wait")) c->opt_spin_wait = value;
-    else if (!strcmp(name, "flag_wait")) c->opt_flag_wait = value;
-    else if (!strcmp(name, "wait_sleep")) c->opt_wait_sleep = value;
-    else if (!strcmp(name, "graphs")) c->opt_graphs = value;
-    else if (!strcmp(name, "stream_priority")) {
-        // the context's own stream (the host entry points run on it) at the device's greatest (< 0), default (0) or least (> 0) priority
-        HIPCHK(c, hipSetDevice(c->device));
-        int least = 0, greatest = 0;
-        HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        const int pr = value < 0 ? greatest : value > 0 ? least : (least + greatest) / 2;
-        hipStream_t ns = nullptr;
-        HIPCHK(c, hipStreamCreateWithPriority(&ns, hipStreamNonBlocking, pr));
-        if (c->stream) { (void)hipStreamSynchronize(c->stream); if (c->stream_owned) (void)hipStreamDestroy(c->stream); }
-        c->stream = ns; c->stream_owned = true;
-    }
-    else if (!strcmp(name, "stream")) {
-        // the host entry points run on the caller's stream (a hipStream_t passed as the value; the caller keeps and destroys it) --
-        // what pnn_streams_on_distinct_queues is for
-        if (!value) return fail(c, PNN_E_ARG, "stream = NULL");
-        HIPCHK(c, hipSetDevice(c->device));
-        if (c->stream) { (void)hipStreamSynchronize(c->stream); if (c->stream_owned) (void)hipStreamDestroy(c->stream); }
-        c->stream = reinterpret_cast<hipStream_t>(value); c->stream_owned = false;
-    }
-    else if (!strcmp(name, "fuse_last")) c->opt_fuse_last = value;
-    else if (!strcmp(name, "f32_seg_mode")) { c->opt_f32_seg_mode = value; c->tuned.clear(); c->tune_gen++; }
-    else if (!strcmp(name, "f32_persist")) { c->opt_f32_persist = value; c->tuned.clear(); c->tune_gen++; }
-    else if (!strcmp(name, "fuse_first")) { c->opt_fuse_first = value; c->tuned.clear(); c->tune_gen++; }
-    else if (!strcmp(name, "fuse_gather")) c->opt_fuse_gather = value;
-    else if (!strcmp(name, "fuse_tail")) { c->opt_fuse_tail = value; c->tuned.clear(); c->tune_gen++; }
-    else if (!strcmp(name, "ring_pm")) { c->opt_ring_pm = value; c->tuned.clear(); c->tune_gen++; }
-    else if (!strcmp(name, "branch_streams")) c->opt_branch_streams = value;
-    else if (!strcmp(name, "cache_mb")) { c->opt_cache_mb = value; c->cache_hits = c->cache_misses = 0; }
-    else if (!strcmp(name, "sp_cfg")) c->opt_sp_cfg = value;
-    else if (!strcmp(name, "f32_cfg")) c->opt_f32_cfg = value;
-    else if (!strcmp(name, "f32_overlap")) c->opt_f32_overlap = value;
-    else if (!strcmp(name, "f32_small")) c->opt_f32_small = value;
-    else if (!strcmp(name, "fc_out_f32")) c->opt_fc_out_f32 = value;
-    else if (!strcmp(name, "host_slice")) c->opt_host_slice = value;
-    else if (!strcmp(name, "chain_io")) c->opt_chain_io = value;
-    else if (!strcmp(name, "tails")) c->opt_tails = value;
-    else if (!strcmp(name, "seg_fold")) c->opt_seg_fold = value;
-    else if (!strcmp(name, "f32_small_deep")) c->opt_f32_small_deep = value;
-    else if (!strcmp(name, "f32_small_max_tiles")) c->opt_f32_small_tiles = value;
-    else if (!strcmp(name, "ws_cap_mb")) c->ws_cap_bytes = (size_t)value << 20;
-    else return fail(c, PNN_E_ARG, "unknown option %s", name);
+    if (o->effect == kRetune) c->tuned.clear();
+    if (o->effect != kStore) c->tune_gen++;
     cache_clear(c);                                   // any option may change the arithmetic path: cached predictions are dropped
     return PNN_OK;
 }

@@ -147,7 +147,7 @@ struct pnn_ctx {
     // exact-f32 launches of few output tiles (the in-loop single-block calls, the service's handfuls): tapgemm_f32_small_kernel, the same
     // fmaf chain on the 16x16x4 instruction (10 instead of 32 cycles per k of the dependent chain), pnn_gemm_f32_small.hip
     long opt_f32_small = 1;
-    long opt_fc_out_f32 = 1;                          // 1: exact-f32 FC passes of <= 512 blocks run the output layer's K segments and their reduction as ONE launch (2: its round-5 form on the 32x32x2 instruction)
+    long opt_fc_out_f32 = 1;                          // nonzero: exact-f32 FC passes of <= 512 blocks run the output layer's K segments and their reduction as ONE launch
     // 1: the K segments of a layer that runs on the small exact-f32 kernel are added up inside its launch (the last workgroup of a tile
     // to arrive, see tapgemm_f32_small_body) instead of by a seg_reduce launch behind it: the same additions in the same order
     long opt_seg_fold = 1;
@@ -179,11 +179,6 @@ struct pnn_ctx {
     long opt_small = 1;                               // 1: split GEMMs with few output tiles run on tapgemm_small_kernel (one wave per 32 x 32 tile)
     long opt_small_tiles = 512;                       // ... "few" = at most this many tiles (two one-wave workgroups per CU)
     long opt_pair = 1;                                // 1: small conv passes run the same layer of both branches as ONE launch
-    // Two round-3 experiments on the single-block call, both bit-identical, both measured WITHOUT gain and therefore off by default
-    // (tools/batch1_latency.py, profiles/r03_batch1_latency.txt): the call's time is the chain of dependent
-    // launches on the device (~4 us each whatever they do) plus ~10 us of first-launch latency and completion hand-over.
-    long opt_fc_out = 0;                              // 1: small FC passes run the <= 64-output layer (K segments + reduction) as ONE launch (5 -> 4 launches)
-    long opt_spin_wait = 0;                           // 1: host calls poll the stream (hipStreamQuery) instead of blocking in hipStreamSynchronize
     long opt_convimg = 1;                             // 1: stride/tap layers whose images fit LDS use convimg_sp_kernel
     long opt_autotune = 2;                            // on-device choice of the split-GEMM configuration: 0 never, 1 always, 2 big launches only
     std::map<std::pair<const void*, long>, int> tuned;

@@ -636,96 +636,19 @@ hipError_t launch_fc_out_f32(const TapGemmParams& p, hipStream_t s, int* segment
     return hipGetLastError();
 }
 
-// The same output layer AND its reduction in ONE launch, for small M (round 5): a single-block call is a chain of dependent launches
+// The same output layer AND its reduction in ONE launch, for small M: a single-block call is a chain of dependent launches
 // that cost 3-4 us each on the host and more on the device once the batching service's five width workers share the chip
-// (tools/corun_threads.cpp), so fc_out_f32_kernel + fuse_reduce_kernel become one workgroup of 8 waves per (32-row tile, 32-column tile):
-// wave z runs fc_out_f32_kernel's chain for K segment z of that tile (half the chain of that kernel's wave, which owns both column
-// tiles), all its operands requested up front (two waves per SIMD: 256 registers per lane; a 16-wave form that owned both column
-// tiles had 128, fetched block by block and paid the memory latency five times: 16.6 us), the partial sums meet in LDS and are added
-// in segment order, + bias, HM epilogue -- fuse_reduce_kernel's arithmetic.
-struct FcOutF32Args { TapGemmParams p; DoneSignal done; };
-__global__ __launch_bounds__(512) void fc_out_f32_small_kernel(const FcOutF32Args a)
-{
-    touch_kernargs<sizeof(FcOutF32Args)>();
-#ifdef PNN_F32_DIAG
-    const unsigned long long de0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long dr0 = 0, dr1 = 0;
-#endif
-    const TapGemmParams& p = a.p;
-    constexpr int NT = 5;
-    __shared__ __attribute__((aligned(16))) float part[8][32][32];
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    const int z = __builtin_amdgcn_readfirstlane(tid >> 6), ot = blockIdx.y;
-    const int mblk = blockIdx.x * 32;
-    const int segs = (p.Cin + 159) / 160;
-    if (z < segs) {
-        const int m = mblk + l31, n0 = z * 32 * NT;
-        const bool mv = m < p.M;
-        const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.X, 0, p.x_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wp, 0, (unsigned)p.chunk_begin[1] * 4u * (unsigned)p.Npad * 16u, 0x00020000);
-        f32x16 acc2;
-#pragma unroll
-        for (int i = 0; i < 16; i++) acc2[i] = 0.f;
-        f32x4 x[NT][4], w2[NT][4];
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++)
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const int n = n0 + 32 * nt + 8 * g + 4 * h;
-                const unsigned xo = (mv && n < p.Cin) ? ((unsigned)m * (unsigned)p.Cin + (unsigned)n) << 2 : 0x80000000u;
-                x[nt][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, xo, 0, 0));
-                w2[nt][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (unsigned)((n >> 2) * p.Npad + ot * 32 + l31) << 4, 0, 0));
-            }
-        __builtin_amdgcn_sched_barrier(0);           // every request before the first MFMA: ONE memory latency, not one per block
-#ifdef PNN_F32_DIAG
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        dr0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++)
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2[nt][g][r], x[nt][g][r], acc2, 0, 0, 0);
-#pragma unroll
-        for (int g = 0; g < 4; g++)
-            *reinterpret_cast<f32x4*>(&part[z][l31][8 * g + 4 * h]) = (f32x4){acc2[4 * g], acc2[4 * g + 1], acc2[4 * g + 2], acc2[4 * g + 3]};
-#ifdef PNN_F32_DIAG
-        dr1 = __builtin_amdgcn_s_memrealtime();
-#endif
-    }
-    __syncthreads();
-    const int mr = tid >> 3, nl = (tid & 7) << 2, n = ot * 32 + nl;
-    const int mg = mblk + mr;
-    if (tid < 256 && mg < p.M && n < p.Cout) {
-        f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-        for (int t = 0; t < segs; t++) sum += *reinterpret_cast<const f32x4*>(&part[t][mr][nl]);
-        const f32x4 v = sum + *reinterpret_cast<const f32x4*>(p.bias + n);
-        if (p.Y) *reinterpret_cast<f32x4*>(p.Y + (size_t)mg * p.Cout + n) = v;
-        if (p.Yi) *reinterpret_cast<int4*>(p.Yi + (size_t)mg * p.Cout + n) = make_int4(hm_round(v[0], p.mean), hm_round(v[1], p.mean), hm_round(v[2], p.mean), hm_round(v[3], p.mean));
-    }
-#ifdef PNN_F32_DIAG
-    const unsigned long long dr2 = __builtin_amdgcn_s_memrealtime();
-#endif
-    signal_done(a.done);
-#ifdef PNN_F32_DIAG
-    if (p.Xlo && tid == 0) {
-        unsigned long long* d = (unsigned long long*)p.Xlo + 8 * (blockIdx.y * gridDim.x + blockIdx.x);
-        d[1] = dr1 - dr0; d[3] = dr0; d[4] = de0; d[5] = __builtin_amdgcn_s_memrealtime(); d[6] = dr2;
-    }
-#endif
-}
-
-// Round 6: the same output layer, segments and reduction on v_mfma_f32_16x16x4_f32 -- the last kernel of a single-block FC call was its
-// slowest (profiles/r05_batch1_w8_f32_timeline.txt: 10.9 us of 34.9) with its 160-deep segment chains as 80 dependent 64-cycle
-// instructions.  The chain of segment z, per (column tile nt, group g) of the fused kernel: hidden units 8g + 0, 4, 1, 5, 2, 6, 3, 7
-// (step r of the 32x32x2 instruction adds unit 8g + r from lane half 0, then 8g + 4 + r from lane half 1) -- through the 16x16x4
+// (tools/corun_threads.cpp), so fc_out_f32_kernel + fuse_reduce_kernel become one launch -- on v_mfma_f32_16x16x4_f32 since round 6:
+// on the 32x32x2 instruction this was the slowest kernel of a single-block FC call (profiles/r05_batch1_w8_f32_timeline.txt: 10.9 us
+// of 34.9), its 160-deep segment chains 80 dependent 64-cycle instructions.  The chain of segment z, per (column tile nt, group g)
+// of the fused kernel: hidden units 8g + 0, 4, 1, 5, 2, 6, 3, 7 (step r of the 32x32x2 instruction adds unit 8g + r from lane half 0, then 8g + 4 + r from lane half 1) -- through the 16x16x4
 // form that is two instructions whose lane groups q = 0..3 supply units 8g + 4 (q & 1) + 2 i + (q >> 1), i = 0, 1: 40 dependent
 // instructions of 32 cycles per segment instead of 80 of 64, the same fmaf chain bit for bit (the f32 matrix instructions are a
 // k-ordered fmaf chain, one rounding per product: pnn_gemm_f32_small.hip).  One workgroup of 8 waves per 16 x 16 output tile (a
 // single 8x8 block: four workgroups instead of two), wave z = K segment z; each lane requests its 20 + 20 sixteen-byte operand pieces
 // up front (ONE memory latency) and keeps the two elements of each that its lane group multiplies; the partial sums meet in LDS and
 // wave 0 adds them in segment order, + bias, HM epilogue -- fuse_reduce_kernel's arithmetic.
+struct FcOutF32Args { TapGemmParams p; DoneSignal done; };
 __global__ __launch_bounds__(512) void fc_out_f32_chain_kernel(const FcOutF32Args a)
 {
     touch_kernargs<sizeof(FcOutF32Args)>();
@@ -815,12 +738,11 @@ __global__ __launch_bounds__(512) void fc_out_f32_chain_kernel(const FcOutF32Arg
 // p: the output layer as a one-tap GEMM (X = f32 activations [M][Cin], Wp = its f32 pack, bias, mean, Y / Yi).  false: not this kernel's case.
 bool fc_out_f32_small_fits(const TapGemmParams& p) { return p.ncls == 1 && p.SH * p.SW == 1 && p.Cout <= 64 && p.Cout % 4 == 0 && (p.Cin + 159) / 160 <= 8 && p.M > 0; }
 
-hipError_t launch_fc_out_f32_small(const TapGemmParams& p, hipStream_t s, const DoneSignal& done, bool round5_form)
+hipError_t launch_fc_out_f32_small(const TapGemmParams& p, hipStream_t s, const DoneSignal& done)
 {
     if (!fc_out_f32_small_fits(p)) return hipErrorInvalidValue;
     const FcOutF32Args a{p, done};
-    if (round5_form) pnn_launch(fc_out_f32_small_kernel, dim3((unsigned)((p.M + 31) / 32), (unsigned)((p.Cout + 31) / 32)), dim3(512), 0, s, a);
-    else pnn_launch(fc_out_f32_chain_kernel, dim3((unsigned)((p.M + 15) / 16), (unsigned)((p.Cout + 15) / 16)), dim3(512), 0, s, a);
+    pnn_launch(fc_out_f32_chain_kernel, dim3((unsigned)((p.M + 15) / 16), (unsigned)((p.Cout + 15) / 16)), dim3(512), 0, s, a);
     return hipGetLastError();
 }
 

@@ -773,8 +773,7 @@ hipError_t launch_fcseg_f32_small(const TapGemmParams& p, hipStream_t s)
     }
     const F32SmallArgs a{p};
     const bool xch = (p.chain_io & 1) != 0;          // the activations are in chain order (see tapgemm_f32_small_body)
-    static const bool no_all = getenv("PNN_FCSEG_RING") != nullptr;   // A/B: the ring form for every layer
-    if (fcseg_all_fits(p) && !no_all) {
+    if (fcseg_all_fits(p)) {
         static int done_all[16] = {};
         if (!__atomic_load_n(&done_all[di], __ATOMIC_ACQUIRE)) {
             if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fcseg_f32_small_all_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFcAllLds)) != hipSuccess) return e;

@@ -163,9 +163,6 @@ hipError_t launch_split(const float* x, long n, void* hi, void* lo, int* range_f
 long tapgemm_small_tiles(const TapGemmParams& p);
 // host_input (optional, with a_is_f32): the same rows in HOST memory; when they fit they travel inside the argument block
 hipError_t launch_tapgemm_small(const TapGemmParams& p, bool a_is_f32, int seg_chunks, hipStream_t s, const float* host_input = nullptr);
-// Output layer (<= 64 outputs) of an FC net at small M in one launch: K segments + their reduction (pnn_gemm_small.hip)
-bool fc_out_small_fits(const TapGemmParams& p, int seg_chunks);
-hipError_t launch_fc_out_small(const TapGemmParams& p, int seg_chunks, hipStream_t s, const DoneSignal& done = DoneSignal{nullptr, nullptr, 0, 0});
 hipError_t launch_tapgemm_small_pair(const TapGemmParams& a, const TapGemmParams& b, hipStream_t s);   // two independent layers, one launch
 // Exact-f32 tap GEMM on v_mfma_f32_32x32x2_f32, one wave per SIMD (pnn_gemm_f32.hip): the canonical f32 summation order.
 // fuse: apply the output layer p.W2p (f32 pack, <= 64 outputs) to the activated tile, partial sums to p.part[column tile][M][64]
@@ -189,7 +186,7 @@ hipError_t launch_fcseg_f32_small(const TapGemmParams& p, hipStream_t s);
 hipError_t launch_fc_out_f32(const TapGemmParams& p, hipStream_t s, int* segments);
 // ... and, for small M, the same segments AND their reduction (+ bias, HM epilogue) in one launch: fuse_reduce_kernel's bits
 bool fc_out_f32_small_fits(const TapGemmParams& p);
-hipError_t launch_fc_out_f32_small(const TapGemmParams& p, hipStream_t s, const DoneSignal& done = DoneSignal{nullptr, nullptr, 0, 0}, bool round5_form = false);
+hipError_t launch_fc_out_f32_small(const TapGemmParams& p, hipStream_t s, const DoneSignal& done = DoneSignal{nullptr, nullptr, 0, 0});
 
 // Cin == 1 forward convolution (first layer of each branch): direct VALU kernel.
 struct Conv1Params {

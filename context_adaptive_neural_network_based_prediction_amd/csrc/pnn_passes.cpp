@@ -26,6 +26,41 @@ void* diag_stamp_slot(pnn_ctx* c, const char* name, long wgs, double k)
 
 namespace {
 
+// One tap-GEMM launch of kernel family `kind` (pnn_launch_times), counted in the call's statistics (pnn_last_call_stats).  Under
+// "time_launches" -- or PNN_PROFILE where the caller passes `profile` -- the launch itself records HIP events around its kernel
+// (g_launch_events): kept for pnn_launch_times, or, under PNN_PROFILE, waited for and printed as `fmt` with `args`, then the time in
+// microseconds and the TFLOP/s (the [pnn-prof] lines tools/conv_layers.py reads).
+template <typename Launch, typename... Args>
+int timed_launch(pnn_ctx* c, int kind, double flops, bool profile, Launch&& launch, const char* fmt = nullptr, Args... args)
+{
+    if (profile || c->opt_time_launches) {
+        pnn_ctx::LaunchRec r;
+        HIPCHK(c, hipEventCreate(&r.e0));
+        HIPCHK(c, hipEventCreate(&r.e1));
+        r.kind = kind; r.flops = flops;
+        const LaunchEvents ev{r.e0, r.e1};            // recorded by the launch itself: the kernel's own begin -> end
+        g_launch_events = &ev;
+        const hipError_t le = launch();
+        g_launch_events = nullptr;
+        HIPCHK(c, le);
+        if (profile) {
+            HIPCHK(c, hipEventSynchronize(r.e1));
+            float ms = 0.f;
+            HIPCHK(c, hipEventElapsedTime(&ms, r.e0, r.e1));
+            fprintf(stderr, fmt, args..., ms * 1e3, flops / (ms * 1e-3) / 1e12);
+            (void)hipEventDestroy(r.e0);
+            (void)hipEventDestroy(r.e1);
+        } else {
+            c->launch_recs.push_back(r);
+        }
+    } else {
+        HIPCHK(c, launch());
+    }
+    c->stat_gemm_launches++; c->stat_launches++;
+    c->stat_gemm_flops += flops;
+    return PNN_OK;
+}
+
 // Would run_gemm send this layer (nb blocks, no fused next layer) to the small exact-f32 kernels?  The ONE statement of that rule:
 // run_gemm decides by it, and the passes by it which tensors travel in chain order (both ends on those kernels, pnn_gemm_f32_small.hip).
 bool f32_small_applies(const pnn_ctx* c, const GemmLayer& L, long nb, bool has_next, bool has_yi)
@@ -114,32 +149,8 @@ int run_gemm(pnn_ctx* c, const GemmLayer& L, const float* X, float* Y, int32_t* 
         ps.chain_io = chain_io;
         if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d nseg=%d -> f32 small kernel, %d K segments side by side (%ld tiles of 16 x 16)\n", M, L.k_total, p.Cout, L.nseg, L.nseg, fcseg_f32_small_tiles(p));
         if (void* slot = diag_stamp_slot(c, "fcseg_f32_small", fcseg_f32_small_tiles(p), L.k_total)) ps.Xlo = slot;   // (diagnostic library, PNN_B1_STAMPS)
-        if (profile || c->opt_time_launches) {
-            pnn_ctx::LaunchRec r;
-            HIPCHK(c, hipEventCreate(&r.e0));
-            HIPCHK(c, hipEventCreate(&r.e1));
-            r.kind = 6; r.flops = flops;
-            const LaunchEvents ev{r.e0, r.e1};
-            g_launch_events = &ev;
-            const hipError_t le = launch_fcseg_f32_small(ps, s);
-            g_launch_events = nullptr;
-            HIPCHK(c, le);
-            if (profile) {
-                HIPCHK(c, hipEventSynchronize(r.e1));
-                float ms = 0.f;
-                HIPCHK(c, hipEventElapsedTime(&ms, r.e0, r.e1));
-                fprintf(stderr, "[pnn-prof] M=%ld K=%.0f N=%d nseg=%d f32-small-fcseg us=%.1f tflops=%.2f\n", M, L.k_total, p.Cout, L.nseg, ms * 1e3, r.flops / (ms * 1e-3) / 1e12);
-                (void)hipEventDestroy(r.e0);
-                (void)hipEventDestroy(r.e1);
-            } else {
-                c->launch_recs.push_back(r);
-            }
-        } else {
-            HIPCHK(c, launch_fcseg_f32_small(ps, s));
-        }
-        c->stat_gemm_launches++; c->stat_launches++;
-        c->stat_gemm_flops += flops;
-        return PNN_OK;
+        return timed_launch(c, 6, flops, profile, [&] { return launch_fcseg_f32_small(ps, s); },
+                            "[pnn-prof] M=%ld K=%.0f N=%d nseg=%d f32-small-fcseg us=%.1f tflops=%.2f\n", M, L.k_total, p.Cout, L.nseg);
     }
     if (!fcseg && small_f32) {
         TapGemmParams ps = p;
@@ -164,34 +175,15 @@ int run_gemm(pnn_ctx* c, const GemmLayer& L, const float* X, float* Y, int32_t* 
         }
         if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d ncls=%d nseg=%d -> f32 small kernel (%ld tiles of 16 x 16)\n", M, L.k_total, p.Cout, p.ncls, nseg, tapgemm_f32_small_tiles(p));
         if (void* slot = diag_stamp_slot(c, "tapgemm_f32_small", tapgemm_f32_small_tiles(p), L.k_total)) ps.Xlo = slot;   // (diagnostic library, PNN_B1_STAMPS)
-        if (profile || c->opt_time_launches) {
-            pnn_ctx::LaunchRec r;
-            HIPCHK(c, hipEventCreate(&r.e0));
-            HIPCHK(c, hipEventCreate(&r.e1));
-            r.kind = 6; r.flops = flops;
-            const LaunchEvents ev{r.e0, r.e1};
-            g_launch_events = &ev;
-            const hipError_t le = launch_tapgemm_f32_small(ps, s, host_rows, (int)c->opt_f32_small_deep);
-            g_launch_events = nullptr;
-            HIPCHK(c, le);
-            if (profile) {
-                HIPCHK(c, hipEventSynchronize(r.e1));
-                float ms = 0.f;
-                HIPCHK(c, hipEventElapsedTime(&ms, r.e0, r.e1));
-                fprintf(stderr, "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d f32-small us=%.1f tflops=%.2f\n", M, L.k_total, p.Cout, p.ncls, ms * 1e3, r.flops / (ms * 1e-3) / 1e12);
-                (void)hipEventDestroy(r.e0);
-                (void)hipEventDestroy(r.e1);
-            } else {
-                c->launch_recs.push_back(r);
-            }
-        } else if (tail && tail_ran && nseg == 1 && !(chain_io & 2) && f32_small_cout1_tail_ok(ps, tail->t)) {
-            // the net's last layer as this launch's tail (SmallTail kind 2): per block, by the last of the block's tiles to arrive
-            if (debug) fprintf(stderr, "[pnn]   ... with the last transposed convolution as its tail\n");
-            HIPCHK(c, launch_tapgemm_f32_small_tail(ps, *tail, s, (int)c->opt_f32_small_deep));
-            *tail_ran = true;
-        } else {
-            HIPCHK(c, launch_tapgemm_f32_small(ps, s, host_rows, (int)c->opt_f32_small_deep));
-        }
+        // the net's last layer as this launch's tail (SmallTail kind 2): per block, by the last of the block's tiles to arrive; never timed
+        const bool with_tail = !profile && !c->opt_time_launches && tail && tail_ran && nseg == 1 && !(chain_io & 2) && f32_small_cout1_tail_ok(ps, tail->t);
+        if (with_tail && debug) fprintf(stderr, "[pnn]   ... with the last transposed convolution as its tail\n");
+        const int rc = timed_launch(c, 6, flops, profile, [&] {
+            return with_tail ? launch_tapgemm_f32_small_tail(ps, *tail, s, (int)c->opt_f32_small_deep)
+                             : launch_tapgemm_f32_small(ps, s, host_rows, (int)c->opt_f32_small_deep);
+        }, "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d f32-small us=%.1f tflops=%.2f\n", M, L.k_total, p.Cout, p.ncls);
+        if (rc) return rc;
+        if (with_tail) *tail_ran = true;
         if (nseg > 1 && !fold) {
             if (chain_io & 2) return fail(c, PNN_E_ARG, "internal: chain-order output of a layer whose K segments are reduced by a second launch");
             HIPCHK(c, launch_seg_reduce(p.Y, nseg, out_floats, p.Cout, L.d_bias, L.proto.act, Y, s));
@@ -215,8 +207,6 @@ int run_gemm(pnn_ctx* c, const GemmLayer& L, const float* X, float* Y, int32_t* 
             fprintf(stderr, "[pnn-f32s-diag] M=%ld K=%.0f N=%d ncls=%d nseg=%d: %zu WGs, loop %.0f cycles for %.0f chunks = %.0f cycles per chunk (160 = the chain), %.2f us, clock %.0f MHz; first loop start -> last loop end %.1f us\n",
                     M, L.k_total, p.Cout, p.ncls, nseg, nwg, cyc / nwg, chunks / nwg, cyc / std::max(1.0, chunks), ticks / nwg / 100.0, cyc / std::max(1.0, ticks) * 100.0, (double)(r1 - r0) / 100.0);
         }
-        c->stat_gemm_launches++; c->stat_launches++;
-        c->stat_gemm_flops += flops;
         return PNN_OK;
     }
     if (f32k) {
@@ -279,32 +269,12 @@ int run_gemm(pnn_ctx* c, const GemmLayer& L, const float* X, float* Y, int32_t* 
     if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d ncls=%d -> %s cfg %d {rt %d, nt %d, kc %d}%s%s\n", M, L.k_total, p.Cout, p.ncls,
                        f32k ? "f32" : "legacy", cfg, t.rt, t.nt, t.kc, next ? " + fused output layer" : "",
                        nseg > 1 ? (seq ? ", K segments in sequence" : ", K segments in parallel + reduce") : "");
-    if (profile || c->opt_time_launches) {
-        pnn_ctx::LaunchRec r;
-        HIPCHK(c, hipEventCreate(&r.e0));
-        HIPCHK(c, hipEventCreate(&r.e1));
-        r.kind = 0;
-        r.flops = flops;
-        const LaunchEvents ev{r.e0, r.e1};            // recorded by the launch itself: the kernel's own begin -> end
-        g_launch_events = &ev;
-        const hipError_t le = launch(cfg);
-        g_launch_events = nullptr;
-        HIPCHK(c, le);
-        if (profile) {
-            HIPCHK(c, hipEventSynchronize(r.e1));
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, r.e0, r.e1));
-            fprintf(stderr, "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d %s cfg=%d rt=%d nt=%d kc=%d mf=%d us=%.1f tflops=%.1f\n", M, L.k_total,
-                    p.Cout, p.ncls, f32k ? "f32" : "legacy", cfg, t.rt, t.nt, t.kc, t.mf, ms * 1e3, r.flops / (ms * 1e-3) / 1e12);
-            (void)hipEventDestroy(r.e0);
-            (void)hipEventDestroy(r.e1);
-        } else {
-            c->launch_recs.push_back(r);
-        }
-    } else {
-        HIPCHK(c, launch(cfg));
-    }
+    const int trc = timed_launch(c, 0, flops, profile, [&] { return launch(cfg); },
+                                 "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d %s cfg=%d rt=%d nt=%d kc=%d mf=%d us=%.1f tflops=%.1f\n", M, L.k_total,
+                                 p.Cout, p.ncls, f32k ? "f32" : "legacy", cfg, t.rt, t.nt, t.kc, t.mf);
+    if (trc) return trc;
     if (nseg > 1 && !seq) c->stat_launches++;          // the reduction of the parallel form (launched by `launch`)
+    c->stat_gemm_flops_skipped += flops * (1.0 - g_last_issued_frac);
     static const bool diag = getenv("PNN_F32_DIAG") != nullptr;     // diagnostic library only (make diag): per-workgroup cycle stamps
     if (diag && f32k) {
         HIPCHK(c, hipStreamSynchronize(s));
@@ -334,9 +304,6 @@ int run_gemm(pnn_ctx* c, const GemmLayer& L, const float* X, float* Y, int32_t* 
                 sum[0] / nwg, sum[1] / nwg, chunks * 8 * t.rt * t.nt * 64, chunks * 8 * t.rt * t.nt * 64 / (sum[1] / nwg), sum[2] / nwg, rt_ticks / 100.0, (double)life_max / 100.0,
                 cyc / (rt_ticks / 100.0), (double)(r1 - r0) / 100.0, late);
     }
-    c->stat_gemm_launches++; c->stat_launches++;
-    c->stat_gemm_flops += flops;
-    c->stat_gemm_flops_skipped += flops * (1.0 - g_last_issued_frac);
     return PNN_OK;
 }
 
@@ -391,23 +358,9 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
         static const bool dbg = getenv("PNN_DEBUG") != nullptr;
         if (dbg) fprintf(stderr, "[pnn] sp-gemm M=%ld K=%.0f N=%d ncls=%d -> small kernel (%ld tiles%s%s)\n", M, L.k_total, p.Cout, p.ncls,
                          tapgemm_small_tiles(p), x_is_f32 ? ", f32 input" : "", seg_chunks ? ", K segments" : "");
-        const double flops = 2.0 * (double)M * L.k_total * p.Cout;
-        if (c->opt_time_launches) {
-            pnn_ctx::LaunchRec r;
-            HIPCHK(c, hipEventCreate(&r.e0));
-            HIPCHK(c, hipEventCreate(&r.e1));
-            r.kind = 5; r.flops = flops;
-            const LaunchEvents ev{r.e0, r.e1};
-            g_launch_events = &ev;
-            const hipError_t le = launch_tapgemm_small(p, x_is_f32, seg_chunks, s, x_is_f32 ? c->host_input : nullptr);
-            g_launch_events = nullptr;
-            HIPCHK(c, le);
-            c->launch_recs.push_back(r);
-        } else {
-            HIPCHK(c, launch_tapgemm_small(p, x_is_f32, seg_chunks, s, x_is_f32 ? c->host_input : nullptr));
-        }
-        c->stat_gemm_launches++; c->stat_launches++;
-        c->stat_gemm_flops += flops;
+        const int trc = timed_launch(c, 5, 2.0 * (double)M * L.k_total * p.Cout, false,
+                                     [&] { return launch_tapgemm_small(p, x_is_f32, seg_chunks, s, x_is_f32 ? c->host_input : nullptr); });
+        if (trc) return trc;
         if (tiles_out) *tiles_out = seg_chunks > 0 ? (int)(((long)(L.k_total / 16.0) + seg_chunks - 1) / seg_chunks) : 0;
         if (lastp) { HIPCHK(c, launch_tconv_cout1(*lastp, s)); c->stat_launches++; }
         return PNN_OK;
@@ -539,31 +492,14 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
     const TileCfg t = cfg_of(cfg);
     if (debug) fprintf(stderr, "[pnn] sp-gemm M=%ld K=%.0f N=%d ncls=%d -> cfg %d %s{rt %d, nt %d, kc %d, wm %d, d %d}\n", M, L.k_total, p.Cout, p.ncls,
                        cfg, kind_of(cfg), t.rt, t.nt, t.kc, t.wm, t.d);
-    if (profile || c->opt_time_launches) {
-        pnn_ctx::LaunchRec r;
-        HIPCHK(c, hipEventCreate(&r.e0));
-        HIPCHK(c, hipEventCreate(&r.e1));
-        r.kind = cfg < nsp ? 2 : cfg < nsp + nci ? 3 : 4;
-        r.flops = 2.0 * (double)M * L.k_total * p.Cout + (next ? 2.0 * (double)M * next->k_total * next->proto.Cout : 0.0);
-        const LaunchEvents ev{r.e0, r.e1};            // recorded by the launch itself: the kernel's own begin -> end
-        g_launch_events = &ev;
-        const hipError_t le = launch(cfg);
-        g_launch_events = nullptr;
-        HIPCHK(c, le);
-        if (profile) {
-            HIPCHK(c, hipEventSynchronize(r.e1));
-            float ms = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms, r.e0, r.e1));
-            fprintf(stderr, "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d cfg=%d rt=%d nt=%d kc=%d mf=%d us=%.1f tflops=%.1f\n", M, L.k_total,
-                    p.Cout, p.ncls, cfg, t.rt, t.nt, t.kc, t.mf, ms * 1e3, r.flops / (ms * 1e-3) / 1e12);
-            (void)hipEventDestroy(r.e0);
-            (void)hipEventDestroy(r.e1);
-        } else {
-            c->launch_recs.push_back(r);
-        }
-    } else {
-        HIPCHK(c, launch(cfg));
-    }
+    const double flops = 2.0 * (double)M * L.k_total * p.Cout;
+    const int lrc = timed_launch(c, cfg < nsp ? 2 : cfg < nsp + nci ? 3 : 4,
+                                 flops + (next ? 2.0 * (double)M * next->k_total * next->proto.Cout : 0.0), profile, [&] { return launch(cfg); },
+                                 "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d cfg=%d rt=%d nt=%d kc=%d mf=%d us=%.1f tflops=%.1f\n", M, L.k_total,
+                                 p.Cout, p.ncls, cfg, t.rt, t.nt, t.kc, t.mf);
+    if (lrc) return lrc;
+    if (lastp && !fused_last) c->stat_launches++;    // the net's last layer went out as a launch of its own
+    if (cfg >= nsp + nci) c->stat_gemm_flops_skipped += flops * (1.0 - g_last_issued_frac);   // (ring launches may skip padding taps)
     if (diag) {
         HIPCHK(c, hipStreamSynchronize(s));
         const TileCfg tt = tapgemm_sp_cfg(cfg);   // (diag runs never take the convimg kernel)
@@ -577,14 +513,7 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
         fprintf(stderr, "[pnn-diag] M=%ld K=%.0f N=%d cfg {%d,%d,%d,wm%d}: per stage (cycles, wave 0 mean over %zu WGs): issue %.0f  mfma %.0f  store %.0f  barrier %.0f\n",
                 M, L.k_total, p.Cout, tt.rt, tt.nt, tt.kc, tt.wm, nwg, sum[0] / nwg / stages, sum[1] / nwg / stages, sum[2] / nwg / stages, sum[3] / nwg / stages);
     }
-    c->stat_gemm_launches++; c->stat_launches++;
-    if (lastp && !fused_last) c->stat_launches++;    // the net's last layer went out as a launch of its own
-    c->stat_gemm_flops += 2.0 * (double)M * L.k_total * p.Cout;
-    if (cfg >= nsp + nci) c->stat_gemm_flops_skipped += 2.0 * (double)M * L.k_total * p.Cout * (1.0 - g_last_issued_frac);   // (ring launches may skip padding taps)
-    if (next) {
-        c->stat_gemm_flops += 2.0 * (double)M * next->k_total * next->proto.Cout;
-        if (tiles_out) *tiles_out = (int)((p.Cout + 32L * t.nt * (4 / t.wm) - 1) / (32L * t.nt * (4 / t.wm)));
-    }
+    if (next && tiles_out) *tiles_out = (int)((p.Cout + 32L * t.nt * (4 / t.wm) - 1) / (32L * t.nt * (4 / t.wm)));
     return PNN_OK;
 }
 
@@ -683,31 +612,6 @@ int fc_pass(pnn_ctx* c, Model* m, const float* d_ctx, bool ctx_is_split, long nb
                 if ((rc = run_gemm_sp(c, m->fc[2], P1, nullptr, nullptr, nullptr, nullptr, nullptr, nb, s, &m->fc[3], part, &tiles))) return rc;
             } else {
                 if ((rc = run_gemm_sp(c, m->fc[2], P1, nullptr, nullptr, P0, nullptr, nullptr, nb, s))) return rc;
-                // small passes: K segments and their reduction in ONE launch (fc_out_small_kernel; the same bits as the small
-                // kernel's K-segment mode + fuse_reduce_kernel, two launch floors of ~4 us less per single-block call)
-                TapGemmParams q = m->fc[3].proto;
-                q.X = P0; q.Wp = m->fc[3].d_w_sp; q.bias = m->fc[3].d_bias; q.out_scale = m->fc[3].sp_inv_scale; q.mean = c->mean;
-                q.Y = d_out; q.Yi = d_dst; q.M = (int)nb;
-                if (c->opt_fc_out && c->opt_small && c->opt_sp_cfg < 0 && nb <= 2048 && fc_out_small_fits(q, kFuseSegChunks)) {
-                    const double flops = 2.0 * (double)nb * m->fc[3].k_total * q.Cout;
-                    if (c->opt_time_launches) {
-                        pnn_ctx::LaunchRec r;
-                        HIPCHK(c, hipEventCreate(&r.e0));
-                        HIPCHK(c, hipEventCreate(&r.e1));
-                        r.kind = 5; r.flops = flops;
-                        const LaunchEvents ev{r.e0, r.e1};
-                        g_launch_events = &ev;
-                        const hipError_t le = launch_fc_out_small(q, kFuseSegChunks, s, take_done_signal(c));
-                        g_launch_events = nullptr;
-                        HIPCHK(c, le);
-                        c->launch_recs.push_back(r);
-                    } else {
-                        HIPCHK(c, launch_fc_out_small(q, kFuseSegChunks, s, take_done_signal(c)));
-                    }
-                    c->stat_gemm_launches++; c->stat_launches++;
-                    c->stat_gemm_flops += flops;
-                    return PNN_OK;
-                }
                 if ((rc = run_gemm_sp(c, m->fc[3], P0, nullptr, nullptr, nullptr, nullptr, nullptr, nb, s, nullptr, part, &tiles, nullptr, false, kFuseSegChunks))) return rc;
             }
             if (tiles <= 0 || tiles > 20) return fail(c, PNN_E_ARG, "output layer: %d K segments do not fit the partial buffer", tiles);
@@ -743,15 +647,15 @@ int fc_pass(pnn_ctx* c, Model* m, const float* d_ctx, bool ctx_is_split, long nb
             if ((rc = run_gemm(c, m->fc[2], P1, P0, nullptr, nb, s, nullptr, nullptr, nullptr, nullptr, chain ? 1 : 0))) return rc;
             TapGemmParams q = m->fc[3].proto;
             q.X = P0; q.Wp = m->fc[3].d_w; q.part = part; q.M = (int)nb; q.x_bytes = (unsigned)(4.0 * (double)nb * q.Cin);
-            // small passes: the K segments and their reduction in ONE launch (fc_out_f32_small_kernel: the same bits, one launch less
+            // small passes: the K segments and their reduction in ONE launch (fc_out_f32_chain_kernel: the same bits, one launch less
             // in the chain of a single-block call)
             if (c->opt_fc_out_f32 && nb <= 512 && !c->opt_time_launches) {
                 TapGemmParams r = q;
                 r.part = nullptr; r.bias = m->fc[3].d_bias; r.mean = c->mean; r.Y = d_out; r.Yi = d_dst;
                 if (fc_out_f32_small_fits(r)) {
-                    if (void* slot = diag_stamp_slot(c, c->opt_fc_out_f32 == 2 ? "fc_out_f32_small (32x32x2)" : "fc_out_f32_chain", (long)((nb + 15) / 16) * ((n_out + 15) / 16), 1200.0)) r.Xlo = slot;
                     const int nwg = (int)((nb + 15) / 16) * ((n_out + 15) / 16);      // fc_out_f32_chain_kernel's workgroups: a completion flag each
-                    HIPCHK(c, launch_fc_out_f32_small(r, s, c->opt_fc_out_f32 == 2 ? take_done_signal(c) : take_done_signal_per_wg(c, nwg), c->opt_fc_out_f32 == 2));
+                    if (void* slot = diag_stamp_slot(c, "fc_out_f32_chain", nwg, 1200.0)) r.Xlo = slot;
+                    HIPCHK(c, launch_fc_out_f32_small(r, s, take_done_signal_per_wg(c, nwg)));
                     c->stat_gemm_launches++; c->stat_launches++;
                     c->stat_gemm_flops += 2.0 * (double)nb * m->fc[3].k_total * n_out;
                     return PNN_OK;

@@ -78,7 +78,8 @@ float pnn_mean(const pnn_ctx* ctx);
  *   "f32_small"            1   launches of at most "f32_small_max_tiles" (1024) output tiles of 16 x 16 -- single-block calls, the
  *                              batching service's handfuls -- run on tapgemm_f32_small_kernel (the canonical fmaf chain issued through
  *                              v_mfma_f32_16x16x4_f32, one wave per tile); 0: tapgemm_f32_kernel's 128-row tiles at every size
- *   "fc_out_f32"           1   FC passes of <= 512 blocks: output layer's K segments + their reduction in one launch
+ *   "fc_out_f32"           1   nonzero: FC passes of <= 512 blocks run the output layer's K segments + their reduction as one launch;
+ *                              0: two launches (the segments, then their reduction)
  *   "chain_io"             1   tensors between two launches of the small kernels travel with every 16-channel group in the order the 16x16x4
  *                              chain consumes it (one 16-byte LDS-DMA instruction per chunk of activations instead of four 4-byte ones); 0: never
  *   "tails"                1   small exact-f32 conv passes: the merger runs inside the branches' last pair launch (per block and channel group, by the
@@ -94,7 +95,6 @@ float pnn_mean(const pnn_ctx* ctx);
  *   "sp_cfg"              -1   >= 0: force configuration code [0, pnn_num_split_configs()) of the three split-GEMM kernel families
  *   "ring" / "convimg"     1   the LDS-DMA ring kernel / the LDS-resident-image convolution kernel may be chosen
  *   "small"                1   GEMMs of at most "small_max_tiles" (512) tiles of 32 x 32 run on tapgemm_small_kernel (one wave per tile)
- *   "fc_out"               0   1: small FC passes run output-layer segments + reduction as one launch (measured no faster)
  *   "fuse_first"           1   the image kernel computes a branch's first (one-input-channel) convolution itself
  *   "fuse_tail"            1   the image kernel of the last 64-channel layer applies the net's last layer to its output tile
  *   "ring_pm"              1   position-major tiles (skip the taps that only meet SAME padding) where the launch model expects a gain;
@@ -112,7 +112,7 @@ float pnn_mean(const pnn_ctx* ctx);
  *   "cache_mb"             0   > 0: single-block host calls are answered from a direct-mapped cache of that many MiB when the same input
  *                              bytes were predicted before (HM's RD search repeats itself); dropped on any option / model change
  *   "flag_wait"            1   a small host call ends when its LAST kernel raises a sequence number in pinned host memory (3-7 us earlier
- *                              than the runtime's completion signal); "spin_wait" (0): hipStreamQuery polling instead of hipStreamSynchronize
+ *                              than the runtime's completion signal)
  *   "stream_priority"      0   < 0 / > 0: the context's own stream (host entry points) at the device's greatest / least priority
  *   "stream"               -   a hipStream_t (cast to long): the context's host entry points run on the caller's stream from now on
  *   "wait_sleep"           0   1: the thread of a small host call sleeps through the predictable part of its wait (running mean per batch
@@ -135,12 +135,13 @@ float pnn_mean(const pnn_ctx* ctx);
  *   "max_chunk" 0 (blocks per pass, 0 = by workspace), "ws_cap_mb" 8192, "time_launches" 0 (HIP events around every tap-GEMM launch)
  */
 int pnn_set_option(pnn_ctx* ctx, const char* name, long value);
-/* Environment variables read at pnn_create* (same meaning as the options): PNN_PRECISION, PNN_GRAPHS, PNN_AUTOTUNE, PNN_RING, PNN_CONVIMG,
- * PNN_SMALL, PNN_F32_SMALL, PNN_F32_SMALL_TILES, PNN_CACHE_MB, PNN_FC_OUT, PNN_SPIN_WAIT, PNN_FLAG_WAIT, PNN_FUSE_FIRST, PNN_FUSE_GATHER,
- * PNN_FUSE_TAIL, PNN_FUSE_LAST, PNN_RING_PM, PNN_BRANCH_STREAMS, PNN_MAX_CHUNK, PNN_F32_CFG, PNN_F32_OVERLAP, PNN_F32_SEG_MODE,
- * PNN_F32_PERSIST.  Diagnostics: PNN_DEBUG (kernel choice of every GEMM launch on stderr), PNN_DEBUG_TUNE, PNN_PROFILE (synchronous
- * per-launch timing), PNN_HOST_TRACE, PNN_LIB_PATH (Python loader: another build of the library); diagnostic library of `make diag`
- * only: PNN_SP_DIAG, PNN_F32_DIAG, PNN_F32S_DIAG. */
+/* Environment variables read at pnn_create* (same meaning as the options; PNN_F32_SMALL_TILES is "f32_small_max_tiles"): PNN_PRECISION,
+ * PNN_GRAPHS, PNN_AUTOTUNE, PNN_RING, PNN_CONVIMG, PNN_SMALL, PNN_F32_SMALL, PNN_F32_SMALL_TILES, PNN_F32_SMALL_DEEP, PNN_CHAIN_IO,
+ * PNN_TAILS, PNN_CACHE_MB, PNN_FLAG_WAIT, PNN_WAIT_SLEEP, PNN_FUSE_FIRST, PNN_FUSE_GATHER, PNN_FUSE_TAIL, PNN_FUSE_LAST, PNN_RING_PM,
+ * PNN_BRANCH_STREAMS, PNN_MAX_CHUNK, PNN_F32_CFG, PNN_F32_OVERLAP, PNN_F32_SEG_MODE, PNN_F32_PERSIST.
+ * Diagnostics: PNN_DEBUG (kernel choice of every GEMM launch on stderr), PNN_DEBUG_TUNE, PNN_PROFILE (synchronous per-launch timing),
+ * PNN_HOST_TRACE, PNN_LIB_PATH (Python loader: another build of the library); diagnostic library of `make diag` only: PNN_SP_DIAG,
+ * PNN_F32_DIAG, PNN_F32S_DIAG. */
 /* Input-range contract of "precision" 1: operands travel as pairs of f16 values, so every intermediate activation must satisfy
  * |v| < 65504.  8-bit contexts through trained models stay two orders of magnitude below that; arbitrary float inputs or
  * models may not.  The kernels detect a violation (never a silent NaN): host entry points then recompute, on the exact-f32 kernels,

@@ -111,7 +111,7 @@ def test_every_batch_size_matches_the_order_model(pnn, oracle, is_fc, w):
 
 
 # (option, values in the order they are set; the last one is the default)
-OPTIONS = [("f32_small", (0, 1)), ("seg_fold", (0, 1)), ("tails", (0, 1)), ("chain_io", (0, 1)), ("fc_out_f32", (0, 2, 1)),
+OPTIONS = [("f32_small", (0, 1)), ("seg_fold", (0, 1)), ("tails", (0, 1)), ("chain_io", (0, 1)), ("fc_out_f32", (0, 1)),
            ("fuse_last", (0, 1)), ("pair", (0, 1)), ("f32_small_deep", (0, 2, 1))]
 
 

@@ -72,15 +72,28 @@ def test_device_code_has_no_packed_fp32_instructions(tmp_path):
         assert any(k.startswith(family) for k in kernels_seen), "no device code for %s in %s" % (family, _lib.LIB_PATH)
 
 
-def test_every_option_is_documented_in_the_header():
-    """pnn_set_option's names (csrc/pnn_abi.cpp) and the option list in include/pnn_hip.h must not drift apart."""
+def test_option_table_matches_the_header():
+    """pnn_set_option's option table (kOptions, csrc/pnn_abi.cpp) and the option list in include/pnn_hip.h must not drift apart:
+    every option name and environment variable of the table is documented there, and every one documented there is in the table."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, "context_adaptive_neural_network_based_prediction_amd", "csrc", "pnn_abi.cpp")).read()
     hdr = open(os.path.join(root, "include", "pnn_hip.h")).read()
-    names = sorted(set(re.findall(r'strcmp\(name, "([a-z_0-9]+)"\)', src)))
-    assert len(names) >= 14, names
-    missing = [n for n in names if '"%s"' % n not in hdr]
+    table = re.search(r"const OptionRow kOptions\[\] = \{(.*?)\n\};", src, re.S).group(1)
+    rows = re.findall(r'\{"([a-z_0-9]+)",\s*(?:&pnn_ctx::\w+|nullptr),\s*(?:"(PNN_[A-Z0-9_]+)"|nullptr),', table)
+    assert len(rows) == len(re.findall(r"^\s*\{", table, re.M)), "a table row the pattern does not read"
+    names = {n for n, _ in rows}
+    envs = {e for _, e in rows if e}
+    assert len(names) == len(rows) and len(names) >= 30 and len(envs) >= 20, (sorted(names), sorted(envs))
+    missing = sorted(n for n in names if '"%s"' % n not in hdr) + sorted(e for e in envs if not re.search(r"\b%s\b" % e, hdr))
     assert not missing, "options without documentation in pnn_hip.h: %s" % missing
+    # ... and the other way round: the option list in front of pnn_set_option and the environment variables read at pnn_create*
+    doc = hdr[hdr.index("/* Options (name, default, meaning)"):hdr.index("int pnn_set_option(")]
+    env_doc = hdr[hdr.index("/* Environment variables read at pnn_create*"):hdr.index("Diagnostics:")]
+    documented = set(re.findall(r'"([a-z_0-9]+)"', doc + env_doc))
+    documented_env = set(re.findall(r"\bPNN_[A-Z0-9_]+\b", env_doc))
+    assert documented_env and documented, "the option lists of pnn_hip.h moved"
+    unknown = sorted(documented - names) + sorted(documented_env - envs)
+    assert not unknown, "pnn_hip.h documents options the library does not have: %s" % unknown
 
 
 def test_service_header_symbols_exported():
