@@ -72,6 +72,8 @@ SIGNATURES = {
     "pnn_predict_tbs_device": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, vp]),
     "pnn_block_cost_device": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp]),
     "pnn_predict_tbs_cost_device": (ci, [vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp]),
+    "pnn_hevc_intra_predict": (ci, [u8p, ci, ci, ci, ci, u8p]),
+    "pnn_hevc_best_mode_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

@@ -629,6 +629,25 @@ int pnn_block_cost_device(pnn_ctx* c, int width, const void* d_org_plane, int pe
     return PNN_OK;
 }
 
+int pnn_hevc_best_mode_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
+                              const uint8_t* d_targets, int n, uint8_t* d_best_mode, uint32_t* d_best_sse, uint8_t* d_best_pred,
+                              uint32_t* d_mode_sse, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (width_index(width) < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
+    if (pattern_h < width + 1 || pattern_h > 2 * width + 1 || pattern_w < width + 1 || pattern_w > 2 * width + 1)
+        return fail(c, PNN_E_ARG, "intra pattern %dx%d: both sides must lie in [%d, %d]", pattern_h, pattern_w, width + 1, 2 * width + 1);
+    if (n < 0 || (n > 0 && (!d_patterns || !d_targets))) return fail(c, PNN_E_ARG, "bad batch size or input buffers");
+    if (!d_best_mode && !d_best_sse && !d_best_pred && !d_mode_sse) return fail(c, PNN_E_ARG, "every output is NULL");
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HevcBestModeParams p;
+    p.patterns = d_patterns; p.ph = pattern_h; p.pw = pattern_w; p.targets = d_targets; p.N = n; p.w = width;
+    p.best_mode = d_best_mode; p.best_sse = d_best_sse; p.best_pred = d_best_pred; p.mode_sse = d_mode_sse;
+    HIPCHK(c, launch_hevc_best_mode(p, (hipStream_t)stream));
+    return PNN_OK;
+}
+
 int pnn_predict_tbs_cost_device(pnn_ctx* c, int width, const void* d_plane, const void* d_org_plane, int pel_bytes,
                                 const pnn_tb_dev* d_tbs, int n, int hadamard, uint32_t* d_cost, int32_t* d_dst, void* stream)
 {

@@ -1,0 +1,204 @@
+// HEVC best-intra-mode search for the evaluator's competitor (comparing_pnn_ipfcns_hevc_best_mode.py:162-322 via
+// hevc/intraprediction/intraprediction.py:231-294): for each of N blocks, all 35 luma predictions of HM's xPredIntraPlanar /
+// DC / xPredIntraAng from the block's intra pattern (no reference smoothing: the reference did not extract it), the SSE of
+// each against the target, and the mode of smallest SSE (lowest index among ties -- the reference keeps a mode only when its
+// PSNR, strictly decreasing in the SSE, is strictly larger).  Integer VALU arithmetic only; bit-exact against the host twin
+// (pnn_hevc_intra.cpp), which builds refMain the way HM does.
+//
+// Layout.  A workgroup of 7 waves takes G blocks and stages their 4w+1 reference samples (padded as the reference pads them)
+// and targets in LDS.  Its 35 * 64 tasks are (mode, block, row group): each wave runs one mode at a time (5 rounds), so the
+// mode -- planar, DC or one angle -- is wave-uniform and nothing diverges.  A lane covers R rows of one block in the mode's own
+// orientation (v along the side reference, u along the main one); w <= 8: the whole block (R = w, no reduction), w >= 16: R = 4
+// rows, partial SSEs added with LDS integer atomics (exact in any order).  The angular prediction is the closed form of
+// refMain: index k >= 0 reads the main reference, k < 0 the side one at (128 - k * invAngle) >> 8, as HM's projection loop fills it.
+// Then one lane per block picks the best mode and the workgroup recomputes that mode's prediction only if it is asked for.
+#include "pnn_kernels.h"
+
+namespace pnn {
+namespace {
+
+constexpr int kThreads = 448;                     // 7 waves: 35 modes in 5 rounds
+constexpr int kRounds = 35 / (kThreads / 64);
+
+__device__ inline int intra_angle(int mode)       // angTable with its sign, modes 2..34
+{
+    const int rel = mode >= 18 ? mode - 26 : 10 - mode, a = rel < 0 ? -rel : rel;
+    const int t = a == 0 ? 0 : a == 1 ? 2 : a == 2 ? 5 : a == 3 ? 9 : a == 4 ? 13 : a == 5 ? 17 : a == 6 ? 21 : a == 7 ? 26 : 32;
+    return rel < 0 ? -t : t;
+}
+
+__device__ inline int intra_inv_angle(int ang)     // invAngTable for a negative angle
+{
+    const int a = -ang;
+    return a == 2 ? 4096 : a == 5 ? 1638 : a == 9 ? 910 : a == 13 ? 630 : a == 17 ? 482 : a == 21 ? 390 : a == 26 ? 315 : 256;
+}
+
+// refMain[k] in the orientation S (+1: vertical modes, main = above; -1: horizontal, main = left); rf[j], j in [-2w, 2w], holds
+// left[-j - 1] for j < 0, the corner at 0 and above[j - 1] for j > 0.  k <= 2w + 1 (the +1 only where its weight is zero).
+template <int W, int S>
+__device__ inline int ref_main(const int* rf, int k, int inv)
+{
+    const int idx = k >= 0 ? min(k, 2 * W) : -((128 - k * inv) >> 8);
+    return rf[S * idx];
+}
+
+template <int W, int S>
+__device__ inline int angular_pixel(const int* rf, int ang, int inv, int v, int u)
+{
+    const int pos = (v + 1) * ang, f = pos & 31, k = u + (pos >> 5) + 1;
+    const int a = ref_main<W, S>(rf, k, inv);
+    int p = ((32 - f) * a + f * ref_main<W, S>(rf, k + 1, inv) + 16) >> 5;
+    if (W <= 16 && ang == 0 && u == 0) p = min(max(a + ((rf[-S * (v + 1)] - rf[0]) >> 1), 0), 255);
+    return p;
+}
+
+template <int W>
+__device__ inline int planar_pixel(const int* rf, int y, int x)
+{
+    constexpr int shift = W == 4 ? 2 : W == 8 ? 3 : W == 16 ? 4 : W == 32 ? 5 : 6;
+    return ((W - 1 - x) * rf[-1 - y] + (x + 1) * rf[1 + W] + (W - 1 - y) * rf[1 + x] + (y + 1) * rf[-1 - W] + W) >> (shift + 1);
+}
+
+template <int W>
+__device__ inline int dc_pixel(const int* rf, int dc, int y, int x)
+{
+    if (W > 16 || (x > 0 && y > 0)) return dc;
+    if (x == 0 && y == 0) return (rf[1] + rf[-1] + 2 * dc + 2) >> 2;
+    return ((y == 0 ? rf[1 + x] : rf[-1 - y]) + 3 * dc + 2) >> 2;
+}
+
+template <int W>
+__device__ inline int mode_pixel(const int* rf, int dc, int mode, int y, int x)
+{
+    if (mode == 0) return planar_pixel<W>(rf, y, x);
+    if (mode == 1) return dc_pixel<W>(rf, dc, y, x);
+    const int ang = intra_angle(mode), inv = ang < 0 ? intra_inv_angle(ang) : 0;
+    return mode >= 18 ? angular_pixel<W, 1>(rf, ang, inv, y, x) : angular_pixel<W, -1>(rf, ang, inv, x, y);
+}
+
+// SSE of rows v = rg, rg + RG, ... (R of them) of an angular mode in its own orientation; target element (y, x) at tg[y * W + x]
+template <int W, int R, int RG, int S>
+__device__ inline unsigned angular_rows_sse(const int* rf, const uint8_t* tg, int ang, int inv, int rg)
+{
+    unsigned acc = 0;
+#pragma unroll 1
+    for (int r = 0; r < R; r++) {
+        const int v = rg + RG * r;
+        const int pos = (v + 1) * ang, f = pos & 31;
+        int k = (pos >> 5) + 1;
+        int a = ref_main<W, S>(rf, k, inv);
+#pragma unroll 8
+        for (int u = 0; u < W; u++, k++) {
+            const int b = ref_main<W, S>(rf, k + 1, inv);
+            int p = ((32 - f) * a + f * b + 16) >> 5;
+            if (W <= 16 && u == 0 && ang == 0) p = min(max(a + ((rf[-S * (v + 1)] - rf[0]) >> 1), 0), 255);
+            const int d = p - (int)tg[S > 0 ? v * W + u : u * W + v];
+            acc += (unsigned)(d * d);
+            a = b;
+        }
+    }
+    return acc;
+}
+
+template <int W>
+__global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBestModeParams p)
+{
+    constexpr int R = W <= 8 ? W : 4, RG = W / R, G = 64 / RG;    // rows per lane, lanes per block, blocks per workgroup
+    constexpr int RS = 4 * W + 1, TS = W * W + 4;                 // LDS strides (odd in dwords: lanes of different blocks spread over banks)
+    __shared__ int ref[G * RS];
+    __shared__ uint8_t tgt[G * TS];
+    __shared__ unsigned sse[G * 35];
+    __shared__ int dcv[G], best[G];
+    const int tid = threadIdx.x;
+    const long blk0 = (long)blockIdx.x * G;
+
+    for (int i = tid; i < G * RS; i += kThreads) {
+        const int g = i / RS, j = i % RS - 2 * W;
+        int v = 0;
+        if (blk0 + g < p.N) {
+            const uint8_t* pat = p.patterns + (size_t)(blk0 + g) * p.ph * p.pw;
+            v = j >= 0 ? pat[min(j, p.pw - 1)] : pat[min(-j, p.ph - 1) * p.pw];
+        }
+        ref[i] = v;
+    }
+    for (int i = tid; i < G * W * W; i += kThreads) {
+        const int g = i / (W * W), e = i % (W * W);
+        tgt[g * TS + e] = blk0 + g < p.N ? p.targets[(size_t)(blk0 + g) * W * W + e] : 0;
+    }
+    for (int i = tid; i < G * 35; i += kThreads) sse[i] = 0;
+    __syncthreads();
+    if (tid < G) {
+        const int* rf = ref + tid * RS + 2 * W;
+        int sum = 0;
+        for (int i = 1; i <= W; i++) sum += rf[i] + rf[-i];
+        dcv[tid] = (sum + W) / (2 * W);
+    }
+    __syncthreads();
+
+    const int lane = tid & 63, g = lane / RG, rg = lane % RG;
+    const int* rf = ref + g * RS + 2 * W;
+    const uint8_t* tg = tgt + g * TS;
+    for (int round = 0; round < kRounds; round++) {
+        const int mode = __builtin_amdgcn_readfirstlane(round * (kThreads / 64) + tid / 64);
+        unsigned acc = 0;
+        if (mode <= 1) {
+            const int dc = dcv[g];
+#pragma unroll 1
+            for (int r = 0; r < R; r++) {
+                const int y = rg + RG * r;
+#pragma unroll 8
+                for (int x = 0; x < W; x++) {
+                    const int d = (mode == 0 ? planar_pixel<W>(rf, y, x) : dc_pixel<W>(rf, dc, y, x)) - (int)tg[y * W + x];
+                    acc += (unsigned)(d * d);
+                }
+            }
+        } else {
+            const int ang = intra_angle(mode), inv = ang < 0 ? intra_inv_angle(ang) : 0;
+            acc = mode >= 18 ? angular_rows_sse<W, R, RG, 1>(rf, tg, ang, inv, rg) : angular_rows_sse<W, R, RG, -1>(rf, tg, ang, inv, rg);
+        }
+        if (RG == 1) sse[g * 35 + mode] = acc;
+        else atomicAdd(&sse[g * 35 + mode], acc);
+    }
+    __syncthreads();
+
+    if (tid < G && blk0 + tid < p.N) {
+        const unsigned* s = sse + tid * 35;
+        int m = 0;
+        for (int i = 1; i < 35; i++) m = s[i] < s[m] ? i : m;
+        if (p.best_mode) p.best_mode[blk0 + tid] = (uint8_t)m;
+        if (p.best_sse) p.best_sse[blk0 + tid] = s[m];
+        best[tid] = s[m] == 65025u * W * W ? -1 : m;   // no mode beats the reference's 0 dB start: index 0, all-zero prediction
+    }
+    if (p.mode_sse)
+        for (int i = tid; i < G * 35; i += kThreads)
+            if (blk0 + i / 35 < p.N) p.mode_sse[blk0 * 35 + i] = sse[i];
+    if (!p.best_pred) return;
+    __syncthreads();
+    for (int i = tid; i < G * W * W; i += kThreads) {
+        const int gg = i / (W * W), e = i % (W * W);
+        if (blk0 + gg >= p.N) break;
+        const int m = best[gg];
+        const int v = m < 0 ? 0 : mode_pixel<W>(ref + gg * RS + 2 * W, dcv[gg], m, e / W, e % W);
+        p.best_pred[blk0 * W * W + i] = (uint8_t)v;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    const int rows_per_lane = p.w <= 8 ? p.w : 4, blocks_per_wg = 64 / (p.w / rows_per_lane);
+    const dim3 grid((unsigned)((p.N + blocks_per_wg - 1) / blocks_per_wg)), block(kThreads);
+    switch (p.w) {
+    case 4: hipLaunchKernelGGL(hevc_best_mode_kernel<4>, grid, block, 0, s, p); break;
+    case 8: hipLaunchKernelGGL(hevc_best_mode_kernel<8>, grid, block, 0, s, p); break;
+    case 16: hipLaunchKernelGGL(hevc_best_mode_kernel<16>, grid, block, 0, s, p); break;
+    case 32: hipLaunchKernelGGL(hevc_best_mode_kernel<32>, grid, block, 0, s, p); break;
+    case 64: hipLaunchKernelGGL(hevc_best_mode_kernel<64>, grid, block, 0, s, p); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace pnn

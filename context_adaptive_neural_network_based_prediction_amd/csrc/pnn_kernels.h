@@ -256,6 +256,14 @@ struct BlockCostParams {
 };
 hipError_t launch_block_cost(const BlockCostParams& p, hipStream_t s);
 
+// HEVC best intra mode (pnn_hevc_intra.hip): N intra patterns [N][ph][pw] (first row and column used) and targets [N][w][w], all uint8;
+// any of the four outputs may be NULL.
+struct HevcBestModeParams {
+    const uint8_t* patterns; int ph; int pw; const uint8_t* targets; int N; int w;
+    uint8_t* best_mode; uint32_t* best_sse; uint8_t* best_pred; uint32_t* mode_sse;
+};
+hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s);
+
 // Stand-alone HM epilogue for float predictions.
 hipError_t launch_epilogue(const float* pred, long n, float mean, int32_t* dst, hipStream_t s);
 

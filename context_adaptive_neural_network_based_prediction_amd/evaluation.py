@@ -1,11 +1,13 @@
 """Python-side evaluation of PNN predictions on images, mirroring the PNN half of the reference's
 comparing_pnn_ipfcns_hevc_best_mode.py:162-322 (`predict_mask`) without TensorFlow: contexts by the GPU gather
 (context.py), predictions by libpnn_hip.so (predict_by_batch_via_pnn), then the reference's own uint8 cast and
-PSNR definitions.  The HEVC-best-mode competitor (Cython, hevc/intraprediction) is out of scope.
+PSNR definitions.  predict_mask_vs_hevc_best_mode adds the paper's competitor, the best HEVC intra mode per block
+(intraprediction.py: all 35 modes, their SSEs and the winner of every block in one GPU launch), and the reference's
+dictionary_performance (indices and PSNRs of the best mode, PNN PSNRs, PNN's win frequency, its mean PSNR).
 """
 import numpy as np
 
-from . import context
+from . import context, intraprediction
 from .prediction_neural_network import predict_by_batch_via_pnn
 
 
@@ -48,3 +50,37 @@ def predict_mask(channels_uint8, width_target, row_1sts, col_1sts, predictor, ba
     psnrs = np.array([compute_psnr(targets_uint8[i], predictions_uint8[i]) for i in range(n)])
     return {'predictions_pnn_uint8': predictions_uint8, 'targets_uint8': targets_uint8, 'psnrs_pnn': psnrs,
             'mean_psnr_pnn': float(np.mean(psnrs))}
+
+
+def compute_performance_neural_network_vs_hevc_best_mode(targets_uint8, predictions_nn_uint8, psnrs_hevc_best_mode):
+    """comparing_pnn_ipfcns_hevc_best_mode.py:39-88: (PSNRs float64 [N] of the network's predictions, frequency with which
+    they beat the best HEVC intra mode's)."""
+    nb_targets = targets_uint8.shape[0]
+    psnrs_nn = np.zeros(nb_targets)
+    for i in range(nb_targets):
+        psnrs_nn[i] = compute_psnr(np.squeeze(targets_uint8[i, :, :, :], axis=2), np.squeeze(predictions_nn_uint8[i, :, :, :], axis=2))
+    frequency_win_nn = float(np.count_nonzero(psnrs_nn - psnrs_hevc_best_mode > 0.)) / nb_targets
+    return (psnrs_nn, frequency_win_nn)
+
+
+def predict_mask_vs_hevc_best_mode(channels_uint8, width_target, row_1sts, col_1sts, predictor, batch_size, mean_training,
+                                   tuple_width_height_masks=(0, 0)):
+    """predict_mask plus its competitor, as comparing_pnn_ipfcns_hevc_best_mode.py:162-322 scores them: the intra pattern of
+    every target (its first row and column start one pixel above-left of the target, i.e. at (row_1st + w - 1,
+    col_1st + w - 1)) predicted by the best HEVC intra mode on the GPU.
+
+    Returns the reference's dictionary_performance -- 'indices_hevc_best_mode' [N] uint8, 'psnrs_hevc_best_mode' [N],
+    'psnrs_pnn' [N], 'frequency_win_pnn', 'mean_psnr_pnn' -- plus 'predictions_pnn_uint8', 'predictions_hevc_best_mode_uint8'
+    and 'targets_uint8' ([N,w,w,1] uint8), N = images x positions, image-major."""
+    pnn = predict_mask(channels_uint8, width_target, row_1sts, col_1sts, predictor, batch_size, mean_training,
+                       tuple_width_height_masks)
+    intra_patterns_uint8 = intraprediction.extract_intra_patterns(channels_uint8, width_target, row_1sts + width_target - 1,
+                                                                  col_1sts + width_target - 1, tuple_width_height_masks)
+    indices, psnrs_hevc, predictions_hevc = intraprediction.predict_series_via_hevc_best_mode(
+        intra_patterns_uint8, pnn['targets_uint8'], device=predictor.device)
+    psnrs_pnn, frequency_win_pnn = compute_performance_neural_network_vs_hevc_best_mode(
+        pnn['targets_uint8'], pnn['predictions_pnn_uint8'], psnrs_hevc)
+    return {'indices_hevc_best_mode': indices, 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
+            'frequency_win_pnn': frequency_win_pnn, 'mean_psnr_pnn': np.mean(psnrs_pnn).item(),
+            'predictions_pnn_uint8': pnn['predictions_pnn_uint8'], 'predictions_hevc_best_mode_uint8': predictions_hevc,
+            'targets_uint8': pnn['targets_uint8']}

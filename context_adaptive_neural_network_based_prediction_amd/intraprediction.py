@@ -1,0 +1,191 @@
+"""HEVC intra prediction for the evaluator's best-mode competitor, mirroring the reference's
+hevc/intraprediction/intraprediction.py (extract_intra_pattern(s), predict_via_hevc_best_mode,
+predict_series_via_hevc_best_mode) and interface.pyx (predict_via_hevc_mode): same names, arguments, return
+dtypes and shapes, same exceptions for bad arguments.
+
+predict_via_hevc_mode is the per-block host twin (pnn_hevc_intra_predict, pure host code).  The best-mode search runs
+on the GPU (pnn_hevc_best_mode_device: all 35 modes, their SSEs and the winner of n blocks in one launch) through a
+model-less context per device; there is no CPU fallback.  PSNRs are recomputed on the host from the integer SSEs with
+the reference's float64 expression: SSE / w^2 is exactly numpy.mean of the squared differences, so they match the
+reference bit for bit.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+NB_MODES = 35
+WIDTHS = (4, 8, 16, 32, 64)
+_contexts = {}                                  # device -> model-less pnn_ctx
+
+
+def extract_intra_pattern(channel_uint8, width_target, row_ref, col_ref, tuple_width_height_masks):
+    """intraprediction.py:10-101: the (2w+1-mask_h, 2w+1-mask_w, 1) uint8 intra pattern whose first row and column hold the
+    channel's samples from (row_ref, col_ref) on; the rest is 255."""
+    if channel_uint8.dtype != np.uint8:
+        raise TypeError('`channel_uint8.dtype` is not equal to `numpy.uint8`.')
+    if channel_uint8.ndim != 3:
+        raise ValueError('`channel_uint8.ndim` is not equal to 3.')
+    _check_position(width_target, row_ref, col_ref, tuple_width_height_masks)
+    height_pattern = 2 * width_target + 1 - tuple_width_height_masks[1]
+    width_pattern = 2 * width_target + 1 - tuple_width_height_masks[0]
+    intra_pattern_uint8 = np.full((height_pattern, width_pattern, 1), 255, dtype=np.uint8)
+    intra_pattern_uint8[:, 0, :] = channel_uint8[row_ref:row_ref + height_pattern, col_ref, :]
+    intra_pattern_uint8[0, :, :] = channel_uint8[row_ref, col_ref:col_ref + width_pattern, :]
+    return intra_pattern_uint8
+
+
+def _check_position(width_target, row_ref, col_ref, tuple_width_height_masks):
+    if width_target < 0:
+        raise ValueError('`width_target` is not positive.')
+    if row_ref < 0:
+        raise ValueError('`row_ref` is not positive.')
+    if col_ref < 0:
+        raise ValueError('`col_ref` is not positive.')
+    (width_mask_above, height_mask_left) = tuple_width_height_masks
+    if width_mask_above < 0 or width_mask_above > width_target or width_mask_above % 4 != 0:
+        raise ValueError('`tuple_width_height_masks[0]` does not belong to {0, 4, ..., `width_target`}.')
+    if height_mask_left < 0 or height_mask_left > width_target or height_mask_left % 4 != 0:
+        raise ValueError('`tuple_width_height_masks[1]` does not belong to {0, 4, ..., `width_target`}.')
+
+
+def extract_intra_patterns(channels_uint8, width_target, row_refs, col_refs, tuple_width_height_masks):
+    """intraprediction.py:103-181, vectorised: [images * positions, 2w+1-mask_h, 2w+1-mask_w, 1] uint8, image-major."""
+    if not np.issubdtype(row_refs.dtype, np.integer):
+        raise TypeError('`row_refs.dtype` is not smaller than `numpy.integer` in type hierarchy.')
+    if not np.issubdtype(col_refs.dtype, np.integer):
+        raise TypeError('`col_refs.dtype` is not smaller than `numpy.integer` in type hierarchy.')
+    size_row_refs = row_refs.size
+    if col_refs.size != size_row_refs:
+        raise ValueError('`col_refs.size` is not equal to `row_refs.size`.')
+    height_pattern = 2 * width_target + 1 - tuple_width_height_masks[1]
+    width_pattern = 2 * width_target + 1 - tuple_width_height_masks[0]
+    nb_images = channels_uint8.shape[0]
+    intra_patterns_uint8 = np.zeros((nb_images * size_row_refs, height_pattern, width_pattern, 1), dtype=np.uint8)
+    if intra_patterns_uint8.shape[0] == 0:
+        return intra_patterns_uint8
+    # the reference's per-pattern checks, on the first image and the extreme positions
+    if channels_uint8.ndim < 4:
+        raise IndexError('too many indices for array')
+    if channels_uint8.dtype != np.uint8:
+        raise TypeError('`channel_uint8.dtype` is not equal to `numpy.uint8`.')
+    if channels_uint8.ndim != 4:
+        raise ValueError('`channel_uint8.ndim` is not equal to 3.')
+    rows, cols = row_refs.astype(np.int64).ravel(), col_refs.astype(np.int64).ravel()
+    _check_position(width_target, int(rows.min()), int(cols.min()), tuple_width_height_masks)
+    if channels_uint8.shape[3] != 1:
+        raise ValueError('could not broadcast: `channels_uint8.shape[3]` is not equal to 1.')
+    if rows.max() + height_pattern > channels_uint8.shape[1] or cols.max() + width_pattern > channels_uint8.shape[2]:
+        raise ValueError('could not broadcast: an intra pattern does not fit into the channel.')
+    out = np.full((nb_images, size_row_refs, height_pattern, width_pattern), 255, dtype=np.uint8)
+    out[:, :, :, 0] = channels_uint8[:, rows[:, None] + np.arange(height_pattern), cols[:, None], 0]
+    out[:, :, 0, :] = channels_uint8[:, rows[:, None], cols[:, None] + np.arange(width_pattern), 0]
+    return out.reshape(intra_patterns_uint8.shape)
+
+
+def predict_via_hevc_mode(intra_pattern_uint8, width_target, index_mode):
+    """interface.pyx:15-64: the [w, w, 1] uint8 prediction of mode `index_mode` from a [h, w', 1] intra pattern (host twin)."""
+    if not isinstance(intra_pattern_uint8, np.ndarray):
+        raise TypeError('Argument \'intra_pattern_uint8\' has incorrect type (expected numpy.ndarray)')
+    if intra_pattern_uint8.ndim != 3:
+        raise ValueError('Buffer has wrong number of dimensions (expected 3, got %d)' % intra_pattern_uint8.ndim)
+    if intra_pattern_uint8.dtype != np.uint8:
+        raise ValueError('Buffer dtype mismatch, expected \'uint8_t\' but got \'%s\'' % intra_pattern_uint8.dtype)
+    if index_mode < 0:
+        raise OverflowError('can\'t convert negative value to unsigned int')
+    if not intra_pattern_uint8.flags.c_contiguous:
+        raise ValueError('`intra_pattern_uint8` is not C-contiguous.')
+    if intra_pattern_uint8.shape[2] != 1:
+        raise ValueError('`intra_pattern_uint8.shape[2]` is not equal to 1.')
+    prediction_uint8 = np.zeros((width_target, width_target, 1), dtype=np.uint8)
+    rc = _lib.lib().pnn_hevc_intra_predict(intra_pattern_uint8.ctypes.data_as(_lib.u8p), intra_pattern_uint8.shape[0],
+                                           intra_pattern_uint8.shape[1], width_target, int(index_mode),
+                                           prediction_uint8.ctypes.data_as(_lib.u8p))
+    if rc != 0:
+        raise ValueError('hevc_intraprediction refused the arguments (pattern %dx%d, width %d, mode %d).'
+                         % (intra_pattern_uint8.shape[0], intra_pattern_uint8.shape[1], width_target, index_mode))
+    return prediction_uint8
+
+
+def psnrs_from_sses(sses, width_target):
+    """10 log10(255^2 / (SSE / w^2 + 1e-6)) in float64, tools/tools.py:364-401 term by term (SSE / w^2 == numpy.mean of the
+    squared differences, exactly)."""
+    mse_float64 = np.asarray(sses, dtype=np.uint64).astype(np.float64) / (width_target * width_target)
+    return 10. * np.log10(255. ** 2 / (mse_float64 + 1.e-6))
+
+
+def _context(device):
+    if device not in _contexts:
+        L = _lib.lib()
+        ctx = ctypes.c_void_p()
+        _lib.check(L.pnn_create_empty(ctypes.byref(ctx), ctypes.c_float(0.), device))
+        _contexts[device] = ctx
+    return _contexts[device]
+
+
+def best_modes_device(intra_patterns, targets, width_target, best_pred=True, mode_sse=False, device=0):
+    """The GPU search on torch uint8 tensors already on `device`: patterns [n, h, w'] and targets [n, w, w].
+    Returns (best index uint8 [n], best SSE int32 [n], best prediction uint8 [n, w, w] or None, SSE of every mode int32 [n, 35]
+    or None), torch tensors on `device`, after the stream has finished."""
+    import torch
+    n = targets.shape[0]
+    dev = torch.device("cuda", device)
+    index = torch.empty(n, dtype=torch.uint8, device=dev)
+    sse = torch.empty(n, dtype=torch.int32, device=dev)
+    pred = torch.empty((n, width_target, width_target), dtype=torch.uint8, device=dev) if best_pred else None
+    all_sse = torch.empty((n, NB_MODES), dtype=torch.int32, device=dev) if mode_sse else None
+    stream = torch.cuda.current_stream(dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        _lib.check(L.pnn_hevc_best_mode_device(_context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1],
+                                               intra_patterns.shape[2], targets.data_ptr(), n, index.data_ptr(), sse.data_ptr(),
+                                               pred.data_ptr() if best_pred else None,
+                                               all_sse.data_ptr() if mode_sse else None,
+                                               ctypes.c_void_p(stream.cuda_stream)), _context(device))
+    stream.synchronize()
+    return index, sse, pred, all_sse
+
+
+def predict_series_via_hevc_best_mode(intra_patterns_uint8, targets_uint8, device=0):
+    """intraprediction.py:183-229 on the GPU: (indices uint8 [N], PSNRs float64 [N], predictions uint8 [N, w, w, 1]) of the
+    best HEVC intra mode per target (smallest SSE, lowest index among ties; index 0, 0 dB and zeros when no mode beats 0 dB)."""
+    import torch
+    if targets_uint8.dtype != np.uint8:
+        raise TypeError('`array_0_uint8.dtype` is not equal to `numpy.uint8`.')
+    if targets_uint8.ndim != 4 or targets_uint8.shape[3] != 1:
+        raise ValueError('cannot select an axis to squeeze out which has size not equal to one')
+    if intra_patterns_uint8.dtype != np.uint8 or intra_patterns_uint8.ndim != 4:
+        raise ValueError('Buffer dtype mismatch or wrong number of dimensions (expected uint8, 4 dimensions)')
+    if intra_patterns_uint8.shape[3] != 1:
+        raise ValueError('`intra_pattern_uint8.shape[2]` is not equal to 1.')
+    nb_targets, width_target = targets_uint8.shape[0], targets_uint8.shape[1]
+    if targets_uint8.shape[2] != width_target or width_target not in WIDTHS:
+        raise ValueError('the target patches are not w x w with w in {4, 8, 16, 32, 64}.')
+    if intra_patterns_uint8.shape[0] < nb_targets:
+        raise IndexError('fewer intra patterns than target patches')
+    h, w = intra_patterns_uint8.shape[1:3]
+    if not (width_target < h <= 2 * width_target + 1 and width_target < w <= 2 * width_target + 1):
+        raise ValueError('The height or the width of the intra pattern does not belong to [%d, %d].'
+                         % (width_target + 1, 2 * width_target + 1))
+    if nb_targets == 0:
+        return (np.zeros(0, dtype=np.uint8), np.zeros(0), np.zeros(targets_uint8.shape, dtype=np.uint8))
+    dev = torch.device("cuda", device)
+    d_patterns = torch.from_numpy(np.ascontiguousarray(intra_patterns_uint8[:nb_targets, :, :, 0])).to(dev)
+    d_targets = torch.from_numpy(np.ascontiguousarray(targets_uint8[:, :, :, 0])).to(dev)
+    index, sse, pred, _ = best_modes_device(d_patterns, d_targets, width_target, device=device)
+    indices = index.cpu().numpy()
+    sses = sse.cpu().numpy().view(np.uint32)
+    psnrs = psnrs_from_sses(sses, width_target)
+    psnrs[sses == 65025 * width_target * width_target] = 0.          # the reference's start value, never beaten
+    return (indices, psnrs, pred.cpu().numpy()[..., None])
+
+
+def predict_via_hevc_best_mode(intra_pattern_uint8, target_uint8, device=0):
+    """intraprediction.py:231-294 on the GPU: (index int, PSNR numpy.float64, prediction uint8 [w, w, 1])."""
+    if target_uint8.dtype != np.uint8:
+        raise TypeError('`array_0_uint8.dtype` is not equal to `numpy.uint8`.')
+    if target_uint8.ndim != 3 or intra_pattern_uint8.ndim != 3:
+        raise ValueError('Buffer has wrong number of dimensions (expected 3)')
+    indices, psnrs, predictions = predict_series_via_hevc_best_mode(intra_pattern_uint8[None], target_uint8[None], device)
+    return (int(indices[0]), psnrs[0], predictions[0])

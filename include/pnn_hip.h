@@ -249,6 +249,28 @@ int pnn_block_cost_device(pnn_ctx* ctx, int width, const void* d_org_plane, int 
 int pnn_predict_tbs_cost_device(pnn_ctx* ctx, int width, const void* d_plane, const void* d_org_plane, int pel_bytes,
                                 const pnn_tb_dev* d_tbs, int n, int hadamard, uint32_t* d_cost, int32_t* d_dst, void* stream);
 
+/* ---- HEVC intra prediction: the evaluator's best-mode competitor ------------------------------------- */
+
+/* == hevc_intraprediction (hevc/intraprediction/c++/source/extracted_hevc_intraprediction.cpp:3-134, called per mode by
+ * interface.pyx:15-64): the prediction [width][width] of HEVC intra mode `mode` (0 planar, 1 DC, 2..34 angular; 8-bit luma)
+ * from a dense uint8 intra pattern [pattern_h][pattern_w] of which only the first row (corner, above, above-right) and the
+ * first column (corner, left, below-left) are read; a shorter row / column is padded with its last sample.  No reference
+ * sample smoothing (the reference did not extract it); DC filtering and the mode 10 / 26 edge filter for width <= 16.
+ * Returns -1 + a line on stderr where the reference throws: NULL pointers, mode > 34, a side of the pattern outside
+ * [width + 1, 2 width + 1]; also for a width other than 4, 8, 16, 32, 64 and for mode < 0.  Pure host code. */
+int pnn_hevc_intra_predict(const uint8_t* intra_pattern, int pattern_h, int pattern_w, int width, int mode, uint8_t* out);
+
+/* == predict_via_hevc_best_mode (hevc/intraprediction/intraprediction.py:231-294) for n blocks at once, on the GPU.
+ * Inputs: dense patterns [n][pattern_h][pattern_w] (as above) and targets [n][width][width], uint8.  For each block all 35
+ * predictions and their SSE against the target; the best mode is the one of smallest SSE, the lowest index among ties (the
+ * reference keeps a mode only when its PSNR 10 log10(255^2 / (SSE / width^2 + 1e-6)) is strictly larger than the best so far,
+ * starting from 0 dB).  Outputs, each NULL or [n]: d_best_mode (uint8), d_best_sse (uint32), d_best_pred [n][width][width]
+ * (uint8; all zeros when even the best SSE is 65025 width^2, as the reference keeps its zero start), d_mode_sse [n][35]
+ * (uint32).  Not every output may be NULL; n == 0 does nothing.  A context without models (pnn_create_empty) suffices. */
+int pnn_hevc_best_mode_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
+                              const uint8_t* d_targets, int n, uint8_t* d_best_mode, uint32_t* d_best_sse,
+                              uint8_t* d_best_pred, uint32_t* d_mode_sse, void* stream);
+
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
 int pnn_last_call_stats(const pnn_ctx* ctx, int* n_gemm_launches, double* gemm_flops, int* n_launches);
