@@ -426,7 +426,9 @@ void pnn_destroy(pnn_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     cache_clear(c);
     for (Model*& m : c->models) { free_model(m); m = nullptr; }
+    for (Model*& m : c->ipfcns) { free_model(m); m = nullptr; }
     for (DevBuf& b : c->ws) if (b.p) (void)hipFree(b.p);
+    for (DevBuf& b : c->ipfcns_ws) if (b.p) (void)hipFree(b.p);
     for (DevBuf& b : c->stage_in) if (b.p) (void)hipFree(b.p);
     for (DevBuf& b : c->stage_out) if (b.p) (void)hipFree(b.p);
     if (c->stage_tbs.p) (void)hipFree(c->stage_tbs.p);
@@ -645,6 +647,102 @@ int pnn_hevc_best_mode_device(pnn_ctx* c, int width, const uint8_t* d_patterns, 
     p.patterns = d_patterns; p.ph = pattern_h; p.pw = pattern_w; p.targets = d_targets; p.N = n; p.w = width;
     p.best_mode = d_best_mode; p.best_sse = d_best_sse; p.best_pred = d_best_pred; p.mode_sse = d_mode_sse;
     HIPCHK(c, launch_hevc_best_mode(p, (hipStream_t)stream));
+    return PNN_OK;
+}
+
+int pnn_ipfcns_load(pnn_ctx* c, int width, const float* params, size_t n_floats)
+{
+    if (!c) return PNN_E_ARG;
+    const int idx = ipfcns_index(width);
+    if (idx < 0) return fail(c, PNN_E_ARG, "no IPFCN-S for width %d (4, 8, 16 or 32)", width);
+    if (!params) return fail(c, PNN_E_ARG, "NULL parameters");
+    HIPCHK(c, hipSetDevice(c->device));
+    Model* m = nullptr;
+    const int rc = build_ipfcns_model(c, width, params, n_floats, &m);
+    if (rc) return rc;
+    PNN_UNSAFE_CALLS_GUARD;
+    if (c->ipfcns[idx]) HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_model(c->ipfcns[idx]);
+    c->ipfcns[idx] = m;
+    c->tuned.clear(); c->tune_gen++;                                 // keys point into the replaced net
+    return PNN_OK;
+}
+
+static Model* ipfcns_for(pnn_ctx* c, int width, int* rc)
+{
+    const int idx = ipfcns_index(width);
+    if (idx < 0) { *rc = fail(c, PNN_E_ARG, "no IPFCN-S for width %d (4, 8, 16 or 32)", width); return nullptr; }
+    if (!c->ipfcns[idx]) { *rc = fail(c, PNN_E_ARG, "no IPFCN-S loaded for width %d", width); return nullptr; }
+    *rc = PNN_OK;
+    return c->ipfcns[idx];
+}
+
+int pnn_ipfcns_forward_device(pnn_ctx* c, int width, const float* d_x, int n, float* d_out_f32, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    const Model* m = ipfcns_for(c, width, &rc);
+    if (!m) return rc;
+    if (n < 0 || (n > 0 && (!d_x || !d_out_f32))) return fail(c, PNN_E_ARG, "bad batch size or buffers");
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    reset_stats(c);
+    return ipfcns_pass(c, m, d_x, n, d_out_f32, (hipStream_t)stream);
+}
+
+int pnn_ipfcns_predict_device(pnn_ctx* c, int width, const uint8_t* d_channels, int images, int height, int width_ch,
+                              const int32_t* d_rows, const int32_t* d_cols, int positions, const uint8_t* d_targets,
+                              uint8_t* d_pred_u8, float* d_pred_f32, float* d_means, uint32_t* d_sse, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    const Model* m = ipfcns_for(c, width, &rc);
+    if (!m) return rc;
+    if (images < 0 || positions < 0 || height < 0 || width_ch < 0) return fail(c, PNN_E_ARG, "negative sizes");
+    if (d_sse && !d_targets) return fail(c, PNN_E_ARG, "d_sse needs d_targets");
+    const long n = (long)images * positions;
+    if (n > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks");
+    if (n == 0) return PNN_OK;
+    if (!d_channels || !d_rows || !d_cols) return fail(c, PNN_E_ARG, "NULL input buffers");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    {   // every line origin inside the picture, checked before any launch
+        std::vector<int32_t> rows(positions), cols(positions);
+        {
+            PNN_UNSAFE_CALLS_GUARD;
+            HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(cols.data(), d_cols, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
+        const int span = 2 * width + 8;
+        for (int i = 0; i < positions; i++)
+            if (rows[i] < 0 || cols[i] < 0 || (long)rows[i] + span > height || (long)cols[i] + span > width_ch)
+                return fail(c, PNN_E_ARG, "line origin %d (%d, %d): the %dx%d lines leave the %dx%d picture", i, rows[i], cols[i], span, span, height, width_ch);
+    }
+    reset_stats(c);
+    int K, H;
+    ipfcns_dims(width, &K, &H);
+    const long w2 = (long)width * width, chunk = std::min(n, ipfcns_chunk(c, m));
+    if ((rc = dev_reserve(c, c->ipfcns_ws[0], (size_t)chunk * K * 4))) return rc;
+    if ((rc = dev_reserve(c, c->ipfcns_ws[3], (size_t)chunk * (w2 + 1) * 4))) return rc;
+    float* rows_f = (float*)c->ipfcns_ws[0].p;
+    float* fc4 = (float*)c->ipfcns_ws[3].p;
+    float* means_ws = fc4 + chunk * w2;
+    for (long b0 = 0; b0 < n; b0 += chunk) {
+        const int nb = (int)std::min(chunk, n - b0);
+        float* means = d_means ? d_means + b0 : means_ws;
+        IpfcnsGatherParams g;
+        g.channels = d_channels; g.H = height; g.W = width_ch; g.rows = d_rows; g.cols = d_cols; g.positions = positions;
+        g.b0 = b0; g.nb = nb; g.w = width; g.x = rows_f; g.mean = means;
+        HIPCHK(c, launch_ipfcns_gather(g, s));
+        if ((rc = ipfcns_pass(c, m, rows_f, nb, fc4, s))) return rc;
+        IpfcnsEpilogueParams e;
+        e.fc4 = fc4; e.mean = means; e.nb = nb; e.w2 = (int)w2;
+        e.u8 = d_pred_u8 ? d_pred_u8 + b0 * w2 : nullptr; e.f32 = d_pred_f32 ? d_pred_f32 + b0 * w2 : nullptr;
+        e.targets = d_targets ? d_targets + b0 * w2 : nullptr; e.sse = d_sse ? d_sse + b0 : nullptr;
+        HIPCHK(c, launch_ipfcns_epilogue(e, s));
+        c->stat_launches += 2;
+    }
     return PNN_OK;
 }
 

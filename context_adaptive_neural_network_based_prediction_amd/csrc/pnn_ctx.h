@@ -40,6 +40,28 @@ inline int width_index(int w)                                // TComPrediction.c
     switch (w) { case 4: return 0; case 8: return 1; case 16: return 2; case 32: return 3; case 64: return 4; default: return -1; }
 }
 
+// IPFCN-S (IntraFCN205_deploy_Size{w}.prototxt): input K = 64 + 32 w, hidden H of fc1 .. fc3, output w^2; false for other widths
+inline bool ipfcns_dims(int w, int* K, int* H)
+{
+    switch (w) {
+    case 4: *H = 512; break;
+    case 8: case 16: *H = 1024; break;
+    case 32: *H = 2048; break;
+    default: return false;
+    }
+    *K = 64 + 32 * w;
+    return true;
+}
+inline int ipfcns_index(int w) { return w == 4 ? 0 : w == 8 ? 1 : w == 16 ? 2 : w == 32 ? 3 : -1; }
+// parameters of the canonical order W1[H][K], b1, a1, W2[H][H], b2, a2, W3[H][H], b3, a3, W4[w^2][H], b4
+inline long ipfcns_n_params(int w)
+{
+    int K, H;
+    if (!ipfcns_dims(w, &K, &H)) return -1;
+    const long o = (long)w * w;
+    return (long)H * K + 2L * H + 2L * ((long)H * H + 2L * H) + o * H + o;
+}
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -79,6 +101,7 @@ struct Model {
     TConv1Layer last;
     int C = 0;                                        // channels at the merger
     long pmax = 0;                                    // largest intermediate activation (floats / block)
+    float* d_slope[3] = {nullptr, nullptr, nullptr};  // IPFCN-S nets (build_ipfcns_model): the PReLU slopes behind fc1 .. fc3
     std::vector<void*> allocs;
 };
 
@@ -89,6 +112,8 @@ struct pnn_ctx {
     float mean = 0.f;
     hipStream_t stream = nullptr;
     pnn::Model* models[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    pnn::Model* ipfcns[4] = {nullptr, nullptr, nullptr, nullptr};   // IPFCN-S nets of widths 4, 8, 16, 32 (pnn_ipfcns_load)
+    pnn::DevBuf ipfcns_ws[4];                              // ... their pass: rows, hidden activations (two), means + fc4 outputs
     pnn::DevBuf ws[6];                                     // P0, P1, F0, F1 (FC uses P0, P1); P2, P3: the left branch's own pair when the branches overlap
     // Small conv passes (the in-loop single-block calls): the two branches are independent chains of 4-5 launches that
     // each fill a fraction of the chip; the left branch runs on a side stream, forked and joined by events.
@@ -249,6 +274,8 @@ std::recursive_mutex& unsafe_calls_lock();
 int dev_reserve(pnn_ctx* c, DevBuf& b, size_t bytes);
 // pnn_model.cpp
 int build_model(pnn_ctx* c, int width, int is_fc, const float* params, size_t n, Model** out);
+// IPFCN-S: params in the canonical order of pnn_ipfcns_load (include/pnn_hip.h); fc[0..3] with act = 0, slopes in d_slope
+int build_ipfcns_model(pnn_ctx* c, int width, const float* params, size_t n, Model** out);
 void free_model(Model* m);
 // pnn_tiles.cpp
 int convimg_images(const TapGemmParams& p, const TileCfg& t, bool one_tap);
@@ -287,6 +314,9 @@ void* diag_stamp_slot(pnn_ctx* c, const char* name, long wgs, double k);
 long chunk_blocks(const pnn_ctx* c, const Model* m);
 bool pass_uses_split(const pnn_ctx* c, const Model* m, long nb);
 bool conv_pass_fuses_first(pnn_ctx* c, Model* m, long nb);
+// IPFCN-S pass over n blocks of flattened rows d_x [n][K]: fc4 outputs (no mean) to d_fc4 [n][w^2]; slices by ipfcns_chunk
+long ipfcns_chunk(const pnn_ctx* c, const Model* m);
+int ipfcns_pass(pnn_ctx* c, const Model* m, const float* d_x, long n, float* d_fc4, hipStream_t s);
 int run_net(pnn_ctx* c, Model* m, const float* d_a, long pitch_a, const float* d_l, long pitch_l, long n, float* d_out,
             int32_t* d_dst, hipStream_t s, bool ctx_is_split = false);
 

@@ -264,6 +264,24 @@ struct HevcBestModeParams {
 };
 hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s);
 
+// IPFCN-S, the evaluator's second competitor (pnn_ipfcns.hip).  Blocks b0 .. b0 + nb - 1 of images x positions (image-major): the
+// two groups of 8 reference lines at line origin (rows[pos], cols[pos]) of uint8 picture `img` [H][W] -- rows [r, r + 8) x columns
+// [c, c + 2w + 8), then rows [r + 8, r + 2w + 8) x columns [c, c + 8), both row-major -- minus their mean fl32(S / K) (S the integer
+// sum of the K = 64 + 32w samples): x [nb][K] and mean [nb].  The caller has checked that every origin lies inside the picture.
+struct IpfcnsGatherParams {
+    const uint8_t* channels; int H, W; const int32_t* rows; const int32_t* cols; int positions; long b0; int nb; int w;
+    float* x; float* mean;
+};
+hipError_t launch_ipfcns_gather(const IpfcnsGatherParams& p, hipStream_t s);
+// y[i] = y[i] > 0 ? y[i] : slope[i % H] * y[i] in place, i < total (total and H multiples of 4)
+hipError_t launch_ipfcns_prelu(float* y, const float* slope, long total, int H, hipStream_t s);
+// Output epilogue of nb blocks of w2 = w^2 values: pred = fl32(fc4 + mean[b]); f32 (optional) = pred; u8 (optional) =
+// rint(clip(pred, 0, 255)) (half to even); sse (optional, with targets) = per-block uint32 sum of squared uint8 differences.
+struct IpfcnsEpilogueParams {
+    const float* fc4; const float* mean; int nb; int w2; uint8_t* u8; float* f32; const uint8_t* targets; uint32_t* sse;
+};
+hipError_t launch_ipfcns_epilogue(const IpfcnsEpilogueParams& p, hipStream_t s);
+
 // Stand-alone HM epilogue for float predictions.
 hipError_t launch_epilogue(const float* pred, long n, float mean, int32_t* dst, hipStream_t s);
 

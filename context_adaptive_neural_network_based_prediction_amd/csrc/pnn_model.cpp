@@ -386,4 +386,38 @@ int build_model(pnn_ctx* c, int width, int is_fc, const float* params, size_t n,
     return PNN_OK;
 }
 
+// IPFCN-S: four InnerProduct layers (Caffe, weights [out][in], y = W x + b) as one-tap exact-f32 GEMM layers WITHOUT activation
+// -- the PReLU behind fc1 .. fc3 is its own launch (launch_ipfcns_prelu) -- so that every layer keeps the order of items 4, 6, 8.
+int build_ipfcns_model(pnn_ctx* c, int width, const float* params, size_t n, Model** out)
+{
+    int K, H;
+    if (!ipfcns_dims(width, &K, &H)) return fail(c, PNN_E_ARG, "no IPFCN-S for width %d (4, 8, 16 or 32)", width);
+    if ((long)n != ipfcns_n_params(width))
+        return fail(c, PNN_E_ARG, "%zu parameters given, the width-%d IPFCN-S needs %ld", n, width, ipfcns_n_params(width));
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(params[i])) return fail(c, PNN_E_ARG, "parameter %zu of the width-%d IPFCN-S is not finite", i, width);
+    Model* m = new Model();
+    m->width = width; m->is_fc = true; m->n_params = (long)n; m->n_layers = 4; m->pmax = H;
+    m->fc.resize(4);
+    const int dims[5] = {K, H, H, H, width * width};
+    const float* p = params;
+    int rc = PNN_OK;
+    for (int i = 0; i < 4 && rc == PNN_OK; i++) {
+        const int ki = dims[i], ni = dims[i + 1];
+        std::vector<float> kn((size_t)ki * ni);      // [out][in] -> the [in][out] rows of a tap GEMM layer
+        for (int o = 0; o < ni; o++)
+            for (int k = 0; k < ki; k++) kn[(size_t)k * ni + o] = p[(size_t)o * ki + k];
+        p += (size_t)ki * ni;
+        rc = build_fc_layer(c, m, kn.data(), p, ki, ni, 0, &m->fc[i]);
+        p += ni;
+        if (rc == PNN_OK && i < 3) {
+            rc = upload(c, m, p, (size_t)ni, &m->d_slope[i]);
+            p += ni;
+        }
+    }
+    if (rc != PNN_OK) { free_model(m); return rc; }
+    *out = m;
+    return PNN_OK;
+}
+
 }  // namespace pnn

@@ -1011,4 +1011,42 @@ int run_net(pnn_ctx* c, Model* m, const float* d_a, long pitch_a, const float* d
     return rc;
 }
 
+// IPFCN-S (pnn_ipfcns.hip): blocks per slice -- the "max_chunk" option, else what the workspace bound holds of the pass's buffers (rows,
+// two hidden activations, means and fc4 outputs), and never an activation tensor past the 2 GiB descriptor bound of run_gemm
+long ipfcns_chunk(const pnn_ctx* c, const Model* m)
+{
+    int K, H;
+    ipfcns_dims(m->width, &K, &H);
+    const double per_block = 4.0 * (K + 2.0 * H + 1.0 + (double)m->width * m->width);
+    long n = c->opt_max_chunk > 0 ? c->opt_max_chunk : (long)((double)c->ws_cap_bytes / per_block);
+    n = std::min(n, (long)(2147483000.0 / (4.0 * std::max(K, H))));
+    return std::max(1L, std::min(n, 1L << 20));
+}
+
+// fc1 .. fc4 of n blocks: four exact-f32 tap-GEMM layers (act = 0: items 4, 6, 8 of the order, any tile, any kernel family, the same
+// bits) with the PReLU behind the first three as a launch of its own.  d_x [n][K] -> d_fc4 [n][w^2], in slices of ipfcns_chunk.
+int ipfcns_pass(pnn_ctx* c, const Model* m, const float* d_x, long n, float* d_fc4, hipStream_t s)
+{
+    int K, H;
+    if (!ipfcns_dims(m->width, &K, &H)) return fail(c, PNN_E_ARG, "not an IPFCN-S width");
+    const long w2 = (long)m->width * m->width, chunk = std::min(n, ipfcns_chunk(c, m));
+    int rc;
+    if ((rc = dev_reserve(c, c->ipfcns_ws[1], (size_t)chunk * H * 4))) return rc;
+    if ((rc = dev_reserve(c, c->ipfcns_ws[2], (size_t)chunk * H * 4))) return rc;
+    float* P0 = (float*)c->ipfcns_ws[1].p;
+    float* P1 = (float*)c->ipfcns_ws[2].p;
+    for (long b0 = 0; b0 < n; b0 += chunk) {
+        const long nb = std::min(chunk, n - b0);
+        if ((rc = run_gemm(c, m->fc[0], d_x + b0 * K, P0, nullptr, nb, s))) return rc;
+        HIPCHK(c, launch_ipfcns_prelu(P0, m->d_slope[0], nb * H, H, s));
+        if ((rc = run_gemm(c, m->fc[1], P0, P1, nullptr, nb, s))) return rc;
+        HIPCHK(c, launch_ipfcns_prelu(P1, m->d_slope[1], nb * H, H, s));
+        if ((rc = run_gemm(c, m->fc[2], P1, P0, nullptr, nb, s))) return rc;
+        HIPCHK(c, launch_ipfcns_prelu(P0, m->d_slope[2], nb * H, H, s));
+        if ((rc = run_gemm(c, m->fc[3], P0, d_fc4 + b0 * w2, nullptr, nb, s))) return rc;
+        c->stat_launches += 3;
+    }
+    return PNN_OK;
+}
+
 }  // namespace pnn

@@ -4,6 +4,8 @@ comparing_pnn_ipfcns_hevc_best_mode.py:162-322 (`predict_mask`) without TensorFl
 PSNR definitions.  predict_mask_vs_hevc_best_mode adds the paper's competitor, the best HEVC intra mode per block
 (intraprediction.py: all 35 modes, their SSEs and the winner of every block in one GPU launch), and the reference's
 dictionary_performance (indices and PSNRs of the best mode, PNN PSNRs, PNN's win frequency, its mean PSNR).
+predict_mask_vs_hevc_best_mode_and_ipfcns adds the third column, IPFCN-S (ipfcns.py: line gather, the four layers and the
+uint8 epilogue with the per-block SSE in one GPU call), as the reference does only when nothing is masked.
 """
 import numpy as np
 
@@ -84,3 +86,49 @@ def predict_mask_vs_hevc_best_mode(channels_uint8, width_target, row_1sts, col_1
             'frequency_win_pnn': frequency_win_pnn, 'mean_psnr_pnn': np.mean(psnrs_pnn).item(),
             'predictions_pnn_uint8': pnn['predictions_pnn_uint8'], 'predictions_hevc_best_mode_uint8': predictions_hevc,
             'targets_uint8': pnn['targets_uint8']}
+
+
+def predict_without_mask_via_ipfcns(channels_uint8, width_target, row_1sts, col_1sts, batch_size, net_ipfcns,
+                                    dictionary_performance):
+    """comparing_pnn_ipfcns_hevc_best_mode.py:633-711 on the GPU: the reference lines of every target (line origin
+    (row_1st + w - 8, col_1st + w - 8)), IPFCN-S, pred = fl32(fc4 + mean), uint8 by rint (half to even) and the SSE against
+    dictionary_performance['targets_uint8'] in one call.  FILLS dictionary_performance with 'psnrs_ipfcns' (float64 [N], from
+    the integer SSEs by intraprediction.psnrs_from_sses, equal to compute_psnr), 'frequency_win_ipfcns' (against
+    'psnrs_hevc_best_mode'), 'mean_psnr_ipfcns' and 'predictions_ipfcns_uint8' [N,w,w,1]."""
+    import torch
+    targets_uint8 = dictionary_performance['targets_uint8']
+    nb_targets = targets_uint8.shape[0]
+    if nb_targets % batch_size:
+        raise ValueError('`numerator` is not divisible by `denominator`.')
+    if net_ipfcns.width_target != width_target:
+        raise ValueError('the net is the width-%d IPFCN-S, not the width-%d one' % (net_ipfcns.width_target, width_target))
+    if channels_uint8.dtype != np.uint8 or channels_uint8.ndim != 4 or channels_uint8.shape[3] != 1:
+        raise ValueError('`channels_uint8` must be uint8 [images, H, W, 1].')
+    rows = np.ascontiguousarray(row_1sts + width_target - 8, dtype=np.int32)
+    cols = np.ascontiguousarray(col_1sts + width_target - 8, dtype=np.int32)
+    if channels_uint8.shape[0] * rows.size != nb_targets:
+        raise ValueError('images x positions is not the number of targets.')
+    dev = torch.device('cuda', net_ipfcns.device)
+    d_channels = torch.from_numpy(np.ascontiguousarray(channels_uint8[..., 0])).to(dev)
+    d_targets = torch.from_numpy(np.ascontiguousarray(targets_uint8[..., 0])).to(dev)
+    pred_u8, _, _, sses = net_ipfcns.predict_from_channels_device(d_channels, torch.from_numpy(rows).to(dev),
+                                                                  torch.from_numpy(cols).to(dev), d_targets)
+    psnrs = intraprediction.psnrs_from_sses(sses, width_target)
+    dictionary_performance['psnrs_ipfcns'] = psnrs
+    dictionary_performance['frequency_win_ipfcns'] = \
+        float(np.count_nonzero(psnrs - dictionary_performance['psnrs_hevc_best_mode'] > 0.)) / nb_targets
+    dictionary_performance['mean_psnr_ipfcns'] = np.mean(psnrs).item()
+    dictionary_performance['predictions_ipfcns_uint8'] = pred_u8[..., None]
+
+
+def predict_mask_vs_hevc_best_mode_and_ipfcns(channels_uint8, width_target, row_1sts, col_1sts, predictor, batch_size,
+                                              mean_training, net_ipfcns, tuple_width_height_masks=(0, 0)):
+    """The three columns of the paper's table, as comparing_pnn_ipfcns_hevc_best_mode.py:162-322 fills them:
+    predict_mask_vs_hevc_best_mode's dictionary plus, when net_ipfcns is given and nothing is masked (masks == (0, 0)), the
+    IPFCN-S keys of predict_without_mask_via_ipfcns."""
+    dictionary_performance = predict_mask_vs_hevc_best_mode(channels_uint8, width_target, row_1sts, col_1sts, predictor,
+                                                            batch_size, mean_training, tuple_width_height_masks)
+    if net_ipfcns is not None and tuple(tuple_width_height_masks) == (0, 0):
+        predict_without_mask_via_ipfcns(channels_uint8, width_target, row_1sts, col_1sts, batch_size, net_ipfcns,
+                                        dictionary_performance)
+    return dictionary_performance

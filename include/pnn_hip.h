@@ -271,6 +271,35 @@ int pnn_hevc_best_mode_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns
                               const uint8_t* d_targets, int n, uint8_t* d_best_mode, uint32_t* d_best_sse,
                               uint8_t* d_best_pred, uint32_t* d_mode_sse, void* stream);
 
+/* ---- IPFCN-S: the evaluator's second competitor ------------------------------------------------------ */
+
+/* IPFCN-S (Li et al.; the reference's ipfcns/ipfcns.py with IntraFCN205_deploy_Size{4,8,16,32}.prototxt): four InnerProduct
+ * layers, input K = 64 + 32 width, hidden H = 512 (width 4), 1024 (8, 16), 2048 (32), output width^2, PReLU (one slope per
+ * channel, v > 0 ? v : a v) behind fc1 .. fc3.  `params` in ONE flat canonical order, Caffe's own layouts:
+ *   W1[H][K], b1[H], a1[H], W2[H][H], b2, a2, W3[H][H], b3, a3, W4[width^2][H], b4[width^2].
+ * Arithmetic: exact-f32 order revision 6, items 4, 6 and 8 on every layer ("IPFCN-S").
+ *
+ * Host twin (pure host code, threads over blocks; the bits do not depend on their number): x [n][K] -> the activations after
+ * layer `layers` (1 .. 3: [n][H] behind the PReLU; 4: fc4 [n][width^2], without the mean).  PNN_E_ARG for a bad width / layers. */
+int pnn_ipfcns_forward_host(int width, const float* params, const float* x, int n, int layers, float* out);
+/* Loads (or replaces) the IPFCN-S of `width` on the context; a model-less pnn_create_empty context suffices.  PNN_E_ARG for a
+ * width outside {4, 8, 16, 32}, a count other than the architecture's, a non-finite parameter. */
+int pnn_ipfcns_load(pnn_ctx* ctx, int width, const float* params, size_t n_floats);
+/* The reference's flattened-input entry (predict_by_batch_via_ipfcns): d_x [n][K] (mean-subtracted rows) -> d_out_f32 [n][width^2]
+ * = fc4, asynchronous on `stream`; bit-identical to pnn_ipfcns_forward_host(..., 4, ...).  n == 0 does nothing. */
+int pnn_ipfcns_forward_device(pnn_ctx* ctx, int width, const float* d_x, int n, float* d_out_f32, void* stream);
+/* The fused path from pictures: d_channels uint8 [images][height][width_ch]; line origins (d_rows[p], d_cols[p]), int32
+ * [positions]; blocks image-major (b = image * positions + p).  Per block the two groups of 8 reference lines (rows [r, r + 8) x
+ * columns [c, c + 2 width + 8), then rows [r + 8, r + 2 width + 8) x columns [c, c + 8), row-major), S their integer sum,
+ * mean = fl32(S / K), x = fl32(sample - mean); fc1 .. fc4; pred = fl32(fc4 + mean).  Outputs, each NULL or per block:
+ * d_pred_u8 [n][width][width] = rint(clip(pred, 0, 255)) (half to even, tools.cast_float_to_uint8), d_pred_f32 = pred,
+ * d_means [n], d_sse [n] uint32 = sum of squared differences of d_pred_u8 against d_targets [n][width][width] (needs d_targets).
+ * n == 0 does nothing.  PNN_E_ARG, before any launch, for an origin whose lines leave the picture, a width outside
+ * {4, 8, 16, 32} or no net loaded for it.  Reads d_rows / d_cols back to the host (the call waits for `stream` once). */
+int pnn_ipfcns_predict_device(pnn_ctx* ctx, int width, const uint8_t* d_channels, int images, int height, int width_ch,
+                              const int32_t* d_rows, const int32_t* d_cols, int positions, const uint8_t* d_targets,
+                              uint8_t* d_pred_u8, float* d_pred_f32, float* d_means, uint32_t* d_sse, void* stream);
+
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
 int pnn_last_call_stats(const pnn_ctx* ctx, int* n_gemm_launches, double* gemm_flops, int* n_launches);

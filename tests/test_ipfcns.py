@@ -1,0 +1,472 @@
+"""CPU tests of IPFCN-S (context_adaptive_neural_network_based_prediction_amd/ipfcns.py, csrc/pnn_ipfcns.cpp): the pure-Python
+caffemodel reader against protobuf's own decoder, the line extraction and its float32 preprocessing against a per-block loop
+written from the reference's ipfcns.py:97-494 (and against the reference itself where its checkout exists), the host twin
+layer by layer against float64 within a derived rounding bound, end to end against float64 within the reference's own kind
+of float32 error, and the trained 4x4 net's sanity on natural pictures."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from context_adaptive_neural_network_based_prediction_amd import evaluation
+from context_adaptive_neural_network_based_prediction_amd import ipfcns as I
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NATURAL = os.path.join(ROOT, "oracle", "_ref", "natural_luma.npz")
+REFERENCE = "/root/reference"
+SIZE4 = os.path.join(REFERENCE, "ipfcns", "models", "ipfcns", "IntraFCN205_Size4_iter_1638700.caffemodel")
+U = 2.0 ** -24                       # unit roundoff of float32
+ETA = 2.0 ** -150                    # largest absolute error of one float32 rounding in the subnormal range
+
+
+def recipe_params(w, seed, gain=1.0):
+    """Seeded IPFCN-S weights: N(0, s_l) with s = (0.032 sqrt(192/K), 0.0188 sqrt(512/H), 0.0168 sqrt(512/H), 0.092 sqrt(512/H)),
+    biases N(0, 0.02), slopes U(-0.3, 0.6); `gain` scales fc4."""
+    K, H, O = I.layer_dims(w)
+    rng = np.random.default_rng(seed)
+    s = (0.032 * np.sqrt(192 / K), 0.0188 * np.sqrt(512 / H), 0.0168 * np.sqrt(512 / H), 0.092 * np.sqrt(512 / H) * gain)
+    dims = (K, H, H, H, O)
+    parts = []
+    for l in range(4):
+        parts.append(rng.normal(0, s[l], dims[l + 1] * dims[l]))
+        parts.append(rng.normal(0, 0.02, dims[l + 1]))
+        if l < 3:
+            parts.append(rng.uniform(-0.3, 0.6, dims[l + 1]))
+    return np.concatenate(parts).astype(np.float32)
+
+
+def unpack(params, w):
+    """[(W [out][in], b, slope or None)] views of the canonical order."""
+    K, H, O = I.layer_dims(w)
+    dims = (K, H, H, H, O)
+    out, o = [], 0
+    for l in range(4):
+        W = params[o:o + dims[l + 1] * dims[l]].reshape(dims[l + 1], dims[l]); o += W.size
+        b = params[o:o + dims[l + 1]]; o += dims[l + 1]
+        a = None
+        if l < 3:
+            a = params[o:o + dims[l + 1]]; o += dims[l + 1]
+        out.append((W, b, a))
+    assert o == params.size
+    return out
+
+
+def forward(params, w, x, dtype, layers=4):
+    h = x.astype(dtype)
+    for l, (W, b, a) in enumerate(unpack(params, w)[:layers]):
+        h = (h @ W.T.astype(dtype) + b.astype(dtype)).astype(dtype)
+        if a is not None:
+            h = np.where(h > 0, h, a.astype(dtype) * h).astype(dtype)
+    return h
+
+
+def pictures(n_images, H, W, seed):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    out = []
+    for i in range(n_images):
+        f = rng.uniform(0.02, 0.2, 4)
+        img = 128 + 60 * np.sin(f[0] * xx + f[1] * yy) + 40 * np.cos(f[2] * xx - f[3] * yy) + rng.normal(0, 6, (H, W))
+        out.append(np.clip(img, 0, 255))
+    return np.array(out).astype(np.uint8)[..., None]
+
+
+def natural():
+    return np.load(NATURAL) if os.path.exists(NATURAL) else None
+
+
+# ---- the caffemodel reader ------------------------------------------------------------------------------------------------
+
+def caffe_classes(packed_data=True):
+    """NetParameter / LayerParameter / BlobProto / BlobShape (caffe.proto's field numbers) as protobuf dynamic messages, plus an
+    unknown field (LayerParameter 99, BlobProto 15) and V1's `layers` (2) as raw bytes."""
+    from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
+    F = descriptor_pb2.FieldDescriptorProto
+    fd = descriptor_pb2.FileDescriptorProto(name="caffe_test_%d.proto" % packed_data, package="caffetest%d" % packed_data, syntax="proto2")
+
+    def msg(name, fields):
+        m = fd.message_type.add(name=name)
+        for (fname, num, ftype, label, type_name, packed) in fields:
+            f = m.field.add(name=fname, number=num, type=ftype, label=label)
+            if type_name:
+                f.type_name = type_name
+            if packed:
+                f.options.packed = True
+    pkg = ".caffetest%d." % packed_data
+    msg("BlobShape", [("dim", 1, F.TYPE_INT64, F.LABEL_REPEATED, None, True)])
+    msg("BlobProto", [("num", 1, F.TYPE_INT32, F.LABEL_OPTIONAL, None, False),
+                      ("channels", 2, F.TYPE_INT32, F.LABEL_OPTIONAL, None, False),
+                      ("height", 3, F.TYPE_INT32, F.LABEL_OPTIONAL, None, False),
+                      ("width", 4, F.TYPE_INT32, F.LABEL_OPTIONAL, None, False),
+                      ("data", 5, F.TYPE_FLOAT, F.LABEL_REPEATED, None, packed_data),
+                      ("shape", 7, F.TYPE_MESSAGE, F.LABEL_OPTIONAL, pkg + "BlobShape", False),
+                      ("extra", 15, F.TYPE_STRING, F.LABEL_OPTIONAL, None, False)])
+    msg("LayerParameter", [("name", 1, F.TYPE_STRING, F.LABEL_OPTIONAL, None, False),
+                           ("type", 2, F.TYPE_STRING, F.LABEL_OPTIONAL, None, False),
+                           ("blobs", 7, F.TYPE_MESSAGE, F.LABEL_REPEATED, pkg + "BlobProto", False),
+                           ("unknown_int", 99, F.TYPE_INT64, F.LABEL_OPTIONAL, None, False)])
+    msg("NetParameter", [("name", 1, F.TYPE_STRING, F.LABEL_OPTIONAL, None, False),
+                         ("layers", 2, F.TYPE_BYTES, F.LABEL_REPEATED, None, False),
+                         ("layer", 100, F.TYPE_MESSAGE, F.LABEL_REPEATED, pkg + "LayerParameter", False),
+                         ("unknown_fixed", 77, F.TYPE_FIXED64, F.LABEL_OPTIONAL, None, False)])
+    pool = descriptor_pool.DescriptorPool()
+    pool.Add(fd)
+    get = (lambda n: message_factory.GetMessageClass(pool.FindMessageTypeByName("caffetest%d.%s" % (packed_data, n))))
+    return get("NetParameter"), get("BlobProto")
+
+
+def write_net(path, layers, packed_data=True, legacy=False, v1=False):
+    Net, _ = caffe_classes(packed_data)
+    net = Net(name="IntraFCN", unknown_fixed=12345)
+    if v1:
+        net.layers.append(b"\x0a\x03fc1")
+    for name, kind, blobs in layers:
+        L = net.layer.add(name=name, type=kind, unknown_int=7)
+        for b in blobs:
+            B = L.blobs.add(extra="ignored")
+            if legacy:
+                dims = (1,) * (4 - b.ndim) + b.shape
+                B.num, B.channels, B.height, B.width = dims
+            else:
+                B.shape.dim.extend(b.shape)
+            B.data.extend(b.reshape(-1).tolist())
+    with open(path, "wb") as f:
+        f.write(net.SerializeToString())
+
+
+def synthetic_layers(w, seed):
+    p = recipe_params(w, seed)
+    out = [("data", "HDF5Data", [])]
+    for l, (W, b, a) in enumerate(unpack(p, w)):
+        out.append(("fc%d" % (l + 1), "InnerProduct", [W.copy(), b.copy()]))
+        if a is not None:
+            out.append(("relu%d" % (l + 1), "PReLU", [a.copy()]))
+    out.append(("loss", "EuclideanLoss", []))
+    return p, out
+
+
+@pytest.mark.parametrize("packed_data,legacy", [(True, False), (False, False), (True, True), (False, True)])
+def test_reader_decodes_synthetic_files(tmp_path, packed_data, legacy):
+    p, layers = synthetic_layers(4, 11)
+    path = str(tmp_path / "net.caffemodel")
+    write_net(path, layers, packed_data, legacy)
+    got = I.read_caffemodel(path)
+    assert [(n, t) for n, t, _ in got] == [(n, t) for n, t, _ in layers]
+    for (_, _, gb), (_, _, wb) in zip(got, layers):
+        assert len(gb) == len(wb)
+        for g, want in zip(gb, wb):
+            assert g.dtype == np.float32
+            assert g.reshape(-1).tobytes() == want.reshape(-1).tobytes()
+            assert g.shape == (((1,) * (4 - want.ndim) + want.shape) if legacy else want.shape)
+    assert I.params_from_caffemodel(got, 4).tobytes() == p.tobytes()
+
+
+def test_reader_refusals(tmp_path):
+    p, layers = synthetic_layers(4, 12)
+    path = str(tmp_path / "v1.caffemodel")
+    write_net(path, layers, v1=True)
+    with pytest.raises(ValueError, match="V1"):
+        I.read_caffemodel(path)
+    good = str(tmp_path / "good.caffemodel")
+    write_net(good, layers)
+    raw = open(good, "rb").read()
+    trunc = str(tmp_path / "trunc.caffemodel")
+    open(trunc, "wb").write(raw[:len(raw) // 2])
+    with pytest.raises(ValueError):
+        I.read_caffemodel(trunc)
+    # a blob whose shape does not match its value count
+    Net, Blob = caffe_classes(True)
+    bad = Net()
+    L = bad.layer.add(name="fc1", type="InnerProduct")
+    B = L.blobs.add()
+    B.shape.dim.extend([3, 4])
+    B.data.extend([1.0] * 11)
+    path = str(tmp_path / "count.caffemodel")
+    open(path, "wb").write(bad.SerializeToString())
+    with pytest.raises(ValueError, match="holds 11 values"):
+        I.read_caffemodel(path)
+    # missing layer, missing blob, misshapen blob
+    ok = I.read_caffemodel(good)
+    with pytest.raises(ValueError, match="no layer `fc3`"):
+        I.params_from_caffemodel([t for t in ok if t[0] != "fc3"], 4)
+    with pytest.raises(ValueError, match="blobs"):
+        I.params_from_caffemodel([(n, k, b[:1]) if n == "fc2" else (n, k, b) for n, k, b in ok], 4)
+    with pytest.raises(ValueError, match="shape"):
+        I.params_from_caffemodel([(n, k, [b[0].reshape(192, 512), b[1]]) if n == "fc1" else (n, k, b) for n, k, b in ok], 4)
+    with pytest.raises(ValueError):
+        I.params_from_caffemodel(ok, 8)                  # a width-4 file is not the width-8 net
+
+
+@pytest.mark.skipif(not os.path.exists(SIZE4), reason="needs the reference checkout's trained 4x4 IPFCN-S")
+def test_reader_on_the_trained_size4_file():
+    got = I.read_caffemodel(SIZE4)
+    assert [(n, t, [b.shape for b in bl]) for n, t, bl in got] == [
+        ("data", "HDF5Data", []), ("fc1", "InnerProduct", [(512, 192), (512,)]), ("relu1", "PReLU", [(512,)]),
+        ("fc2", "InnerProduct", [(512, 512), (512,)]), ("relu2", "PReLU", [(512,)]),
+        ("fc3", "InnerProduct", [(512, 512), (512,)]), ("relu3", "PReLU", [(512,)]),
+        ("fc4", "InnerProduct", [(16, 512), (16,)]), ("loss", "EuclideanLoss", [])]
+    Net, _ = caffe_classes(True)
+    net = Net()
+    net.ParseFromString(open(SIZE4, "rb").read())
+    assert [L.name for L in net.layer] == [n for n, _, _ in got]
+    for L, (_, _, blobs) in zip(net.layer, got):
+        for B, b in zip(L.blobs, blobs):
+            assert np.array(B.data, dtype=np.float32).tobytes() == b.reshape(-1).tobytes()
+            assert tuple(B.shape.dim) == b.shape
+    assert I.params_from_caffemodel(got, 4).size == I.n_params(4)
+
+
+# ---- line extraction and preprocessing ------------------------------------------------------------------------------------
+
+def loop_extract(channels, w, rows, cols):
+    """ipfcns.py:97-494, block by block, with the pinned float32 semantics."""
+    above, left, flat, means = [], [], [], []
+    for img in channels:
+        for r, c in zip(rows, cols):
+            a = img[r:r + 8, c:c + 2 * w + 8, -1:]
+            l_ = img[r + 8:r + 2 * w + 8, c:c + 8, -1:]
+            above.append(a)
+            left.append(l_)
+            v = np.concatenate((a.reshape(-1), l_.reshape(-1)))
+            s = int(v.astype(np.int64).sum())
+            m = np.float32(np.float32(s) / np.float32(v.size))
+            means.append(m)
+            flat.append(np.array([np.float32(np.float32(p) - m) for p in v], dtype=np.float32))
+    return np.array(above), np.array(left), np.array(flat), np.array(means, dtype=np.float32)
+
+
+@pytest.mark.parametrize("w", I.WIDTHS)
+def test_extraction_and_preprocessing_equal_the_per_block_loop(w):
+    imgs = pictures(2, 3 * w + 40, 3 * w + 52, 7 + w)
+    H, W = imgs.shape[1:3]
+    rng = np.random.default_rng(w)
+    rows = np.concatenate(([0, H - 2 * w - 8], rng.integers(0, H - 2 * w - 7, 10))).astype(np.int32)
+    cols = np.concatenate(([W - 2 * w - 8, 0], rng.integers(0, W - 2 * w - 7, 10))).astype(np.int32)
+    a, l_, flat, means = loop_extract(imgs, w, rows, cols)
+    ga, gl = I.extract_pairs_groups_lines_from_channels(imgs, w, rows, cols)
+    np.testing.assert_array_equal(ga, a)
+    np.testing.assert_array_equal(gl, l_)
+    gf, gm = I.extract_pairs_groups_lines_from_channels_plus_preprocessing(imgs, w, rows, cols)
+    assert gf.dtype == np.float32 and gm.dtype == np.float32 and gf.shape == (2 * rows.size, 64 + 32 * w)
+    assert gf.tobytes() == flat.tobytes() and gm.tobytes() == means.tobytes()
+    one_a, one_l = I.extract_pair_groups_lines_from_channel(imgs[1], w, int(rows[3]), int(cols[3]))
+    np.testing.assert_array_equal(one_a, a[rows.size + 3])
+    np.testing.assert_array_equal(one_l, l_[rows.size + 3])
+    ca, cl = I.extract_pairs_groups_lines_from_channel(imgs[0], w, rows, cols)
+    np.testing.assert_array_equal(ca, a[:rows.size])
+    np.testing.assert_array_equal(cl, l_[:rows.size])
+    # two channels: the second one is read
+    pair = np.concatenate((imgs, 255 - imgs), axis=3)
+    pa, _ = I.extract_pairs_groups_lines_from_channels(pair, w, rows, cols)
+    np.testing.assert_array_equal(pa, 255 - a)
+
+
+def test_means_keep_the_float32_division():
+    """A block whose S / K differs in float32 and float64 rounding: the float32 quotient is the one kept."""
+    w = 4
+    rng = np.random.default_rng(5)
+    imgs = rng.integers(0, 256, (1, 64, 64, 1)).astype(np.uint8)
+    rows = np.arange(0, 40, dtype=np.int32)
+    cols = np.arange(0, 40, dtype=np.int32)
+    _, means = I.extract_pairs_groups_lines_from_channels_plus_preprocessing(imgs, w, rows, cols)
+    a, l_ = I.extract_pairs_groups_lines_from_channels(imgs, w, rows, cols)
+    s = a.reshape(40, -1).astype(np.int64).sum(1) + l_.reshape(40, -1).astype(np.int64).sum(1)
+    assert means.tobytes() == (s.astype(np.float32) / np.float32(192)).astype(np.float32).tobytes()
+
+
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "ipfcns")), reason="needs the reference checkout")
+@pytest.mark.parametrize("w", I.WIDTHS)
+def test_line_groups_equal_the_reference(w):
+    sys.path.insert(0, REFERENCE)
+    try:
+        import ipfcns.ipfcns as ref
+    finally:
+        sys.path.remove(REFERENCE)
+    imgs = pictures(2, 3 * w + 30, 3 * w + 33, 70 + w)
+    H, W = imgs.shape[1:3]
+    rng = np.random.default_rng(9 + w)
+    rows = np.concatenate(([0, H - 2 * w - 8], rng.integers(0, H - 2 * w - 7, 14)))
+    cols = np.concatenate(([W - 2 * w - 8, 0], rng.integers(0, W - 2 * w - 7, 14)))
+    ra, rl = ref.extract_pairs_groups_lines_from_channels(imgs, w, rows, cols)
+    ga, gl = I.extract_pairs_groups_lines_from_channels(imgs, w, rows, cols)
+    np.testing.assert_array_equal(ga, ra)
+    np.testing.assert_array_equal(gl, rl)
+
+
+def test_extraction_bad_arguments():
+    imgs = pictures(1, 40, 40, 1)
+    r = np.array([0, 4], dtype=np.int32)
+    with pytest.raises(TypeError):
+        I.extract_pairs_groups_lines_from_channels(imgs, 4, r.astype(np.float32), r)
+    with pytest.raises(TypeError):
+        I.extract_pairs_groups_lines_from_channels(imgs, 4, r, r.astype(np.float64))
+    with pytest.raises(ValueError, match="col_1sts.size"):
+        I.extract_pairs_groups_lines_from_channels(imgs, 4, r, r[:1])
+    with pytest.raises(ValueError, match="row_1st` is not positive"):
+        I.extract_pairs_groups_lines_from_channels(imgs, 4, np.array([-1, 0]), r)
+    with pytest.raises(ValueError, match="col_1st` is not positive"):
+        I.extract_pairs_groups_lines_from_channels(imgs, 4, r, np.array([0, -3]))
+    with pytest.raises(ValueError, match="row_1st \\+ 2\\*width_target \\+ 8"):
+        I.extract_pairs_groups_lines_from_channels(imgs, 4, np.array([0, 25]), r)
+    with pytest.raises(ValueError, match="col_1st \\+ 2\\*width_target \\+ 8"):
+        I.extract_pairs_groups_lines_from_channels(imgs, 4, r, np.array([0, 25]))
+    with pytest.raises(TypeError):
+        I.extract_pairs_groups_lines_from_channels(imgs.astype(np.float32), 4, r, r)
+    with pytest.raises(ValueError, match="does not belong to"):
+        I.extract_pairs_groups_lines_from_channels(np.repeat(imgs, 3, axis=3), 4, r, r)
+    with pytest.raises(TypeError):
+        I.extract_pair_groups_lines_from_channel(imgs[0].astype(np.int16), 4, 0, 0)
+    with pytest.raises(ValueError):
+        I.extract_pair_groups_lines_from_channel(imgs[0], -1, 0, 0)
+    with pytest.raises(ValueError):
+        I.layer_dims(64)
+    with pytest.raises(ValueError, match="divisible"):
+        I.predict_by_batch_via_ipfcns(np.zeros((10, 192), np.float32), None, 4, 4)
+    with pytest.raises(ValueError):
+        I.forward_host(recipe_params(4, 1)[:-1], 4, np.zeros((2, 192), np.float32))
+    with pytest.raises(ValueError):
+        I.forward_host(recipe_params(4, 1), 4, np.zeros((2, 191), np.float32))
+
+
+# ---- the host twin --------------------------------------------------------------------------------------------------------
+
+def layer_inputs(w, params, seed, n=48):
+    """Rows from pictures, all-equal lines (x = 0) and 0 / 255 extremes, preprocessed as the evaluator does."""
+    K = I.input_size(w)
+    imgs = pictures(1, 2 * w + 40, 2 * w + 40, seed)
+    rng = np.random.default_rng(seed)
+    rows = rng.integers(0, 33, n - 6).astype(np.int32)
+    cols = rng.integers(0, 33, n - 6).astype(np.int32)
+    x, _ = I.extract_pairs_groups_lines_from_channels_plus_preprocessing(imgs, w, rows, cols)
+    extra = np.zeros((6, K), dtype=np.uint8)
+    extra[1] = 255
+    extra[2, :K // 2] = 255
+    extra[3, ::2] = 255
+    extra[4, :8 * (2 * w + 8)] = 255                  # above group white, left group black
+    extra[5] = 77
+    a = extra[:, :8 * (2 * w + 8)].reshape(6, 8, 2 * w + 8, 1)
+    l_ = extra[:, 8 * (2 * w + 8):].reshape(6, 2 * w, 8, 1)
+    xe, _ = I.preprocess_pairs_groups_lines(a, l_)
+    return np.concatenate((x, xe))
+
+
+def check_layers(w, params, x):
+    """Layer l fed with the twin's own layer l - 1 output: |twin - f64| <= gamma_n (sum |w x| + |b|) + n eta, n = K + nseg + 1
+    (every one of the K chained roundings, nseg - 1 segment additions and the bias addition can err by u relative or eta
+    absolute), and behind the PReLU max(1, |a|) E + u |a| (|v| + E) + eta (the slope multiply; a sign flip near 0 is covered by
+    max(1, |a|))."""
+    prev = x
+    for l, (W, b, a) in enumerate(unpack(params, w)):
+        got = I.forward_host(params, w, x, layers=l + 1)
+        K = W.shape[1]
+        nseg = -(-(K // 16) // 20)
+        n = K + nseg + 1
+        gamma = n * U / (1 - n * U)
+        xd, Wd = prev.astype(np.float64), W.astype(np.float64)
+        v = xd @ Wd.T + b.astype(np.float64)
+        E = gamma * (np.abs(xd) @ np.abs(Wd).T + np.abs(b.astype(np.float64))) + n * ETA
+        if a is not None:
+            ad = a.astype(np.float64)
+            ref = np.where(v > 0, v, ad * v)
+            bound = np.maximum(1.0, np.abs(ad)) * E + U * np.abs(ad) * (np.abs(v) + E) + ETA
+        else:
+            ref, bound = v, E
+        err = np.abs(got.astype(np.float64) - ref)
+        assert got.dtype == np.float32 and got.shape == ref.shape
+        assert (err <= bound).all(), "w %d layer %d: worst error / bound = %g" % (w, l + 1, (err / bound).max())
+        prev = got
+
+
+@pytest.mark.parametrize("w", I.WIDTHS)
+def test_twin_per_layer_within_the_derived_bound(w):
+    params = recipe_params(w, 100 + w)
+    check_layers(w, params, layer_inputs(w, params, 200 + w))
+
+
+@pytest.mark.parametrize("w", (4, 16))
+def test_twin_per_layer_with_subnormal_products(w):
+    params = recipe_params(w, 300 + w)
+    K, H, O = I.layer_dims(w)
+    small = params.copy()
+    small[:H * K] *= np.float32(2.0 ** -125)         # fc1 products far below 2^-126
+    x = layer_inputs(w, params, 400 + w, n=16)
+    out = I.forward_host(small, w, x, layers=1)
+    check_layers(w, small, x)
+    prods = np.abs(x[:, :16].astype(np.float64)[:, None, :] * small[:16 * K].reshape(16, K)[None, :, :16].astype(np.float64))
+    assert ((prods > 0) & (prods < 2.0 ** -126)).any()
+    assert np.isfinite(out).all()
+
+
+def test_twin_bits_do_not_depend_on_the_batch():
+    w = 8
+    params = recipe_params(w, 17)
+    x = layer_inputs(w, params, 18, n=37)
+    full = I.forward_host(params, w, x)
+    for lo, hi in ((0, 1), (5, 13), (13, 37)):
+        assert I.forward_host(params, w, x[lo:hi]).tobytes() == full[lo:hi].tobytes()
+
+
+def end_to_end_blocks(w, n, seed):
+    """(uint8 pictures [1, H, W, 1], line origins) -- a natural window when the fixture exists, random pictures otherwise."""
+    nat = natural()
+    rng = np.random.default_rng(seed)
+    if nat is not None:
+        img = nat["kimono" if w == 4 else "cactus"][None, :, :, None]
+    else:
+        img = pictures(1, 768, 1152, seed)
+    H, W = img.shape[1:3]
+    rows = rng.integers(0, H - 3 * w - 8, n).astype(np.int32)
+    cols = rng.integers(0, W - 3 * w - 8, n).astype(np.int32)
+    return img, rows, cols
+
+
+@pytest.mark.parametrize("w,n", [(4, 16384), (8, 4096), (16, 2048), (32, 512)])
+def test_twin_end_to_end_against_float64(w, n):
+    """delta = 4 x max |numpy-f32 forward - f64 forward| (the reference's own kind of float32 arithmetic: Caffe ran sgemm);
+    max |twin - f64| <= delta; uint8 pixels whose f64 value lies farther than delta from a k + 0.5 boundary or a clip edge
+    match exactly, and such tie-exempt pixels are at most 0.1 % of all."""
+    params = recipe_params(w, 500 + w)
+    img, rows, cols = end_to_end_blocks(w, n, 600 + w)
+    x, means = I.extract_pairs_groups_lines_from_channels_plus_preprocessing(img, w, rows, cols)
+    twin = I.forward_host(params, w, x)
+    f64 = forward(params, w, x, np.float64)
+    f32 = forward(params, w, x, np.float32)
+    delta = 4.0 * np.abs(f32.astype(np.float64) - f64).max()
+    err = np.abs(twin.astype(np.float64) - f64).max()
+    print("w %d: delta %.3g, max |twin - f64| %.3g" % (w, delta, err))
+    assert err <= delta
+    pred64 = f64 + means.astype(np.float64)[:, None]
+    u8_twin = evaluation.cast_float_to_uint8(twin + means[:, None])
+    u8_64 = evaluation.cast_float_to_uint8(pred64)
+    frac = pred64 - np.floor(pred64)
+    exempt = (np.abs(frac - 0.5) <= delta) | (np.abs(pred64) <= delta) | (np.abs(pred64 - 255.0) <= delta)
+    share = exempt.mean()
+    print("w %d: %d tie-exempt pixels (%.4f %%), %d mismatches outside them" % (w, exempt.sum(), 100 * share,
+                                                                                 (u8_twin != u8_64)[~exempt].sum()))
+    assert share <= 0.001
+    np.testing.assert_array_equal(u8_twin[~exempt], u8_64[~exempt])
+
+
+@pytest.mark.skipif(not (os.path.exists(SIZE4) and os.path.exists(NATURAL)),
+                    reason="needs the reference checkout's trained 4x4 IPFCN-S and oracle/_ref/natural_luma.npz")
+def test_trained_size4_beats_the_constant_mean_predictor():
+    """The loader's [out][in] reading, which a float64 forward through the same loader cannot see: on 5 000 random blocks of
+    each natural window the twin's mean PSNR exceeds the constant-mean predictor's by >= 2 dB."""
+    w = 4
+    params = I.params_from_caffemodel(I.read_caffemodel(SIZE4), w)
+    nat = natural()
+    for name in ("cactus", "kimono", "parkscene"):
+        img = nat[name][None, :, :, None]
+        H, W = img.shape[1:3]
+        rng = np.random.default_rng(len(name))
+        rows = rng.integers(0, H - 2 * w - 8, 5000).astype(np.int32)
+        cols = rng.integers(0, W - 2 * w - 8, 5000).astype(np.int32)
+        x, means = I.extract_pairs_groups_lines_from_channels_plus_preprocessing(img, w, rows, cols)
+        pred = evaluation.cast_float_to_uint8(I.forward_host(params, w, x) + means[:, None]).reshape(-1, w, w)
+        flat = evaluation.cast_float_to_uint8(np.repeat(means[:, None], w * w, axis=1)).reshape(-1, w, w)
+        tg = img[0, rows[:, None, None] + 8 + np.arange(w)[None, :, None], cols[:, None, None] + 8 + np.arange(w)[None, None, :], 0]
+        p_net = np.mean([evaluation.compute_psnr(tg[i], pred[i]) for i in range(len(rows))])
+        p_flat = np.mean([evaluation.compute_psnr(tg[i], flat[i]) for i in range(len(rows))])
+        print("%s: IPFCN-S %.2f dB, constant mean %.2f dB" % (name, p_net, p_flat))
+        assert p_net >= p_flat + 2.0
