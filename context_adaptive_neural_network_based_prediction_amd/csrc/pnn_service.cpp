@@ -33,6 +33,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -331,6 +332,7 @@ struct Server {
     struct Flight {
         std::vector<Req> batch;
         std::vector<float> above, left;
+        std::vector<int> rc;                         // the code each request is answered with (worker(): a refused batch is re-issued in halves)
         bool any_f32 = false, any_pel = false;
         double waited = 0;                           // seconds the requests sat in the queue, summed
     };
@@ -424,7 +426,7 @@ struct Server {
         }
     }
     // the replies of one finished batch to the I/O threads that own the connections, and the statistics
-    void reply(int k, Flight& f, int rc, const int32_t* dst, const float* out, double busy)
+    void reply(int k, Flight& f, long issued, const int32_t* dst, const float* out, double busy)
     {
         const size_t n = f.batch.size(), w2 = (size_t)f.batch[0].width * f.batch[0].width;
         const int wi = nworkers == 1 ? k : widx(f.batch[0].width);   // the statistics are kept per WIDTH (two widths may share a worker thread)
@@ -434,6 +436,7 @@ struct Server {
         double shm_resident = 0;
         long shm_n = 0;
         for (size_t i = 0; i < n; i++) {
+            const int rc = f.rc[i];
             const RspHeader rh{rc, rc == 0 ? (uint32_t)w2 : 0u};
             if (f.batch[i].shm) {                      // into the client's slot, by this thread: values, header, state, wake-up
                 ShmSlot* sl = f.batch[i].shm->slot;
@@ -472,8 +475,8 @@ struct Server {
         const uint64_t one = 1;
         for (int t = 0; t < nio; t++) if (woke[t]) (void)!write(wake_fd[t], &one, 8);
         std::lock_guard<std::mutex> lk(mu);
-        served += (long)n; ++calls; largest = std::max<long>(largest, (long)n);
-        ++calls_w[wi]; served_w[wi] += (long)n; busy_s[wi] += busy; wait_s[wi] += f.waited;
+        served += (long)n; calls += issued; largest = std::max<long>(largest, (long)n);
+        calls_w[wi] += issued; served_w[wi] += (long)n; busy_s[wi] += busy; wait_s[wi] += f.waited;
         shm_resident_s[wi] += shm_resident; shm_resident_n[wi] += shm_n;
     }
     // Blocks until worker k has something to do (false: the server stops).  An idle worker sleeps on its doorbell (a futex word the
@@ -538,6 +541,7 @@ struct Server {
         Flight f;
         std::vector<float> out;
         std::vector<int32_t> dst;
+        std::vector<std::pair<size_t, size_t>> todo;  // ranges [lo, hi) of the batch still to be issued
         for (;;) {
             if (!wait_for_work(k, f.batch)) return;
             if (f.batch.empty()) continue;
@@ -546,10 +550,38 @@ struct Server {
             const size_t n = f.batch.size(), w2 = (size_t)w * w;
             if (f.any_pel) dst.resize(n * w2);
             if (f.any_f32) out.resize(n * w2);
+            const size_t na = f.batch[0].na, nl = f.batch[0].nl;
             const auto tb0 = Clock::now();
-            const int rc = backend(users[widx(w)][r], w, f.above.data(), f.left.empty() ? nullptr : f.left.data(), (int)n, f.any_pel ? dst.data() : nullptr,
-                                   f.any_f32 ? out.data() : nullptr);
-            reply(k, f, rc, dst.data(), out.data(), std::chrono::duration<double>(Clock::now() - tb0).count());
+            // Every request gets the code a call of its own would have got (pnn_service.h, "Errors stay with their owner"): the batch is
+            // ONE backend call, and when that call is refused for its arguments (PNN_E_ARG: pnn_predict_f32_pel refuses a call that holds a
+            // non-finite input, before anything reaches the GPU) its two halves are issued in its place, down to single requests -- the
+            // offender alone keeps the refusal.  Any other failure (PNN_E_HIP first of all) is never retried: it is the answer of every
+            // request of the batch that has none yet, and nothing more is issued for the batch.
+            f.rc.assign(n, PNN_OK);
+            long issued = 0;
+            int fatal = PNN_OK;
+            todo.clear();
+            todo.emplace_back((size_t)0, n);
+            while (!todo.empty()) {
+                const size_t lo = todo.back().first, hi = todo.back().second;
+                todo.pop_back();
+                int rc = fatal;
+                if (rc == PNN_OK) {
+                    ++issued;
+                    rc = backend(users[widx(w)][r], w, f.above.data() + lo * na, nl ? f.left.data() + lo * nl : nullptr, (int)(hi - lo),
+                                 f.any_pel ? dst.data() + lo * w2 : nullptr, f.any_f32 ? out.data() + lo * w2 : nullptr);
+                    if (rc == PNN_OK) continue;
+                    if (rc == PNN_E_ARG && hi - lo > 1) {
+                        const size_t mid = lo + (hi - lo) / 2;
+                        todo.emplace_back(mid, hi);
+                        todo.emplace_back(lo, mid);
+                        continue;
+                    }
+                    if (rc != PNN_E_ARG) fatal = rc;
+                }
+                std::fill(f.rc.begin() + (long)lo, f.rc.begin() + (long)hi, rc);
+            }
+            reply(k, f, issued, dst.data(), out.data(), std::chrono::duration<double>(Clock::now() - tb0).count());
         }
     }
 

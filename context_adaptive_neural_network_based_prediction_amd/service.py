@@ -37,8 +37,10 @@ class Server:
                 a = np.ctypeslib.as_array(above, shape=(n, na))
                 l = np.ctypeslib.as_array(left, shape=(n, 2 * w2)) if left else None
                 try:
-                    # a stand-in backend returns the Pel blocks, or (Pel blocks, float predictions)
+                    # a stand-in backend returns the Pel blocks, or (Pel blocks, float predictions), or a negative code of pnn_hip.h
                     res = backend(width, a, l)
+                    if isinstance(res, int):
+                        return res
                     pel, f32 = res if isinstance(res, tuple) else (res, np.asarray(res, np.float32))
                     if dst:
                         np.ctypeslib.as_array(dst, shape=(n, width, width))[...] = pel
@@ -60,10 +62,13 @@ class Server:
         self._thread = threading.Thread(target=run, daemon=True)
         self._thread.start()
 
-    def stop(self):
-        """Stops the loop and returns {"requests", "backend_calls", "largest_batch", "clients"}."""
+    def stop(self, timeout=None):
+        """Stops the loop and returns {"requests", "backend_calls", "largest_batch", "clients"}; TimeoutError when the loop has not
+        ended `timeout` seconds later (None: wait for it)."""
         self._stop.value = 1
-        self._thread.join()
+        self._thread.join(timeout)
+        if self._thread.is_alive():
+            raise TimeoutError("the PNN service loop did not end within %s s" % timeout)
         s = self._stats
         return {"requests": s[0], "backend_calls": s[1], "largest_batch": s[2], "clients": s[3]}
 
@@ -113,6 +118,14 @@ class Client:
         if rc != 0:
             raise _lib.PnnError("service returned %d" % rc)
         return buf.value.decode()
+
+    def cache_stats(self):
+        """(hits, misses) of this client's prediction cache (`pnn_client_cache_stats`; $PNN_CACHE_MB, read at connect)."""
+        h, m = ctypes.c_long(), ctypes.c_long()
+        rc = self._L.pnn_client_cache_stats(self._c, ctypes.byref(h), ctypes.byref(m))
+        if rc != 0:
+            raise _lib.PnnError("pnn_client_cache_stats returned %d" % rc)
+        return h.value, m.value
 
     def close(self):
         if self._c:

@@ -7,6 +7,14 @@
  * issue locally; the server coalesces the requests of one width that are pending at the same time into ONE batched
  * pnn_predict_pel call and routes the results back.  Blocking, one outstanding request per client -- exactly HM's
  * calling pattern.  Same error conventions as pnn_hip.h (0 / negative, nothing throws).
+ *
+ * Errors stay with their owner: every request is answered with the code the same single-block call would have returned locally,
+ * whatever batch it travelled in.  A coalesced batch is one backend call; when that call is refused for its arguments (PNN_E_ARG:
+ * pnn_predict_f32_pel refuses a call that holds a non-finite input, on the host, before anything reaches the GPU) the worker issues
+ * its two halves in its place, and theirs in turn, down to single requests -- the requests beside the offender get their
+ * predictions, the offender alone gets PNN_E_ARG (one bad request among n costs at most 2 log2(n) + 1 extra calls; a campaign never
+ * takes this path).  Every other failure -- PNN_E_HIP first of all -- is never retried: it is the answer of every request of the
+ * batch that has none yet, and nothing more is issued for that batch.  The statistics count the backend calls actually made.
  */
 #ifndef PNN_SERVICE_H
 #define PNN_SERVICE_H
