@@ -429,6 +429,7 @@ void pnn_destroy(pnn_ctx* c)
     for (Model*& m : c->ipfcns) { free_model(m); m = nullptr; }
     for (DevBuf& b : c->ws) if (b.p) (void)hipFree(b.p);
     for (DevBuf& b : c->ipfcns_ws) if (b.p) (void)hipFree(b.p);
+    for (DevBuf& b : c->score_ws) if (b.p) (void)hipFree(b.p);
     for (DevBuf& b : c->stage_in) if (b.p) (void)hipFree(b.p);
     for (DevBuf& b : c->stage_out) if (b.p) (void)hipFree(b.p);
     if (c->stage_tbs.p) (void)hipFree(c->stage_tbs.p);
@@ -577,23 +578,18 @@ int pnn_gather_device(pnn_ctx* c, int width, int unit, const void* d_plane, int 
     return PNN_OK;
 }
 
-int pnn_predict_tbs_device(pnn_ctx* c, int width, const void* d_plane, int pel_bytes, const pnn_tb_dev* d_tbs, int n,
-                           int32_t* d_dst, float* d_out_f32, void* stream)
+// gather -> net for n TBs of model m, in slices of chunk_blocks: what pnn_predict_tbs_device enqueues
+static int tbs_pass(pnn_ctx* c, Model* m, const void* d_plane, int pel_bytes, const pnn_tb_dev* d_tbs, long n, int32_t* d_dst,
+                    float* d_out_f32, hipStream_t s)
 {
     int rc;
-    Model* m = model_for(c, width, -1, &rc);
-    if (!m) return rc;
-    if (n < 0 || (n > 0 && (!d_plane || !d_tbs || (!d_dst && !d_out_f32)))) return fail(c, PNN_E_ARG, "bad buffers / batch size");
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = pending_range_error(c))) return rc;
-    reset_stats(c);
-    hipStream_t s = (hipStream_t)stream;
+    const int width = m->width;
     const long w2 = (long)width * width;
-    const long chunk = std::min((long)n, chunk_blocks(c, m));
+    const long chunk = std::min(n, chunk_blocks(c, m));
     if ((rc = dev_reserve(c, c->stage_in[0], (size_t)chunk * 5 * w2 * 4))) return rc;
     float* ctxbuf = (float*)c->stage_in[0].p;
     for (long b0 = 0; b0 < n; b0 += chunk) {
-        const long nb = std::min(chunk, (long)n - b0);
+        const long nb = std::min(chunk, n - b0);
         float* ab = ctxbuf;
         float* lf = m->is_fc ? ctxbuf + 3 * w2 : ctxbuf + nb * 3 * w2;
         const long pa = m->is_fc ? 5 * w2 : 3 * w2, pl = m->is_fc ? 5 * w2 : 2 * w2;
@@ -615,6 +611,19 @@ int pnn_predict_tbs_device(pnn_ctx* c, int width, const void* d_plane, int pel_b
         if (rc) return rc;
     }
     return PNN_OK;
+}
+
+int pnn_predict_tbs_device(pnn_ctx* c, int width, const void* d_plane, int pel_bytes, const pnn_tb_dev* d_tbs, int n,
+                           int32_t* d_dst, float* d_out_f32, void* stream)
+{
+    int rc;
+    Model* m = model_for(c, width, -1, &rc);
+    if (!m) return rc;
+    if (n < 0 || (n > 0 && (!d_plane || !d_tbs || (!d_dst && !d_out_f32)))) return fail(c, PNN_E_ARG, "bad buffers / batch size");
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = pending_range_error(c))) return rc;
+    reset_stats(c);
+    return tbs_pass(c, m, d_plane, pel_bytes, d_tbs, n, d_dst, d_out_f32, (hipStream_t)stream);
 }
 
 int pnn_block_cost_device(pnn_ctx* c, int width, const void* d_org_plane, int pel_bytes, const pnn_tb_dev* d_tbs, int n,
@@ -646,6 +655,7 @@ int pnn_hevc_best_mode_device(pnn_ctx* c, int width, const uint8_t* d_patterns, 
     HevcBestModeParams p;
     p.patterns = d_patterns; p.ph = pattern_h; p.pw = pattern_w; p.targets = d_targets; p.N = n; p.w = width;
     p.best_mode = d_best_mode; p.best_sse = d_best_sse; p.best_pred = d_best_pred; p.mode_sse = d_mode_sse;
+    p.pic = PictureBlocks{};
     HIPCHK(c, launch_hevc_best_mode(p, (hipStream_t)stream));
     return PNN_OK;
 }
@@ -743,6 +753,118 @@ int pnn_ipfcns_predict_device(pnn_ctx* c, int width, const uint8_t* d_channels, 
         HIPCHK(c, launch_ipfcns_epilogue(e, s));
         c->stat_launches += 2;
     }
+    return PNN_OK;
+}
+
+// Arguments common to the two scoring entries, checked before any launch; the positions are read back once (the call waits for the stream).
+static int check_picture_blocks(pnn_ctx* c, int width, const uint8_t* d_channels, int images, int height, int width_ch,
+                                const int32_t* d_rows, const int32_t* d_cols, int positions, hipStream_t s)
+{
+    if (!d_channels || !d_rows || !d_cols) return fail(c, PNN_E_ARG, "NULL input buffers");
+    std::vector<int32_t> rows(positions), cols(positions);
+    {
+        PNN_UNSAFE_CALLS_GUARD;
+        HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(cols.data(), d_cols, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    for (int i = 0; i < positions; i++)
+        if (rows[i] < 0 || cols[i] < 0 || (long)rows[i] + 3 * width > height || (long)cols[i] + 3 * width > width_ch)
+            return fail(c, PNN_E_ARG, "position %d (%d, %d): the %dx%d context leaves the %dx%d picture", i, rows[i], cols[i], 3 * width,
+                        3 * width, height, width_ch);
+    return PNN_OK;
+}
+
+int pnn_score_pictures_device(pnn_ctx* c, int width, const uint8_t* d_channels, int images, int height, int width_ch,
+                              const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w, int mask_h,
+                              uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
+                              uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    const int idx = width_index(width);
+    if (idx < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
+    if (mask_w < 0 || mask_w > width || mask_w % 4 || mask_h < 0 || mask_h > width || mask_h % 4)
+        return fail(c, PNN_E_ARG, "masks (%d, %d): both must belong to {0, 4, ..., %d}", mask_w, mask_h, width);
+    if (images < 0 || positions < 0 || height < 0 || width_ch < 0) return fail(c, PNN_E_ARG, "negative sizes");
+    const bool want_pnn = d_pnn_u8 || d_pnn_f32 || d_pnn_sse, want_hevc = d_hevc_mode || d_hevc_sse || d_hevc_pred;
+    if (!d_targets && !want_pnn && !want_hevc) return fail(c, PNN_E_ARG, "every output is NULL");
+    Model* m = want_pnn ? c->models[idx] : nullptr;
+    if (want_pnn && !m) return fail(c, PNN_E_ARG, "a PNN output is asked for, but no model is loaded for width %d", width);
+    const long n = (long)images * positions;
+    if (n > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks");
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = check_picture_blocks(c, width, d_channels, images, height, width_ch, d_rows, d_cols, positions, s))) return rc;
+    if (want_pnn && (rc = pending_range_error(c))) return rc;
+    reset_stats(c);
+    PictureBlocks pic;
+    pic.channels = d_channels; pic.H = height; pic.W = width_ch; pic.rows = d_rows; pic.cols = d_cols; pic.positions = positions;
+    const long w2 = (long)width * width;
+    // the PNN half in slices (descriptors -> gather -> net -> epilogue); the bits of a block do not depend on its slice
+    const long chunk = want_pnn ? std::min(n, chunk_blocks(c, m)) : n;
+    float* ws_f32 = nullptr;
+    if (want_pnn) {
+        if ((rc = dev_reserve(c, c->score_ws[0], (size_t)chunk * sizeof(TbDev)))) return rc;
+        if (!d_pnn_f32) {
+            if ((rc = dev_reserve(c, c->score_ws[1], (size_t)chunk * w2 * 4))) return rc;
+            ws_f32 = (float*)c->score_ws[1].p;
+        }
+    }
+    for (long b0 = 0; b0 < n && (want_pnn || d_targets); b0 += chunk) {
+        const int nb = (int)std::min(chunk, n - b0);
+        float* pred = nullptr;
+        if (want_pnn) {
+            ScoreDescParams d;
+            d.pic = pic; d.b0 = b0; d.nb = nb; d.w = width; d.mask_w = mask_w; d.mask_h = mask_h; d.tbs = (TbDev*)c->score_ws[0].p;
+            HIPCHK(c, launch_score_desc(d, s));
+            pred = d_pnn_f32 ? d_pnn_f32 + b0 * w2 : ws_f32;
+            if ((rc = tbs_pass(c, m, d_channels, 1, (const pnn_tb_dev*)c->score_ws[0].p, nb, nullptr, pred, s))) return rc;
+            c->stat_launches++;
+        }
+        if (d_targets || d_pnn_u8 || d_pnn_sse) {
+            ScoreEpilogueParams e;
+            e.pic = pic; e.b0 = b0; e.nb = nb; e.w = width; e.pred = pred; e.mean = c->mean;
+            e.u8 = d_pnn_u8 ? d_pnn_u8 + b0 * w2 : nullptr; e.targets = d_targets ? d_targets + b0 * w2 : nullptr;
+            e.sse = d_pnn_sse ? d_pnn_sse + b0 : nullptr;
+            HIPCHK(c, launch_score_epilogue(e, s));
+            c->stat_launches++;
+        }
+    }
+    if (want_hevc) {
+        HevcBestModeParams p;
+        p.patterns = nullptr; p.ph = 2 * width + 1 - mask_h; p.pw = 2 * width + 1 - mask_w; p.targets = nullptr; p.N = (int)n; p.w = width;
+        p.best_mode = d_hevc_mode; p.best_sse = d_hevc_sse; p.best_pred = d_hevc_pred; p.mode_sse = nullptr;
+        p.pic = pic;
+        HIPCHK(c, launch_hevc_best_mode(p, s));
+        c->stat_launches++;
+    }
+    return PNN_OK;
+}
+
+int pnn_score_f32_device(pnn_ctx* c, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,
+                         int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, uint8_t* d_pred_u8,
+                         uint32_t* d_sse, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (width_index(width) < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
+    if (images < 0 || positions < 0 || height < 0 || width_ch < 0) return fail(c, PNN_E_ARG, "negative sizes");
+    if (!d_pred_u8 && !d_sse) return fail(c, PNN_E_ARG, "every output is NULL");
+    const long n = (long)images * positions;
+    if (n > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks");
+    if (n == 0) return PNN_OK;
+    if (!d_pred_f32) return fail(c, PNN_E_ARG, "NULL input buffers");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = check_picture_blocks(c, width, d_channels, images, height, width_ch, d_rows, d_cols, positions, s))) return rc;
+    reset_stats(c);
+    ScoreEpilogueParams e;
+    e.pic.channels = d_channels; e.pic.H = height; e.pic.W = width_ch; e.pic.rows = d_rows; e.pic.cols = d_cols; e.pic.positions = positions;
+    e.b0 = 0; e.nb = (int)n; e.w = width; e.pred = d_pred_f32; e.mean = c->mean; e.u8 = d_pred_u8; e.targets = nullptr; e.sse = d_sse;
+    HIPCHK(c, launch_score_epilogue(e, s));
+    c->stat_launches++;
     return PNN_OK;
 }
 

@@ -114,6 +114,7 @@ struct pnn_ctx {
     pnn::Model* models[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     pnn::Model* ipfcns[4] = {nullptr, nullptr, nullptr, nullptr};   // IPFCN-S nets of widths 4, 8, 16, 32 (pnn_ipfcns_load)
     pnn::DevBuf ipfcns_ws[4];                              // ... their pass: rows, hidden activations (two), means + fc4 outputs
+    pnn::DevBuf score_ws[2];                               // pnn_score_pictures_device: a slice's descriptors, its float predictions
     pnn::DevBuf ws[6];                                     // P0, P1, F0, F1 (FC uses P0, P1); P2, P3: the left branch's own pair when the branches overlap
     // Small conv passes (the in-loop single-block calls): the two branches are independent chains of 4-5 launches that
     // each fill a fraction of the chip; the left branch runs on a side stream, forked and joined by events.

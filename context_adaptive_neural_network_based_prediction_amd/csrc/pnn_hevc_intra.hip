@@ -12,6 +12,8 @@
 // rows, partial SSEs added with LDS integer atomics (exact in any order).  The angular prediction is the closed form of
 // refMain: index k >= 0 reads the main reference, k < 0 the side one at (128 - k * invAngle) >> 8, as HM's projection loop fills it.
 // Then one lane per block picks the best mode and the workgroup recomputes that mode's prediction only if it is asked for.
+// The staging loops have a second source: the evaluator's pictures themselves (PIC), 4w + 1 + w^2 bytes per block instead of a
+// dense (2w + 1)^2 pattern and a target copy; everything after the staging is shared.
 #include "pnn_kernels.h"
 
 namespace pnn {
@@ -100,7 +102,16 @@ __device__ inline unsigned angular_rows_sse(const int* rf, const uint8_t* tg, in
     return acc;
 }
 
-template <int W>
+// offset of the top-left pixel of block b's context square from the first picture (b = image * positions + position)
+__device__ inline size_t picture_corner(const PictureBlocks& pic, long b)
+{
+    const long img = b / pic.positions;
+    const int pos = (int)(b - img * pic.positions);
+    return ((size_t)img * pic.H + pic.rows[pos]) * pic.W + pic.cols[pos];
+}
+
+// PIC = false: reference samples from dense intra patterns, targets from their own array; true: both from the pictures (p.pic)
+template <int W, bool PIC>
 __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBestModeParams p)
 {
     constexpr int R = W <= 8 ? W : 4, RG = W / R, G = 64 / RG;    // rows per lane, lanes per block, blocks per workgroup
@@ -109,21 +120,36 @@ __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBest
     __shared__ uint8_t tgt[G * TS];
     __shared__ unsigned sse[G * 35];
     __shared__ int dcv[G], best[G];
+    __shared__ size_t corner[PIC ? G : 1];
     const int tid = threadIdx.x;
     const long blk0 = (long)blockIdx.x * G;
 
+    if (PIC) {
+        if (tid < G && blk0 + tid < p.N) corner[tid] = picture_corner(p.pic, blk0 + tid);
+        __syncthreads();
+    }
     for (int i = tid; i < G * RS; i += kThreads) {
         const int g = i / RS, j = i % RS - 2 * W;
         int v = 0;
         if (blk0 + g < p.N) {
-            const uint8_t* pat = p.patterns + (size_t)(blk0 + g) * p.ph * p.pw;
-            v = j >= 0 ? pat[min(j, p.pw - 1)] : pat[min(-j, p.ph - 1) * p.pw];
+            if (PIC) {                                 // the dense form's padding rule in picture coordinates: inside the block's 3w x 3w context square
+                const uint8_t* pat = p.pic.channels + corner[g] + (size_t)(W - 1) * p.pic.W + W - 1;
+                v = j >= 0 ? pat[min(j, p.pw - 1)] : pat[(size_t)min(-j, p.ph - 1) * p.pic.W];
+            } else {
+                const uint8_t* pat = p.patterns + (size_t)(blk0 + g) * p.ph * p.pw;
+                v = j >= 0 ? pat[min(j, p.pw - 1)] : pat[min(-j, p.ph - 1) * p.pw];
+            }
         }
         ref[i] = v;
     }
     for (int i = tid; i < G * W * W; i += kThreads) {
         const int g = i / (W * W), e = i % (W * W);
-        tgt[g * TS + e] = blk0 + g < p.N ? p.targets[(size_t)(blk0 + g) * W * W + e] : 0;
+        int v = 0;
+        if (blk0 + g < p.N) {
+            if (PIC) v = p.pic.channels[corner[g] + (size_t)(W + e / W) * p.pic.W + W + e % W];
+            else v = p.targets[(size_t)(blk0 + g) * W * W + e];
+        }
+        tgt[g * TS + e] = (uint8_t)v;
     }
     for (int i = tid; i < G * 35; i += kThreads) sse[i] = 0;
     __syncthreads();
@@ -190,14 +216,16 @@ hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s)
     if (p.N <= 0) return hipSuccess;
     const int rows_per_lane = p.w <= 8 ? p.w : 4, blocks_per_wg = 64 / (p.w / rows_per_lane);
     const dim3 grid((unsigned)((p.N + blocks_per_wg - 1) / blocks_per_wg)), block(kThreads);
+    const bool pic = p.patterns == nullptr;
+#define PNN_HEVC_LAUNCH(W_) \
+    case W_: if (pic) hipLaunchKernelGGL((hevc_best_mode_kernel<W_, true>), grid, block, 0, s, p); \
+             else hipLaunchKernelGGL((hevc_best_mode_kernel<W_, false>), grid, block, 0, s, p); \
+             break;
     switch (p.w) {
-    case 4: hipLaunchKernelGGL(hevc_best_mode_kernel<4>, grid, block, 0, s, p); break;
-    case 8: hipLaunchKernelGGL(hevc_best_mode_kernel<8>, grid, block, 0, s, p); break;
-    case 16: hipLaunchKernelGGL(hevc_best_mode_kernel<16>, grid, block, 0, s, p); break;
-    case 32: hipLaunchKernelGGL(hevc_best_mode_kernel<32>, grid, block, 0, s, p); break;
-    case 64: hipLaunchKernelGGL(hevc_best_mode_kernel<64>, grid, block, 0, s, p); break;
+    PNN_HEVC_LAUNCH(4) PNN_HEVC_LAUNCH(8) PNN_HEVC_LAUNCH(16) PNN_HEVC_LAUNCH(32) PNN_HEVC_LAUNCH(64)
     default: return hipErrorInvalidValue;
     }
+#undef PNN_HEVC_LAUNCH
     return hipGetLastError();
 }
 

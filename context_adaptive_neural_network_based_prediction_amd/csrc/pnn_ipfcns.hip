@@ -4,7 +4,10 @@
 //   ipfcns_gather_kernel    uint8 picture -> the two groups of reference lines minus their mean (ipfcns.py:97-494)
 //   ipfcns_prelu_kernel     Caffe PReLU, one slope per channel, in place
 //   ipfcns_epilogue_kernel  + mean, clip, rint (half to even, tools.cast_float_to_uint8), optional f32 copy and per-block SSE
-// One wave per block in the gather and the epilogue (K <= 1088, w^2 <= 1024 values), four waves per workgroup.  All plain f32
+// ... and the two element-wise kernels of the evaluator's scoring path from pictures (pnn_score_pictures_device):
+//   score_desc_kernel       (picture, position, masks) -> the gather's descriptor of every block
+//   score_epilogue_kernel   the same uint8 rule on any predictor's floats, with the target read from the picture
+// One wave per block in the gather and the epilogues (K <= 1088, w^2 <= 4096 values), four waves per workgroup.  All plain f32
 // operations: nothing here can contract (a subtraction, an addition, one multiply, a division by __fdiv_rn).
 #include "pnn_kernels.h"
 
@@ -82,6 +85,51 @@ __global__ __launch_bounds__(64 * kWaves) void ipfcns_epilogue_kernel(const Ipfc
     }
 }
 
+__global__ __launch_bounds__(256) void score_desc_kernel(const ScoreDescParams p)
+{
+    const long bb = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (bb >= p.nb) return;
+    const long gb = p.b0 + bb;
+    const long img = gb / p.pic.positions;
+    const int pos = (int)(gb - img * p.pic.positions);
+    const int units = 2 * p.w / 4;
+    TbDev d;
+    d.origin = (img * p.pic.H + p.pic.rows[pos] + p.w) * p.pic.W + p.pic.cols[pos] + p.w;
+    d.stride = p.pic.W;
+    d.above_mask = (uint32_t)((1ull << (units - p.mask_w / 4)) - 1ull);    // 64 bits: the count is 32 at w = 64 without a mask
+    d.left_units = units - p.mask_h / 4;
+    d.reserved = 0;
+    p.tbs[bb] = d;
+}
+
+__global__ __launch_bounds__(64 * kWaves) void score_epilogue_kernel(const ScoreEpilogueParams p)
+{
+    const int lane = threadIdx.x & 63;
+    const long bb = (long)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    if (bb >= p.nb) return;
+    const long gb = p.b0 + bb;
+    const long img = gb / p.pic.positions;
+    const int pos = (int)(gb - img * p.pic.positions);
+    const uint8_t* tg = p.pic.channels + ((size_t)img * p.pic.H + p.pic.rows[pos] + p.w) * p.pic.W + p.pic.cols[pos] + p.w;
+    const int w2 = p.w * p.w;
+    const size_t o = (size_t)bb * w2;
+    int acc = 0;
+    for (int e = lane; e < w2; e += 64) {
+        const int t = tg[(size_t)(e / p.w) * p.pic.W + e % p.w];
+        if (p.targets) p.targets[o + e] = (uint8_t)t;
+        if (!p.pred) continue;
+        const float v = __fadd_rn(p.pred[o + e], p.mean);
+        const int q = (int)rintf(fminf(fmaxf(v, 0.f), 255.f));
+        if (p.u8) p.u8[o + e] = (uint8_t)q;
+        const int d = q - t;
+        acc += d * d;
+    }
+    if (p.sse) {
+        acc = wave_sum(acc);                           // <= 65025 * 4096 < 2^31
+        if (lane == 0) p.sse[bb] = (uint32_t)acc;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_ipfcns_gather(const IpfcnsGatherParams& p, hipStream_t s)
@@ -106,6 +154,21 @@ hipError_t launch_ipfcns_epilogue(const IpfcnsEpilogueParams& p, hipStream_t s)
     if (p.nb <= 0) return hipSuccess;
     if (p.sse && !p.targets) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ipfcns_epilogue_kernel, dim3((unsigned)((p.nb + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_desc(const ScoreDescParams& p, hipStream_t s)
+{
+    if (p.nb <= 0) return hipSuccess;
+    hipLaunchKernelGGL(score_desc_kernel, dim3((unsigned)((p.nb + 255) / 256)), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_epilogue(const ScoreEpilogueParams& p, hipStream_t s)
+{
+    if (p.nb <= 0) return hipSuccess;
+    if ((p.u8 || p.sse) && !p.pred) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(score_epilogue_kernel, dim3((unsigned)((p.nb + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, s, p);
     return hipGetLastError();
 }
 

@@ -256,11 +256,20 @@ struct BlockCostParams {
 };
 hipError_t launch_block_cost(const BlockCostParams& p, hipStream_t s);
 
+// Blocks of the evaluator's pictures (pnn_score_pictures_device): uint8 pictures [images][H][W], context corners (rows[pos], cols[pos])
+// of `positions` positions, block b = image * positions + pos.  The block's 3w x 3w context square starts at its corner, its w x w
+// target at (row + w, col + w).  The caller has checked that every square lies inside the picture.
+struct PictureBlocks {
+    const uint8_t* channels; int H, W; const int32_t* rows; const int32_t* cols; int positions;
+};
+
 // HEVC best intra mode (pnn_hevc_intra.hip): N intra patterns [N][ph][pw] (first row and column used) and targets [N][w][w], all uint8;
-// any of the four outputs may be NULL.
+// any of the four outputs may be NULL.  With patterns == NULL the reference samples and the targets of block b come from `pic`
+// instead: the pattern's first row and column start at (row + w - 1, col + w - 1), ph and pw say how much of them is not masked.
 struct HevcBestModeParams {
     const uint8_t* patterns; int ph; int pw; const uint8_t* targets; int N; int w;
     uint8_t* best_mode; uint32_t* best_sse; uint8_t* best_pred; uint32_t* mode_sse;
+    PictureBlocks pic;
 };
 hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s);
 
@@ -281,6 +290,20 @@ struct IpfcnsEpilogueParams {
     const float* fc4; const float* mean; int nb; int w2; uint8_t* u8; float* f32; const uint8_t* targets; uint32_t* sse;
 };
 hipError_t launch_ipfcns_epilogue(const IpfcnsEpilogueParams& p, hipStream_t s);
+
+// Picture scoring (pnn_ipfcns.hip), blocks b0 .. b0 + nb - 1 of `pic`; every output pointer addresses block b0.
+// Descriptors of the blocks' L-shaped contexts, as context.py builds them: origin = (image * H + row + w) * W + col + w (the target's
+// top-left pixel), stride = W, above_mask = 2^(units - mask_w / 4) - 1 (units = 2w / 4; all 32 bits at w = 64 without a mask),
+// left_units = units - mask_h / 4.
+struct ScoreDescParams { PictureBlocks pic; long b0; int nb; int w; int mask_w, mask_h; TbDev* tbs; };
+hipError_t launch_score_desc(const ScoreDescParams& p, hipStream_t s);
+// Score epilogue: q = rint(clip(fl32(pred + mean), 0, 255)) (half to even) against the target read from the picture.  Each of u8
+// [nb][w][w], targets [nb][w][w] (a copy of the picture's) and sse [nb] (uint32, exact) is optional; pred [nb][w][w] may be NULL
+// when only the targets are wanted.
+struct ScoreEpilogueParams {
+    PictureBlocks pic; long b0; int nb; int w; const float* pred; float mean; uint8_t* u8; uint8_t* targets; uint32_t* sse;
+};
+hipError_t launch_score_epilogue(const ScoreEpilogueParams& p, hipStream_t s);
 
 // Stand-alone HM epilogue for float predictions.
 hipError_t launch_epilogue(const float* pred, long n, float mean, int32_t* dst, hipStream_t s);

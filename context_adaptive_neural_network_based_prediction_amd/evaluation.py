@@ -6,10 +6,15 @@ PSNR definitions.  predict_mask_vs_hevc_best_mode adds the paper's competitor, t
 dictionary_performance (indices and PSNRs of the best mode, PNN PSNRs, PNN's win frequency, its mean PSNR).
 predict_mask_vs_hevc_best_mode_and_ipfcns adds the third column, IPFCN-S (ipfcns.py: line gather, the four layers and the
 uint8 epilogue with the per-block SSE in one GPU call), as the reference does only when nothing is masked.
+score_masks_from_pictures is the reference's loop over a list of masks (predict_masks, :324-452) on pictures that stay on the
+GPU: per mask one pnn_score_pictures_device call (descriptors, PNN pass, uint8 epilogue with its SSE, best-mode search from
+the pictures) and one download; the same dictionaries as predict_mask_vs_hevc_best_mode[_and_ipfcns], bit for bit.
 """
+import ctypes
+
 import numpy as np
 
-from . import context, intraprediction
+from . import _lib, context, intraprediction
 from .prediction_neural_network import predict_by_batch_via_pnn
 
 
@@ -132,3 +137,134 @@ def predict_mask_vs_hevc_best_mode_and_ipfcns(channels_uint8, width_target, row_
         predict_without_mask_via_ipfcns(channels_uint8, width_target, row_1sts, col_1sts, batch_size, net_ipfcns,
                                         dictionary_performance)
     return dictionary_performance
+
+
+def context_descriptor_fields(width_target, height, width, index_image, row_1st, col_1st, tuple_width_height_masks):
+    """The pnn_tb_dev fields of one block (context.py's descriptor loop; what the descriptor kernel of pnn_score_pictures_device
+    writes): {'origin', 'stride', 'above_mask', 'left_units'} for the target whose context starts at (row_1st, col_1st) of image
+    `index_image` in pictures of height x width.  With units = 2w / 4: origin = (index_image * height + row_1st + w) * width +
+    col_1st + w, stride = width, above_mask = 2^(units - mask_w / 4) - 1 (0xFFFFFFFF at w = 64 without a mask: a 32-bit shift
+    by 32 would not give that), left_units = units - mask_h / 4.  Raises context.py's ValueError for a mask outside {0, 4, ..., w}."""
+    w = width_target
+    (mask_w, mask_h) = tuple_width_height_masks
+    if mask_w < 0 or mask_w > w or mask_w % 4 != 0:
+        raise ValueError('`tuple_width_height_masks[0]` does not belong to {0, 4, ..., `targets_uint8.shape[1]`}.')
+    if mask_h < 0 or mask_h > w or mask_h % 4 != 0:
+        raise ValueError('`tuple_width_height_masks[1]` does not belong to {0, 4, ..., `targets_uint8.shape[1]`}.')
+    units = 2 * w // 4
+    return {'origin': (int(index_image) * int(height) + int(row_1st) + w) * int(width) + int(col_1st) + w, 'stride': int(width),
+            'above_mask': (1 << (units - int(mask_w) // 4)) - 1, 'left_units': units - int(mask_h) // 4}
+
+
+def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
+                              tuples_width_height_masks, net_ipfcns=None, keep_predictions=True):
+    """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
+    predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
+    dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
+
+    channels_uint8 [images, H, W, 1], row_1sts / col_1sts (the contexts' top-left corners) are uploaded once.  Per mask ONE
+    pnn_score_pictures_device call -- the descriptors of context_descriptor_fields, the PNN pass, the uint8 cast and its
+    integer SSE, the best HEVC mode searched in the pictures themselves -- and ONE download; PSNRs from the SSEs by
+    intraprediction.psnrs_from_sses (equal to compute_psnr), 0 dB where no HEVC mode beats the reference's start value.
+    keep_predictions=False leaves out (and never downloads) 'predictions_*_uint8' and 'targets_uint8'.
+    Argument errors are those of context.extract_context_portions_targets_from_channels_plus_preprocessing, raised before
+    anything touches the GPU."""
+    ch = channels_uint8
+    if ch.dtype != np.uint8:
+        raise TypeError('`channels_single_or_pair_uint8.dtype` is not equal to `numpy.uint8`.')
+    if not np.issubdtype(row_1sts.dtype, np.integer):
+        raise TypeError('`row_1sts.dtype` is not smaller than `numpy.integer` in type hierarchy.')
+    if not np.issubdtype(col_1sts.dtype, np.integer):
+        raise TypeError('`col_1sts.dtype` is not smaller than `numpy.integer` in type hierarchy.')
+    if col_1sts.size != row_1sts.size:
+        raise ValueError('`col_1sts.size` is not equal to `row_1sts.size`.')
+    if ch.ndim != 4:
+        raise ValueError('`channels_uint8.ndim` is not equal to 4.')
+    nb_images, height, width, nb_channels = ch.shape
+    if nb_channels not in (1, 2):
+        raise ValueError('`channel_single_or_pair_uint8.shape[2]` does not belong to {1, 2}.')
+    if nb_channels != 1:
+        raise ValueError('`channels_uint8.shape[3]` is not equal to 1 (pairs of channels: context.py).')
+    w = width_target
+    if w not in intraprediction.WIDTHS:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    masks = [(int(m[0]), int(m[1])) for m in tuples_width_height_masks]
+    rows, cols = row_1sts.astype(np.int64).ravel(), col_1sts.astype(np.int64).ravel()
+    n_pos = rows.size
+    n = nb_images * n_pos
+    if n == 0:
+        raise ValueError('there is no target: no image or no position.')
+    for mask in masks:
+        context_descriptor_fields(w, height, width, nb_images - 1, rows[-1], cols[-1], mask)
+    if rows.min() < 0 or cols.min() < 0:
+        raise ValueError('`row_1st` / `col_1st` is not positive.')
+    if rows.max() + 3 * w > height or cols.max() + 3 * w > width:
+        raise ValueError('the context does not fit into the channel.')
+    if predictor is None:
+        raise ValueError("`predictor` (a PredictionNeuralNetwork holding the GPU context) is required")
+    if predictor.width_target != w:
+        raise ValueError('the predictor is for width %d, not %d' % (predictor.width_target, w))
+    if net_ipfcns is not None and (0, 0) in masks:
+        if net_ipfcns.width_target != w:
+            raise ValueError('the net is the width-%d IPFCN-S, not the width-%d one' % (net_ipfcns.width_target, w))
+        if net_ipfcns.device != predictor.device:
+            raise ValueError('the IPFCN-S and the predictor are on different devices')
+    L = _lib.lib()
+    ctx_mean = ctypes.c_float(L.pnn_mean(predictor.ctx)).value
+    if abs(ctx_mean - np.float32(mean_training)) > 1e-6:
+        raise ValueError("`mean_training` differs from the predictor's mean")
+
+    import torch
+    dev = torch.device('cuda', predictor.device)
+    w2 = w * w
+    d_channels = torch.from_numpy(np.ascontiguousarray(ch[..., 0])).to(dev)
+    d_rows = torch.from_numpy(rows.astype(np.int32)).to(dev)
+    d_cols = torch.from_numpy(cols.astype(np.int32)).to(dev)
+    # every output of a call in ONE buffer: [PNN SSE u32 n | HEVC SSE u32 n | HEVC index n | PNN uint8 | HEVC uint8 | targets]
+    nb_small = 9 * n
+    off_pnn, off_hevc, off_targets = nb_small, nb_small + n * w2, nb_small + 2 * n * w2
+    d_out = torch.empty(off_targets + n * w2, dtype=torch.uint8, device=dev)
+    base = d_out.data_ptr()
+    stream = torch.cuda.current_stream(dev)
+    results = {}
+    targets_uint8 = None
+    for i, mask in enumerate(masks):
+        if mask in results:
+            continue
+        first = i == 0
+        with torch.cuda.device(dev):
+            _lib.check(L.pnn_score_pictures_device(
+                predictor.ctx, w, d_channels.data_ptr(), nb_images, height, width, d_rows.data_ptr(), d_cols.data_ptr(), n_pos,
+                mask[0], mask[1], base + off_targets if first else None, base + off_pnn if keep_predictions else None, None, base,
+                base + 8 * n, base + 4 * n, base + off_hevc if keep_predictions else None,
+                ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
+        nb_bytes = (off_targets + (n * w2 if first else 0)) if keep_predictions else nb_small
+        out = d_out[:nb_bytes].cpu().numpy()              # (waits for the stream)
+        sses_pnn, sses_hevc = out[:4 * n].view(np.uint32), out[4 * n:8 * n].view(np.uint32)
+        psnrs_pnn = intraprediction.psnrs_from_sses(sses_pnn, w)
+        psnrs_hevc = intraprediction.psnrs_from_sses(sses_hevc, w)
+        psnrs_hevc[sses_hevc == 65025 * w2] = 0.          # the reference's start value, never beaten
+        dictionary_performance = {
+            'indices_hevc_best_mode': out[8 * n:9 * n].copy(), 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
+            'frequency_win_pnn': float(np.count_nonzero(psnrs_pnn - psnrs_hevc > 0.)) / n, 'mean_psnr_pnn': np.mean(psnrs_pnn).item()}
+        if keep_predictions:
+            if first:
+                targets_uint8 = out[off_targets:].reshape(n, w, w, 1).copy()
+            dictionary_performance['predictions_pnn_uint8'] = out[off_pnn:off_hevc].reshape(n, w, w, 1).copy()
+            dictionary_performance['predictions_hevc_best_mode_uint8'] = out[off_hevc:off_targets].reshape(n, w, w, 1).copy()
+            dictionary_performance['targets_uint8'] = targets_uint8
+        results[mask] = dictionary_performance
+    if net_ipfcns is not None and (0, 0) in results:
+        # the reference lines' origin is (row_1st + w - 8, col_1st + w - 8); the targets are on the device already
+        d_targets = d_out[off_targets:].view(n, w, w)
+        pred_u8, _, _, sses = net_ipfcns.predict_from_channels_device(d_channels, d_rows + (w - 8), d_cols + (w - 8), d_targets,
+                                                                      pred_u8=keep_predictions)
+        dictionary_performance = results[(0, 0)]
+        psnrs = intraprediction.psnrs_from_sses(sses, w)
+        dictionary_performance['psnrs_ipfcns'] = psnrs
+        dictionary_performance['frequency_win_ipfcns'] = \
+            float(np.count_nonzero(psnrs - dictionary_performance['psnrs_hevc_best_mode'] > 0.)) / n
+        dictionary_performance['mean_psnr_ipfcns'] = np.mean(psnrs).item()
+        if keep_predictions:
+            dictionary_performance['predictions_ipfcns_uint8'] = pred_u8[..., None]
+    return results

@@ -300,6 +300,39 @@ int pnn_ipfcns_predict_device(pnn_ctx* ctx, int width, const uint8_t* d_channels
                               const int32_t* d_rows, const int32_t* d_cols, int positions, const uint8_t* d_targets,
                               uint8_t* d_pred_u8, float* d_pred_f32, float* d_means, uint32_t* d_sse, void* stream);
 
+/* ---- the evaluator's scores from pictures --------------------------------------------------------------- */
+
+/* The columns of the reference's predict_mask (comparing_pnn_ipfcns_hevc_best_mode.py:162-322) for one mask, from uint8 pictures
+ * that stay on the device: d_channels [images][height][width_ch]; (d_rows[p], d_cols[p]), int32 [positions], is the top-left
+ * corner of a block's 3 width x 3 width context square (the evaluator's row_1sts / col_1sts), its target the width x width
+ * square at (row + width, col + width); blocks image-major (b = image * positions + p), n = images * positions of them.
+ * (mask_w, mask_h) in {0, 4, .., width}: the rightmost mask_w columns of the above portion and the lowest mask_h rows of the left
+ * one are masked for the PNN (the descriptors of pnn_gather_device), and the intra pattern of the HEVC search ends there.
+ * Outputs, each NULL or per block:
+ *   d_targets   uint8 [n][width][width]  the targets, copied from the pictures
+ *   d_pnn_f32   float [n][width][width]  the raw net output without the mean, as pnn_predict_tbs_device's d_out_f32 gives it
+ *   d_pnn_u8    uint8 [n][width][width]  rint(clip(fl32(net + mean), 0, 255)), half to even (tools.cast_float_to_uint8)
+ *   d_pnn_sse   uint32 [n]               sum of squared differences of d_pnn_u8 against the target
+ *   d_hevc_mode / d_hevc_sse / d_hevc_pred   as d_best_mode / d_best_sse / d_best_pred of pnn_hevc_best_mode_device on the
+ *               intra pattern at (row + width - 1, col + width - 1); the search reads the pictures, no dense pattern is built
+ * The PNN half is descriptors -> the pass of pnn_predict_tbs_device (pel_bytes 1) -> epilogue, in slices that keep the workspace
+ * bounded ("max_chunk"); a block's bits do not depend on the slice it travels in.  The three PNN outputs need a model of that
+ * width on the context (PNN_E_ARG without one); for the targets and the HEVC outputs alone a pnn_create_empty context suffices.
+ * n == 0 does nothing.  PNN_E_ARG, before any launch, for a width outside {4, 8, 16, 32, 64}, a mask outside {0, 4, .., width},
+ * a negative position, row + 3 width > height or col + 3 width > width_ch, or every output NULL.  Reads d_rows / d_cols back to
+ * the host to check them (the call waits for `stream` once); everything after that is asynchronous on `stream`. */
+int pnn_score_pictures_device(pnn_ctx* ctx, int width, const uint8_t* d_channels, int images, int height, int width_ch,
+                              const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w, int mask_h,
+                              uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
+                              uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream);
+/* The epilogue alone, on any predictor's floats: d_pred_f32 [n][width][width] (mean-subtracted) -> d_pred_u8 = rint(clip(fl32(pred
+ * + pnn_mean(ctx)), 0, 255)), half to even, and d_sse [n] against the targets in the pictures (either may be NULL, not both).
+ * Same geometry, same checks and the same read-back of d_rows / d_cols as above.  The result for a non-finite prediction is
+ * unspecified (none can come from a uint8 picture through a loaded model). */
+int pnn_score_f32_device(pnn_ctx* ctx, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,
+                         int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                         uint8_t* d_pred_u8, uint32_t* d_sse, void* stream);
+
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
 int pnn_last_call_stats(const pnn_ctx* ctx, int* n_gemm_launches, double* gemm_flops, int* n_launches);
