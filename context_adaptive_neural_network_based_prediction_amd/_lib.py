@@ -79,6 +79,7 @@ SIGNATURES = {
     "pnn_ipfcns_forward_device": (ci, [vp, ci, vp, ci, vp, vp]),
     "pnn_ipfcns_predict_device": (ci, [vp, ci, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
     "pnn_score_pictures_device": (ci, [vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pnn_score_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "pnn_score_f32_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),

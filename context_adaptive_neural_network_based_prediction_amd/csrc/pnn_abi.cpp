@@ -655,7 +655,7 @@ int pnn_hevc_best_mode_device(pnn_ctx* c, int width, const uint8_t* d_patterns, 
     HevcBestModeParams p;
     p.patterns = d_patterns; p.ph = pattern_h; p.pw = pattern_w; p.targets = d_targets; p.N = n; p.w = width;
     p.best_mode = d_best_mode; p.best_sse = d_best_sse; p.best_pred = d_best_pred; p.mode_sse = d_mode_sse;
-    p.pic = PictureBlocks{};
+    p.pic = PictureBlocks{}; p.pic_targets = nullptr;
     HIPCHK(c, launch_hevc_best_mode(p, (hipStream_t)stream));
     return PNN_OK;
 }
@@ -780,7 +780,19 @@ int pnn_score_pictures_device(pnn_ctx* c, int width, const uint8_t* d_channels, 
                               uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
                               uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
 {
+    // a single picture is the pair of one plane with itself
+    return pnn_score_picture_pairs_device(c, width, d_channels, d_channels, images, height, width_ch, d_rows, d_cols, positions, mask_w,
+                                          mask_h, d_targets, d_pnn_u8, d_pnn_f32, d_pnn_sse, d_hevc_mode, d_hevc_sse, d_hevc_pred, stream);
+}
+
+int pnn_score_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                   int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
+                                   int mask_h, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
+                                   uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
+{
     if (!c) return PNN_E_ARG;
+    if (!d_context_channels != !d_target_channels)
+        return fail(c, PNN_E_ARG, "one plane of the pair is NULL (%s)", d_context_channels ? "d_target_channels" : "d_context_channels");
     const int idx = width_index(width);
     if (idx < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
     if (mask_w < 0 || mask_w > width || mask_w % 4 || mask_h < 0 || mask_h > width || mask_h % 4)
@@ -796,11 +808,13 @@ int pnn_score_pictures_device(pnn_ctx* c, int width, const uint8_t* d_channels, 
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if ((rc = check_picture_blocks(c, width, d_channels, images, height, width_ch, d_rows, d_cols, positions, s))) return rc;
+    if ((rc = check_picture_blocks(c, width, d_context_channels, images, height, width_ch, d_rows, d_cols, positions, s))) return rc;
     if (want_pnn && (rc = pending_range_error(c))) return rc;
     reset_stats(c);
-    PictureBlocks pic;
-    pic.channels = d_channels; pic.H = height; pic.W = width_ch; pic.rows = d_rows; pic.cols = d_cols; pic.positions = positions;
+    // contexts and intra patterns from the context plane, targets (hence both SSEs) from the target plane
+    PictureBlocks pic, pic_tg;
+    pic.channels = d_context_channels; pic.H = height; pic.W = width_ch; pic.rows = d_rows; pic.cols = d_cols; pic.positions = positions;
+    pic_tg = pic; pic_tg.channels = d_target_channels;
     const long w2 = (long)width * width;
     // the PNN half in slices (descriptors -> gather -> net -> epilogue); the bits of a block do not depend on its slice
     const long chunk = want_pnn ? std::min(n, chunk_blocks(c, m)) : n;
@@ -820,12 +834,12 @@ int pnn_score_pictures_device(pnn_ctx* c, int width, const uint8_t* d_channels, 
             d.pic = pic; d.b0 = b0; d.nb = nb; d.w = width; d.mask_w = mask_w; d.mask_h = mask_h; d.tbs = (TbDev*)c->score_ws[0].p;
             HIPCHK(c, launch_score_desc(d, s));
             pred = d_pnn_f32 ? d_pnn_f32 + b0 * w2 : ws_f32;
-            if ((rc = tbs_pass(c, m, d_channels, 1, (const pnn_tb_dev*)c->score_ws[0].p, nb, nullptr, pred, s))) return rc;
+            if ((rc = tbs_pass(c, m, d_context_channels, 1, (const pnn_tb_dev*)c->score_ws[0].p, nb, nullptr, pred, s))) return rc;
             c->stat_launches++;
         }
         if (d_targets || d_pnn_u8 || d_pnn_sse) {
             ScoreEpilogueParams e;
-            e.pic = pic; e.b0 = b0; e.nb = nb; e.w = width; e.pred = pred; e.mean = c->mean;
+            e.pic = pic_tg; e.b0 = b0; e.nb = nb; e.w = width; e.pred = pred; e.mean = c->mean;
             e.u8 = d_pnn_u8 ? d_pnn_u8 + b0 * w2 : nullptr; e.targets = d_targets ? d_targets + b0 * w2 : nullptr;
             e.sse = d_pnn_sse ? d_pnn_sse + b0 : nullptr;
             HIPCHK(c, launch_score_epilogue(e, s));
@@ -836,7 +850,7 @@ int pnn_score_pictures_device(pnn_ctx* c, int width, const uint8_t* d_channels, 
         HevcBestModeParams p;
         p.patterns = nullptr; p.ph = 2 * width + 1 - mask_h; p.pw = 2 * width + 1 - mask_w; p.targets = nullptr; p.N = (int)n; p.w = width;
         p.best_mode = d_hevc_mode; p.best_sse = d_hevc_sse; p.best_pred = d_hevc_pred; p.mode_sse = nullptr;
-        p.pic = pic;
+        p.pic = pic; p.pic_targets = d_target_channels;
         HIPCHK(c, launch_hevc_best_mode(p, s));
         c->stat_launches++;
     }

@@ -13,7 +13,8 @@
 // refMain: index k >= 0 reads the main reference, k < 0 the side one at (128 - k * invAngle) >> 8, as HM's projection loop fills it.
 // Then one lane per block picks the best mode and the workgroup recomputes that mode's prediction only if it is asked for.
 // The staging loops have a second source: the evaluator's pictures themselves (PIC), 4w + 1 + w^2 bytes per block instead of a
-// dense (2w + 1)^2 pattern and a target copy; everything after the staging is shared.
+// dense (2w + 1)^2 pattern and a target copy; everything after the staging is shared.  The pictures are a pair of planes (decoded
+// for the reference samples, original for the targets); a single picture is the pair of one plane with itself.
 #include "pnn_kernels.h"
 
 namespace pnn {
@@ -110,7 +111,9 @@ __device__ inline size_t picture_corner(const PictureBlocks& pic, long b)
     return ((size_t)img * pic.H + pic.rows[pos]) * pic.W + pic.cols[pos];
 }
 
-// PIC = false: reference samples from dense intra patterns, targets from their own array; true: both from the pictures (p.pic)
+// PIC = false: reference samples from dense intra patterns, targets from their own array; true: both from pictures -- the reference
+// samples from the context plane (p.pic.channels), the targets from the target plane (p.pic_targets), which have one geometry and
+// so share each block's offset `corner`.  For single pictures the two pointers are equal.
 template <int W, bool PIC>
 __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBestModeParams p)
 {
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBest
         const int g = i / (W * W), e = i % (W * W);
         int v = 0;
         if (blk0 + g < p.N) {
-            if (PIC) v = p.pic.channels[corner[g] + (size_t)(W + e / W) * p.pic.W + W + e % W];
+            if (PIC) v = p.pic_targets[corner[g] + (size_t)(W + e / W) * p.pic.W + W + e % W];   // the target plane, same offset
             else v = p.targets[(size_t)(blk0 + g) * W * W + e];
         }
         tgt[g * TS + e] = (uint8_t)v;
@@ -217,6 +220,7 @@ hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s)
     const int rows_per_lane = p.w <= 8 ? p.w : 4, blocks_per_wg = 64 / (p.w / rows_per_lane);
     const dim3 grid((unsigned)((p.N + blocks_per_wg - 1) / blocks_per_wg)), block(kThreads);
     const bool pic = p.patterns == nullptr;
+    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
 #define PNN_HEVC_LAUNCH(W_) \
     case W_: if (pic) hipLaunchKernelGGL((hevc_best_mode_kernel<W_, true>), grid, block, 0, s, p); \
              else hipLaunchKernelGGL((hevc_best_mode_kernel<W_, false>), grid, block, 0, s, p); \

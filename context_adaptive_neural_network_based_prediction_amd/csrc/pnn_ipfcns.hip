@@ -7,6 +7,7 @@
 // ... and the two element-wise kernels of the evaluator's scoring path from pictures (pnn_score_pictures_device):
 //   score_desc_kernel       (picture, position, masks) -> the gather's descriptor of every block
 //   score_epilogue_kernel   the same uint8 rule on any predictor's floats, with the target read from the picture
+// Of a pair of planes (decoded, original) score_desc_kernel's descriptors address the decoded one, the epilogue's picture is the original.
 // One wave per block in the gather and the epilogues (K <= 1088, w^2 <= 4096 values), four waves per workgroup.  All plain f32
 // operations: nothing here can contract (a subtraction, an addition, one multiply, a division by __fdiv_rn).
 #include "pnn_kernels.h"

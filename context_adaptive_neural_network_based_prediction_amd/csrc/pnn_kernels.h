@@ -266,10 +266,13 @@ struct PictureBlocks {
 // HEVC best intra mode (pnn_hevc_intra.hip): N intra patterns [N][ph][pw] (first row and column used) and targets [N][w][w], all uint8;
 // any of the four outputs may be NULL.  With patterns == NULL the reference samples and the targets of block b come from `pic`
 // instead: the pattern's first row and column start at (row + w - 1, col + w - 1), ph and pw say how much of them is not masked.
+// The picture form has two planes of equal geometry: the reference samples are read from pic.channels (the context plane -- the
+// decoded picture of a pair), the targets from pic_targets (the original; the same pointer for single pictures).
 struct HevcBestModeParams {
     const uint8_t* patterns; int ph; int pw; const uint8_t* targets; int N; int w;
     uint8_t* best_mode; uint32_t* best_sse; uint8_t* best_pred; uint32_t* mode_sse;
     PictureBlocks pic;
+    const uint8_t* pic_targets;   // last, so that the dense form's arguments keep their offsets
 };
 hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s);
 
@@ -291,7 +294,9 @@ struct IpfcnsEpilogueParams {
 };
 hipError_t launch_ipfcns_epilogue(const IpfcnsEpilogueParams& p, hipStream_t s);
 
-// Picture scoring (pnn_ipfcns.hip), blocks b0 .. b0 + nb - 1 of `pic`; every output pointer addresses block b0.
+// Picture scoring (pnn_ipfcns.hip), blocks b0 .. b0 + nb - 1 of `pic`; every output pointer addresses block b0.  Of a pair of planes
+// (pnn_score_picture_pairs_device) each kernel sees ONE: the descriptors address the context plane (they go to tbs_pass with it), the
+// epilogue's pic.channels is the target plane.  Positions and geometry are those of both.
 // Descriptors of the blocks' L-shaped contexts, as context.py builds them: origin = (image * H + row + w) * W + col + w (the target's
 // top-left pixel), stride = W, above_mask = 2^(units - mask_w / 4) - 1 (units = 2w / 4; all 32 bits at w = 64 without a mask),
 // left_units = units - mask_h / 4.

@@ -9,6 +9,7 @@ uint8 epilogue with the per-block SSE in one GPU call), as the reference does on
 score_masks_from_pictures is the reference's loop over a list of masks (predict_masks, :324-452) on pictures that stay on the
 GPU: per mask one pnn_score_pictures_device call (descriptors, PNN pass, uint8 epilogue with its SSE, best-mode search from
 the pictures) and one download; the same dictionaries as predict_mask_vs_hevc_best_mode[_and_ipfcns], bit for bit.
+score_masks_from_picture_pairs is the same loop on [images, H, W, 2] pairs (original, HEVC-decoded) for the pair models.
 """
 import ctypes
 
@@ -163,13 +164,37 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
 
     channels_uint8 [images, H, W, 1], row_1sts / col_1sts (the contexts' top-left corners) are uploaded once.  Per mask ONE
-    pnn_score_pictures_device call -- the descriptors of context_descriptor_fields, the PNN pass, the uint8 cast and its
-    integer SSE, the best HEVC mode searched in the pictures themselves -- and ONE download; PSNRs from the SSEs by
+    pnn_score_pictures_device call (made as pnn_score_picture_pairs_device with one plane in both places) -- the descriptors of
+    context_descriptor_fields, the PNN pass, the uint8 cast and its integer SSE, the best HEVC mode searched in the pictures
+    themselves -- and ONE download; PSNRs from the SSEs by
     intraprediction.psnrs_from_sses (equal to compute_psnr), 0 dB where no HEVC mode beats the reference's start value.
     keep_predictions=False leaves out (and never downloads) 'predictions_*_uint8' and 'targets_uint8'.
     Argument errors are those of context.extract_context_portions_targets_from_channels_plus_preprocessing, raised before
     anything touches the GPU."""
-    ch = channels_uint8
+    return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
+                        net_ipfcns, keep_predictions)
+
+
+def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
+                                   tuples_width_height_masks, net_ipfcns=None, keep_predictions=True):
+    """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
+    channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
+    Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
+
+    Which plane feeds what (pnn_score_picture_pairs_device):
+      decoded (last channel):  the PNN's contexts (sets/common.py reads them there), the intra pattern of the HEVC search (this
+                               project's definition -- the reference's extract_intra_patterns has no pair form; the decoded
+                               neighbourhood is what an encoder holds), the reference lines of IPFCN-S (ipfcns.py:60-65)
+      original (channel 0):    'targets_uint8' and the targets of every SSE, hence of every PSNR
+    The pair is de-interleaved once on the host and uploaded once; per mask ONE call and ONE download, as for single pictures."""
+    return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
+                        tuples_width_height_masks, net_ipfcns, keep_predictions)
+
+
+def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
+                 keep_predictions):
+    """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
+    everything a predictor reads from the last channel; with one plane the two are the same device buffer."""
     if ch.dtype != np.uint8:
         raise TypeError('`channels_single_or_pair_uint8.dtype` is not equal to `numpy.uint8`.')
     if not np.issubdtype(row_1sts.dtype, np.integer):
@@ -183,8 +208,10 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     nb_images, height, width, nb_channels = ch.shape
     if nb_channels not in (1, 2):
         raise ValueError('`channel_single_or_pair_uint8.shape[2]` does not belong to {1, 2}.')
-    if nb_channels != 1:
+    if nb_planes == 1 and nb_channels != 1:
         raise ValueError('`channels_uint8.shape[3]` is not equal to 1 (pairs of channels: context.py).')
+    if nb_planes == 2 and nb_channels != 2:
+        raise ValueError('`channels_pair_uint8.shape[3]` is not equal to 2 (single pictures: score_masks_from_pictures).')
     w = width_target
     if w not in intraprediction.WIDTHS:
         raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
@@ -217,7 +244,8 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     import torch
     dev = torch.device('cuda', predictor.device)
     w2 = w * w
-    d_channels = torch.from_numpy(np.ascontiguousarray(ch[..., 0])).to(dev)
+    d_planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(ch, 3, 0))).to(dev)      # [planes, images, H, W]: one copy, one upload
+    d_target_channels, d_context_channels = d_planes[0], d_planes[nb_planes - 1]
     d_rows = torch.from_numpy(rows.astype(np.int32)).to(dev)
     d_cols = torch.from_numpy(cols.astype(np.int32)).to(dev)
     # every output of a call in ONE buffer: [PNN SSE u32 n | HEVC SSE u32 n | HEVC index n | PNN uint8 | HEVC uint8 | targets]
@@ -233,8 +261,9 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
             continue
         first = i == 0
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_score_pictures_device(
-                predictor.ctx, w, d_channels.data_ptr(), nb_images, height, width, d_rows.data_ptr(), d_cols.data_ptr(), n_pos,
+            _lib.check(L.pnn_score_picture_pairs_device(
+                predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
+                d_rows.data_ptr(), d_cols.data_ptr(), n_pos,
                 mask[0], mask[1], base + off_targets if first else None, base + off_pnn if keep_predictions else None, None, base,
                 base + 8 * n, base + 4 * n, base + off_hevc if keep_predictions else None,
                 ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
@@ -255,9 +284,10 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
             dictionary_performance['targets_uint8'] = targets_uint8
         results[mask] = dictionary_performance
     if net_ipfcns is not None and (0, 0) in results:
-        # the reference lines' origin is (row_1st + w - 8, col_1st + w - 8); the targets are on the device already
+        # the reference lines' origin is (row_1st + w - 8, col_1st + w - 8), in the context plane; the targets (of the target plane)
+        # are on the device already
         d_targets = d_out[off_targets:].view(n, w, w)
-        pred_u8, _, _, sses = net_ipfcns.predict_from_channels_device(d_channels, d_rows + (w - 8), d_cols + (w - 8), d_targets,
+        pred_u8, _, _, sses = net_ipfcns.predict_from_channels_device(d_context_channels, d_rows + (w - 8), d_cols + (w - 8), d_targets,
                                                                       pred_u8=keep_predictions)
         dictionary_performance = results[(0, 0)]
         psnrs = intraprediction.psnrs_from_sses(sses, w)

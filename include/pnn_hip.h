@@ -325,6 +325,27 @@ int pnn_score_pictures_device(pnn_ctx* ctx, int width, const uint8_t* d_channels
                               const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w, int mask_h,
                               uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
                               uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream);
+/* pnn_score_pictures_device on PAIRS of pictures, as the reference carries the data of its "pair" models ([images, H, W, 2]: channel 0
+ * the original, channel 1 the HEVC-decoded picture; sets/common.py gathers contexts from the last channel and targets from channel 0):
+ * d_context_channels (the decoded pictures) and d_target_channels (the originals), both uint8 [images][height][width_ch], in place of
+ * d_channels.  The caller de-interleaves; the planes have one geometry and share positions, masks and block order.
+ *   read from the CONTEXT plane:  the PNN's contexts (descriptors and gather of the pass), and the intra pattern of the HEVC search at
+ *                                 (row + width - 1, col + width - 1)
+ *   read from the TARGET plane:   d_targets, and the targets of both SSEs (d_pnn_sse, d_hevc_sse; d_hevc_mode minimises the latter)
+ * The reference's extract_intra_patterns takes single-channel pictures only and has no pair form, so which plane feeds the intra
+ * pattern is THIS PROJECT'S DEFINITION: the decoded plane, because the reconstructed neighbourhood is what an encoder holds when it
+ * predicts a block (the original's samples are not available to a decoder at all).
+ * Outputs, slices, checks (all before any launch) and the read-back of d_rows / d_cols are those of pnn_score_pictures_device; in
+ * addition PNN_E_ARG when exactly one of the two planes is NULL.  With d_context_channels == d_target_channels every output has the
+ * bits of pnn_score_pictures_device, which is this entry called that way.
+ * The two entries that take the targets apart from the pictures need no pair form.  A pair caller passes
+ *   pnn_score_f32_device:       d_channels = the TARGET plane (the entry reads nothing but targets from it);
+ *   pnn_ipfcns_predict_device:  d_channels = the CONTEXT plane (the reference lines, ipfcns.py:60-65 reads the last channel), d_targets =
+ *                               target blocks taken from the target plane (the d_targets output of this entry). */
+int pnn_score_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                   int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                   int mask_w, int mask_h, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
+                                   uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream);
 /* The epilogue alone, on any predictor's floats: d_pred_f32 [n][width][width] (mean-subtracted) -> d_pred_u8 = rint(clip(fl32(pred
  * + pnn_mean(ctx)), 0, 255)), half to even, and d_sse [n] against the targets in the pictures (either may be NULL, not both).
  * Same geometry, same checks and the same read-back of d_rows / d_cols as above.  The result for a non-finite prediction is

@@ -12,7 +12,7 @@
       `--warmup` ones.  The figure of the picture entry INCLUDES its read-back of the positions (the argument check), which the
       dense entry does not have: the comparison is conservative for the new path.
 
-    python tools/picture_score_rate.py            # on the GPU box
+    python tools/picture_score_rate.py            # on the GPU box; --pairs adds the call on pairs of planes to (b)
 """
 import argparse
 import ctypes
@@ -115,9 +115,15 @@ def search_kernel(args, out):
                                                          res["dense"][1].data_ptr(), None, None, sp),
             "pic": lambda: L.pnn_score_pictures_device(ctx, w, d_imgs.data_ptr(), images, H, W, d_rows.data_ptr(), d_cols.data_ptr(), positions, 0, 0,
                                                        None, None, None, None, res["pic"][0].data_ptr(), res["pic"][1].data_ptr(), None, sp)}
-        times = {"dense": [], "pic": []}
+        if args.pairs:                                     # the same search on a pair: samples from an inverted copy, targets as before
+            d_dec = 255 - d_imgs
+            res["pair"] = (torch.empty(n, dtype=torch.uint8, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda"))
+            calls["pair"] = lambda: L.pnn_score_picture_pairs_device(ctx, w, d_dec.data_ptr(), d_imgs.data_ptr(), images, H, W, d_rows.data_ptr(),
+                                                                     d_cols.data_ptr(), positions, 0, 0, None, None, None, None,
+                                                                     res["pair"][0].data_ptr(), res["pair"][1].data_ptr(), None, sp)
+        times = {name: [] for name in calls}
         for i in range(args.warmup + args.reps):
-            for name in ("dense", "pic"):
+            for name in calls:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(s)
                 assert calls[name]() == 0
@@ -130,12 +136,16 @@ def search_kernel(args, out):
         fmt = lambda k: "%.1f [%.1f .. %.1f]" % (med[k], min(times[k]), max(times[k]))
         out("%-3d %8d %5d / %-5d %24s %12.4g %24s %12.4g %7.2fx" % (w, n, (2 * w + 1) ** 2 + w * w, 4 * w + 1 + w * w, fmt("dense"), n / med["dense"] * 1e6,
                                                                  fmt("pic"), n / med["pic"] * 1e6, med["dense"] / med["pic"]))
+        if args.pairs:
+            out("%-3d %8d   pair of planes, %d bytes/block: %s us, %.4g blocks/s, %.2fx the single-picture call"
+                % (w, n, 4 * w + 1 + w * w, fmt("pair"), n / med["pair"] * 1e6, med["pic"] / med["pair"]))
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--pairs", action="store_true", help="(b) also times pnn_score_picture_pairs_device (two planes) beside the single-picture call")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "picture_score_rate.txt"))
     args = ap.parse_args()
     import torch
