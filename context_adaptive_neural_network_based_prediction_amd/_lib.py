@@ -74,6 +74,10 @@ SIGNATURES = {
     "pnn_predict_tbs_cost_device": (ci, [vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp]),
     "pnn_hevc_intra_predict": (ci, [u8p, ci, ci, ci, ci, u8p]),
     "pnn_hevc_best_mode_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
+    "pnn_first_pass_list_size": (ci, [ci]),
+    "pnn_hevc_mode_hads_host": (ci, [vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp]),
+    "pnn_hevc_mode_hads_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "pnn_first_pass_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
     "pnn_ipfcns_forward_host": (ci, [ci, f32p, f32p, ci, ci, f32p]),
     "pnn_ipfcns_load": (ci, [vp, ci, f32p, ctypes.c_size_t]),
     "pnn_ipfcns_forward_device": (ci, [vp, ci, vp, ci, vp, vp]),

@@ -660,6 +660,27 @@ int pnn_hevc_best_mode_device(pnn_ctx* c, int width, const uint8_t* d_patterns, 
     return PNN_OK;
 }
 
+int pnn_hevc_mode_hads_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets,
+                              int n, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes,
+                              uint32_t* d_list_costs, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (width_index(width) < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
+    if (pattern_h < width + 1 || pattern_h > 2 * width + 1 || pattern_w < width + 1 || pattern_w > 2 * width + 1)
+        return fail(c, PNN_E_ARG, "intra pattern %dx%d: both sides must lie in [%d, %d]", pattern_h, pattern_w, width + 1, 2 * width + 1);
+    if (n < 0 || (n > 0 && (!d_patterns || !d_targets))) return fail(c, PNN_E_ARG, "bad batch size or input buffers");
+    if (!d_mode_hads && !d_cand_hads && !d_list_modes && !d_list_costs) return fail(c, PNN_E_ARG, "every output is NULL");
+    if (d_cand_hads && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_hads needs d_cand_pred");
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HevcModeHadsParams p;
+    p.patterns = d_patterns; p.ph = pattern_h; p.pw = pattern_w; p.targets = d_targets; p.N = n; p.w = width;
+    p.cand_pred = d_cand_pred; p.mode_hads = d_mode_hads; p.cand_hads = d_cand_hads; p.list_modes = d_list_modes; p.list_costs = d_list_costs;
+    p.pic = PictureBlocks{}; p.pic_targets = nullptr;
+    HIPCHK(c, launch_hevc_mode_hads(p, (hipStream_t)stream));
+    return PNN_OK;
+}
+
 int pnn_ipfcns_load(pnn_ctx* c, int width, const float* params, size_t n_floats)
 {
     if (!c) return PNN_E_ARG;
@@ -854,6 +875,38 @@ int pnn_score_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_conte
         HIPCHK(c, launch_hevc_best_mode(p, s));
         c->stat_launches++;
     }
+    return PNN_OK;
+}
+
+int pnn_first_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                        int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
+                                        int mask_h, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads,
+                                        uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (!d_context_channels != !d_target_channels)
+        return fail(c, PNN_E_ARG, "one plane of the pair is NULL (%s)", d_context_channels ? "d_target_channels" : "d_context_channels");
+    if (width_index(width) < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
+    if (mask_w < 0 || mask_w > width || mask_w % 4 || mask_h < 0 || mask_h > width || mask_h % 4)
+        return fail(c, PNN_E_ARG, "masks (%d, %d): both must belong to {0, 4, ..., %d}", mask_w, mask_h, width);
+    if (images < 0 || positions < 0 || height < 0 || width_ch < 0) return fail(c, PNN_E_ARG, "negative sizes");
+    if (!d_mode_hads && !d_cand_hads && !d_list_modes && !d_list_costs) return fail(c, PNN_E_ARG, "every output is NULL");
+    if (d_cand_hads && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_hads needs d_cand_pred");
+    const long n = (long)images * positions;
+    if (n > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks");
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = check_picture_blocks(c, width, d_context_channels, images, height, width_ch, d_rows, d_cols, positions, s))) return rc;
+    reset_stats(c);
+    HevcModeHadsParams p;
+    p.patterns = nullptr; p.ph = 2 * width + 1 - mask_h; p.pw = 2 * width + 1 - mask_w; p.targets = nullptr; p.N = (int)n; p.w = width;
+    p.cand_pred = d_cand_pred; p.mode_hads = d_mode_hads; p.cand_hads = d_cand_hads; p.list_modes = d_list_modes; p.list_costs = d_list_costs;
+    p.pic.channels = d_context_channels; p.pic.H = height; p.pic.W = width_ch; p.pic.rows = d_rows; p.pic.cols = d_cols; p.pic.positions = positions;
+    p.pic_targets = d_target_channels;
+    HIPCHK(c, launch_hevc_mode_hads(p, s));
+    c->stat_launches++;
     return PNN_OK;
 }
 

@@ -4,9 +4,13 @@
 // reference's hevc_intraprediction (hevc/intraprediction/c++/source/extracted_hevc_intraprediction.cpp:3-134): no reference
 // sample smoothing, 8-bit luma, DC filtering and the mode 10 / 26 edge filter for w <= 16; -1 where the reference throws.
 // pnn_hevc_intra.hip computes the same predictions in closed form; tests/test_gpu_hevc_intra.py checks one against the other.
+// pnn_hevc_mode_hads_host is the host twin of the first-pass ranking (hevc_mode_hads_kernel): the 35 predictions above, HM's
+// xGetHADs written from its rule, and xUpdateCandList; tests/test_gpu_mode_hads.py checks the kernel against it.
 #include "../../include/pnn_hip.h"
 
+#include <cstdint>
 #include <cstdio>
+#include <vector>
 
 namespace {
 
@@ -73,7 +77,97 @@ void predict(const int* top, const int* left, int w, int mode, int* pred)
     }
 }
 
+// TComRdCost::xGetHADs for 8-bit video (TComRdCost.cpp:1753-1824): per t x t sub-block (t = 8, 4 for 4-wide blocks) the Walsh-Hadamard
+// transform of org - pred, the sum of the absolute coefficients rounded (s + 2) >> 2 (t = 8) or (s + 1) >> 1 (t = 4); summed over the block.
+uint32_t hads(const uint8_t* org, const int* pred, int w)
+{
+    const int t = w == 4 ? 4 : 8;
+    uint32_t total = 0;
+    for (int by = 0; by < w; by += t)
+        for (int bx = 0; bx < w; bx += t) {
+            int d[64];
+            for (int y = 0; y < t; y++)
+                for (int x = 0; x < t; x++) d[y * t + x] = (int)org[(by + y) * w + bx + x] - pred[(by + y) * w + bx + x];
+            for (int pass = 0; pass < 2; pass++) {                            // rows, then columns
+                const int es = pass == 0 ? 1 : t, vs = pass == 0 ? t : 1;
+                for (int v = 0; v < t; v++)
+                    for (int len = 1; len < t; len <<= 1)
+                        for (int i = 0; i < t; i += len << 1)
+                            for (int j = i; j < i + len; j++) {
+                                const int a = d[v * vs + j * es], b = d[v * vs + (j + len) * es];
+                                d[v * vs + j * es] = a + b;
+                                d[v * vs + (j + len) * es] = a - b;
+                            }
+            }
+            uint32_t sum = 0;
+            for (int k = 0; k < t * t; k++) sum += (uint32_t)(d[k] < 0 ? -d[k] : d[k]);
+            total += t == 8 ? (sum + 2) >> 2 : (sum + 1) >> 1;
+        }
+    return total;
+}
+
+// TEncSearch::xUpdateCandList with the cost alone: the entry goes in front of the first strictly larger cost, the last one drops out
+void update_cand_list(int mode, uint32_t cost, int k, int* list_modes, uint64_t* list_costs)
+{
+    int shift = 0;
+    while (shift < k && cost < list_costs[k - 1 - shift]) shift++;
+    if (!shift) return;
+    for (int i = 1; i < shift; i++) {
+        list_modes[k - i] = list_modes[k - 1 - i];
+        list_costs[k - i] = list_costs[k - 1 - i];
+    }
+    list_modes[k - shift] = mode;
+    list_costs[k - shift] = cost;
+}
+
 }  // namespace
+
+extern "C" int pnn_first_pass_list_size(int width)
+{
+    if (log2_width(width) < 0) return PNN_E_ARG;
+    return width <= 8 ? 8 : 3;                                                // g_aucIntraModeNumFast_UseMPM
+}
+
+extern "C" int pnn_hevc_mode_hads_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                                       const uint8_t* cand_pred, uint32_t* mode_hads, uint32_t* cand_hads, uint8_t* list_modes,
+                                       uint32_t* list_costs)
+{
+    if (log2_width(width) < 0) return PNN_E_ARG;
+    if (pattern_h < width + 1 || pattern_h > 2 * width + 1 || pattern_w < width + 1 || pattern_w > 2 * width + 1) return PNN_E_ARG;
+    if (n < 0 || (n > 0 && (!patterns || !targets))) return PNN_E_ARG;
+    if (!mode_hads && !cand_hads && !list_modes && !list_costs) return PNN_E_ARG;
+    if (cand_hads && !cand_pred) return PNN_E_ARG;
+    const int w2 = width * width, k = width <= 8 ? 8 : 3;
+    std::vector<int> pred(w2);
+    for (long b = 0; b < n; b++) {
+        const uint8_t* pat = patterns + (size_t)b * pattern_h * pattern_w;
+        const uint8_t* org = targets + (size_t)b * w2;
+        int top[2 * 64 + 1], left[2 * 64 + 1], modes[8];
+        uint64_t costs[8];
+        for (int i = 0; i < k; i++) { modes[i] = 255; costs[i] = UINT64_MAX; }  // HM starts the list at MAX_DOUBLE
+        for (int i = 0; i <= 2 * width; i++) {
+            top[i] = pat[i < pattern_w ? i : pattern_w - 1];
+            left[i] = pat[(i < pattern_h ? i : pattern_h - 1) * pattern_w];
+        }
+        for (int mode = 0; mode < 35; mode++) {
+            predict(top, left, width, mode, pred.data());
+            const uint32_t c = hads(org, pred.data(), width);
+            if (mode_hads) mode_hads[b * 35 + mode] = c;
+            update_cand_list(mode, c, k, modes, costs);
+        }
+        if (cand_pred) {
+            for (int i = 0; i < w2; i++) pred[i] = cand_pred[(size_t)b * w2 + i];
+            const uint32_t c = hads(org, pred.data(), width);
+            if (cand_hads) cand_hads[b] = c;
+            update_cand_list(35, c, k, modes, costs);
+        }
+        for (int i = 0; i < k; i++) {
+            if (list_modes) list_modes[b * k + i] = (uint8_t)modes[i];
+            if (list_costs) list_costs[b * k + i] = (uint32_t)costs[i];
+        }
+    }
+    return PNN_OK;
+}
 
 extern "C" int pnn_hevc_intra_predict(const uint8_t* intra_pattern, int pattern_h, int pattern_w, int width, int mode,
                                       uint8_t* out)

@@ -15,7 +15,15 @@
 // The staging loops have a second source: the evaluator's pictures themselves (PIC), 4w + 1 + w^2 bytes per block instead of a
 // dense (2w + 1)^2 pattern and a target copy; everything after the staging is shared.  The pictures are a pair of planes (decoded
 // for the reference samples, original for the targets); a single picture is the pair of one plane with itself.
+//
+// hevc_mode_hads_kernel is the SATD twin of the search, the metric of HM's first intra pass (TEncSearch.cpp:2376-2492): the same
+// staging and the same per-pixel mode functions, but a lane owns one T x T sub-block (T = 8, 4 at w = 4) of one block and one mode at
+// a time -- its T^2 residuals in registers, the Walsh-Hadamard butterflies of pnn_wht.h, the rounding of TComRdCost::xGetHADs -- and
+// adds the sub-block's cost into cost[block][mode] in LDS.  A candidate prediction handed in (the PNN's) is costed as index 35 in a
+// sixth round of one wave; then one lane per block builds HM's sorted candidate list (xUpdateCandList).  No reference smoothing (as
+// above) and no modeBits * sqrtLambda term: the costs are the distortions alone.
 #include "pnn_kernels.h"
+#include "pnn_wht.h"
 
 namespace pnn {
 namespace {
@@ -111,22 +119,15 @@ __device__ inline size_t picture_corner(const PictureBlocks& pic, long b)
     return ((size_t)img * pic.H + pic.rows[pos]) * pic.W + pic.cols[pos];
 }
 
-// PIC = false: reference samples from dense intra patterns, targets from their own array; true: both from pictures -- the reference
-// samples from the context plane (p.pic.channels), the targets from the target plane (p.pic_targets), which have one geometry and
-// so share each block's offset `corner`.  For single pictures the two pointers are equal.
-template <int W, bool PIC>
-__global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBestModeParams p)
+// Staging shared by the two kernels: the padded 4w + 1 reference samples (ref, stride RS ints) and the w^2 targets (tgt, stride TS
+// bytes) of the workgroup's G blocks, zeros for blocks past p.N; `Params` is either kernel's.  PIC = false: reference samples from dense
+// intra patterns, targets from their own array; true: both from pictures -- the reference samples from the context plane (p.pic.channels),
+// the targets from the target plane (p.pic_targets), which have one geometry and so share each block's offset `corner`.  For single
+// pictures the two pointers are equal.
+template <int W, int G, bool PIC, typename Params>
+__device__ __forceinline__ void stage_blocks(const Params& p, long blk0, int tid, int* ref, uint8_t* tgt, size_t* corner)
 {
-    constexpr int R = W <= 8 ? W : 4, RG = W / R, G = 64 / RG;    // rows per lane, lanes per block, blocks per workgroup
     constexpr int RS = 4 * W + 1, TS = W * W + 4;                 // LDS strides (odd in dwords: lanes of different blocks spread over banks)
-    __shared__ int ref[G * RS];
-    __shared__ uint8_t tgt[G * TS];
-    __shared__ unsigned sse[G * 35];
-    __shared__ int dcv[G], best[G];
-    __shared__ size_t corner[PIC ? G : 1];
-    const int tid = threadIdx.x;
-    const long blk0 = (long)blockIdx.x * G;
-
     if (PIC) {
         if (tid < G && blk0 + tid < p.N) corner[tid] = picture_corner(p.pic, blk0 + tid);
         __syncthreads();
@@ -154,14 +155,37 @@ __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBest
         }
         tgt[g * TS + e] = (uint8_t)v;
     }
-    for (int i = tid; i < G * 35; i += kThreads) sse[i] = 0;
-    __syncthreads();
+}
+
+// predIntraGetPredValDC of the G staged blocks, one lane each
+template <int W, int G>
+__device__ __forceinline__ void stage_dc(const int* ref, int* dcv, int tid)
+{
     if (tid < G) {
-        const int* rf = ref + tid * RS + 2 * W;
+        const int* rf = ref + tid * (4 * W + 1) + 2 * W;
         int sum = 0;
         for (int i = 1; i <= W; i++) sum += rf[i] + rf[-i];
         dcv[tid] = (sum + W) / (2 * W);
     }
+}
+
+template <int W, bool PIC>
+__global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBestModeParams p)
+{
+    constexpr int R = W <= 8 ? W : 4, RG = W / R, G = 64 / RG;    // rows per lane, lanes per block, blocks per workgroup
+    constexpr int RS = 4 * W + 1, TS = W * W + 4;                 // LDS strides, those of stage_blocks
+    __shared__ int ref[G * RS];
+    __shared__ uint8_t tgt[G * TS];
+    __shared__ unsigned sse[G * 35];
+    __shared__ int dcv[G], best[G];
+    __shared__ size_t corner[PIC ? G : 1];
+    const int tid = threadIdx.x;
+    const long blk0 = (long)blockIdx.x * G;
+
+    stage_blocks<W, G, PIC>(p, blk0, tid, ref, tgt, corner);
+    for (int i = tid; i < G * 35; i += kThreads) sse[i] = 0;
+    __syncthreads();
+    stage_dc<W, G>(ref, dcv, tid);
     __syncthreads();
 
     const int lane = tid & 63, g = lane / RG, rg = lane % RG;
@@ -212,6 +236,120 @@ __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBest
     }
 }
 
+// Hadamard cost of the T x T sub-block at (by, bx) of one block: residual = target - pred(y, x) in registers, transform, sum of
+// absolute coefficients, xGetHADs' rounding.  Target rows are read as 32-bit words (tg and every row start are 4-byte aligned).
+template <int W, int T, typename Pred>
+__device__ __forceinline__ unsigned sub_block_hads(const uint8_t* tg, int by, int bx, Pred pred)
+{
+    int d[T * T];
+#pragma unroll
+    for (int y = 0; y < T; y++) {
+        const uint32_t* row = reinterpret_cast<const uint32_t*>(tg + (by + y) * W + bx);
+#pragma unroll
+        for (int x4 = 0; x4 < T; x4 += 4) {
+            const uint32_t word = row[x4 / 4];
+#pragma unroll
+            for (int x = x4; x < x4 + 4; x++) d[y * T + x] = (int)((word >> (8 * (x - x4))) & 255u) - pred(by + y, bx + x);
+        }
+        __builtin_amdgcn_sched_barrier(0);             // a row at a time: hoisting all T^2 pixels' loads and addresses costs > 200 VGPRs
+    }
+    wht_rows_cols<T>(d);
+    unsigned s = 0;
+#pragma unroll
+    for (int k = 0; k < T * T; k++) s += (unsigned)abs(d[k]);
+    return hads_round<T>(s);
+}
+
+// The SATD twin of hevc_best_mode_kernel (same staging, same forms PIC).  Lane = (block g, sub-block sb) of the workgroup's G =
+// 64 / (w / T)^2 blocks; wave = one mode per round, so the mode is wave-uniform.  cost[g][0 .. 34] the modes, [35] the candidate.
+template <int W, bool PIC>
+__global__ __launch_bounds__(kThreads) void hevc_mode_hads_kernel(const HevcModeHadsParams p)
+{
+    constexpr int T = W == 4 ? 4 : 8, SB = W / T, NSB = SB * SB, G = 64 / NSB;   // sub-block side, sub-blocks per side / block, blocks per workgroup
+    constexpr int K = W <= 8 ? 8 : 3, NC = 36;                                  // list entries, costs per block
+    constexpr int RS = 4 * W + 1, TS = W * W + 4;                               // LDS strides, those of stage_blocks
+    __shared__ int ref[G * RS];
+    __shared__ __attribute__((aligned(4))) uint8_t tgt[G * TS];
+    __shared__ __attribute__((aligned(4))) uint8_t cnd[G * TS];
+    __shared__ unsigned cost[G * NC];
+    __shared__ int dcv[G];
+    __shared__ size_t corner[PIC ? G : 1];
+    const int tid = threadIdx.x;
+    const long blk0 = (long)blockIdx.x * G;
+
+    stage_blocks<W, G, PIC>(p, blk0, tid, ref, tgt, corner);
+    if (p.cand_pred)
+        for (int i = tid; i < G * W * W; i += kThreads) {
+            const int g = i / (W * W), e = i % (W * W);
+            cnd[g * TS + e] = blk0 + g < p.N ? p.cand_pred[blk0 * W * W + i] : (uint8_t)0;
+        }
+    for (int i = tid; i < G * NC; i += kThreads) cost[i] = 0;
+    __syncthreads();
+    stage_dc<W, G>(ref, dcv, tid);
+    __syncthreads();
+
+    const int lane = tid & 63, g = lane / NSB, sb = lane % NSB;
+    const int by = sb / SB * T, bx = sb % SB * T;
+    const int* rf = ref + g * RS + 2 * W;
+    const uint8_t* tg = tgt + g * TS;
+    for (int round = 0; round < kRounds; round++) {
+        const int mode = __builtin_amdgcn_readfirstlane(round * (kThreads / 64) + tid / 64);
+        unsigned acc;
+        if (mode == 0) {
+            acc = sub_block_hads<W, T>(tg, by, bx, [&](int y, int x) { return planar_pixel<W>(rf, y, x); });
+        } else if (mode == 1) {
+            const int dc = dcv[g];
+            acc = sub_block_hads<W, T>(tg, by, bx, [&](int y, int x) { return dc_pixel<W>(rf, dc, y, x); });
+        } else {
+            const int ang = intra_angle(mode), inv = ang < 0 ? intra_inv_angle(ang) : 0;
+            if (mode >= 18) acc = sub_block_hads<W, T>(tg, by, bx, [&](int y, int x) { return angular_pixel<W, 1>(rf, ang, inv, y, x); });
+            else acc = sub_block_hads<W, T>(tg, by, bx, [&](int y, int x) { return angular_pixel<W, -1>(rf, ang, inv, x, y); });
+        }
+        if (NSB == 1) cost[g * NC + mode] = acc;
+        else atomicAdd(&cost[g * NC + mode], acc);
+    }
+    if (p.cand_pred && tid < 64) {                     // the sixth round: the candidate, one wave
+        const uint8_t* cd = cnd + g * TS;
+        const unsigned acc = sub_block_hads<W, T>(tg, by, bx, [&](int y, int x) { return (int)cd[y * W + x]; });
+        if (NSB == 1) cost[g * NC + 35] = acc;
+        else atomicAdd(&cost[g * NC + 35], acc);
+    }
+    __syncthreads();
+
+    if (p.mode_hads)
+        for (int i = tid; i < G * 35; i += kThreads)
+            if (blk0 + i / 35 < p.N) p.mode_hads[blk0 * 35 + i] = cost[i / 35 * NC + i % 35];
+    if (p.cand_hads && tid < G && blk0 + tid < p.N) p.cand_hads[blk0 + tid] = cost[tid * NC + 35];
+    if ((p.list_modes || p.list_costs) && tid < G && blk0 + tid < p.N) {
+        // xUpdateCandList for indices 0, 1, ... in turn: an entry goes in front of the first strictly larger cost, the rest moves down
+        const unsigned* c = cost + tid * NC;
+        const int nc = p.cand_pred ? 36 : 35;
+        unsigned lc[K];
+        int lm[K];
+#pragma unroll
+        for (int j = 0; j < K; j++) { lc[j] = 0xffffffffu; lm[j] = 255; }
+#pragma unroll 1
+        for (int i = 0; i < nc; i++) {
+            unsigned ci = c[i];
+            int mi = i;
+            bool in = false;
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                in = in || ci < lc[j];
+                const unsigned tc = lc[j];
+                const int tm = lm[j];
+                lc[j] = in ? ci : tc; lm[j] = in ? mi : tm;
+                ci = in ? tc : ci; mi = in ? tm : mi;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            if (p.list_modes) p.list_modes[(blk0 + tid) * K + j] = (uint8_t)lm[j];
+            if (p.list_costs) p.list_costs[(blk0 + tid) * K + j] = lc[j];
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s)
@@ -230,6 +368,25 @@ hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s)
     default: return hipErrorInvalidValue;
     }
 #undef PNN_HEVC_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    const int t = p.w == 4 ? 4 : 8, blocks_per_wg = 64 / ((p.w / t) * (p.w / t));
+    const dim3 grid((unsigned)((p.N + blocks_per_wg - 1) / blocks_per_wg)), block(kThreads);
+    const bool pic = p.patterns == nullptr;
+    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+#define PNN_HADS_LAUNCH(W_) \
+    case W_: if (pic) hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, true>), grid, block, 0, s, p); \
+             else hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, false>), grid, block, 0, s, p); \
+             break;
+    switch (p.w) {
+    PNN_HADS_LAUNCH(4) PNN_HADS_LAUNCH(8) PNN_HADS_LAUNCH(16) PNN_HADS_LAUNCH(32) PNN_HADS_LAUNCH(64)
+    default: return hipErrorInvalidValue;
+    }
+#undef PNN_HADS_LAUNCH
     return hipGetLastError();
 }
 

@@ -276,6 +276,19 @@ struct HevcBestModeParams {
 };
 hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s);
 
+// First-pass ranking (pnn_hevc_intra.hip): the same inputs in the same two forms, plus an optional candidate prediction cand_pred
+// [N][w][w] uint8.  Per block the Hadamard cost (TComRdCost::xGetHADs, 8-bit) of the 35 predictions and of the candidate (index 35)
+// against the target, and HM's sorted candidate list of K = hevc_first_pass_list_size(w) entries (ascending cost, the lower index
+// first among equal costs).  Outputs, each NULL or per block: mode_hads [N][35], cand_hads [N], list_modes [N][K], list_costs [N][K].
+struct HevcModeHadsParams {
+    const uint8_t* patterns; int ph; int pw; const uint8_t* targets; int N; int w;
+    const uint8_t* cand_pred; uint32_t* mode_hads; uint32_t* cand_hads; uint8_t* list_modes; uint32_t* list_costs;
+    PictureBlocks pic;
+    const uint8_t* pic_targets;
+};
+inline int hevc_first_pass_list_size(int w) { return w <= 8 ? 8 : 3; }   // g_aucIntraModeNumFast_UseMPM for w = 4 .. 64
+hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s);
+
 // IPFCN-S, the evaluator's second competitor (pnn_ipfcns.hip).  Blocks b0 .. b0 + nb - 1 of images x positions (image-major): the
 // two groups of 8 reference lines at line origin (rows[pos], cols[pos]) of uint8 picture `img` [H][W] -- rows [r, r + 8) x columns
 // [c, c + 2w + 8), then rows [r + 8, r + 2w + 8) x columns [c, c + 8), both row-major -- minus their mean fl32(S / K) (S the integer

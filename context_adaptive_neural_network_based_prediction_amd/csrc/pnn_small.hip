@@ -11,6 +11,7 @@
 #include <time.h>
 #include "pnn_device_common.h"
 #include "pnn_small_bodies.h"
+#include "pnn_wht.h"
 
 namespace pnn {
 
@@ -616,28 +617,7 @@ hipError_t launch_epilogue(const float* pred, long n, float mean, int32_t* dst, 
 // (f4) Distortion of N predicted blocks against the original picture, as HM's first intra pass computes it for a
 // candidate mode (TEncSearch.cpp:2376-2389 -> TComRdCost::xGetHADs / xGetSAD, TComRdCost.cpp:1753-1824, 1549-1751):
 // one thread per 8x8 (4x4 for 4-wide blocks) sub-block, Walsh-Hadamard transform in registers, integer adds only
-// (the per-block sum over sub-blocks is an integer atomicAdd: order-independent, bit-exact).
-template <int T>
-__device__ __forceinline__ void wht_rows_cols(int (&d)[T * T])
-{
-#pragma unroll
-    for (int pass = 0; pass < 2; pass++) {            // rows, then columns
-        const int es = pass == 0 ? 1 : T, vs = pass == 0 ? T : 1;
-#pragma unroll
-        for (int v = 0; v < T; v++)
-#pragma unroll
-            for (int len = 1; len < T; len <<= 1)
-#pragma unroll
-                for (int i = 0; i < T; i += len << 1)
-#pragma unroll
-                    for (int j = i; j < i + len; j++) {
-                        const int a = d[v * vs + j * es], b = d[v * vs + (j + len) * es];
-                        d[v * vs + j * es] = a + b;
-                        d[v * vs + (j + len) * es] = a - b;
-                    }
-    }
-}
-
+// (the per-block sum over sub-blocks is an integer atomicAdd: order-independent, bit-exact).  wht_rows_cols: pnn_wht.h.
 template <typename Pel, int T>
 __global__ __launch_bounds__(256) void block_cost_kernel(const BlockCostParams p)
 {

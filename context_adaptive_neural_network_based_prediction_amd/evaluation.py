@@ -10,6 +10,8 @@ score_masks_from_pictures is the reference's loop over a list of masks (predict_
 GPU: per mask one pnn_score_pictures_device call (descriptors, PNN pass, uint8 epilogue with its SSE, best-mode search from
 the pictures) and one download; the same dictionaries as predict_mask_vs_hevc_best_mode[_and_ipfcns], bit for bit.
 score_masks_from_picture_pairs is the same loop on [images, H, W, 2] pairs (original, HEVC-decoded) for the pair models.
+Both take first_pass=True for one more column per mask: the PNN and the 35 modes ranked by the Hadamard cost of HM's first intra
+pass (pnn_first_pass_picture_pairs_device: one more call per mask, the same download).
 """
 import ctypes
 
@@ -158,7 +160,7 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 
 
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
-                              tuples_width_height_masks, net_ipfcns=None, keep_predictions=True):
+                              tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -170,13 +172,22 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     intraprediction.psnrs_from_sses (equal to compute_psnr), 0 dB where no HEVC mode beats the reference's start value.
     keep_predictions=False leaves out (and never downloads) 'predictions_*_uint8' and 'targets_uint8'.
     Argument errors are those of context.extract_context_portions_targets_from_channels_plus_preprocessing, raised before
-    anything touches the GPU."""
+    anything touches the GPU.
+
+    first_pass=True adds, per mask, the ranking of HM's first intra pass (TEncSearch.cpp:2376-2492) by ONE more call,
+    pnn_first_pass_picture_pairs_device, with the uint8 PNN predictions the score call left on the device as candidate 35; its results
+    join the one download.  New keys: 'hads_pnn' uint32 [N] and 'hads_hevc_modes' uint32 [N, 35] (TComRdCost::xGetHADs of the
+    predictions against the targets), 'first_pass_list' uint8 [N, K] and 'first_pass_costs' uint32 [N, K] (HM's sorted candidate list,
+    K = 8 for w <= 8, else 3; ascending cost, the lower index first among equal costs, 35 = the PNN),
+    'frequency_pnn_in_first_pass_list' and 'frequency_pnn_first_pass_best' (float: the share of blocks whose list contains 35 / starts
+    with 35).  The costs are those of this evaluator's competitor (no reference-sample smoothing) and leave out HM's
+    modeBits * sqrtLambda term (include/pnn_hip.h).  With first_pass=False nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
-                        net_ipfcns, keep_predictions)
+                        net_ipfcns, keep_predictions, first_pass)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
-                                   tuples_width_height_masks, net_ipfcns=None, keep_predictions=True):
+                                   tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -186,13 +197,15 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
                                project's definition -- the reference's extract_intra_patterns has no pair form; the decoded
                                neighbourhood is what an encoder holds), the reference lines of IPFCN-S (ipfcns.py:60-65)
       original (channel 0):    'targets_uint8' and the targets of every SSE, hence of every PSNR
-    The pair is de-interleaved once on the host and uploaded once; per mask ONE call and ONE download, as for single pictures."""
+    The pair is de-interleaved once on the host and uploaded once; per mask ONE call and ONE download, as for single pictures.
+    first_pass=True: the keys of score_masks_from_pictures; reference samples from the decoded plane, targets of the costs from the
+    original, as in the table above."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
-                        tuples_width_height_masks, net_ipfcns, keep_predictions)
+                        tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass)
 
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                 keep_predictions):
+                 keep_predictions, first_pass=False):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer."""
     if ch.dtype != np.uint8:
@@ -250,6 +263,14 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     d_cols = torch.from_numpy(cols.astype(np.int32)).to(dev)
     # every output of a call in ONE buffer: [PNN SSE u32 n | HEVC SSE u32 n | HEVC index n | PNN uint8 | HEVC uint8 | targets]
     nb_small = 9 * n
+    if first_pass:
+        # ... then, 4-byte aligned, [mode costs u32 n x 35 | PNN cost u32 n | list costs u32 n x K | list indices n x K]
+        nb_list = intraprediction.first_pass_list_size(w)
+        off_hads = (nb_small + 3) // 4 * 4
+        off_hads_pnn = off_hads + 4 * intraprediction.NB_MODES * n
+        off_list_costs = off_hads_pnn + 4 * n
+        off_list = off_list_costs + 4 * nb_list * n
+        nb_small = off_list + nb_list * n
     off_pnn, off_hevc, off_targets = nb_small, nb_small + n * w2, nb_small + 2 * n * w2
     d_out = torch.empty(off_targets + n * w2, dtype=torch.uint8, device=dev)
     base = d_out.data_ptr()
@@ -264,9 +285,14 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
             _lib.check(L.pnn_score_picture_pairs_device(
                 predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
                 d_rows.data_ptr(), d_cols.data_ptr(), n_pos,
-                mask[0], mask[1], base + off_targets if first else None, base + off_pnn if keep_predictions else None, None, base,
-                base + 8 * n, base + 4 * n, base + off_hevc if keep_predictions else None,
+                mask[0], mask[1], base + off_targets if first else None, base + off_pnn if keep_predictions or first_pass else None, None,
+                base, base + 8 * n, base + 4 * n, base + off_hevc if keep_predictions else None,
                 ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
+            if first_pass:                                # the PNN's uint8 predictions are on the device: candidate 35
+                _lib.check(L.pnn_first_pass_picture_pairs_device(
+                    predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
+                    d_rows.data_ptr(), d_cols.data_ptr(), n_pos, mask[0], mask[1], base + off_pnn, base + off_hads, base + off_hads_pnn,
+                    base + off_list, base + off_list_costs, ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
         nb_bytes = (off_targets + (n * w2 if first else 0)) if keep_predictions else nb_small
         out = d_out[:nb_bytes].cpu().numpy()              # (waits for the stream)
         sses_pnn, sses_hevc = out[:4 * n].view(np.uint32), out[4 * n:8 * n].view(np.uint32)
@@ -276,6 +302,16 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         dictionary_performance = {
             'indices_hevc_best_mode': out[8 * n:9 * n].copy(), 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
             'frequency_win_pnn': float(np.count_nonzero(psnrs_pnn - psnrs_hevc > 0.)) / n, 'mean_psnr_pnn': np.mean(psnrs_pnn).item()}
+        if first_pass:
+            first_pass_list = out[off_list:off_list + nb_list * n].reshape(n, nb_list).copy()
+            dictionary_performance['hads_pnn'] = out[off_hads_pnn:off_list_costs].view(np.uint32).copy()
+            dictionary_performance['hads_hevc_modes'] = out[off_hads:off_hads_pnn].view(np.uint32).reshape(n, intraprediction.NB_MODES).copy()
+            dictionary_performance['first_pass_list'] = first_pass_list
+            dictionary_performance['first_pass_costs'] = out[off_list_costs:off_list].view(np.uint32).reshape(n, nb_list).copy()
+            dictionary_performance['frequency_pnn_in_first_pass_list'] = \
+                float(np.count_nonzero((first_pass_list == intraprediction.NB_MODES).any(axis=1))) / n
+            dictionary_performance['frequency_pnn_first_pass_best'] = \
+                float(np.count_nonzero(first_pass_list[:, 0] == intraprediction.NB_MODES)) / n
         if keep_predictions:
             if first:
                 targets_uint8 = out[off_targets:].reshape(n, w, w, 1).copy()

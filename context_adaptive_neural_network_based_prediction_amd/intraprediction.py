@@ -147,6 +147,81 @@ def best_modes_device(intra_patterns, targets, width_target, best_pred=True, mod
     return index, sse, pred, all_sse
 
 
+def first_pass_list_size(width_target):
+    """K of HM's first-pass candidate list (g_aucIntraModeNumFast_UseMPM): 8, 8, 3, 3, 3 for w = 4 .. 64."""
+    k = _lib.lib().pnn_first_pass_list_size(int(width_target))
+    if k < 0:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    return k
+
+
+def _check_mode_hads_arguments(intra_patterns, targets, width_target, candidate_predictions):
+    """Shapes of mode_hads_device / mode_hads_host: patterns [n, h, w'], targets [n, w, w], candidate None or [n, w, w]."""
+    if width_target not in WIDTHS:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    if len(intra_patterns.shape) != 3 or len(targets.shape) != 3:
+        raise ValueError('the intra patterns and the targets must have 3 dimensions.')
+    n = targets.shape[0]
+    if tuple(targets.shape[1:]) != (width_target, width_target):
+        raise ValueError('the target patches are not w x w.')
+    if intra_patterns.shape[0] != n:
+        raise ValueError('the numbers of intra patterns and target patches differ.')
+    if candidate_predictions is not None and tuple(candidate_predictions.shape) != tuple(targets.shape):
+        raise ValueError('`candidate_predictions.shape` is not equal to `targets.shape`.')
+    return n
+
+
+def mode_hads_device(intra_patterns, targets, width_target, candidate_predictions=None, device=0):
+    """HM's first intra pass on the GPU (pnn_hevc_mode_hads_device) on torch uint8 tensors already on `device`: patterns [n, h, w'],
+    targets [n, w, w], candidate_predictions None or [n, w, w] (the PNN's uint8 predictions, candidate 35).  One launch.
+    Returns numpy arrays {'hads_modes': uint32 [n, 35], 'hads_candidate': uint32 [n] or None, 'list_modes': uint8 [n, K],
+    'list_costs': uint32 [n, K]}, K = first_pass_list_size(width_target); the list is in ascending cost, the lower index first among
+    equal costs.  Costs: TComRdCost::xGetHADs of this competitor's predictions (no reference smoothing), without HM's mode-bit term."""
+    import torch
+    n = _check_mode_hads_arguments(intra_patterns, targets, width_target, candidate_predictions)
+    k = first_pass_list_size(width_target)
+    dev = torch.device("cuda", device)
+    tensors = (intra_patterns, targets) + (() if candidate_predictions is None else (candidate_predictions,))
+    if any(t.dtype != torch.uint8 or not t.is_contiguous() or t.device != dev for t in tensors):
+        raise ValueError('the tensors must be contiguous uint8 tensors on the device.')
+    hads = torch.empty((n, NB_MODES), dtype=torch.int32, device=dev)
+    cand = torch.empty(n, dtype=torch.int32, device=dev) if candidate_predictions is not None else None
+    modes = torch.empty((n, k), dtype=torch.uint8, device=dev)
+    costs = torch.empty((n, k), dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().pnn_hevc_mode_hads_device(
+            _context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1], intra_patterns.shape[2],
+            targets.data_ptr(), n, None if candidate_predictions is None else candidate_predictions.data_ptr(), hads.data_ptr(),
+            None if cand is None else cand.data_ptr(), modes.data_ptr(), costs.data_ptr(),
+            ctypes.c_void_p(stream.cuda_stream)), _context(device))
+    stream.synchronize()
+    return {'hads_modes': hads.cpu().numpy().view(np.uint32), 'hads_candidate': None if cand is None else cand.cpu().numpy().view(np.uint32),
+            'list_modes': modes.cpu().numpy(), 'list_costs': costs.cpu().numpy().view(np.uint32)}
+
+
+def mode_hads_host(intra_patterns, targets, width_target, candidate_predictions=None):
+    """mode_hads_device's host twin (pnn_hevc_mode_hads_host, pure host code) on numpy uint8 arrays: same arguments, same dictionary,
+    same bits."""
+    arrays = [intra_patterns, targets] + ([] if candidate_predictions is None else [candidate_predictions])
+    if any(not isinstance(a, np.ndarray) or a.dtype != np.uint8 for a in arrays):
+        raise TypeError('the arrays must be `numpy.ndarray`s of dtype `numpy.uint8`.')
+    n = _check_mode_hads_arguments(intra_patterns, targets, width_target, candidate_predictions)
+    k = first_pass_list_size(width_target)
+    patterns, targets = np.ascontiguousarray(intra_patterns), np.ascontiguousarray(targets)
+    candidate = None if candidate_predictions is None else np.ascontiguousarray(candidate_predictions)
+    hads = np.zeros((n, NB_MODES), np.uint32)
+    cand = None if candidate is None else np.zeros(n, np.uint32)
+    modes, costs = np.zeros((n, k), np.uint8), np.zeros((n, k), np.uint32)
+    rc = _lib.lib().pnn_hevc_mode_hads_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, width_target, n,
+                                            None if candidate is None else candidate.ctypes.data, hads.ctypes.data,
+                                            None if cand is None else cand.ctypes.data, modes.ctypes.data, costs.ctypes.data)
+    if rc != 0:
+        raise ValueError('pnn_hevc_mode_hads_host refused the arguments (patterns %dx%d, width %d).'
+                         % (patterns.shape[1], patterns.shape[2], width_target))
+    return {'hads_modes': hads, 'hads_candidate': cand, 'list_modes': modes, 'list_costs': costs}
+
+
 def predict_series_via_hevc_best_mode(intra_patterns_uint8, targets_uint8, device=0):
     """intraprediction.py:183-229 on the GPU: (indices uint8 [N], PSNRs float64 [N], predictions uint8 [N, w, w, 1]) of the
     best HEVC intra mode per target (smallest SSE, lowest index among ties; index 0, 0 dB and zeros when no mode beats 0 dB)."""

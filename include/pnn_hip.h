@@ -354,6 +354,50 @@ int pnn_score_f32_device(pnn_ctx* ctx, int width, const float* d_pred_f32, const
                          int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
                          uint8_t* d_pred_u8, uint32_t* d_sse, void* stream);
 
+/* ---- HM's first intra pass: the 35 modes and a candidate ranked by Hadamard cost ------------------------ */
+
+/* The SATD twin of pnn_hevc_best_mode_device: where does a candidate prediction (the PNN's) rank among the 35 modes in the metric HM's
+ * first intra pass selects by (TEncSearch.cpp:2376-2492)?
+ *   Predictions.  The 35 predictions of pnn_hevc_intra_predict, from the same intra patterns.  HM also smooths the reference samples
+ *     for some modes and sizes (filteringIntraReferenceSamples); the reference's extracted predictor, hence this library's competitor,
+ *     does not.  THE COSTS ARE THEREFORE THOSE OF THE EVALUATOR'S COMPETITOR, not of HM's filtered predictor.
+ *   Cost of one prediction.  TComRdCost::xGetHADs for 8-bit video (TComRdCost.cpp:1753-1824) against the width x width target: the
+ *     Walsh-Hadamard transform of target - prediction per T x T sub-block, T = 8 (4 at width 4); per sub-block the sum s of the
+ *     absolute coefficients, rounded (s + 2) >> 2 for T = 8 and (s + 1) >> 1 for T = 4; the (width / T)^2 sub-block sums added.
+ *     All integers, exact in any order, uint32 (below 2^25 at width 64).
+ *   The list.  xUpdateCandList applied to modes 0 .. 34 in index order, then to the candidate as index 35 if one was given, with the
+ *     cost alone: K = pnn_first_pass_list_size(width) entries in ascending cost; among equal costs the lower index comes first (HM
+ *     inserts on strict <, so the candidate loses every tie).  HM adds modeBits * sqrtLambda to each cost; that term depends on the
+ *     neighbours' coded modes and on QP, does not exist open-loop and IS LEFT OUT.  (The switch encoder appends mode 35 to its list
+ *     unconditionally, TEncSearch.cpp:2476-2491; this list says whether it would have entered on merit.)
+ * K = 8, 8, 3, 3, 3 for width 4, 8, 16, 32, 64 (g_aucIntraModeNumFast_UseMPM); PNN_E_ARG for another width. */
+int pnn_first_pass_list_size(int width);
+/* Inputs: dense patterns [n][pattern_h][pattern_w] and targets [n][width][width] as for pnn_hevc_best_mode_device; cand_pred NULL or
+ * [n][width][width] uint8, the candidate's predictions.  Outputs, each NULL or per block: mode_hads [n][35] (uint32), cand_hads [n]
+ * (uint32; needs cand_pred), list_modes [n][K] (uint8; 35 = the candidate), list_costs [n][K] (uint32).  Without a candidate the list
+ * ranges over the 35 modes.  n == 0 does nothing.  PNN_E_ARG for a width outside {4, 8, 16, 32, 64}, a pattern side outside
+ * [width + 1, 2 width + 1], n < 0, NULL inputs with n > 0, every output NULL, cand_hads without cand_pred.
+ * The host twin: pure host code, the zero-tolerance yardstick of the device entries and what a CPU-only user calls. */
+int pnn_hevc_mode_hads_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                            const uint8_t* cand_pred, uint32_t* mode_hads, uint32_t* cand_hads, uint8_t* list_modes,
+                            uint32_t* list_costs);
+/* The same on the GPU, all 35 modes x cost, the candidate and the list of n blocks in one launch; device pointers, asynchronous on
+ * `stream`, every argument error reported before the launch.  A context without models (pnn_create_empty) suffices. */
+int pnn_hevc_mode_hads_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
+                              const uint8_t* d_targets, int n, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads,
+                              uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream);
+/* The same from the evaluator's pictures: geometry, block order (n = images * positions, image-major), masks and checks of
+ * pnn_score_picture_pairs_device.  The reference samples (the intra pattern at (row + width - 1, col + width - 1), ending where the
+ * mask says) come from the CONTEXT (decoded) plane, the targets from the TARGET (original) plane; d_cand_pred [n][width][width] is
+ * what that entry's d_pnn_u8 holds.  With d_context_channels == d_target_channels it is the single-picture form.  PNN_E_ARG, before
+ * any launch, for a width outside {4, 8, 16, 32, 64}, a mask outside {0, 4, .., width}, a negative position, row + 3 width > height
+ * or col + 3 width > width_ch, exactly one NULL plane, every output NULL, d_cand_hads without d_cand_pred.  n == 0 does nothing.
+ * Reads d_rows / d_cols back to the host to check them (the call waits for `stream` once); everything after is asynchronous. */
+int pnn_first_pass_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                        int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols,
+                                        int positions, int mask_w, int mask_h, const uint8_t* d_cand_pred, uint32_t* d_mode_hads,
+                                        uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream);
+
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
 int pnn_last_call_stats(const pnn_ctx* ctx, int* n_gemm_launches, double* gemm_flops, int* n_launches);
