@@ -1,6 +1,7 @@
 // C-ABI layer of libpnn_hip.so (declared in include/pnn_hip.h): contexts, model files, staging buffers, the prediction
-// cache and the entry points.  The launch sequences live in pnn_passes.cpp, model building in pnn_model.cpp, tile rules
-// in pnn_tiles.cpp, the autotuner in pnn_tuner.cpp (shared types: pnn_ctx.h).
+// cache and the entry points of the predictor (HM's).  The Python evaluator's entries live in pnn_eval.cpp, the launch
+// sequences in pnn_passes.cpp, model building in pnn_model.cpp, tile rules in pnn_tiles.cpp, the autotuner in pnn_tuner.cpp
+// (shared types: pnn_ctx.h).
 //
 // Reference behaviour reproduced here (not code): TComPrediction::initTempBuff (model selection,
 // hm_16_15_substitution/source/Lib/TLibCommon/TComPrediction.cpp:108-178), load_graphs
@@ -63,12 +64,6 @@ int fail(pnn_ctx* c, int code, const char* fmt, ...)
 
 namespace {
 
-// While ONE thread captures a launch chain (host_predict, option "graphs"), no other thread of the process may allocate, free or copy
-// synchronously: in this runtime such a call invalidates the capture whatever the capture mode (thread-local: one HM run in five,
-// relaxed: two in three -- the reference's HM loads its five graphs on five threads while the main thread is already predicting).
-// Everything of that kind that this library does takes the lock; a capture holds it from begin to end.
-#define PNN_UNSAFE_CALLS_GUARD std::lock_guard<std::recursive_mutex> unsafe_guard_(pnn::unsafe_calls_lock())
-
 void cache_clear(pnn_ctx* c)                          // (every option change / model load: cached predictions and captured launch chains go)
 {
     for (auto& t : c->cache) { t.clear(); t.shrink_to_fit(); }
@@ -94,6 +89,53 @@ int dev_reserve(pnn_ctx* c, DevBuf& b, size_t bytes)
     return PNN_OK;
 }
 
+void reset_stats(pnn_ctx* c) { c->stat_gemm_launches = 0; c->stat_launches = 0; c->stat_gemm_flops = 0; c->stat_gemm_flops_skipped = 0; }
+
+// Device (asynchronous) entry points cannot wait for their own pass; a pass that left the f16 range is reported by the
+// next call on the context (and by pnn_check_range, which waits for the stream).
+int pending_range_error(pnn_ctx* c)
+{
+    if (!c->h_range || !*c->h_range) return PNN_OK;
+    *c->h_range = 0;
+    return fail(c, PNN_E_RANGE, "an earlier asynchronous pass produced activations outside the f16 range of the split-precision "
+                                "kernels (|v| >= 65504): its predictions are invalid; repeat it with pnn_set_option(ctx, \"precision\", 0)");
+}
+
+// gather -> net for n TBs of model m, in slices of chunk_blocks: what pnn_predict_tbs_device enqueues
+int tbs_pass(pnn_ctx* c, Model* m, const void* d_plane, int pel_bytes, const pnn_tb_dev* d_tbs, long n, int32_t* d_dst,
+             float* d_out_f32, hipStream_t s)
+{
+    int rc;
+    const int width = m->width;
+    const long w2 = (long)width * width;
+    const long chunk = std::min(n, chunk_blocks(c, m));
+    if ((rc = dev_reserve(c, c->stage_in[0], (size_t)chunk * 5 * w2 * 4))) return rc;
+    float* ctxbuf = (float*)c->stage_in[0].p;
+    for (long b0 = 0; b0 < n; b0 += chunk) {
+        const long nb = std::min(chunk, n - b0);
+        float* ab = ctxbuf;
+        float* lf = m->is_fc ? ctxbuf + 3 * w2 : ctxbuf + nb * 3 * w2;
+        const long pa = m->is_fc ? 5 * w2 : 3 * w2, pl = m->is_fc ? 5 * w2 : 2 * w2;
+        const bool split_ctx = m->is_fc && pass_uses_split(c, m, nb);   // the FC chain starts on the split-precision GEMM
+        // convolutional nets whose first convolutions run inside the image kernel: the gather goes in there too
+        const bool lazy = !m->is_fc && nb <= chunk_blocks(c, m) && conv_pass_fuses_first(c, m, nb);
+        if (lazy) {
+            c->lazy.plane = d_plane; c->lazy.tbs = reinterpret_cast<const TbDev*>(d_tbs + b0); c->lazy.pel_bytes = pel_bytes; c->lazy.unit = 4;
+            ab = lf = nullptr;
+        } else {
+            GatherParams g;
+            g.plane = d_plane; g.pel_bytes = pel_bytes; g.tbs = reinterpret_cast<const TbDev*>(d_tbs + b0); g.N = (int)nb; g.w = width;
+            g.unit = 4; g.mean = c->mean; g.above = ab; g.left = lf; g.pitch_above = pa; g.pitch_left = pl; g.split = split_ctx ? 1 : 0;
+            HIPCHK(c, launch_gather(g, s));
+            c->stat_launches++;
+        }
+        rc = run_net(c, m, ab, pa, lf, pl, nb, d_out_f32 ? d_out_f32 + b0 * w2 : nullptr, d_dst ? d_dst + b0 * w2 : nullptr, s, split_ctx);
+        c->lazy = pnn_ctx::LazyGather();
+        if (rc) return rc;
+    }
+    return PNN_OK;
+}
+
 }  // namespace pnn
 
 namespace {
@@ -110,18 +152,6 @@ Model* model_for(pnn_ctx* c, int width, int want_fc /* -1 any */, int* rc)
     }
     *rc = PNN_OK;
     return m;
-}
-
-void reset_stats(pnn_ctx* c) { c->stat_gemm_launches = 0; c->stat_launches = 0; c->stat_gemm_flops = 0; c->stat_gemm_flops_skipped = 0; }
-
-// Device (asynchronous) entry points cannot wait for their own pass; a pass that left the f16 range is reported by the
-// next call on the context (and by pnn_check_range, which waits for the stream).
-int pending_range_error(pnn_ctx* c)
-{
-    if (!c->h_range || !*c->h_range) return PNN_OK;
-    *c->h_range = 0;
-    return fail(c, PNN_E_RANGE, "an earlier asynchronous pass produced activations outside the f16 range of the split-precision "
-                                "kernels (|v| >= 65504): its predictions are invalid; repeat it with pnn_set_option(ctx, \"precision\", 0)");
 }
 
 // End of a synchronous host call whose last kernel took no completion signal: wait for the context's stream.
@@ -578,41 +608,6 @@ int pnn_gather_device(pnn_ctx* c, int width, int unit, const void* d_plane, int 
     return PNN_OK;
 }
 
-// gather -> net for n TBs of model m, in slices of chunk_blocks: what pnn_predict_tbs_device enqueues
-static int tbs_pass(pnn_ctx* c, Model* m, const void* d_plane, int pel_bytes, const pnn_tb_dev* d_tbs, long n, int32_t* d_dst,
-                    float* d_out_f32, hipStream_t s)
-{
-    int rc;
-    const int width = m->width;
-    const long w2 = (long)width * width;
-    const long chunk = std::min(n, chunk_blocks(c, m));
-    if ((rc = dev_reserve(c, c->stage_in[0], (size_t)chunk * 5 * w2 * 4))) return rc;
-    float* ctxbuf = (float*)c->stage_in[0].p;
-    for (long b0 = 0; b0 < n; b0 += chunk) {
-        const long nb = std::min(chunk, n - b0);
-        float* ab = ctxbuf;
-        float* lf = m->is_fc ? ctxbuf + 3 * w2 : ctxbuf + nb * 3 * w2;
-        const long pa = m->is_fc ? 5 * w2 : 3 * w2, pl = m->is_fc ? 5 * w2 : 2 * w2;
-        const bool split_ctx = m->is_fc && pass_uses_split(c, m, nb);   // the FC chain starts on the split-precision GEMM
-        // convolutional nets whose first convolutions run inside the image kernel: the gather goes in there too
-        const bool lazy = !m->is_fc && nb <= chunk_blocks(c, m) && conv_pass_fuses_first(c, m, nb);
-        if (lazy) {
-            c->lazy.plane = d_plane; c->lazy.tbs = reinterpret_cast<const TbDev*>(d_tbs + b0); c->lazy.pel_bytes = pel_bytes; c->lazy.unit = 4;
-            ab = lf = nullptr;
-        } else {
-            GatherParams g;
-            g.plane = d_plane; g.pel_bytes = pel_bytes; g.tbs = reinterpret_cast<const TbDev*>(d_tbs + b0); g.N = (int)nb; g.w = width;
-            g.unit = 4; g.mean = c->mean; g.above = ab; g.left = lf; g.pitch_above = pa; g.pitch_left = pl; g.split = split_ctx ? 1 : 0;
-            HIPCHK(c, launch_gather(g, s));
-            c->stat_launches++;
-        }
-        rc = run_net(c, m, ab, pa, lf, pl, nb, d_out_f32 ? d_out_f32 + b0 * w2 : nullptr, d_dst ? d_dst + b0 * w2 : nullptr, s, split_ctx);
-        c->lazy = pnn_ctx::LazyGather();
-        if (rc) return rc;
-    }
-    return PNN_OK;
-}
-
 int pnn_predict_tbs_device(pnn_ctx* c, int width, const void* d_plane, int pel_bytes, const pnn_tb_dev* d_tbs, int n,
                            int32_t* d_dst, float* d_out_f32, void* stream)
 {
@@ -637,301 +632,6 @@ int pnn_block_cost_device(pnn_ctx* c, int width, const void* d_org_plane, int pe
     b.org_plane = d_org_plane; b.pel_bytes = pel_bytes; b.tbs = reinterpret_cast<const TbDev*>(d_tbs); b.N = n; b.w = width;
     b.pred = d_pred; b.hadamard = hadamard; b.cost = d_cost;
     HIPCHK(c, launch_block_cost(b, (hipStream_t)stream));
-    return PNN_OK;
-}
-
-int pnn_hevc_best_mode_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
-                              const uint8_t* d_targets, int n, uint8_t* d_best_mode, uint32_t* d_best_sse, uint8_t* d_best_pred,
-                              uint32_t* d_mode_sse, void* stream)
-{
-    if (!c) return PNN_E_ARG;
-    if (width_index(width) < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
-    if (pattern_h < width + 1 || pattern_h > 2 * width + 1 || pattern_w < width + 1 || pattern_w > 2 * width + 1)
-        return fail(c, PNN_E_ARG, "intra pattern %dx%d: both sides must lie in [%d, %d]", pattern_h, pattern_w, width + 1, 2 * width + 1);
-    if (n < 0 || (n > 0 && (!d_patterns || !d_targets))) return fail(c, PNN_E_ARG, "bad batch size or input buffers");
-    if (!d_best_mode && !d_best_sse && !d_best_pred && !d_mode_sse) return fail(c, PNN_E_ARG, "every output is NULL");
-    if (n == 0) return PNN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    HevcBestModeParams p;
-    p.patterns = d_patterns; p.ph = pattern_h; p.pw = pattern_w; p.targets = d_targets; p.N = n; p.w = width;
-    p.best_mode = d_best_mode; p.best_sse = d_best_sse; p.best_pred = d_best_pred; p.mode_sse = d_mode_sse;
-    p.pic = PictureBlocks{}; p.pic_targets = nullptr;
-    HIPCHK(c, launch_hevc_best_mode(p, (hipStream_t)stream));
-    return PNN_OK;
-}
-
-int pnn_hevc_mode_hads_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets,
-                              int n, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes,
-                              uint32_t* d_list_costs, void* stream)
-{
-    if (!c) return PNN_E_ARG;
-    if (width_index(width) < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
-    if (pattern_h < width + 1 || pattern_h > 2 * width + 1 || pattern_w < width + 1 || pattern_w > 2 * width + 1)
-        return fail(c, PNN_E_ARG, "intra pattern %dx%d: both sides must lie in [%d, %d]", pattern_h, pattern_w, width + 1, 2 * width + 1);
-    if (n < 0 || (n > 0 && (!d_patterns || !d_targets))) return fail(c, PNN_E_ARG, "bad batch size or input buffers");
-    if (!d_mode_hads && !d_cand_hads && !d_list_modes && !d_list_costs) return fail(c, PNN_E_ARG, "every output is NULL");
-    if (d_cand_hads && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_hads needs d_cand_pred");
-    if (n == 0) return PNN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    HevcModeHadsParams p;
-    p.patterns = d_patterns; p.ph = pattern_h; p.pw = pattern_w; p.targets = d_targets; p.N = n; p.w = width;
-    p.cand_pred = d_cand_pred; p.mode_hads = d_mode_hads; p.cand_hads = d_cand_hads; p.list_modes = d_list_modes; p.list_costs = d_list_costs;
-    p.pic = PictureBlocks{}; p.pic_targets = nullptr;
-    HIPCHK(c, launch_hevc_mode_hads(p, (hipStream_t)stream));
-    return PNN_OK;
-}
-
-int pnn_ipfcns_load(pnn_ctx* c, int width, const float* params, size_t n_floats)
-{
-    if (!c) return PNN_E_ARG;
-    const int idx = ipfcns_index(width);
-    if (idx < 0) return fail(c, PNN_E_ARG, "no IPFCN-S for width %d (4, 8, 16 or 32)", width);
-    if (!params) return fail(c, PNN_E_ARG, "NULL parameters");
-    HIPCHK(c, hipSetDevice(c->device));
-    Model* m = nullptr;
-    const int rc = build_ipfcns_model(c, width, params, n_floats, &m);
-    if (rc) return rc;
-    PNN_UNSAFE_CALLS_GUARD;
-    if (c->ipfcns[idx]) HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_model(c->ipfcns[idx]);
-    c->ipfcns[idx] = m;
-    c->tuned.clear(); c->tune_gen++;                                 // keys point into the replaced net
-    return PNN_OK;
-}
-
-static Model* ipfcns_for(pnn_ctx* c, int width, int* rc)
-{
-    const int idx = ipfcns_index(width);
-    if (idx < 0) { *rc = fail(c, PNN_E_ARG, "no IPFCN-S for width %d (4, 8, 16 or 32)", width); return nullptr; }
-    if (!c->ipfcns[idx]) { *rc = fail(c, PNN_E_ARG, "no IPFCN-S loaded for width %d", width); return nullptr; }
-    *rc = PNN_OK;
-    return c->ipfcns[idx];
-}
-
-int pnn_ipfcns_forward_device(pnn_ctx* c, int width, const float* d_x, int n, float* d_out_f32, void* stream)
-{
-    if (!c) return PNN_E_ARG;
-    int rc;
-    const Model* m = ipfcns_for(c, width, &rc);
-    if (!m) return rc;
-    if (n < 0 || (n > 0 && (!d_x || !d_out_f32))) return fail(c, PNN_E_ARG, "bad batch size or buffers");
-    if (n == 0) return PNN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    reset_stats(c);
-    return ipfcns_pass(c, m, d_x, n, d_out_f32, (hipStream_t)stream);
-}
-
-int pnn_ipfcns_predict_device(pnn_ctx* c, int width, const uint8_t* d_channels, int images, int height, int width_ch,
-                              const int32_t* d_rows, const int32_t* d_cols, int positions, const uint8_t* d_targets,
-                              uint8_t* d_pred_u8, float* d_pred_f32, float* d_means, uint32_t* d_sse, void* stream)
-{
-    if (!c) return PNN_E_ARG;
-    int rc;
-    const Model* m = ipfcns_for(c, width, &rc);
-    if (!m) return rc;
-    if (images < 0 || positions < 0 || height < 0 || width_ch < 0) return fail(c, PNN_E_ARG, "negative sizes");
-    if (d_sse && !d_targets) return fail(c, PNN_E_ARG, "d_sse needs d_targets");
-    const long n = (long)images * positions;
-    if (n > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks");
-    if (n == 0) return PNN_OK;
-    if (!d_channels || !d_rows || !d_cols) return fail(c, PNN_E_ARG, "NULL input buffers");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    {   // every line origin inside the picture, checked before any launch
-        std::vector<int32_t> rows(positions), cols(positions);
-        {
-            PNN_UNSAFE_CALLS_GUARD;
-            HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipMemcpyAsync(cols.data(), d_cols, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-        }
-        const int span = 2 * width + 8;
-        for (int i = 0; i < positions; i++)
-            if (rows[i] < 0 || cols[i] < 0 || (long)rows[i] + span > height || (long)cols[i] + span > width_ch)
-                return fail(c, PNN_E_ARG, "line origin %d (%d, %d): the %dx%d lines leave the %dx%d picture", i, rows[i], cols[i], span, span, height, width_ch);
-    }
-    reset_stats(c);
-    int K, H;
-    ipfcns_dims(width, &K, &H);
-    const long w2 = (long)width * width, chunk = std::min(n, ipfcns_chunk(c, m));
-    if ((rc = dev_reserve(c, c->ipfcns_ws[0], (size_t)chunk * K * 4))) return rc;
-    if ((rc = dev_reserve(c, c->ipfcns_ws[3], (size_t)chunk * (w2 + 1) * 4))) return rc;
-    float* rows_f = (float*)c->ipfcns_ws[0].p;
-    float* fc4 = (float*)c->ipfcns_ws[3].p;
-    float* means_ws = fc4 + chunk * w2;
-    for (long b0 = 0; b0 < n; b0 += chunk) {
-        const int nb = (int)std::min(chunk, n - b0);
-        float* means = d_means ? d_means + b0 : means_ws;
-        IpfcnsGatherParams g;
-        g.channels = d_channels; g.H = height; g.W = width_ch; g.rows = d_rows; g.cols = d_cols; g.positions = positions;
-        g.b0 = b0; g.nb = nb; g.w = width; g.x = rows_f; g.mean = means;
-        HIPCHK(c, launch_ipfcns_gather(g, s));
-        if ((rc = ipfcns_pass(c, m, rows_f, nb, fc4, s))) return rc;
-        IpfcnsEpilogueParams e;
-        e.fc4 = fc4; e.mean = means; e.nb = nb; e.w2 = (int)w2;
-        e.u8 = d_pred_u8 ? d_pred_u8 + b0 * w2 : nullptr; e.f32 = d_pred_f32 ? d_pred_f32 + b0 * w2 : nullptr;
-        e.targets = d_targets ? d_targets + b0 * w2 : nullptr; e.sse = d_sse ? d_sse + b0 : nullptr;
-        HIPCHK(c, launch_ipfcns_epilogue(e, s));
-        c->stat_launches += 2;
-    }
-    return PNN_OK;
-}
-
-// Arguments common to the two scoring entries, checked before any launch; the positions are read back once (the call waits for the stream).
-static int check_picture_blocks(pnn_ctx* c, int width, const uint8_t* d_channels, int images, int height, int width_ch,
-                                const int32_t* d_rows, const int32_t* d_cols, int positions, hipStream_t s)
-{
-    if (!d_channels || !d_rows || !d_cols) return fail(c, PNN_E_ARG, "NULL input buffers");
-    std::vector<int32_t> rows(positions), cols(positions);
-    {
-        PNN_UNSAFE_CALLS_GUARD;
-        HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(cols.data(), d_cols, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    for (int i = 0; i < positions; i++)
-        if (rows[i] < 0 || cols[i] < 0 || (long)rows[i] + 3 * width > height || (long)cols[i] + 3 * width > width_ch)
-            return fail(c, PNN_E_ARG, "position %d (%d, %d): the %dx%d context leaves the %dx%d picture", i, rows[i], cols[i], 3 * width,
-                        3 * width, height, width_ch);
-    return PNN_OK;
-}
-
-int pnn_score_pictures_device(pnn_ctx* c, int width, const uint8_t* d_channels, int images, int height, int width_ch,
-                              const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w, int mask_h,
-                              uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
-                              uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
-{
-    // a single picture is the pair of one plane with itself
-    return pnn_score_picture_pairs_device(c, width, d_channels, d_channels, images, height, width_ch, d_rows, d_cols, positions, mask_w,
-                                          mask_h, d_targets, d_pnn_u8, d_pnn_f32, d_pnn_sse, d_hevc_mode, d_hevc_sse, d_hevc_pred, stream);
-}
-
-int pnn_score_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
-                                   int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
-                                   int mask_h, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
-                                   uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
-{
-    if (!c) return PNN_E_ARG;
-    if (!d_context_channels != !d_target_channels)
-        return fail(c, PNN_E_ARG, "one plane of the pair is NULL (%s)", d_context_channels ? "d_target_channels" : "d_context_channels");
-    const int idx = width_index(width);
-    if (idx < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
-    if (mask_w < 0 || mask_w > width || mask_w % 4 || mask_h < 0 || mask_h > width || mask_h % 4)
-        return fail(c, PNN_E_ARG, "masks (%d, %d): both must belong to {0, 4, ..., %d}", mask_w, mask_h, width);
-    if (images < 0 || positions < 0 || height < 0 || width_ch < 0) return fail(c, PNN_E_ARG, "negative sizes");
-    const bool want_pnn = d_pnn_u8 || d_pnn_f32 || d_pnn_sse, want_hevc = d_hevc_mode || d_hevc_sse || d_hevc_pred;
-    if (!d_targets && !want_pnn && !want_hevc) return fail(c, PNN_E_ARG, "every output is NULL");
-    Model* m = want_pnn ? c->models[idx] : nullptr;
-    if (want_pnn && !m) return fail(c, PNN_E_ARG, "a PNN output is asked for, but no model is loaded for width %d", width);
-    const long n = (long)images * positions;
-    if (n > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks");
-    if (n == 0) return PNN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = check_picture_blocks(c, width, d_context_channels, images, height, width_ch, d_rows, d_cols, positions, s))) return rc;
-    if (want_pnn && (rc = pending_range_error(c))) return rc;
-    reset_stats(c);
-    // contexts and intra patterns from the context plane, targets (hence both SSEs) from the target plane
-    PictureBlocks pic, pic_tg;
-    pic.channels = d_context_channels; pic.H = height; pic.W = width_ch; pic.rows = d_rows; pic.cols = d_cols; pic.positions = positions;
-    pic_tg = pic; pic_tg.channels = d_target_channels;
-    const long w2 = (long)width * width;
-    // the PNN half in slices (descriptors -> gather -> net -> epilogue); the bits of a block do not depend on its slice
-    const long chunk = want_pnn ? std::min(n, chunk_blocks(c, m)) : n;
-    float* ws_f32 = nullptr;
-    if (want_pnn) {
-        if ((rc = dev_reserve(c, c->score_ws[0], (size_t)chunk * sizeof(TbDev)))) return rc;
-        if (!d_pnn_f32) {
-            if ((rc = dev_reserve(c, c->score_ws[1], (size_t)chunk * w2 * 4))) return rc;
-            ws_f32 = (float*)c->score_ws[1].p;
-        }
-    }
-    for (long b0 = 0; b0 < n && (want_pnn || d_targets); b0 += chunk) {
-        const int nb = (int)std::min(chunk, n - b0);
-        float* pred = nullptr;
-        if (want_pnn) {
-            ScoreDescParams d;
-            d.pic = pic; d.b0 = b0; d.nb = nb; d.w = width; d.mask_w = mask_w; d.mask_h = mask_h; d.tbs = (TbDev*)c->score_ws[0].p;
-            HIPCHK(c, launch_score_desc(d, s));
-            pred = d_pnn_f32 ? d_pnn_f32 + b0 * w2 : ws_f32;
-            if ((rc = tbs_pass(c, m, d_context_channels, 1, (const pnn_tb_dev*)c->score_ws[0].p, nb, nullptr, pred, s))) return rc;
-            c->stat_launches++;
-        }
-        if (d_targets || d_pnn_u8 || d_pnn_sse) {
-            ScoreEpilogueParams e;
-            e.pic = pic_tg; e.b0 = b0; e.nb = nb; e.w = width; e.pred = pred; e.mean = c->mean;
-            e.u8 = d_pnn_u8 ? d_pnn_u8 + b0 * w2 : nullptr; e.targets = d_targets ? d_targets + b0 * w2 : nullptr;
-            e.sse = d_pnn_sse ? d_pnn_sse + b0 : nullptr;
-            HIPCHK(c, launch_score_epilogue(e, s));
-            c->stat_launches++;
-        }
-    }
-    if (want_hevc) {
-        HevcBestModeParams p;
-        p.patterns = nullptr; p.ph = 2 * width + 1 - mask_h; p.pw = 2 * width + 1 - mask_w; p.targets = nullptr; p.N = (int)n; p.w = width;
-        p.best_mode = d_hevc_mode; p.best_sse = d_hevc_sse; p.best_pred = d_hevc_pred; p.mode_sse = nullptr;
-        p.pic = pic; p.pic_targets = d_target_channels;
-        HIPCHK(c, launch_hevc_best_mode(p, s));
-        c->stat_launches++;
-    }
-    return PNN_OK;
-}
-
-int pnn_first_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
-                                        int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
-                                        int mask_h, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads,
-                                        uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
-{
-    if (!c) return PNN_E_ARG;
-    if (!d_context_channels != !d_target_channels)
-        return fail(c, PNN_E_ARG, "one plane of the pair is NULL (%s)", d_context_channels ? "d_target_channels" : "d_context_channels");
-    if (width_index(width) < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
-    if (mask_w < 0 || mask_w > width || mask_w % 4 || mask_h < 0 || mask_h > width || mask_h % 4)
-        return fail(c, PNN_E_ARG, "masks (%d, %d): both must belong to {0, 4, ..., %d}", mask_w, mask_h, width);
-    if (images < 0 || positions < 0 || height < 0 || width_ch < 0) return fail(c, PNN_E_ARG, "negative sizes");
-    if (!d_mode_hads && !d_cand_hads && !d_list_modes && !d_list_costs) return fail(c, PNN_E_ARG, "every output is NULL");
-    if (d_cand_hads && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_hads needs d_cand_pred");
-    const long n = (long)images * positions;
-    if (n > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks");
-    if (n == 0) return PNN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = check_picture_blocks(c, width, d_context_channels, images, height, width_ch, d_rows, d_cols, positions, s))) return rc;
-    reset_stats(c);
-    HevcModeHadsParams p;
-    p.patterns = nullptr; p.ph = 2 * width + 1 - mask_h; p.pw = 2 * width + 1 - mask_w; p.targets = nullptr; p.N = (int)n; p.w = width;
-    p.cand_pred = d_cand_pred; p.mode_hads = d_mode_hads; p.cand_hads = d_cand_hads; p.list_modes = d_list_modes; p.list_costs = d_list_costs;
-    p.pic.channels = d_context_channels; p.pic.H = height; p.pic.W = width_ch; p.pic.rows = d_rows; p.pic.cols = d_cols; p.pic.positions = positions;
-    p.pic_targets = d_target_channels;
-    HIPCHK(c, launch_hevc_mode_hads(p, s));
-    c->stat_launches++;
-    return PNN_OK;
-}
-
-int pnn_score_f32_device(pnn_ctx* c, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,
-                         int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, uint8_t* d_pred_u8,
-                         uint32_t* d_sse, void* stream)
-{
-    if (!c) return PNN_E_ARG;
-    if (width_index(width) < 0) return fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", width);
-    if (images < 0 || positions < 0 || height < 0 || width_ch < 0) return fail(c, PNN_E_ARG, "negative sizes");
-    if (!d_pred_u8 && !d_sse) return fail(c, PNN_E_ARG, "every output is NULL");
-    const long n = (long)images * positions;
-    if (n > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks");
-    if (n == 0) return PNN_OK;
-    if (!d_pred_f32) return fail(c, PNN_E_ARG, "NULL input buffers");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = check_picture_blocks(c, width, d_channels, images, height, width_ch, d_rows, d_cols, positions, s))) return rc;
-    reset_stats(c);
-    ScoreEpilogueParams e;
-    e.pic.channels = d_channels; e.pic.H = height; e.pic.W = width_ch; e.pic.rows = d_rows; e.pic.cols = d_cols; e.pic.positions = positions;
-    e.b0 = 0; e.nb = (int)n; e.w = width; e.pred = d_pred_f32; e.mean = c->mean; e.u8 = d_pred_u8; e.targets = nullptr; e.sse = d_sse;
-    HIPCHK(c, launch_score_epilogue(e, s));
-    c->stat_launches++;
     return PNN_OK;
 }
 

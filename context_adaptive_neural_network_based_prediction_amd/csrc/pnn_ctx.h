@@ -3,7 +3,8 @@
 //   pnn_tiles.cpp   rule-based choice of the kernel family / tile configuration of a tap GEMM
 //   pnn_tuner.cpp   on-device choice among the legal configurations, remembered per (layer, M)
 //   pnn_passes.cpp  the launch sequences of one pass of the fully-connected / convolutional nets
-//   pnn_abi.cpp     the extern "C" entry points, contexts, staging and the prediction cache
+//   pnn_abi.cpp     contexts, staging, the prediction cache and the extern "C" entry points of the predictor
+//   pnn_eval.cpp    the extern "C" entry points of the Python evaluator (HEVC modes, IPFCN-S, scores from pictures)
 #pragma once
 #include "../../include/pnn_hip.h"
 #include "pnn_kernels.h"
@@ -264,6 +265,11 @@ namespace pnn {
 int fail(pnn_ctx* c, int code, const char* fmt, ...);
 // process-wide: held by a stream capture from begin to end and by every allocation / free / synchronous copy of the library (pnn_abi.cpp)
 std::recursive_mutex& unsafe_calls_lock();
+// While ONE thread captures a launch chain (host_predict, option "graphs"), no other thread of the process may allocate, free or copy
+// synchronously: in this runtime such a call invalidates the capture whatever the capture mode (thread-local: one HM run in five,
+// relaxed: two in three -- the reference's HM loads its five graphs on five threads while the main thread is already predicting).
+// Everything of that kind that this library does takes the lock; a capture holds it from begin to end.
+#define PNN_UNSAFE_CALLS_GUARD std::lock_guard<std::recursive_mutex> unsafe_guard_(pnn::unsafe_calls_lock())
 
 #define HIPCHK(c, expr)                                                                             \
     do {                                                                                            \
@@ -273,6 +279,11 @@ std::recursive_mutex& unsafe_calls_lock();
 
 // pnn_abi.cpp
 int dev_reserve(pnn_ctx* c, DevBuf& b, size_t bytes);
+void reset_stats(pnn_ctx* c);
+int pending_range_error(pnn_ctx* c);                  // PNN_E_RANGE once if an earlier asynchronous pass left the f16 range
+// gather -> net for n TBs of model m, in slices of chunk_blocks: what pnn_predict_tbs_device enqueues
+int tbs_pass(pnn_ctx* c, Model* m, const void* d_plane, int pel_bytes, const pnn_tb_dev* d_tbs, long n, int32_t* d_dst, float* d_out_f32,
+             hipStream_t s);
 // pnn_model.cpp
 int build_model(pnn_ctx* c, int width, int is_fc, const float* params, size_t n, Model** out);
 // IPFCN-S: params in the canonical order of pnn_ipfcns_load (include/pnn_hip.h); fc[0..3] with act = 0, slopes in d_slope

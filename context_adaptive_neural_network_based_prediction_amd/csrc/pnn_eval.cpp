@@ -1,0 +1,357 @@
+// The C-ABI entries of the Python evaluator (include/pnn_hip.h; HM calls none of them): the best HEVC intra mode and the first-pass
+// Hadamard ranking on dense patterns, IPFCN-S, the scores from pictures and pairs of pictures.  Contexts, models, staging and the
+// predictor's entries: pnn_abi.cpp.  Each argument check is written once and composed per entry; an entry's ORDER of checks is part of
+// its behaviour (which of two bad arguments pnn_last_error names), so it is spelled out in the entry.
+#include "pnn_ctx.h"
+
+#include <algorithm>
+
+using namespace pnn;
+
+namespace {
+
+// ---- every check once: PNN_OK, or the refusal with its text left for pnn_last_error ----
+int check_width(pnn_ctx* c, int w) { return width_index(w) >= 0 ? PNN_OK : fail(c, PNN_E_ARG, "width %d is not 4, 8, 16, 32 or 64", w); }
+int check_ipfcns_width(pnn_ctx* c, int w) { return ipfcns_index(w) >= 0 ? PNN_OK : fail(c, PNN_E_ARG, "no IPFCN-S for width %d (4, 8, 16 or 32)", w); }
+int check_some_output(pnn_ctx* c, bool any) { return any ? PNN_OK : fail(c, PNN_E_ARG, "every output is NULL"); }
+int check_sizes(pnn_ctx* c, int images, int positions, int height, int width_ch)
+{
+    return images < 0 || positions < 0 || height < 0 || width_ch < 0 ? fail(c, PNN_E_ARG, "negative sizes") : PNN_OK;
+}
+int check_masks(pnn_ctx* c, int width, int mask_w, int mask_h)
+{
+    if (mask_w < 0 || mask_w > width || mask_w % 4 || mask_h < 0 || mask_h > width || mask_h % 4)
+        return fail(c, PNN_E_ARG, "masks (%d, %d): both must belong to {0, 4, ..., %d}", mask_w, mask_h, width);
+    return PNN_OK;
+}
+int count_blocks(pnn_ctx* c, int images, int positions, long* n)
+{
+    *n = (long)images * positions;
+    return *n > 0x7fffffffL ? fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks") : PNN_OK;
+}
+// the outputs of the first-pass ranking, dense or from pictures
+int check_hads_outputs(pnn_ctx* c, const void* d_cand_pred, const void* d_mode_hads, const void* d_cand_hads, const void* d_list_modes,
+                       const void* d_list_costs)
+{
+    if (const int rc = check_some_output(c, d_mode_hads || d_cand_hads || d_list_modes || d_list_costs)) return rc;
+    return d_cand_hads && !d_cand_pred ? fail(c, PNN_E_ARG, "d_cand_hads needs d_cand_pred") : PNN_OK;
+}
+// dense form of the 35-mode kernels, everything in front of the outputs
+int check_dense_blocks(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n)
+{
+    if (const int rc = check_width(c, width)) return rc;
+    if (pattern_h < width + 1 || pattern_h > 2 * width + 1 || pattern_w < width + 1 || pattern_w > 2 * width + 1)
+        return fail(c, PNN_E_ARG, "intra pattern %dx%d: both sides must lie in [%d, %d]", pattern_h, pattern_w, width + 1, 2 * width + 1);
+    return n < 0 || (n > 0 && (!d_patterns || !d_targets)) ? fail(c, PNN_E_ARG, "bad batch size or input buffers") : PNN_OK;
+}
+// picture-pair form, everything in front of the outputs: both planes or none, width, masks, sizes
+int check_pair_geometry(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images, int height,
+                        int width_ch, int positions, int mask_w, int mask_h)
+{
+    int rc;
+    if (!d_context_channels != !d_target_channels)
+        return fail(c, PNN_E_ARG, "one plane of the pair is NULL (%s)", d_context_channels ? "d_target_channels" : "d_context_channels");
+    if ((rc = check_width(c, width)) || (rc = check_masks(c, width, mask_w, mask_h))) return rc;
+    return check_sizes(c, images, positions, height, width_ch);
+}
+
+// The positions are read back once (the call waits for the stream) and checked before any launch: the span x span pixels at each of
+// them lie inside the picture.  `what` and `leaves` word the refusal: "position" / "context leaves" for the 3w contexts, "line origin" /
+// "lines leave" for the 2w + 8 reference lines of IPFCN-S.
+int check_positions(pnn_ctx* c, const int32_t* d_rows, const int32_t* d_cols, int positions, int span, int height, int width_ch,
+                    const char* what, const char* leaves, hipStream_t s)
+{
+    std::vector<int32_t> rows(positions), cols(positions);
+    {
+        PNN_UNSAFE_CALLS_GUARD;
+        HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(cols.data(), d_cols, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    for (int i = 0; i < positions; i++)
+        if (rows[i] < 0 || cols[i] < 0 || (long)rows[i] + span > height || (long)cols[i] + span > width_ch)
+            return fail(c, PNN_E_ARG, "%s %d (%d, %d): the %dx%d %s the %dx%d picture", what, i, rows[i], cols[i], span, span, leaves, height, width_ch);
+    return PNN_OK;
+}
+
+// inputs common to the scoring entries: the buffers, then every 3w x 3w context inside the picture
+int check_picture_blocks(pnn_ctx* c, int width, const PictureBlocks& pic, hipStream_t s)
+{
+    if (!pic.channels || !pic.rows || !pic.cols) return fail(c, PNN_E_ARG, "NULL input buffers");
+    return check_positions(c, pic.rows, pic.cols, pic.positions, 3 * width, pic.H, pic.W, "position", "context leaves", s);
+}
+
+PictureBlocks picture_blocks(const uint8_t* d_channels, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions)
+{
+    PictureBlocks b;
+    b.channels = d_channels; b.H = height; b.W = width_ch; b.rows = d_rows; b.cols = d_cols; b.positions = positions;
+    return b;
+}
+
+// Where a 35-mode kernel reads its blocks, the fields both parameter structs have (pnn_kernels.h).  Dense form: patterns and targets, no
+// picture.  Picture form: patterns == NULL, the planes in *pic and pic_targets, ph / pw = 2w + 1 - mask_h / mask_w (what the masks leave
+// of the pattern's first column and row).
+template <typename P>
+void set_blocks(P& p, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets, long n, int width)
+{
+    p.patterns = patterns; p.ph = ph; p.pw = pw; p.targets = targets; p.N = (int)n; p.w = width;
+    p.pic = pic ? *pic : PictureBlocks{}; p.pic_targets = pic_targets;
+}
+HevcBestModeParams best_mode_params(const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets,
+                                    long n, int width, uint8_t* best_mode, uint32_t* best_sse, uint8_t* best_pred, uint32_t* mode_sse)
+{
+    HevcBestModeParams p;
+    set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width);
+    p.best_mode = best_mode; p.best_sse = best_sse; p.best_pred = best_pred; p.mode_sse = mode_sse;
+    return p;
+}
+HevcModeHadsParams mode_hads_params(const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets,
+                                    long n, int width, const uint8_t* cand_pred, uint32_t* mode_hads, uint32_t* cand_hads, uint8_t* list_modes,
+                                    uint32_t* list_costs)
+{
+    HevcModeHadsParams p;
+    set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width);
+    p.cand_pred = cand_pred; p.mode_hads = mode_hads; p.cand_hads = cand_hads; p.list_modes = list_modes; p.list_costs = list_costs;
+    return p;
+}
+
+Model* ipfcns_for(pnn_ctx* c, int width, int* rc)
+{
+    if ((*rc = check_ipfcns_width(c, width))) return nullptr;
+    Model* m = c->ipfcns[ipfcns_index(width)];
+    if (!m) *rc = fail(c, PNN_E_ARG, "no IPFCN-S loaded for width %d", width);
+    return m;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pnn_hevc_best_mode_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
+                              const uint8_t* d_targets, int n, uint8_t* d_best_mode, uint32_t* d_best_sse, uint8_t* d_best_pred,
+                              uint32_t* d_mode_sse, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) ||
+        (rc = check_some_output(c, d_best_mode || d_best_sse || d_best_pred || d_mode_sse))) return rc;
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const HevcBestModeParams p = best_mode_params(d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, width, d_best_mode, d_best_sse,
+                                                  d_best_pred, d_mode_sse);
+    HIPCHK(c, launch_hevc_best_mode(p, (hipStream_t)stream));
+    return PNN_OK;
+}
+
+int pnn_hevc_mode_hads_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets,
+                              int n, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes,
+                              uint32_t* d_list_costs, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) ||
+        (rc = check_hads_outputs(c, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs))) return rc;
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const HevcModeHadsParams p = mode_hads_params(d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, width, d_cand_pred, d_mode_hads,
+                                                  d_cand_hads, d_list_modes, d_list_costs);
+    HIPCHK(c, launch_hevc_mode_hads(p, (hipStream_t)stream));
+    return PNN_OK;
+}
+
+int pnn_ipfcns_load(pnn_ctx* c, int width, const float* params, size_t n_floats)
+{
+    if (!c) return PNN_E_ARG;
+    if (const int rc = check_ipfcns_width(c, width)) return rc;
+    if (!params) return fail(c, PNN_E_ARG, "NULL parameters");
+    HIPCHK(c, hipSetDevice(c->device));
+    Model* m = nullptr;
+    const int rc = build_ipfcns_model(c, width, params, n_floats, &m);
+    if (rc) return rc;
+    const int idx = ipfcns_index(width);
+    PNN_UNSAFE_CALLS_GUARD;
+    if (c->ipfcns[idx]) HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_model(c->ipfcns[idx]);
+    c->ipfcns[idx] = m;
+    c->tuned.clear(); c->tune_gen++;                                 // keys point into the replaced net
+    return PNN_OK;
+}
+
+int pnn_ipfcns_forward_device(pnn_ctx* c, int width, const float* d_x, int n, float* d_out_f32, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    const Model* m = ipfcns_for(c, width, &rc);
+    if (!m) return rc;
+    if (n < 0 || (n > 0 && (!d_x || !d_out_f32))) return fail(c, PNN_E_ARG, "bad batch size or buffers");
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    reset_stats(c);
+    return ipfcns_pass(c, m, d_x, n, d_out_f32, (hipStream_t)stream);
+}
+
+int pnn_ipfcns_predict_device(pnn_ctx* c, int width, const uint8_t* d_channels, int images, int height, int width_ch,
+                              const int32_t* d_rows, const int32_t* d_cols, int positions, const uint8_t* d_targets,
+                              uint8_t* d_pred_u8, float* d_pred_f32, float* d_means, uint32_t* d_sse, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    const Model* m = ipfcns_for(c, width, &rc);
+    if (!m) return rc;
+    if ((rc = check_sizes(c, images, positions, height, width_ch))) return rc;
+    if (d_sse && !d_targets) return fail(c, PNN_E_ARG, "d_sse needs d_targets");
+    long n;
+    if ((rc = count_blocks(c, images, positions, &n))) return rc;
+    if (n == 0) return PNN_OK;
+    if (!d_channels || !d_rows || !d_cols) return fail(c, PNN_E_ARG, "NULL input buffers");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_positions(c, d_rows, d_cols, positions, 2 * width + 8, height, width_ch, "line origin", "lines leave", s))) return rc;
+    reset_stats(c);
+    int K, H;
+    ipfcns_dims(width, &K, &H);
+    const long w2 = (long)width * width, chunk = std::min(n, ipfcns_chunk(c, m));
+    if ((rc = dev_reserve(c, c->ipfcns_ws[0], (size_t)chunk * K * 4))) return rc;
+    if ((rc = dev_reserve(c, c->ipfcns_ws[3], (size_t)chunk * (w2 + 1) * 4))) return rc;
+    float* rows_f = (float*)c->ipfcns_ws[0].p;
+    float* fc4 = (float*)c->ipfcns_ws[3].p;
+    float* means_ws = fc4 + chunk * w2;
+    for (long b0 = 0; b0 < n; b0 += chunk) {
+        const int nb = (int)std::min(chunk, n - b0);
+        float* means = d_means ? d_means + b0 : means_ws;
+        IpfcnsGatherParams g;
+        g.channels = d_channels; g.H = height; g.W = width_ch; g.rows = d_rows; g.cols = d_cols; g.positions = positions;
+        g.b0 = b0; g.nb = nb; g.w = width; g.x = rows_f; g.mean = means;
+        HIPCHK(c, launch_ipfcns_gather(g, s));
+        if ((rc = ipfcns_pass(c, m, rows_f, nb, fc4, s))) return rc;
+        IpfcnsEpilogueParams e;
+        e.fc4 = fc4; e.mean = means; e.nb = nb; e.w2 = (int)w2;
+        e.u8 = d_pred_u8 ? d_pred_u8 + b0 * w2 : nullptr; e.f32 = d_pred_f32 ? d_pred_f32 + b0 * w2 : nullptr;
+        e.targets = d_targets ? d_targets + b0 * w2 : nullptr; e.sse = d_sse ? d_sse + b0 : nullptr;
+        HIPCHK(c, launch_ipfcns_epilogue(e, s));
+        c->stat_launches += 2;
+    }
+    return PNN_OK;
+}
+
+int pnn_score_pictures_device(pnn_ctx* c, int width, const uint8_t* d_channels, int images, int height, int width_ch,
+                              const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w, int mask_h,
+                              uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
+                              uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
+{
+    // a single picture is the pair of one plane with itself
+    return pnn_score_picture_pairs_device(c, width, d_channels, d_channels, images, height, width_ch, d_rows, d_cols, positions, mask_w,
+                                          mask_h, d_targets, d_pnn_u8, d_pnn_f32, d_pnn_sse, d_hevc_mode, d_hevc_sse, d_hevc_pred, stream);
+}
+
+int pnn_score_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                   int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
+                                   int mask_h, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
+                                   uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    long n;
+    const bool want_pnn = d_pnn_u8 || d_pnn_f32 || d_pnn_sse, want_hevc = d_hevc_mode || d_hevc_sse || d_hevc_pred;
+    if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+        (rc = check_some_output(c, d_targets || want_pnn || want_hevc))) return rc;
+    Model* m = want_pnn ? c->models[width_index(width)] : nullptr;
+    if (want_pnn && !m) return fail(c, PNN_E_ARG, "a PNN output is asked for, but no model is loaded for width %d", width);
+    if ((rc = count_blocks(c, images, positions, &n))) return rc;
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    // contexts and intra patterns from the context plane, targets (hence both SSEs) from the target plane
+    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
+    const PictureBlocks pic_tg = picture_blocks(d_target_channels, height, width_ch, d_rows, d_cols, positions);
+    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
+    if (want_pnn && (rc = pending_range_error(c))) return rc;
+    reset_stats(c);
+    const long w2 = (long)width * width;
+    // the PNN half in slices (descriptors -> gather -> net -> epilogue); the bits of a block do not depend on its slice
+    const long chunk = want_pnn ? std::min(n, chunk_blocks(c, m)) : n;
+    float* ws_f32 = nullptr;
+    if (want_pnn) {
+        if ((rc = dev_reserve(c, c->score_ws[0], (size_t)chunk * sizeof(TbDev)))) return rc;
+        if (!d_pnn_f32) {
+            if ((rc = dev_reserve(c, c->score_ws[1], (size_t)chunk * w2 * 4))) return rc;
+            ws_f32 = (float*)c->score_ws[1].p;
+        }
+    }
+    for (long b0 = 0; b0 < n && (want_pnn || d_targets); b0 += chunk) {
+        const int nb = (int)std::min(chunk, n - b0);
+        float* pred = nullptr;
+        if (want_pnn) {
+            ScoreDescParams d;
+            d.pic = pic; d.b0 = b0; d.nb = nb; d.w = width; d.mask_w = mask_w; d.mask_h = mask_h; d.tbs = (TbDev*)c->score_ws[0].p;
+            HIPCHK(c, launch_score_desc(d, s));
+            pred = d_pnn_f32 ? d_pnn_f32 + b0 * w2 : ws_f32;
+            if ((rc = tbs_pass(c, m, d_context_channels, 1, (const pnn_tb_dev*)c->score_ws[0].p, nb, nullptr, pred, s))) return rc;
+            c->stat_launches++;
+        }
+        if (d_targets || d_pnn_u8 || d_pnn_sse) {
+            ScoreEpilogueParams e;
+            e.pic = pic_tg; e.b0 = b0; e.nb = nb; e.w = width; e.pred = pred; e.mean = c->mean;
+            e.u8 = d_pnn_u8 ? d_pnn_u8 + b0 * w2 : nullptr; e.targets = d_targets ? d_targets + b0 * w2 : nullptr;
+            e.sse = d_pnn_sse ? d_pnn_sse + b0 : nullptr;
+            HIPCHK(c, launch_score_epilogue(e, s));
+            c->stat_launches++;
+        }
+    }
+    if (want_hevc) {
+        const HevcBestModeParams p = best_mode_params(nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n,
+                                                      width, d_hevc_mode, d_hevc_sse, d_hevc_pred, nullptr);
+        HIPCHK(c, launch_hevc_best_mode(p, s));
+        c->stat_launches++;
+    }
+    return PNN_OK;
+}
+
+int pnn_first_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                        int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
+                                        int mask_h, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads,
+                                        uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    long n;
+    if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+        (rc = check_hads_outputs(c, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs)) ||
+        (rc = count_blocks(c, images, positions, &n))) return rc;
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
+    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
+    reset_stats(c);
+    const HevcModeHadsParams p = mode_hads_params(nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n,
+                                                  width, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs);
+    HIPCHK(c, launch_hevc_mode_hads(p, s));
+    c->stat_launches++;
+    return PNN_OK;
+}
+
+int pnn_score_f32_device(pnn_ctx* c, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,
+                         int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, uint8_t* d_pred_u8,
+                         uint32_t* d_sse, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    long n;
+    if ((rc = check_width(c, width)) || (rc = check_sizes(c, images, positions, height, width_ch)) ||
+        (rc = check_some_output(c, d_pred_u8 || d_sse)) || (rc = count_blocks(c, images, positions, &n))) return rc;
+    if (n == 0) return PNN_OK;
+    if (!d_pred_f32) return fail(c, PNN_E_ARG, "NULL input buffers");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    ScoreEpilogueParams e;
+    e.pic = picture_blocks(d_channels, height, width_ch, d_rows, d_cols, positions);
+    if ((rc = check_picture_blocks(c, width, e.pic, s))) return rc;
+    reset_stats(c);
+    e.b0 = 0; e.nb = (int)n; e.w = width; e.pred = d_pred_f32; e.mean = c->mean; e.u8 = d_pred_u8; e.targets = nullptr; e.sse = d_sse;
+    HIPCHK(c, launch_score_epilogue(e, s));
+    c->stat_launches++;
+    return PNN_OK;
+}
+
+}  // extern "C"

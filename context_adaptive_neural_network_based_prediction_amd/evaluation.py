@@ -121,12 +121,18 @@ def predict_without_mask_via_ipfcns(channels_uint8, width_target, row_1sts, col_
     d_targets = torch.from_numpy(np.ascontiguousarray(targets_uint8[..., 0])).to(dev)
     pred_u8, _, _, sses = net_ipfcns.predict_from_channels_device(d_channels, torch.from_numpy(rows).to(dev),
                                                                   torch.from_numpy(cols).to(dev), d_targets)
+    _fill_ipfcns_keys(dictionary_performance, sses, width_target, pred_u8)
+
+
+def _fill_ipfcns_keys(dictionary_performance, sses, width_target, pred_u8):
+    """The IPFCN-S keys from the integer SSEs of its uint8 predictions [N,w,w] (None: 'predictions_ipfcns_uint8' is left out)."""
     psnrs = intraprediction.psnrs_from_sses(sses, width_target)
     dictionary_performance['psnrs_ipfcns'] = psnrs
     dictionary_performance['frequency_win_ipfcns'] = \
-        float(np.count_nonzero(psnrs - dictionary_performance['psnrs_hevc_best_mode'] > 0.)) / nb_targets
+        float(np.count_nonzero(psnrs - dictionary_performance['psnrs_hevc_best_mode'] > 0.)) / psnrs.size
     dictionary_performance['mean_psnr_ipfcns'] = np.mean(psnrs).item()
-    dictionary_performance['predictions_ipfcns_uint8'] = pred_u8[..., None]
+    if pred_u8 is not None:
+        dictionary_performance['predictions_ipfcns_uint8'] = pred_u8[..., None]
 
 
 def predict_mask_vs_hevc_best_mode_and_ipfcns(channels_uint8, width_target, row_1sts, col_1sts, predictor, batch_size,
@@ -261,19 +267,22 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     d_target_channels, d_context_channels = d_planes[0], d_planes[nb_planes - 1]
     d_rows = torch.from_numpy(rows.astype(np.int32)).to(dev)
     d_cols = torch.from_numpy(cols.astype(np.int32)).to(dev)
-    # every output of a call in ONE buffer: [PNN SSE u32 n | HEVC SSE u32 n | HEVC index n | PNN uint8 | HEVC uint8 | targets]
-    nb_small = 9 * n
+    # Every output of a call in ONE buffer, described once as (name, dtype, shape): the small results first, then the uint8 blocks
+    # of the PNN, of HEVC and the targets; a download is a prefix of it.  Each section starts at a multiple of its item size.
+    sections = [('sses_pnn', np.uint32, (n,)), ('sses_hevc', np.uint32, (n,)), ('indices_hevc', np.uint8, (n,))]
+    nb_modes = intraprediction.NB_MODES
     if first_pass:
-        # ... then, 4-byte aligned, [mode costs u32 n x 35 | PNN cost u32 n | list costs u32 n x K | list indices n x K]
         nb_list = intraprediction.first_pass_list_size(w)
-        off_hads = (nb_small + 3) // 4 * 4
-        off_hads_pnn = off_hads + 4 * intraprediction.NB_MODES * n
-        off_list_costs = off_hads_pnn + 4 * n
-        off_list = off_list_costs + 4 * nb_list * n
-        nb_small = off_list + nb_list * n
-    off_pnn, off_hevc, off_targets = nb_small, nb_small + n * w2, nb_small + 2 * n * w2
-    d_out = torch.empty(off_targets + n * w2, dtype=torch.uint8, device=dev)
-    base = d_out.data_ptr()
+        sections += [('hads_hevc_modes', np.uint32, (n, nb_modes)), ('hads_pnn', np.uint32, (n,)),
+                     ('first_pass_costs', np.uint32, (n, nb_list)), ('first_pass_list', np.uint8, (n, nb_list))]
+    sections += [(name, np.uint8, (n, w, w, 1)) for name in ('predictions_pnn', 'predictions_hevc', 'targets')]
+    begin, end, offset = {}, {}, 0
+    for name, dtype, shape in sections:
+        size = np.dtype(dtype).itemsize
+        begin[name] = (offset + size - 1) // size * size
+        end[name] = offset = begin[name] + size * int(np.prod(shape))
+    d_out = torch.empty(end['targets'], dtype=torch.uint8, device=dev)       # the last section
+    ptr = {name: d_out.data_ptr() + begin[name] for name in begin}
     stream = torch.cuda.current_stream(dev)
     results = {}
     targets_uint8 = None
@@ -285,52 +294,42 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
             _lib.check(L.pnn_score_picture_pairs_device(
                 predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
                 d_rows.data_ptr(), d_cols.data_ptr(), n_pos,
-                mask[0], mask[1], base + off_targets if first else None, base + off_pnn if keep_predictions or first_pass else None, None,
-                base, base + 8 * n, base + 4 * n, base + off_hevc if keep_predictions else None,
+                mask[0], mask[1], ptr['targets'] if first else None, ptr['predictions_pnn'] if keep_predictions or first_pass else None, None,
+                ptr['sses_pnn'], ptr['indices_hevc'], ptr['sses_hevc'], ptr['predictions_hevc'] if keep_predictions else None,
                 ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
             if first_pass:                                # the PNN's uint8 predictions are on the device: candidate 35
                 _lib.check(L.pnn_first_pass_picture_pairs_device(
                     predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
-                    d_rows.data_ptr(), d_cols.data_ptr(), n_pos, mask[0], mask[1], base + off_pnn, base + off_hads, base + off_hads_pnn,
-                    base + off_list, base + off_list_costs, ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
-        nb_bytes = (off_targets + (n * w2 if first else 0)) if keep_predictions else nb_small
-        out = d_out[:nb_bytes].cpu().numpy()              # (waits for the stream)
-        sses_pnn, sses_hevc = out[:4 * n].view(np.uint32), out[4 * n:8 * n].view(np.uint32)
-        psnrs_pnn = intraprediction.psnrs_from_sses(sses_pnn, w)
-        psnrs_hevc = intraprediction.psnrs_from_sses(sses_hevc, w)
-        psnrs_hevc[sses_hevc == 65025 * w2] = 0.          # the reference's start value, never beaten
+                    d_rows.data_ptr(), d_cols.data_ptr(), n_pos, mask[0], mask[1], ptr['predictions_pnn'], ptr['hads_hevc_modes'],
+                    ptr['hads_pnn'], ptr['first_pass_list'], ptr['first_pass_costs'], ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
+        nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
+        out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
+        view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
+        psnrs_pnn = intraprediction.psnrs_from_sses(view['sses_pnn'], w)
+        psnrs_hevc = intraprediction.psnrs_from_sses(view['sses_hevc'], w)
+        psnrs_hevc[view['sses_hevc'] == 65025 * w2] = 0.  # the reference's start value, never beaten
         dictionary_performance = {
-            'indices_hevc_best_mode': out[8 * n:9 * n].copy(), 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
+            'indices_hevc_best_mode': view['indices_hevc'].copy(), 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
             'frequency_win_pnn': float(np.count_nonzero(psnrs_pnn - psnrs_hevc > 0.)) / n, 'mean_psnr_pnn': np.mean(psnrs_pnn).item()}
         if first_pass:
-            first_pass_list = out[off_list:off_list + nb_list * n].reshape(n, nb_list).copy()
-            dictionary_performance['hads_pnn'] = out[off_hads_pnn:off_list_costs].view(np.uint32).copy()
-            dictionary_performance['hads_hevc_modes'] = out[off_hads:off_hads_pnn].view(np.uint32).reshape(n, intraprediction.NB_MODES).copy()
-            dictionary_performance['first_pass_list'] = first_pass_list
-            dictionary_performance['first_pass_costs'] = out[off_list_costs:off_list].view(np.uint32).reshape(n, nb_list).copy()
+            for key in ('hads_pnn', 'hads_hevc_modes', 'first_pass_list', 'first_pass_costs'):
+                dictionary_performance[key] = view[key].copy()
+            first_pass_list = dictionary_performance['first_pass_list']
             dictionary_performance['frequency_pnn_in_first_pass_list'] = \
-                float(np.count_nonzero((first_pass_list == intraprediction.NB_MODES).any(axis=1))) / n
-            dictionary_performance['frequency_pnn_first_pass_best'] = \
-                float(np.count_nonzero(first_pass_list[:, 0] == intraprediction.NB_MODES)) / n
+                float(np.count_nonzero((first_pass_list == nb_modes).any(axis=1))) / n
+            dictionary_performance['frequency_pnn_first_pass_best'] = float(np.count_nonzero(first_pass_list[:, 0] == nb_modes)) / n
         if keep_predictions:
             if first:
-                targets_uint8 = out[off_targets:].reshape(n, w, w, 1).copy()
-            dictionary_performance['predictions_pnn_uint8'] = out[off_pnn:off_hevc].reshape(n, w, w, 1).copy()
-            dictionary_performance['predictions_hevc_best_mode_uint8'] = out[off_hevc:off_targets].reshape(n, w, w, 1).copy()
+                targets_uint8 = view['targets'].copy()
+            dictionary_performance['predictions_pnn_uint8'] = view['predictions_pnn'].copy()
+            dictionary_performance['predictions_hevc_best_mode_uint8'] = view['predictions_hevc'].copy()
             dictionary_performance['targets_uint8'] = targets_uint8
         results[mask] = dictionary_performance
     if net_ipfcns is not None and (0, 0) in results:
         # the reference lines' origin is (row_1st + w - 8, col_1st + w - 8), in the context plane; the targets (of the target plane)
         # are on the device already
-        d_targets = d_out[off_targets:].view(n, w, w)
+        d_targets = d_out[begin['targets']:].view(n, w, w)
         pred_u8, _, _, sses = net_ipfcns.predict_from_channels_device(d_context_channels, d_rows + (w - 8), d_cols + (w - 8), d_targets,
                                                                       pred_u8=keep_predictions)
-        dictionary_performance = results[(0, 0)]
-        psnrs = intraprediction.psnrs_from_sses(sses, w)
-        dictionary_performance['psnrs_ipfcns'] = psnrs
-        dictionary_performance['frequency_win_ipfcns'] = \
-            float(np.count_nonzero(psnrs - dictionary_performance['psnrs_hevc_best_mode'] > 0.)) / n
-        dictionary_performance['mean_psnr_ipfcns'] = np.mean(psnrs).item()
-        if keep_predictions:
-            dictionary_performance['predictions_ipfcns_uint8'] = pred_u8[..., None]
+        _fill_ipfcns_keys(results[(0, 0)], sses, w, pred_u8)
     return results

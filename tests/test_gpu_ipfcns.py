@@ -2,7 +2,6 @@
 family): bit for bit against the host twin pnn_ipfcns_forward_host at every width, batch size, tile configuration and slice
 size; the fused path from pictures against the twin and numpy; the uint8 epilogue's half-to-even rounding and clipping; NULL
 outputs, empty calls and argument errors; and the evaluator's three-way dictionary.  Seeded weights only."""
-import ctypes
 import os
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 from context_adaptive_neural_network_based_prediction_amd import _lib, evaluation
 from context_adaptive_neural_network_based_prediction_amd import ipfcns as I
 from tests import util
+from tests.util import dev, ipfcns_params, pictures, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -20,41 +20,6 @@ NATURAL = os.path.join(ROOT, "oracle", "_ref", "natural_luma.npz")
 PNN_E_ARG = -1
 
 
-def recipe_params(w, seed, gain=1.0):
-    K, H, O = I.layer_dims(w)
-    rng = np.random.default_rng(seed)
-    s = (0.032 * np.sqrt(192 / K), 0.0188 * np.sqrt(512 / H), 0.0168 * np.sqrt(512 / H), 0.092 * np.sqrt(512 / H) * gain)
-    dims = (K, H, H, H, O)
-    parts = []
-    for l in range(4):
-        parts.append(rng.normal(0, s[l], dims[l + 1] * dims[l]))
-        parts.append(rng.normal(0, 0.02, dims[l + 1]))
-        if l < 3:
-            parts.append(rng.uniform(-0.3, 0.6, dims[l + 1]))
-    return np.concatenate(parts).astype(np.float32)
-
-
-def pictures(n_images, H, W, seed):
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    out = []
-    for i in range(n_images):
-        f = rng.uniform(0.02, 0.2, 4)
-        img = 128 + 60 * np.sin(f[0] * xx + f[1] * yy) + 40 * np.cos(f[2] * xx - f[3] * yy) + rng.normal(0, 6, (H, W))
-        out.append(np.clip(img, 0, 255))
-    return np.array(out).astype(np.uint8)
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def rows_for(w, n, seed):
     rng = np.random.default_rng(seed)
     return rng.normal(0, 40, (n, I.input_size(w))).astype(np.float32)
@@ -62,7 +27,7 @@ def rows_for(w, n, seed):
 
 @pytest.mark.parametrize("w", I.WIDTHS)
 def test_forward_device_equals_the_twin_bit_for_bit(w):
-    params = recipe_params(w, 10 + w)
+    params = ipfcns_params(w, 10 + w)
     net = I.NetIpfcns(w, params)
     sizes = (1, 7, 64, 1000, 2048 if w == 32 else 8192)
     x = rows_for(w, sizes[-1], 20 + w)
@@ -75,7 +40,7 @@ def test_forward_device_equals_the_twin_bit_for_bit(w):
 
 @pytest.mark.parametrize("w", I.WIDTHS)
 def test_every_tile_configuration_and_slice_size_gives_the_twin_bits(w):
-    params = recipe_params(w, 30 + w)
+    params = ipfcns_params(w, 30 + w)
     net = I.NetIpfcns(w, params)
     net.set_option("autotune", 0)
     x = rows_for(w, 300, 40 + w)
@@ -104,7 +69,7 @@ def twin_predict(params, w, imgs, rows, cols, targets=None):
 @pytest.mark.parametrize("w", I.WIDTHS)
 def test_fused_path_equals_twin_and_numpy(w):
     """>= 65 536 positions per width over several pictures, edge origins included, plus constant pictures 0 .. 255."""
-    params = recipe_params(w, 50 + w)
+    params = ipfcns_params(w, 50 + w)
     net = I.NetIpfcns(w, params)
     span = 2 * w + 8
     imgs = pictures(4, 3 * span + 13, 4 * span + 9, 60 + w)
@@ -152,7 +117,7 @@ def raw_predict(net, w, imgs, rows, cols, targets, outs, n_override=None):
 def test_null_outputs_empty_calls_and_bad_arguments():
     import torch
     w = 8
-    params = recipe_params(w, 80)
+    params = ipfcns_params(w, 80)
     net = I.NetIpfcns(w, params)
     span = 2 * w + 8
     imgs = dev(pictures(2, 50, 60, 81))
@@ -198,7 +163,7 @@ def test_null_outputs_empty_calls_and_bad_arguments():
     assert L.pnn_ipfcns_load(net.ctx, 16, p.ctypes.data_as(_lib.f32p), p.size) == PNN_E_ARG
     x = rows_for(w, 9, 83)
     before = net.forward(x)
-    p2 = recipe_params(w, 84)
+    p2 = ipfcns_params(w, 84)
     net.load(p2)
     assert net.forward(x).tobytes() == I.forward_host(p2, w, x).tobytes() != before.tobytes()
     net.close()
@@ -231,7 +196,7 @@ def test_epilogue_rounds_half_to_even_and_clips():
 def check_three_way(img, w, rows, cols):
     import context_adaptive_neural_network_based_prediction_amd as P
     net = P.PredictionNeuralNetwork(4, w, False, path_to_model=os.path.join(GOLD, "conv%d_single.pnnw" % w))
-    params = recipe_params(w, 90 + w)
+    params = ipfcns_params(w, 90 + w)
     ipf = I.NetIpfcns(w, params)
     res = evaluation.predict_mask_vs_hevc_best_mode_and_ipfcns(img, w, rows, cols, net, 4, util.MEAN, ipf)
     base = evaluation.predict_mask_vs_hevc_best_mode(img, w, rows, cols, net, 4, util.MEAN)

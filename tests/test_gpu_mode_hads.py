@@ -5,7 +5,6 @@ Every comparison has zero tolerance, against the host twin pnn_hevc_mode_hads_ho
 code): the costs are integers, exact in any order.  The dense shapes cross one workgroup boundary with a ragged last group (a
 workgroup takes 64, 64, 16, 4, 1 blocks at w = 4 .. 64): the smallest at which the sub-block-to-lane mapping, the LDS atomics
 (w >= 16), the one-block workgroup (w = 64) and the tie rule can each go wrong."""
-import ctypes
 import itertools
 import os
 
@@ -15,6 +14,7 @@ import pytest
 from context_adaptive_neural_network_based_prediction_amd import _lib, evaluation
 from context_adaptive_neural_network_based_prediction_amd import intraprediction as ip
 from tests import util
+from tests.util import dev, picture_pairs, positions, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -24,18 +24,7 @@ PNN_E_ARG = -1                       # include/pnn_hip.h
 DENSE_N = {4: 64 + 3, 8: 64 + 3, 16: 16 + 3, 32: 4 + 3, 64: 3}
 OUTPUTS = ("mode_hads", "cand_hads", "list_modes", "list_costs")
 HOST_KEYS = ("hads_modes", "hads_candidate", "list_modes", "list_costs")
-POSITIONS = ((0, 0), (5, 9), (2, 5))               # the near corner, the far one (H - 3w, W - 3w), one in between
 GUARD, PAD = 0xC5, 256                             # guard bytes in front of and behind every output
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def dense_blocks(w, n, sides, seed):
@@ -133,29 +122,6 @@ def test_dense_form_equals_the_host_twin(w):
             got = ip.mode_hads_device(d_patterns, d_targets, w, d_cand if cand is not None else None)
             for key in HOST_KEYS:
                 assert (got[key] is None and host[key] is None) or got[key].tobytes() == host[key].tobytes(), (w, sides, key)
-
-
-def picture_pairs(n_images, w, seed):
-    """[images, 3w + 5, 3w + 9, 2] uint8: channel 0 seeded pictures with structure and noise, channel 1 a "decoded" version that
-    differs from it at every pixel (each moved by 3 .. 12 levels towards mid-grey)."""
-    H, W = 3 * w + 5, 3 * w + 9
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    planes = []
-    for _ in range(n_images):
-        f = rng.uniform(0.02, 0.2, 4)
-        img = 128 + 60 * np.sin(f[0] * xx + f[1] * yy) + 40 * np.cos(f[2] * xx - f[3] * yy) + rng.normal(0, 6, (H, W))
-        planes.append(np.clip(img, 0, 255))
-    original = np.array(planes).astype(np.int64)
-    shift = rng.integers(3, 13, original.shape)
-    decoded = np.where(original < 128, original + shift, original - shift)
-    pair = np.stack([original, decoded], axis=-1).astype(np.uint8)
-    assert (pair[..., 0] != pair[..., 1]).all()
-    return pair
-
-
-def positions(which=POSITIONS):
-    return np.array([p[0] for p in which], np.int64), np.array([p[1] for p in which], np.int64)
 
 
 def dense_inputs_of_pictures(context_plane, target_plane, w, rows, cols, mask):

@@ -9,7 +9,6 @@ targets for HEVC; the line extraction on the pair and the net's forward for IPFC
 
 Pictures are (3w + 5) x (3w + 9), so the far position (5, 9) touches the last row and column; the decoded plane differs from the
 original at EVERY pixel, so a plane read in the wrong place cannot go unnoticed."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -19,52 +18,19 @@ from context_adaptive_neural_network_based_prediction_amd import intraprediction
 from context_adaptive_neural_network_based_prediction_amd import ipfcns as I
 from context_adaptive_neural_network_based_prediction_amd.prediction_neural_network import predict_by_batch_via_pnn
 from tests import util
+from tests.util import POSITIONS, assert_same_dictionary, dev, ipfcns_params, picture_pairs, positions, stream
 
 pytestmark = pytest.mark.gpu
 
 PNN_E_ARG = -1                       # include/pnn_hip.h
 OUTPUTS = ("targets", "pnn_u8", "pnn_f32", "pnn_sse", "hevc_mode", "hevc_sse", "hevc_pred")
-POSITIONS = ((0, 0), (5, 9), (2, 5))               # the near corner, the far one (H - 3w, W - 3w), one in between
 GUARD, PAD = 0xC5, 256                             # guard bytes in front of and behind every output
-
-
-def picture_pairs(n_images, w, seed):
-    """[images, 3w + 5, 3w + 9, 2] uint8: channel 0 seeded pictures with structure and noise, channel 1 a "decoded" version built
-    from it -- every pixel moved by 3 .. 12 levels towards mid-grey, so the two differ at every pixel and stay inside [0, 255]."""
-    H, W = 3 * w + 5, 3 * w + 9
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    planes = []
-    for _ in range(n_images):
-        f = rng.uniform(0.02, 0.2, 4)
-        img = 128 + 60 * np.sin(f[0] * xx + f[1] * yy) + 40 * np.cos(f[2] * xx - f[3] * yy) + rng.normal(0, 6, (H, W))
-        planes.append(np.clip(img, 0, 255))
-    original = np.array(planes).astype(np.int64)
-    shift = rng.integers(3, 13, original.shape)
-    decoded = np.where(original < 128, original + shift, original - shift)
-    pair = np.stack([original, decoded], axis=-1).astype(np.uint8)
-    assert (pair[..., 0] != pair[..., 1]).all()
-    return pair
-
-
-def positions(which=POSITIONS):
-    return np.array([p[0] for p in which], np.int64), np.array([p[1] for p in which], np.int64)
 
 
 def make_net(w, kind, batch):
     import context_adaptive_neural_network_based_prediction_amd as P
     is_fc = kind == "fc"
     return P.PredictionNeuralNetwork(batch, w, is_fc, params=util.make_params(w, is_fc, seed=70 + w, out_gain=util.out_gain(w, is_fc)))
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def yardstick_outputs(pair, w, rows, cols, net, mask):
@@ -101,17 +67,6 @@ def yardstick_dictionary(pair, w, rows, cols, net, mask):
             'frequency_win_pnn': float(np.count_nonzero(psnrs_pnn - psnrs_hevc > 0.)) / n, 'mean_psnr_pnn': np.mean(psnrs_pnn).item(),
             'predictions_pnn_uint8': predictions_uint8, 'predictions_hevc_best_mode_uint8': predictions_hevc,
             'targets_uint8': targets_uint8}
-
-
-def assert_same_dictionary(got, want, label):
-    assert set(got) == set(want), label
-    for key, v in want.items():
-        g = got[key]
-        if isinstance(v, np.ndarray):
-            assert isinstance(g, np.ndarray) and g.dtype == v.dtype and g.shape == v.shape, (label, key)
-            assert g.tobytes() == v.tobytes(), "%s %s: %d differing values" % (label, key, (g != v).sum())
-        else:
-            assert type(g) is type(v) and g == v, (label, key, g, v)
 
 
 def output_dtypes(n, w):
@@ -290,21 +245,6 @@ def test_bad_arguments_are_refused_before_any_launch():
     rc, got, intact = call("pnn_score_picture_pairs_device", net.ctx, w, (d_context, d_target), rows, cols, mask, shape=(images, H, W))
     assert rc == 0 and intact
     net.close()
-
-
-def ipfcns_params(w, seed):
-    """A seeded IPFCN-S with the layer statistics of tests/test_gpu_ipfcns.py."""
-    K, H, O = I.layer_dims(w)
-    rng = np.random.default_rng(seed)
-    s = (0.032 * np.sqrt(192 / K), 0.0188 * np.sqrt(512 / H), 0.0168 * np.sqrt(512 / H), 0.092 * np.sqrt(512 / H))
-    dims = (K, H, H, H, O)
-    parts = []
-    for l in range(4):
-        parts.append(rng.normal(0, s[l], dims[l + 1] * dims[l]))
-        parts.append(rng.normal(0, 0.02, dims[l + 1]))
-        if l < 3:
-            parts.append(rng.uniform(-0.3, 0.6, dims[l + 1]))
-    return np.concatenate(parts).astype(np.float32)
 
 
 # the reference lines start at (row + w - 8, col + w - 8): at w = 4 the nearest corner a context may have is (4, 4), not (0, 0)

@@ -13,6 +13,7 @@ from context_adaptive_neural_network_based_prediction_amd import _lib, evaluatio
 from context_adaptive_neural_network_based_prediction_amd import intraprediction as ip
 from context_adaptive_neural_network_based_prediction_amd import ipfcns as I
 from tests import util
+from tests.util import assert_same_dictionary, dev, ipfcns_params, pictures, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -21,28 +22,6 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 PNN_E_ARG = -1                       # include/pnn_hip.h
 OUTPUTS = ("targets", "pnn_u8", "pnn_f32", "pnn_sse", "hevc_mode", "hevc_sse", "hevc_pred")
 POSITIONS = ((0, 0), (9, 14), (5, 3))              # the near corner, the far one (odd, no multiple of 4), one in between
-
-
-def pictures(n_images, H, W, seed):
-    """Seeded pictures with structure (so that the modes differ) and noise (so that no two blocks agree)."""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    out = []
-    for _ in range(n_images):
-        f = rng.uniform(0.02, 0.2, 4)
-        img = 128 + 60 * np.sin(f[0] * xx + f[1] * yy) + 40 * np.cos(f[2] * xx - f[3] * yy) + rng.normal(0, 6, (H, W))
-        out.append(np.clip(img, 0, 255))
-    return np.array(out).astype(np.uint8)
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def guarded(n, w):
@@ -86,17 +65,6 @@ def make_net(w, kind, batch):
         return P.PredictionNeuralNetwork(batch, w, False, path_to_model=os.path.join(GOLD, "conv%d_single.pnnw" % w))
     is_fc = kind == "fc"
     return P.PredictionNeuralNetwork(batch, w, is_fc, params=util.make_params(w, is_fc, seed=40 + w, out_gain=util.out_gain(w, is_fc)))
-
-
-def assert_same_dictionary(got, want, label):
-    assert set(got) == set(want), label
-    for key, v in want.items():
-        g = got[key]
-        if isinstance(v, np.ndarray):
-            assert isinstance(g, np.ndarray) and g.dtype == v.dtype and g.shape == v.shape, (label, key)
-            assert g.tobytes() == v.tobytes(), "%s %s: %d differing values" % (label, key, (g != v).sum())
-        else:
-            assert type(g) is type(v) and g == v, (label, key, g, v)
 
 
 CASES = [("trained", 4, ((0, 0), (4, 0), (0, 4), (4, 4))),
@@ -305,21 +273,6 @@ def test_split_precision_mode():
     np.testing.assert_array_equal(sp[1], want)
     np.testing.assert_array_equal(sp[3], ((want.astype(np.int64) - sp[0]) ** 2).sum(axis=(1, 2)))
     net.close()
-
-
-def ipfcns_params(w, seed):
-    """The seeded IPFCN-S of tests/test_gpu_ipfcns.py."""
-    K, H, O = I.layer_dims(w)
-    rng = np.random.default_rng(seed)
-    s = (0.032 * np.sqrt(192 / K), 0.0188 * np.sqrt(512 / H), 0.0168 * np.sqrt(512 / H), 0.092 * np.sqrt(512 / H))
-    dims = (K, H, H, H, O)
-    parts = []
-    for l in range(4):
-        parts.append(rng.normal(0, s[l], dims[l + 1] * dims[l]))
-        parts.append(rng.normal(0, 0.02, dims[l + 1]))
-        if l < 3:
-            parts.append(rng.uniform(-0.3, 0.6, dims[l + 1]))
-    return np.concatenate(parts).astype(np.float32)
 
 
 def test_ipfcns_keys_at_no_mask_only():

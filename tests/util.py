@@ -1,4 +1,7 @@
-"""Shared helpers of the test-suite: seeded weights, synthetic contexts, planes and HM-style flags."""
+"""Shared helpers of the test-suite: seeded weights, synthetic contexts, planes and HM-style flags; seeded pictures, device
+uploads and dictionary comparison for the evaluator's GPU tests (torch is imported where it is needed: CPU tests import this)."""
+import ctypes
+
 import numpy as np
 
 from context_adaptive_neural_network_based_prediction_amd import weights as wts
@@ -79,3 +82,76 @@ def make_tbs(plane_h, plane_w, w, n, seed, partial_fraction=0.3, holes=False):
                 if k_above:
                     flags[i, 2 * units + 1 - k_above:] = 0
     return xs.astype(np.int32), ys.astype(np.int32), flags
+
+
+def _structured(rng, n_images, H, W):
+    yy, xx = np.mgrid[0:H, 0:W]
+    out = []
+    for _ in range(n_images):
+        f = rng.uniform(0.02, 0.2, 4)
+        img = 128 + 60 * np.sin(f[0] * xx + f[1] * yy) + 40 * np.cos(f[2] * xx - f[3] * yy) + rng.normal(0, 6, (H, W))
+        out.append(np.clip(img, 0, 255))
+    return np.array(out)
+
+
+def pictures(n_images, H, W, seed):
+    """Seeded uint8 pictures [images, H, W] with structure (so that the modes differ) and noise (so that no two blocks agree)."""
+    return _structured(np.random.default_rng(seed), n_images, H, W).astype(np.uint8)
+
+
+def picture_pairs(n_images, w, seed):
+    """[images, 3w + 5, 3w + 9, 2] uint8: channel 0 seeded pictures with structure and noise, channel 1 a "decoded" version built
+    from it -- every pixel moved by 3 .. 12 levels towards mid-grey, so the two differ at every pixel and stay inside [0, 255]."""
+    rng = np.random.default_rng(seed)
+    original = _structured(rng, n_images, 3 * w + 5, 3 * w + 9).astype(np.int64)
+    shift = rng.integers(3, 13, original.shape)
+    decoded = np.where(original < 128, original + shift, original - shift)
+    pair = np.stack([original, decoded], axis=-1).astype(np.uint8)
+    assert (pair[..., 0] != pair[..., 1]).all()
+    return pair
+
+
+POSITIONS = ((0, 0), (5, 9), (2, 5))               # of picture_pairs: the near corner, the far one (H - 3w, W - 3w), one in between
+
+
+def positions(which=POSITIONS):
+    return np.array([p[0] for p in which], np.int64), np.array([p[1] for p in which], np.int64)
+
+
+def ipfcns_params(w, seed, gain=1.0):
+    """Seeded IPFCN-S weights: N(0, s_l) with s = (0.032 sqrt(192/K), 0.0188 sqrt(512/H), 0.0168 sqrt(512/H), 0.092 sqrt(512/H)),
+    biases N(0, 0.02), slopes U(-0.3, 0.6); `gain` scales fc4."""
+    from context_adaptive_neural_network_based_prediction_amd import ipfcns as I
+    K, H, O = I.layer_dims(w)
+    rng = np.random.default_rng(seed)
+    s = (0.032 * np.sqrt(192 / K), 0.0188 * np.sqrt(512 / H), 0.0168 * np.sqrt(512 / H), 0.092 * np.sqrt(512 / H) * gain)
+    dims = (K, H, H, H, O)
+    parts = []
+    for l in range(4):
+        parts.append(rng.normal(0, s[l], dims[l + 1] * dims[l]))
+        parts.append(rng.normal(0, 0.02, dims[l + 1]))
+        if l < 3:
+            parts.append(rng.uniform(-0.3, 0.6, dims[l + 1]))
+    return np.concatenate(parts).astype(np.float32)
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def stream():
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def assert_same_dictionary(got, want, label):
+    """Same keys; arrays equal in dtype, shape and bytes; everything else equal in type and value."""
+    assert set(got) == set(want), label
+    for key, v in want.items():
+        g = got[key]
+        if isinstance(v, np.ndarray):
+            assert isinstance(g, np.ndarray) and g.dtype == v.dtype and g.shape == v.shape, (label, key)
+            assert g.tobytes() == v.tobytes(), "%s %s: %d differing values" % (label, key, (g != v).sum())
+        else:
+            assert type(g) is type(v) and g == v, (label, key, g, v)
