@@ -3,6 +3,7 @@
 //   pnn_tiles.cpp   rule-based choice of the kernel family / tile configuration of a tap GEMM
 //   pnn_tuner.cpp   on-device choice among the legal configurations, remembered per (layer, M)
 //   pnn_passes.cpp  the launch sequences of one pass of the fully-connected / convolutional nets
+//   pnn_diag.cpp    the diagnostic switches of the environment and the stamp read-backs of the diagnostic library
 //   pnn_abi.cpp     contexts, staging, the prediction cache and the extern "C" entry points of the predictor
 //   pnn_eval.cpp    the extern "C" entry points of the Python evaluator (HEVC modes, IPFCN-S, scores from pictures)
 #pragma once
@@ -321,8 +322,18 @@ inline DoneSignal take_done_signal_per_wg(pnn_ctx* c, int nwg)
 }
 int tuned_cfg(pnn_ctx* c, const void* key, long M, int ncodes, int rule, const std::function<bool(int)>& legal,
               const std::function<hipError_t(int)>& launch, hipStream_t s, int* cfg, float* best_us);
-// pnn_passes.cpp
+// pnn_diag.cpp: the environment switches (each read once) and, for the diagnostic library (make diag), the stamp read-backs of a
+// launch whose parameters the pass layer has bound
+bool env_debug();
+bool env_profile();
+bool env_f32s_diag();
+bool env_f32_diag();
+bool env_sp_diag();
 void* diag_stamp_slot(pnn_ctx* c, const char* name, long wgs, double k);
+int diag_f32_small(pnn_ctx* c, const GemmLayer& L, const TapGemmParams& ps, int nseg, const float* host_rows, hipStream_t s);
+int diag_f32_tiles(pnn_ctx* c, const GemmLayer& L, const TapGemmParams& p, int tile, bool fused, int par_segs, hipStream_t s);
+int diag_sp(pnn_ctx* c, const GemmLayer& L, const TapGemmParams& p, int cfg, hipStream_t s);
+// pnn_passes.cpp
 long chunk_blocks(const pnn_ctx* c, const Model* m);
 bool pass_uses_split(const pnn_ctx* c, const Model* m, long nb);
 bool conv_pass_fuses_first(pnn_ctx* c, Model* m, long nb);

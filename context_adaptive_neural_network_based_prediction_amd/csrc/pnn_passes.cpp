@@ -13,20 +13,16 @@
 
 namespace pnn {
 
-// Diagnostic library only (make diag) under PNN_B1_STAMPS: the next kernel's slot of per-workgroup 100 MHz stamps (host_predict prints
-// them), or null.  64 bytes per workgroup: [3] loop start, [4] entry, [5] exit (behind the acknowledged stores), [1] loop ticks.
-void* diag_stamp_slot(pnn_ctx* c, const char* name, long wgs, double k)
-{
-    if (!c->diag_stamps || c->diag_launch >= pnn_ctx::kDiagLaunches || wgs > pnn_ctx::kDiagWgs) return nullptr;
-    c->diag_names.push_back(name);
-    c->diag_wgs.push_back((int)wgs);
-    c->diag_k.push_back(k);
-    return (char*)c->diag_stamps + (size_t)c->diag_launch++ * pnn_ctx::kDiagWgs * 64;
-}
-
 namespace {
 
-// One tap-GEMM launch of kernel family `kind` (pnn_launch_times), counted in the call's statistics (pnn_last_call_stats).  Under
+// One tap-GEMM launch in the call's statistics (pnn_last_call_stats)
+void count_gemm(pnn_ctx* c, double flops)
+{
+    c->stat_gemm_launches++; c->stat_launches++;
+    c->stat_gemm_flops += flops;
+}
+
+// One tap-GEMM launch of kernel family `kind` (pnn_launch_times), counted in the call's statistics.  Under
 // "time_launches" -- or PNN_PROFILE where the caller passes `profile` -- the launch itself records HIP events around its kernel
 // (g_launch_events): kept for pnn_launch_times, or, under PNN_PROFILE, waited for and printed as `fmt` with `args`, then the time in
 // microseconds and the TFLOP/s (the [pnn-prof] lines tools/conv_layers.py reads).
@@ -56,37 +52,224 @@ int timed_launch(pnn_ctx* c, int kind, double flops, bool profile, Launch&& laun
     } else {
         HIPCHK(c, launch());
     }
-    c->stat_gemm_launches++; c->stat_launches++;
-    c->stat_gemm_flops += flops;
+    count_gemm(c, flops);
     return PNN_OK;
 }
 
+// The ONE binding of a layer's launch parameters to a pass of nblocks: *p = the layer's prototype with M and x_bytes, both inside
+// their bounds (`noun`: what the caller's message calls the input, "tensor" or "plane").
+int bind_layer(pnn_ctx* c, const GemmLayer& L, long nblocks, const char* noun, TapGemmParams* p)
+{
+    *p = L.proto;
+    const long M = nblocks * p->SH * p->SW;
+    if (M > 0x7fffffffL) return fail(c, PNN_E_ARG, "batch too large for one pass");
+    p->M = (int)M;
+    const double xb = 4.0 * (double)nblocks * p->IH * p->IW * p->Cin;
+    if (xb >= 2147483648.0) return fail(c, PNN_E_ARG, "activation %s of %.0f bytes exceeds the 2 GiB descriptor bound", noun, xb);
+    p->x_bytes = (unsigned)xb;
+    return PNN_OK;
+}
+
+// A segmented ONE-TAP layer (FC, GemmLayer::fc_seg_chunks): folded inside the workgroups at every batch size, never planes
+bool fc_segmented(const GemmLayer& L) { return L.fc_seg_chunks > 0 && L.nseg > 1; }
+
 // Would run_gemm send this layer (nb blocks, no fused next layer) to the small exact-f32 kernels?  The ONE statement of that rule:
 // run_gemm decides by it, and the passes by it which tensors travel in chain order (both ends on those kernels, pnn_gemm_f32_small.hip).
-bool f32_small_applies(const pnn_ctx* c, const GemmLayer& L, long nb, bool has_next, bool has_yi)
+bool f32_small_applies(pnn_ctx* c, const GemmLayer& L, long nb, bool has_next, bool has_yi)
 {
-    static const bool big_diag = getenv("PNN_F32_DIAG") != nullptr;
-    if (has_next || !c->opt_f32_small || c->opt_f32_cfg >= 0 || big_diag) return false;
-    TapGemmParams p = L.proto;
-    const long M = nb * p.SH * p.SW;
-    if (M > 0x7fffffffL) return false;
-    p.M = (int)M;
-    if (L.fc_seg_chunks > 0 && L.nseg > 1) {
+    if (has_next || !c->opt_f32_small || c->opt_f32_cfg >= 0 || env_f32_diag()) return false;
+    TapGemmParams p;
+    if (bind_layer(c, L, nb, "tensor", &p)) return false;   // (run_gemm refuses the layer with the same words)
+    if (fc_segmented(L)) {
         p.nseg = L.nseg; p.seg_chunks = (unsigned)L.fc_seg_chunks;
         return fcseg_f32_small_fits(p) && fcseg_f32_small_tiles(p) <= c->opt_f32_small_tiles;
     }
     p.nseg = (!has_yi && L.nseg > 1) ? L.nseg : 1;
     return tapgemm_f32_small_tiles(p) <= c->opt_f32_small_tiles;
 }
+
+// K segments of a layer on the small exact-f32 kernel (p bound, p.nseg = its segments): does the launch add its planes up itself
+// (the tile's last workgroup to arrive, tapgemm_f32_small_body) -- or a seg_reduce launch behind it?  The ONE statement of that rule.
+bool launch_folds_segments(const pnn_ctx* c, const TapGemmParams& p)
+{
+    return p.nseg > 1 && c->opt_seg_fold && c->d_seg_cnt && !c->opt_time_launches && tapgemm_f32_small_tiles(p) / p.nseg <= pnn_ctx::kSegCntTiles;
+}
+
 // ... and may its OUTPUT be written in chain order?  (a K-segmented layer only when its planes are added up inside the launch: the
 // seg_reduce kernel writes channel order)
-bool f32_small_chain_out_ok(const pnn_ctx* c, const GemmLayer& L, long nb)
+bool f32_small_chain_out_ok(pnn_ctx* c, const GemmLayer& L, long nb)
 {
     if (!c->opt_chain_io || L.proto.Cout % 16) return false;
     if (L.nseg <= 1 || L.fc_seg_chunks > 0) return true;
-    TapGemmParams p = L.proto;
-    p.M = (int)(nb * p.SH * p.SW); p.nseg = L.nseg;
-    return c->opt_seg_fold && c->d_seg_cnt && tapgemm_f32_small_tiles(p) / L.nseg <= pnn_ctx::kSegCntTiles && !c->opt_time_launches;
+    TapGemmParams p;
+    if (bind_layer(c, L, nb, "tensor", &p)) return false;
+    p.nseg = L.nseg;
+    return launch_folds_segments(c, p);
+}
+
+// Which half of the per-stream resources (seg_part, the tiles' counters) a launch on stream s uses: 1 = the side stream's
+int stream_slot(const pnn_ctx* c, hipStream_t s) { return (c->side_stream && s == c->side_stream) ? 1 : 0; }
+
+// Points p at nseg PARALLEL planes of partial sums in sb (out_floats each): raw sums, no bias, no activation -- a second launch, or
+// the folded form below, finishes them
+int seg_planes(pnn_ctx* c, TapGemmParams& p, int nseg, size_t out_floats, DevBuf& sb)
+{
+    int rc;
+    if ((rc = dev_reserve(c, sb, (size_t)nseg * out_floats * 4))) return rc;
+    if (out_floats >= 0xffffffffull) return fail(c, PNN_E_ARG, "batch too large for one pass");
+    p.Y = (float*)sb.p; p.bias = (const float*)c->d_zero; p.act = 0; p.nseg = nseg; p.seg_stride = (unsigned)out_floats;
+    return PNN_OK;
+}
+
+// ... and switches it to the FOLDED form (launch_folds_segments): tile-major planes, 1 KiB per (segment, tile), the counters of half
+// `slot`, and the layer's real output Y, bias and activation for the workgroup that adds the planes up
+int seg_planes_folded(pnn_ctx* c, TapGemmParams& p, const GemmLayer& L, float* Y, DevBuf& sb, int slot)
+{
+    int rc;
+    if ((rc = dev_reserve(c, sb, (size_t)tapgemm_f32_small_tiles(p) * 1024))) return rc;
+    p.Y = (float*)sb.p;
+    p.seg_cnt = c->d_seg_cnt + slot * pnn_ctx::kSegCntTiles;
+    p.seg_Y = Y; p.bias = L.d_bias; p.act = L.proto.act;
+    return PNN_OK;
+}
+
+// Zeroes the arrival counters of tiles and tails before a launch on stream s that counts on them, if a failure may have left them
+// standing (pnn_ctx::seg_cnt_dirty).  sync_for_side: the other branch's launches use the second half on the side stream.
+int clear_tail_counters(pnn_ctx* c, hipStream_t s, bool sync_for_side)
+{
+    if (!c->seg_cnt_dirty) return PNN_OK;
+    HIPCHK(c, hipMemsetAsync(c->d_seg_cnt, 0, pnn_ctx::kCntWords * 4, s));
+    if (sync_for_side && c->side_stream && s != c->side_stream) HIPCHK(c, hipStreamSynchronize(s));
+    c->seg_cnt_dirty = false;
+    return PNN_OK;
+}
+
+// run_gemm, a K-segmented FC layer of few tiles: fcseg_f32_small_kernel, the segments as chains side by side
+int gemm_fcseg_small(pnn_ctx* c, const GemmLayer& L, const TapGemmParams& p, double flops, int chain_io, hipStream_t s)
+{
+    const long M = p.M;
+    TapGemmParams ps = p;
+    ps.Wp = L.d_w_ch;                                 // the weights in the chain waves' lane order
+    ps.chain_io = chain_io;
+    if (env_debug()) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d nseg=%d -> f32 small kernel, %d K segments side by side (%ld tiles of 16 x 16)\n", M, L.k_total, p.Cout, L.nseg, L.nseg, fcseg_f32_small_tiles(p));
+    if (void* slot = diag_stamp_slot(c, "fcseg_f32_small", fcseg_f32_small_tiles(p), L.k_total)) ps.Xlo = slot;   // (diagnostic library, PNN_B1_STAMPS)
+    return timed_launch(c, 6, flops, env_profile(), [&] { return launch_fcseg_f32_small(ps, s); },
+                        "[pnn-prof] M=%ld K=%.0f N=%d nseg=%d f32-small-fcseg us=%.1f tflops=%.2f\n", M, L.k_total, p.Cout, L.nseg);
+}
+
+// run_gemm, few output tiles: tapgemm_f32_small_kernel.  p: bound, pointing at parallel planes when nseg > 1; Y the layer's real output
+int gemm_small(pnn_ctx* c, const GemmLayer& L, const TapGemmParams& p, float* Y, int nseg, long nblocks, double flops, hipStream_t s,
+               const float* host_rows, int chain_io, const SmallTail* tail, bool* tail_ran)
+{
+    const long M = p.M;
+    const bool debug = env_debug(), profile = env_profile();
+    TapGemmParams ps = p;
+    ps.Wp = L.d_w_ch;                                 // the same weights in the small kernel's lane order
+    ps.chain_io = chain_io;
+    if ((chain_io & 1) && host_rows) host_rows = nullptr;   // (the argument-block input is the caller's raw context: never in chain order)
+    // K segments: added up by the launch itself (the tile's last workgroup to arrive) when the tiles have counters
+    const bool fold = nseg > 1 && launch_folds_segments(c, p);
+    if (fold) {
+        int rc;
+        if ((rc = clear_tail_counters(c, s, true))) return rc;
+        if ((rc = seg_planes_folded(c, ps, L, Y, c->seg_part[stream_slot(c, s)], stream_slot(c, s)))) return rc;
+    }
+    if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d ncls=%d nseg=%d -> f32 small kernel (%ld tiles of 16 x 16)\n", M, L.k_total, p.Cout, p.ncls, nseg, tapgemm_f32_small_tiles(p));
+    if (void* slot = diag_stamp_slot(c, "tapgemm_f32_small", tapgemm_f32_small_tiles(p), L.k_total)) ps.Xlo = slot;   // (diagnostic library, PNN_B1_STAMPS)
+    // the net's last layer as this launch's tail (SmallTail kind 2): per block, by the last of the block's tiles to arrive; never timed
+    const bool with_tail = !profile && !c->opt_time_launches && tail && tail_ran && nseg == 1 && !(chain_io & 2) && f32_small_cout1_tail_ok(ps, tail->t);
+    if (with_tail && debug) fprintf(stderr, "[pnn]   ... with the last transposed convolution as its tail\n");
+    const int rc = timed_launch(c, 6, flops, profile, [&] {
+        return with_tail ? launch_tapgemm_f32_small_tail(ps, *tail, s, (int)c->opt_f32_small_deep)
+                         : launch_tapgemm_f32_small(ps, s, host_rows, (int)c->opt_f32_small_deep);
+    }, "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d f32-small us=%.1f tflops=%.2f\n", M, L.k_total, p.Cout, p.ncls);
+    if (rc) return rc;
+    if (with_tail) *tail_ran = true;
+    if (nseg > 1 && !fold) {
+        if (chain_io & 2) return fail(c, PNN_E_ARG, "internal: chain-order output of a layer whose K segments are reduced by a second launch");
+        HIPCHK(c, launch_seg_reduce(p.Y, nseg, (size_t)nblocks * (size_t)L.out_per_block, p.Cout, L.d_bias, L.proto.act, Y, s));
+        c->stat_launches++;
+    }
+    return env_f32s_diag() ? diag_f32_small(c, L, ps, nseg, host_rows, s) : PNN_OK;   // (diagnostic library only)
+}
+
+// run_gemm, the big tiles of tapgemm_f32_kernel: the rule's configuration or the tuner's.  p: bound, pointing at parallel planes when
+// nseg > 1; pseq: the sequential form of the same segments (the real Y, bias and activation)
+int gemm_tiles(pnn_ctx* c, const GemmLayer& L, TapGemmParams& p, const TapGemmParams& pseq, float* Y, int nseg, long nblocks, double flops,
+               hipStream_t s, const GemmLayer* next, float* part, int* tiles_out)
+{
+    const long M = p.M;
+    const bool debug = env_debug(), fcseg = fc_segmented(L);
+    const bool one_tap = (L.k_total == (double)p.Cin);
+    const int cpt = p.Cin / 16;
+    const size_t out_floats = (size_t)nblocks * (size_t)L.out_per_block;
+    // Configuration codes of a segmented layer: [0, ntile) = parallel on tile code, [ntile, 2 ntile) = sequential on tile code - ntile.
+    const int ntile = tapgemm_f32_num_cfgs();
+    if (next) { p.W2p = next->d_w; p.Npad2 = next->proto.Npad; p.K2chunks = next->proto.chunk_begin[1]; p.part = part; }
+    const long seg_mode = c->opt_f32_seg_mode;
+    auto legal = [&](int code) {
+        if (code >= ntile && (nseg == 1 || seg_mode == 0)) return false;
+        if (code < ntile && nseg > 1 && seg_mode == 1) return false;
+        const TileCfg t = tapgemm_f32_cfg(code % ntile);
+        if (fcseg && L.fc_seg_chunks % (2 * t.kc)) return false;  // an even number of whole stages per segment (tapgemm_f32_kernel, SEQ = 2)
+        if (fcseg && t.rt * t.nt >= 8) return false;              // ... and room for the running total beside the accumulators (the 256 x 128 tile spills)
+        return (one_tap || cpt % t.kc == 0) && (!next || tapgemm_f32_can_fuse(code % ntile));
+    };
+    float* const Yreal = Y;
+    const float* const bias_real = L.d_bias;
+    const int act_real = L.proto.act;
+    std::function<hipError_t(int)> launch = [&, p, pseq, Yreal, bias_real, act_real, fcseg](int code) {
+        if (code >= ntile) return launch_tapgemm_f32(pseq, code - ntile, false, s);
+        const hipError_t e = launch_tapgemm_f32(p, code, next != nullptr, s);
+        if (e != hipSuccess || p.nseg <= 1 || fcseg) return e;
+        return launch_seg_reduce(p.Y, p.nseg, out_floats, p.Cout, bias_real, act_real, Yreal, s);
+    };
+    double cost_par = 0, cost_seq = 0;
+    int cfg = choose_cfg_f32(c, M, p.Cout, p.ncls * nseg, p.Cin, L.k_total, next != nullptr, &cost_par);
+    if (cfg < 0) return fail(c, PNN_E_ARG, "no tapgemm_f32 tile fits a layer with %d-deep taps", p.Cin);
+    if (fcseg && !legal(cfg)) {                       // the rule knows nothing of the segments' stage count: the same tile with the legal stage depth, else any legal one
+        const TileCfg want = tapgemm_f32_cfg(cfg);
+        int alt = -1;
+        for (int i = 0; i < ntile; i++) if (legal(i) && (alt < 0 || (tapgemm_f32_cfg(i).rt == want.rt && tapgemm_f32_cfg(i).nt == want.nt))) alt = i;
+        if (alt < 0) return fail(c, PNN_E_ARG, "no tapgemm_f32 tile fits K segments of %d chunks", L.fc_seg_chunks);
+        cfg = alt;
+    }
+    if (nseg > 1) {
+        // the planes cost a write and a read of nseg x the output and a launch (in cycles at 2.4 GHz, ~4 TB/s through L2 / MALL)
+        cost_par += (double)(nseg + 1) * (double)out_floats * 4.0 / 4.0e12 * 2.4e9 + 9000.0;
+        const int cs = choose_cfg_f32(c, M, p.Cout, p.ncls, p.Cin, L.k_total, false, &cost_seq);
+        if (seg_mode == 1 || (seg_mode < 0 && cs >= 0 && cost_seq < cost_par)) cfg = ntile + cs;
+    }
+    bool tune = c->opt_f32_cfg < 0 && (c->opt_autotune == 1 || (c->opt_autotune == 2 && flops >= 4.0e9));
+    if (tune) {                                       // never while the caller's stream is being captured into a hipGraph
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) tune = false;
+    }
+    if (tune) {
+        const void* key = (const void*)((const char*)&L + 8 + (next ? 1 : 0));   // offsets 0-7: the split-precision launches of this layer
+        float best_us = -1.f;
+        const int rule = cfg;
+        const int trc = tuned_cfg(c, key, M, nseg > 1 ? 2 * ntile : ntile, rule, legal, launch, s, &cfg, &best_us);
+        if (trc) return trc;
+        if (best_us >= 0.f && debug) {
+            const TileCfg tb = tapgemm_f32_cfg(cfg % ntile), th = tapgemm_f32_cfg(rule % ntile);
+            fprintf(stderr, "[pnn] f32 autotune M=%ld K=%.0f N=%d ncls=%d nseg=%d: best {%d,%d,%d}%s %.1f us (rule {%d,%d,%d}%s)\n", M, L.k_total, p.Cout, p.ncls, nseg,
+                    tb.rt, tb.nt, tb.kc, cfg >= ntile ? " seq" : "", best_us, th.rt, th.nt, th.kc, rule >= ntile ? " seq" : "");
+        }
+    }
+    const bool seq = nseg > 1 && cfg >= ntile;
+    const TileCfg t = tapgemm_f32_cfg(cfg % ntile);
+    if (tiles_out) *tiles_out = (int)((p.Cout + 32L * t.nt - 1) / (32L * t.nt));
+    if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d ncls=%d -> f32 cfg %d {rt %d, nt %d, kc %d}%s%s\n", M, L.k_total, p.Cout, p.ncls,
+                       cfg, t.rt, t.nt, t.kc, next ? " + fused output layer" : "",
+                       nseg > 1 ? (seq ? ", K segments in sequence" : ", K segments in parallel + reduce") : "");
+    const int trc = timed_launch(c, 0, flops, env_profile(), [&] { return launch(cfg); },
+                                 "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d f32 cfg=%d rt=%d nt=%d kc=%d mf=%d us=%.1f tflops=%.1f\n", M, L.k_total,
+                                 p.Cout, p.ncls, cfg, t.rt, t.nt, t.kc, t.mf);
+    if (trc) return trc;
+    if (nseg > 1 && !seq) c->stat_launches++;          // the reduction of the parallel form (launched by `launch`)
+    c->stat_gemm_flops_skipped += flops * (1.0 - g_last_issued_frac);
+    return env_f32_diag() ? diag_f32_tiles(c, L, seq ? pseq : p, cfg % ntile, next != nullptr, seq ? 1 : nseg, s) : PNN_OK;   // (diagnostic library only)
 }
 
 // Exact-f32 launch.  `next` (optional): the net's output layer (<= 64 outputs) applied to this layer's activated tile inside the
@@ -94,217 +277,43 @@ bool f32_small_chain_out_ok(const pnn_ctx* c, const GemmLayer& L, long nb)
 // their count, and the caller finishes with launch_fuse_reduce.  Y / Yi must be null in that case.
 // chain_io: bit 0 = X is in chain order, bit 1 = write Y in chain order (TapGemmParams::chain_io) -- only for a layer that
 // f32_small_applies() sends to the small kernels; anything else is the caller's mistake and refused.
+// This front binds the layer, plans its K segments and refuses what cannot run; gemm_fcseg_small / gemm_small / gemm_tiles launch.
 int run_gemm(pnn_ctx* c, const GemmLayer& L, const float* X, float* Y, int32_t* Yi, long nblocks, hipStream_t s,
              const GemmLayer* next = nullptr, float* part = nullptr, int* tiles_out = nullptr, const float* host_rows = nullptr, int chain_io = 0,
              const SmallTail* tail = nullptr, bool* tail_ran = nullptr)
 {
-    TapGemmParams p = L.proto;
+    TapGemmParams p;
+    int rc;
+    if ((rc = bind_layer(c, L, nblocks, "tensor", &p))) return rc;
     p.X = X; p.Wp = L.d_w; p.bias = L.d_bias; p.Y = Y; p.Yi = Yi; p.mean = c->mean;
-    const long M = nblocks * p.SH * p.SW;
-    if (M > 0x7fffffffL) return fail(c, PNN_E_ARG, "batch too large for one pass");
-    p.M = (int)M;
-    const double xb = 4.0 * (double)nblocks * p.IH * p.IW * p.Cin;
-    if (xb >= 2147483648.0) return fail(c, PNN_E_ARG, "activation tensor of %.0f bytes exceeds the 2 GiB descriptor bound", xb);
-    p.x_bytes = (unsigned)xb;
-    static const bool debug = getenv("PNN_DEBUG") != nullptr;
-    static const bool profile = getenv("PNN_PROFILE") != nullptr;   // tuning aid: per-launch timing, synchronous
-    const double flops = 2.0 * (double)M * L.k_total * p.Cout + (next ? 2.0 * (double)M * next->k_total * next->proto.Cout : 0.0);
+    const double flops = 2.0 * (double)p.M * L.k_total * p.Cout + (next ? 2.0 * (double)p.M * next->k_total * next->proto.Cout : 0.0);
     const bool one_tap = (L.k_total == (double)p.Cin);
-    const int cpt = p.Cin / 16;
-    constexpr bool f32k = true;                       // (until round 4 an option chose the round-1 kernels here)
-    int cfg = -1;
-    std::function<hipError_t(int)> launch;
     p.pm_groups = c->opt_ring_pm == 0 ? -1 : c->opt_ring_pm == 2 ? 1 : 0;   // position-major tiles: never / whenever possible / by the planner's model (launch_tapgemm_f32)
     // K segments (GemmLayer::nseg, the canonical order of the deep conv layers): the launch leaves nseg planes of partial sums, a
     // second launch adds them in order, + bias, activation
     // A segmented ONE-TAP layer (FC, GemmLayer::fc_seg_chunks) is folded inside the workgroups at every batch size -- no planes, so it may
     // carry the fused output layer or the HM epilogue: four chains side by side at small M, one after the other into a running total at batch
-    const bool fcseg = f32k && L.fc_seg_chunks > 0 && L.nseg > 1;
-    const int nseg = (f32k && !fcseg && !next && !Yi && L.nseg > 1) ? L.nseg : 1;
-    const size_t out_floats = (size_t)nblocks * (size_t)L.out_per_block;
-    if (f32k && !fcseg && L.nseg > 1 && nseg == 1) return fail(c, PNN_E_ARG, "a K-segmented layer cannot carry the HM epilogue or a fused output layer");
+    const bool fcseg = fc_segmented(L);
+    const int nseg = (!fcseg && !next && !Yi && L.nseg > 1) ? L.nseg : 1;
+    if (!fcseg && L.nseg > 1 && nseg == 1) return fail(c, PNN_E_ARG, "a K-segmented layer cannot carry the HM epilogue or a fused output layer");
     if (fcseg) { p.nseg = L.nseg; p.seg_chunks = (unsigned)L.fc_seg_chunks; p.seg_seq = 1; }
     // Two forms with the same bits: PARALLEL segments (grid z = class x segment, planes of partial sums + seg_reduce_kernel: more,
     // shorter workgroups -- what a launch that does not fill the chip needs) and SEQUENTIAL ones (each workgroup runs its segments
     // one after the other and folds them into a running total: no planes, no second launch -- what a big launch wants).
-    // Configuration codes of a segmented layer: [0, ntile) = parallel on tile code, [ntile, 2 ntile) = sequential on tile code - ntile.
-    const int ntile = tapgemm_f32_num_cfgs();
     p.persist = (next || one_tap) ? 0 : (int)c->opt_f32_persist;   // persistent workgroups for the convolution layers, see launch_f32 (pnn_gemm_f32.hip)
     TapGemmParams pseq = p;                           // the sequential form: the real Y, bias and activation
     if (nseg > 1) {
         pseq.nseg = nseg; pseq.seg_seq = 1;
-        DevBuf& sb = c->seg_part[(c->side_stream && s == c->side_stream) ? 1 : 0];
-        int rrc;
-        if ((rrc = dev_reserve(c, sb, (size_t)nseg * out_floats * 4))) return rrc;
-        if (out_floats >= 0xffffffffull) return fail(c, PNN_E_ARG, "batch too large for one pass");
-        p.Y = (float*)sb.p; p.bias = (const float*)c->d_zero; p.act = 0; p.nseg = nseg; p.seg_stride = (unsigned)out_floats; p.seg_seq = 0;
+        if ((rc = seg_planes(c, p, nseg, (size_t)nblocks * (size_t)L.out_per_block, c->seg_part[stream_slot(c, s)]))) return rc;
+        p.seg_seq = 0;
     }
     // Few output tiles (the in-loop single-block calls, the batching service's handfuls): the same fmaf chain per output on the 16x16x4
     // instruction, one wave per 16 x 16 tile over all CUs (pnn_gemm_f32_small.hip) -- bit-identical, 3.2 x shorter dependent chain
-    const bool small_f32 = f32k && f32_small_applies(c, L, nblocks, next != nullptr, Yi != nullptr);
+    const bool small_f32 = f32_small_applies(c, L, nblocks, next != nullptr, Yi != nullptr);
     if (chain_io && !small_f32) return fail(c, PNN_E_ARG, "internal: chain-order activations for a layer that does not run on the small kernels");
-    if (fcseg && small_f32) {
-        TapGemmParams ps = p;
-        ps.Wp = L.d_w_ch;                             // the weights in the chain waves' lane order
-        ps.chain_io = chain_io;
-        if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d nseg=%d -> f32 small kernel, %d K segments side by side (%ld tiles of 16 x 16)\n", M, L.k_total, p.Cout, L.nseg, L.nseg, fcseg_f32_small_tiles(p));
-        if (void* slot = diag_stamp_slot(c, "fcseg_f32_small", fcseg_f32_small_tiles(p), L.k_total)) ps.Xlo = slot;   // (diagnostic library, PNN_B1_STAMPS)
-        return timed_launch(c, 6, flops, profile, [&] { return launch_fcseg_f32_small(ps, s); },
-                            "[pnn-prof] M=%ld K=%.0f N=%d nseg=%d f32-small-fcseg us=%.1f tflops=%.2f\n", M, L.k_total, p.Cout, L.nseg);
-    }
-    if (!fcseg && small_f32) {
-        TapGemmParams ps = p;
-        ps.Wp = L.d_w_ch;                             // the same weights in the small kernel's lane order
-        ps.chain_io = chain_io;
-        if ((chain_io & 1) && host_rows) host_rows = nullptr;   // (the argument-block input is the caller's raw context: never in chain order)
-        // K segments: added up by the launch itself (the tile's last workgroup to arrive) when the tiles have counters
-        const long seg_tiles = nseg > 1 ? tapgemm_f32_small_tiles(p) / nseg : 0;
-        const bool fold = nseg > 1 && c->opt_seg_fold && c->d_seg_cnt && seg_tiles <= pnn_ctx::kSegCntTiles && !c->opt_time_launches;
-        if (fold) {
-            if (c->seg_cnt_dirty) {                   // see pnn_ctx::seg_cnt_dirty
-                HIPCHK(c, hipMemsetAsync(c->d_seg_cnt, 0, pnn_ctx::kCntWords * 4, s));
-                if (c->side_stream && s != c->side_stream) HIPCHK(c, hipStreamSynchronize(s));   // (the other branch's launches use the second half on the side stream)
-                c->seg_cnt_dirty = false;
-            }
-            ps.seg_cnt = c->d_seg_cnt + ((c->side_stream && s == c->side_stream) ? pnn_ctx::kSegCntTiles : 0);
-            ps.seg_Y = Y; ps.bias = L.d_bias; ps.act = L.proto.act;
-            DevBuf& sb = c->seg_part[(c->side_stream && s == c->side_stream) ? 1 : 0];   // tile-major planes: 1 KiB per (segment, tile)
-            int rrc;
-            if ((rrc = dev_reserve(c, sb, (size_t)nseg * seg_tiles * 1024))) return rrc;
-            ps.Y = (float*)sb.p;
-        }
-        if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d ncls=%d nseg=%d -> f32 small kernel (%ld tiles of 16 x 16)\n", M, L.k_total, p.Cout, p.ncls, nseg, tapgemm_f32_small_tiles(p));
-        if (void* slot = diag_stamp_slot(c, "tapgemm_f32_small", tapgemm_f32_small_tiles(p), L.k_total)) ps.Xlo = slot;   // (diagnostic library, PNN_B1_STAMPS)
-        // the net's last layer as this launch's tail (SmallTail kind 2): per block, by the last of the block's tiles to arrive; never timed
-        const bool with_tail = !profile && !c->opt_time_launches && tail && tail_ran && nseg == 1 && !(chain_io & 2) && f32_small_cout1_tail_ok(ps, tail->t);
-        if (with_tail && debug) fprintf(stderr, "[pnn]   ... with the last transposed convolution as its tail\n");
-        const int rc = timed_launch(c, 6, flops, profile, [&] {
-            return with_tail ? launch_tapgemm_f32_small_tail(ps, *tail, s, (int)c->opt_f32_small_deep)
-                             : launch_tapgemm_f32_small(ps, s, host_rows, (int)c->opt_f32_small_deep);
-        }, "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d f32-small us=%.1f tflops=%.2f\n", M, L.k_total, p.Cout, p.ncls);
-        if (rc) return rc;
-        if (with_tail) *tail_ran = true;
-        if (nseg > 1 && !fold) {
-            if (chain_io & 2) return fail(c, PNN_E_ARG, "internal: chain-order output of a layer whose K segments are reduced by a second launch");
-            HIPCHK(c, launch_seg_reduce(p.Y, nseg, out_floats, p.Cout, L.d_bias, L.proto.act, Y, s));
-            c->stat_launches++;
-        }
-        static const bool sdiag = getenv("PNN_F32S_DIAG") != nullptr;   // diagnostic library only (make diag): the MFMA wave's loop, cycles per chunk and clock
-        if (sdiag) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (dev_reserve(c, c->stage_tbs, (size_t)4 << 20)) return PNN_E_NOMEM;
-            HIPCHK(c, hipMemset(c->stage_tbs.p, 0, (size_t)4 << 20));
-            TapGemmParams q = ps;
-            q.Xlo = c->stage_tbs.p;
-            HIPCHK(c, launch_tapgemm_f32_small(q, s, host_rows, (int)c->opt_f32_small_deep));
-            HIPCHK(c, hipStreamSynchronize(s));
-            const size_t nwg = std::min<size_t>((size_t)tapgemm_f32_small_tiles(p), ((size_t)4 << 20) / 64);
-            std::vector<unsigned long long> hbuf(8 * nwg);
-            HIPCHK(c, hipMemcpy(hbuf.data(), c->stage_tbs.p, hbuf.size() * 8, hipMemcpyDeviceToHost));
-            double cyc = 0, ticks = 0, chunks = 0;
-            unsigned long long r0 = ~0ull, r1 = 0;
-            for (size_t i = 0; i < nwg; i++) { cyc += (double)hbuf[8 * i]; ticks += (double)hbuf[8 * i + 1]; chunks += (double)hbuf[8 * i + 2]; r0 = std::min(r0, hbuf[8 * i + 3]); r1 = std::max(r1, hbuf[8 * i + 3] + hbuf[8 * i + 1]); }
-            fprintf(stderr, "[pnn-f32s-diag] M=%ld K=%.0f N=%d ncls=%d nseg=%d: %zu WGs, loop %.0f cycles for %.0f chunks = %.0f cycles per chunk (160 = the chain), %.2f us, clock %.0f MHz; first loop start -> last loop end %.1f us\n",
-                    M, L.k_total, p.Cout, p.ncls, nseg, nwg, cyc / nwg, chunks / nwg, cyc / std::max(1.0, chunks), ticks / nwg / 100.0, cyc / std::max(1.0, ticks) * 100.0, (double)(r1 - r0) / 100.0);
-        }
-        return PNN_OK;
-    }
-    if (f32k) {
-        if (next) { p.W2p = next->d_w; p.Npad2 = next->proto.Npad; p.K2chunks = next->proto.chunk_begin[1]; p.part = part; }
-        const long seg_mode = c->opt_f32_seg_mode;
-        auto legal = [&](int code) {
-            if (code >= ntile && (nseg == 1 || seg_mode == 0)) return false;
-            if (code < ntile && nseg > 1 && seg_mode == 1) return false;
-            const TileCfg t = tapgemm_f32_cfg(code % ntile);
-            if (fcseg && L.fc_seg_chunks % (2 * t.kc)) return false;  // an even number of whole stages per segment (tapgemm_f32_kernel, SEQ = 2)
-            if (fcseg && t.rt * t.nt >= 8) return false;              // ... and room for the running total beside the accumulators (the 256 x 128 tile spills)
-            return (one_tap || cpt % t.kc == 0) && (!next || tapgemm_f32_can_fuse(code % ntile));
-        };
-        float* const Yreal = Y;
-        const float* const bias_real = L.d_bias;
-        const int act_real = L.proto.act;
-        launch = [&, p, pseq, Yreal, bias_real, act_real, fcseg](int code) {
-            if (code >= ntile) return launch_tapgemm_f32(pseq, code - ntile, false, s);
-            const hipError_t e = launch_tapgemm_f32(p, code, next != nullptr, s);
-            if (e != hipSuccess || p.nseg <= 1 || fcseg) return e;
-            return launch_seg_reduce(p.Y, p.nseg, out_floats, p.Cout, bias_real, act_real, Yreal, s);
-        };
-        double cost_par = 0, cost_seq = 0;
-        cfg = choose_cfg_f32(c, M, p.Cout, p.ncls * nseg, p.Cin, L.k_total, next != nullptr, &cost_par);
-        if (cfg < 0) return fail(c, PNN_E_ARG, "no tapgemm_f32 tile fits a layer with %d-deep taps", p.Cin);
-        if (fcseg && !legal(cfg)) {                   // the rule knows nothing of the segments' stage count: the same tile with the legal stage depth, else any legal one
-            const TileCfg want = tapgemm_f32_cfg(cfg);
-            int alt = -1;
-            for (int i = 0; i < ntile; i++) if (legal(i) && (alt < 0 || (tapgemm_f32_cfg(i).rt == want.rt && tapgemm_f32_cfg(i).nt == want.nt))) alt = i;
-            if (alt < 0) return fail(c, PNN_E_ARG, "no tapgemm_f32 tile fits K segments of %d chunks", L.fc_seg_chunks);
-            cfg = alt;
-        }
-        if (nseg > 1) {
-            // the planes cost a write and a read of nseg x the output and a launch (in cycles at 2.4 GHz, ~4 TB/s through L2 / MALL)
-            cost_par += (double)(nseg + 1) * (double)out_floats * 4.0 / 4.0e12 * 2.4e9 + 9000.0;
-            const int cs = choose_cfg_f32(c, M, p.Cout, p.ncls, p.Cin, L.k_total, false, &cost_seq);
-            if (seg_mode == 1 || (seg_mode < 0 && cs >= 0 && cost_seq < cost_par)) cfg = ntile + cs;
-        }
-        bool tune = c->opt_f32_cfg < 0 && (c->opt_autotune == 1 || (c->opt_autotune == 2 && flops >= 4.0e9));
-        if (tune) {                                   // never while the caller's stream is being captured into a hipGraph
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) tune = false;
-        }
-        if (tune) {
-            const void* key = (const void*)((const char*)&L + 8 + (next ? 1 : 0));   // offsets 0-7: the split-precision launches of this layer
-            float best_us = -1.f;
-            const int rule = cfg;
-            const int trc = tuned_cfg(c, key, M, nseg > 1 ? 2 * ntile : ntile, rule, legal, launch, s, &cfg, &best_us);
-            if (trc) return trc;
-            if (best_us >= 0.f && debug) {
-                const TileCfg tb = tapgemm_f32_cfg(cfg % ntile), th = tapgemm_f32_cfg(rule % ntile);
-                fprintf(stderr, "[pnn] f32 autotune M=%ld K=%.0f N=%d ncls=%d nseg=%d: best {%d,%d,%d}%s %.1f us (rule {%d,%d,%d}%s)\n", M, L.k_total, p.Cout, p.ncls, nseg,
-                        tb.rt, tb.nt, tb.kc, cfg >= ntile ? " seq" : "", best_us, th.rt, th.nt, th.kc, rule >= ntile ? " seq" : "");
-            }
-        }
-        if (tiles_out) { const TileCfg t = tapgemm_f32_cfg(cfg % ntile); *tiles_out = (int)((p.Cout + 32L * t.nt - 1) / (32L * t.nt)); }
-    }
-    const bool seq = f32k && nseg > 1 && cfg >= ntile;
-    const TileCfg t = tapgemm_f32_cfg(cfg % ntile);
-    if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d ncls=%d -> %s cfg %d {rt %d, nt %d, kc %d}%s%s\n", M, L.k_total, p.Cout, p.ncls,
-                       f32k ? "f32" : "legacy", cfg, t.rt, t.nt, t.kc, next ? " + fused output layer" : "",
-                       nseg > 1 ? (seq ? ", K segments in sequence" : ", K segments in parallel + reduce") : "");
-    const int trc = timed_launch(c, 0, flops, profile, [&] { return launch(cfg); },
-                                 "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d %s cfg=%d rt=%d nt=%d kc=%d mf=%d us=%.1f tflops=%.1f\n", M, L.k_total,
-                                 p.Cout, p.ncls, f32k ? "f32" : "legacy", cfg, t.rt, t.nt, t.kc, t.mf);
-    if (trc) return trc;
-    if (nseg > 1 && !seq) c->stat_launches++;          // the reduction of the parallel form (launched by `launch`)
-    c->stat_gemm_flops_skipped += flops * (1.0 - g_last_issued_frac);
-    static const bool diag = getenv("PNN_F32_DIAG") != nullptr;     // diagnostic library only (make diag): per-workgroup cycle stamps
-    if (diag && f32k) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (dev_reserve(c, c->stage_tbs, (size_t)16 << 20)) return PNN_E_NOMEM;
-        TapGemmParams q = seq ? pseq : p;
-        if (next) { q.W2p = next->d_w; q.Npad2 = next->proto.Npad; q.K2chunks = next->proto.chunk_begin[1]; q.part = part; }
-        q.Xlo = c->stage_tbs.p;
-        HIPCHK(c, hipMemset(c->stage_tbs.p, 0, (size_t)16 << 20));
-        for (int rep = 0; rep < 400; rep++) HIPCHK(c, launch_tapgemm_f32(q, cfg % ntile, next != nullptr, s));   // back to back: the stamps that
-                                                                                           // stay are the last launch's, at the steady-state clock
-        HIPCHK(c, hipStreamSynchronize(s));
-        const size_t nwg = (size_t)((M + 128L * t.rt - 1) / (128L * t.rt)) * ((p.Cout + 32L * t.nt - 1) / (32L * t.nt)) * p.ncls * (seq ? 1 : nseg);
-        std::vector<unsigned long long> hbuf(8 * nwg);
-        HIPCHK(c, hipMemcpy(hbuf.data(), c->stage_tbs.p, hbuf.size() * 8, hipMemcpyDeviceToHost));
-        double sum[4] = {0, 0, 0, 0};
-        unsigned long long r0 = ~0ull, r1 = 0;
-        for (size_t i = 0; i < nwg; i++) {
-            for (int k = 0; k < 4; k++) sum[k] += (double)hbuf[8 * i + k];
-            r0 = std::min(r0, hbuf[8 * i + 4]); r1 = std::max(r1, hbuf[8 * i + 4] + hbuf[8 * i + 3]);
-        }
-        size_t late = 0; unsigned long long life_max = 0;     // workgroups that start > 5 us behind the first; the longest lifetime
-        for (size_t i = 0; i < nwg; i++) { late += hbuf[8 * i + 4] > r0 + 500; life_max = std::max(life_max, hbuf[8 * i + 3]); }
-        const double chunks = std::ceil(L.k_total / 16.0 / p.ncls / (seq ? 1 : nseg) / t.kc) * t.kc;
-        const double cyc = (sum[0] + sum[1] + sum[2]) / nwg, rt_ticks = sum[3] / nwg;
-        fprintf(stderr, "[pnn-f32diag] M=%ld K=%.0f N=%d {%d,%d,%d}%s: %zu WGs; wave 0 mean cycles: prologue %.0f  loop %.0f (MFMA work %.0f = %.3f)  epilogue %.0f;"
-                " lifetime %.1f us (max %.1f), in-kernel clock %.0f MHz; first start -> last end %.1f us, %zu workgroups start > 5 us late\n", M, L.k_total, p.Cout, t.rt, t.nt, t.kc, next ? "+out" : "", nwg,
-                sum[0] / nwg, sum[1] / nwg, chunks * 8 * t.rt * t.nt * 64, chunks * 8 * t.rt * t.nt * 64 / (sum[1] / nwg), sum[2] / nwg, rt_ticks / 100.0, (double)life_max / 100.0,
-                cyc / (rt_ticks / 100.0), (double)(r1 - r0) / 100.0, late);
-    }
-    return PNN_OK;
+    if (small_f32 && fcseg) return gemm_fcseg_small(c, L, p, flops, chain_io, s);
+    if (small_f32) return gemm_small(c, L, p, Y, nseg, nblocks, flops, s, host_rows, chain_io, tail, tail_ran);
+    return gemm_tiles(c, L, p, pseq, Y, nseg, nblocks, flops, s, next, part, tiles_out);
 }
 
 // `next` (optional): a following fully-connected layer with <= 64 outputs that the ring kernel applies to its output tile
@@ -327,37 +336,34 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
     // `first` (optional): the Cin = 1 convolution that produces this layer's input Xhi.  It has NOT been launched: a
     // convimg configuration computes it inside the kernel (no 50 MB round trip of the maps), any other configuration gets
     // it launched here in front of the GEMM.
-    TapGemmParams p = L.proto;
+    TapGemmParams p;
+    int brc;
+    if ((brc = bind_layer(c, L, nblocks, "plane", &p))) return brc;
+    const long M = p.M;
     if (next) {
         p.W2p = next->d_w_sp; p.Npad2 = next->proto.Npad; p.K2chunks = next->proto.chunk_begin[1]; p.part = part;
     }
     p.X = (const float*)Xhi; p.Xlo = Xlo; p.Wp = L.d_w_sp;
-    static const bool diag = getenv("PNN_SP_DIAG") != nullptr;   // diagnostic library only: phase stamps of every workgroup
+    const bool diag = env_sp_diag();                  // diagnostic library only: phase stamps of every workgroup
     if (diag) {
         if (dev_reserve(c, c->stage_tbs, (size_t)64 << 20)) return PNN_E_NOMEM;
         p.Xlo = c->stage_tbs.p;
-    } p.bias = L.d_bias; p.Y = Y; p.Yhi = Yhi; p.Ylo = Ylo; p.Yi = Yi;
+    }
+    p.bias = L.d_bias; p.Y = Y; p.Yhi = Yhi; p.Ylo = Ylo; p.Yi = Yi;
     p.mean = c->mean; p.out_scale = L.sp_inv_scale; p.range_flag = c->h_range;
     p.pm_groups = c->opt_ring_pm == 0 ? -1 : c->opt_ring_pm == 2 ? 1 : 0;   // ring kernel, position-major tiles: never / whenever possible / by its model (launch_tapgemm_ring)
-    const long M = nblocks * p.SH * p.SW;
-    if (M > 0x7fffffffL) return fail(c, PNN_E_ARG, "batch too large for one pass");
-    p.M = (int)M;
-    const double xb = 4.0 * (double)nblocks * p.IH * p.IW * p.Cin;
-    if (xb >= 2147483648.0) return fail(c, PNN_E_ARG, "activation plane of %.0f bytes exceeds the 2 GiB descriptor bound", xb);
-    p.x_bytes = (unsigned)xb;
     const int cpt = p.Cin / 16;
     const bool one_tap = (L.k_total == (double)p.Cin);
-    static const bool diag0 = getenv("PNN_SP_DIAG") != nullptr;
+    const bool debug = env_debug();
     // Few output tiles (the in-loop single-block calls, the batching service's handfuls): one wave per 32 x 32 tile over all
     // CUs instead of one or two big workgroups walking K alone.  Same per-output summation order: bit-identical.
-    const bool small = seg_chunks > 0 || (!next && !diag0 && c->opt_small && c->opt_sp_cfg < 0 && tapgemm_small_tiles(p) <= c->opt_small_tiles);
+    const bool small = seg_chunks > 0 || (!next && !diag && c->opt_small && c->opt_sp_cfg < 0 && tapgemm_small_tiles(p) <= c->opt_small_tiles);
     if (small && query_fuse_first) return PNN_OK;
     if (small) {
         if (seg_chunks > 0) p.part = part;
         if (first) { HIPCHK(c, launch_conv_cin1(*first, s)); c->stat_launches++; }
-        static const bool dbg = getenv("PNN_DEBUG") != nullptr;
-        if (dbg) fprintf(stderr, "[pnn] sp-gemm M=%ld K=%.0f N=%d ncls=%d -> small kernel (%ld tiles%s%s)\n", M, L.k_total, p.Cout, p.ncls,
-                         tapgemm_small_tiles(p), x_is_f32 ? ", f32 input" : "", seg_chunks ? ", K segments" : "");
+        if (debug) fprintf(stderr, "[pnn] sp-gemm M=%ld K=%.0f N=%d ncls=%d -> small kernel (%ld tiles%s%s)\n", M, L.k_total, p.Cout, p.ncls,
+                           tapgemm_small_tiles(p), x_is_f32 ? ", f32 input" : "", seg_chunks ? ", K segments" : "");
         const int trc = timed_launch(c, 5, 2.0 * (double)M * L.k_total * p.Cout, false,
                                      [&] { return launch_tapgemm_small(p, x_is_f32, seg_chunks, s, x_is_f32 ? c->host_input : nullptr); });
         if (trc) return trc;
@@ -397,10 +403,9 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
                     TapGemmParams q = p;
                     q.X0 = first->X; q.W0 = first->W; q.B0 = first->bias; q.s0 = first->s; q.k0 = first->k; q.pad0 = first->pad;
                     q.W0sp = first->Wsp; q.scale0 = first->out_scale; q.Npad0 = first->npad;
-                    if (!first->X && c->lazy.plane) {  // the gather fused in as well (pnn_predict_tbs_device decided so by query)
-                        q.plane0 = c->lazy.plane; q.tbs0 = c->lazy.tbs; q.pel0 = c->lazy.pel_bytes; q.unit0 = c->lazy.unit;
-                        q.branch0 = first->IH > first->IW ? 1 : 0;       // above portion w x 3w, left portion 2w x w
-                        q.w0 = q.branch0 ? first->IW : first->IH;
+                    if (first->plane) {               // the gather fused in as well (pnn_predict_tbs_device decided so by query; attach_plane)
+                        q.plane0 = first->plane; q.tbs0 = first->tbs; q.pel0 = first->pel_bytes; q.unit0 = first->unit;
+                        q.branch0 = first->branch; q.w0 = first->w;
                     }
                     return launch_convimg_sp(q, code - nsp, g, s);
                 }
@@ -442,14 +447,15 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
     // (~70 x 4 launches) costs a few tens of milliseconds and the choice is worth 10-20 %; 0 = rule-based choice only.
     // All configurations give bit-identical results, so the choice never shows in the predictions.
     bool tune = c->opt_autotune == 1 || (c->opt_autotune == 2 && 2.0 * (double)M * L.k_total * p.Cout >= 4.0e9);
-    if (tune && c->tuned.find(std::make_pair((const void*)((const char*)&L + (next ? 1 : 0) + (first ? 2 : 0) + (lastp ? 4 : 0)), M)) == c->tuned.end()) {
+    // what the tuner remembers this launch by: the layer's address + which of its neighbours ride along (offsets 0-7; run_gemm's start at 8)
+    const void* const key = (const void*)((const char*)&L + (next ? 1 : 0) + (first ? 2 : 0) + (lastp ? 4 : 0));
+    if (tune && c->tuned.find(std::make_pair(key, M)) == c->tuned.end()) {
         // timing configurations means synchronising on the caller's stream: never while that stream is being captured
         // into a hipGraph (the rule-based choice is used instead, nothing is remembered)
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) tune = false;
     }
     if (query_fuse_first) {
-        const void* key = (const void*)((const char*)&L + (next ? 1 : 0) + (first ? 2 : 0) + (lastp ? 4 : 0));
         int code = cfg;
         if (tune && c->opt_sp_cfg < 0) {
             auto it = c->tuned.find(std::make_pair(key, M));
@@ -463,7 +469,6 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
         return PNN_OK;
     }
     if (tune && c->opt_sp_cfg < 0) {
-        const void* key = (const void*)((const char*)&L + (next ? 1 : 0) + (first ? 2 : 0) + (lastp ? 4 : 0));
         const int rule = cfg;
         float best_us = -1.f;
         // The sweep launches every configuration several times; a last layer that carries the completion signal of a host call
@@ -475,7 +480,7 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
         const int trc = tuned_cfg(c, key, M, nsp + nci + nrg, rule, legal, launch, s, &cfg, &best_us);
         lastp = signalled;
         if (trc) return trc;
-        if (best_us >= 0.f && getenv("PNN_DEBUG")) {
+        if (best_us >= 0.f && debug) {
             const TileCfg tb = cfg_of(cfg), th = cfg_of(rule);
             fprintf(stderr, "[pnn] autotune M=%ld K=%.0f N=%d ncls=%d: best %s{%d,%d,%d,wm%d,d%d} %.1f us (heuristic %s{%d,%d,%d,wm%d,d%d})\n", M,
                     L.k_total, p.Cout, p.ncls, kind_of(cfg), tb.rt, tb.nt, tb.kc, tb.wm, tb.d, best_us, kind_of(rule), th.rt, th.nt,
@@ -487,32 +492,18 @@ int run_gemm_sp(pnn_ctx* c, const GemmLayer& L, const void* Xhi, const void* Xlo
         for (int i = nsp + nci; i < nsp + nci + nrg && cfg < 0; i++) if (legal(i)) cfg = i;
         if (cfg < 0) return fail(c, PNN_E_ARG, "no ring configuration can fuse the next layer");
     }
-    static const bool debug = getenv("PNN_DEBUG") != nullptr;
-    static const bool profile = getenv("PNN_PROFILE") != nullptr;
     const TileCfg t = cfg_of(cfg);
     if (debug) fprintf(stderr, "[pnn] sp-gemm M=%ld K=%.0f N=%d ncls=%d -> cfg %d %s{rt %d, nt %d, kc %d, wm %d, d %d}\n", M, L.k_total, p.Cout, p.ncls,
                        cfg, kind_of(cfg), t.rt, t.nt, t.kc, t.wm, t.d);
     const double flops = 2.0 * (double)M * L.k_total * p.Cout;
     const int lrc = timed_launch(c, cfg < nsp ? 2 : cfg < nsp + nci ? 3 : 4,
-                                 flops + (next ? 2.0 * (double)M * next->k_total * next->proto.Cout : 0.0), profile, [&] { return launch(cfg); },
+                                 flops + (next ? 2.0 * (double)M * next->k_total * next->proto.Cout : 0.0), env_profile(), [&] { return launch(cfg); },
                                  "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d cfg=%d rt=%d nt=%d kc=%d mf=%d us=%.1f tflops=%.1f\n", M, L.k_total,
                                  p.Cout, p.ncls, cfg, t.rt, t.nt, t.kc, t.mf);
     if (lrc) return lrc;
     if (lastp && !fused_last) c->stat_launches++;    // the net's last layer went out as a launch of its own
     if (cfg >= nsp + nci) c->stat_gemm_flops_skipped += flops * (1.0 - g_last_issued_frac);   // (ring launches may skip padding taps)
-    if (diag) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        const TileCfg tt = tapgemm_sp_cfg(cfg);   // (diag runs never take the convimg kernel)
-        const long bm = 32L * tt.rt * tt.wm, bn = 32L * tt.nt * (4 / tt.wm);
-        const size_t nwg = (size_t)((M + bm - 1) / bm) * ((p.Cout + bn - 1) / bn) * p.ncls;
-        std::vector<unsigned long long> h(4 * nwg);
-        HIPCHK(c, hipMemcpy(h.data(), c->stage_tbs.p, h.size() * 8, hipMemcpyDeviceToHost));
-        double sum[4] = {0, 0, 0, 0};
-        for (size_t i = 0; i < nwg; i++) for (int k = 0; k < 4; k++) sum[k] += (double)h[4 * i + k];
-        const double stages = std::ceil(L.k_total / 16.0 / p.ncls / tt.kc);
-        fprintf(stderr, "[pnn-diag] M=%ld K=%.0f N=%d cfg {%d,%d,%d,wm%d}: per stage (cycles, wave 0 mean over %zu WGs): issue %.0f  mfma %.0f  store %.0f  barrier %.0f\n",
-                M, L.k_total, p.Cout, tt.rt, tt.nt, tt.kc, tt.wm, nwg, sum[0] / nwg / stages, sum[1] / nwg / stages, sum[2] / nwg / stages, sum[3] / nwg / stages);
-    }
+    if (diag && (brc = diag_sp(c, L, p, cfg, s))) return brc;
     if (next && tiles_out) *tiles_out = (int)((p.Cout + 32L * t.nt * (4 / t.wm) - 1) / (32L * t.nt * (4 / t.wm)));
     return PNN_OK;
 }
@@ -537,8 +528,7 @@ namespace {
 // forces it.  Not under the per-launch timing modes, which assume one stream.
 bool branches_overlap(const pnn_ctx* c, const Model* m, long nb)
 {
-    static const bool profile = getenv("PNN_PROFILE") != nullptr;
-    if (!c->opt_branch_streams || m->is_fc || profile || c->opt_time_launches) return false;
+    if (!c->opt_branch_streams || m->is_fc || env_profile() || c->opt_time_launches) return false;
     return nb * m->width * m->width <= 8192 && (m->width >= 32 || c->opt_branch_streams == 2);
 }
 
@@ -551,8 +541,7 @@ bool branches_overlap(const pnn_ctx* c, const Model* m, long nb)
 // without a tuning sweep (pnn_ctx::overlap_ready), and not under the per-launch timing modes or a forced configuration.
 bool branches_overlap_at_batch(const pnn_ctx* c, const Model* m, long nb)
 {
-    static const bool profile = getenv("PNN_PROFILE") != nullptr;
-    if (!c->opt_branch_streams || m->is_fc || profile || c->opt_time_launches || c->opt_sp_cfg >= 0) return false;
+    if (!c->opt_branch_streams || m->is_fc || env_profile() || c->opt_time_launches || c->opt_sp_cfg >= 0) return false;
     if (m->branch[0].size() < 2 || m->branch[1].size() < 2) return false;
     // (exact-f32 passes too, option f32_kernel: their launches end with a tail of big workgroups -- one or two per CU -- that the other
     // branch's launches fill)
@@ -588,6 +577,24 @@ int ensure_ws(pnn_ctx* c, const Model* m, long nb)
 bool pass_uses_split(const pnn_ctx* c, const Model*, long) { return c->opt_precision == 1; }
 
 namespace {
+
+// Branch br's first (Cin = 1) convolution over nb blocks of contexts X.  The caller sets Y, split and chain.
+Conv1Params first_conv(const pnn_ctx* c, const Model* m, int br, long nb, const float* X)
+{
+    const Conv1Layer& F = m->first[br];
+    Conv1Params f = F.proto;
+    f.X = X; f.W = F.d_w; f.bias = F.d_bias; f.Wsp = F.d_w_sp; f.out_scale = F.sp_inv_scale; f.npad = F.npad;
+    f.B = (int)nb; f.range_flag = c->h_range;
+    return f;
+}
+
+// ... reading its contexts straight from the picture plane (X == NULL: pnn_predict_tbs_device decided to fuse the gather in).  An
+// exact-f32 pass has conv_cin1_kernel read through these fields; a split-precision one hands them to the image kernel (run_gemm_sp).
+void attach_plane(const pnn_ctx* c, const Model* m, int br, Conv1Params& f)
+{
+    f.plane = c->lazy.plane; f.tbs = reinterpret_cast<const TbDev*>(c->lazy.tbs); f.pel_bytes = c->lazy.pel_bytes; f.unit = c->lazy.unit;
+    f.w = m->width; f.branch = br; f.mean = c->mean;   // (branch 0: the above portion w x 3w, 1: the left portion 2w x w)
+}
 
 int fc_pass(pnn_ctx* c, Model* m, const float* d_ctx, bool ctx_is_split, long nb, float* d_out, int32_t* d_dst, hipStream_t s)
 {
@@ -645,8 +652,10 @@ int fc_pass(pnn_ctx* c, Model* m, const float* d_ctx, bool ctx_is_split, long nb
             if ((rc = run_gemm(c, m->fc[2], P1, nullptr, nullptr, nb, s, &m->fc[3], part, &tiles))) return rc;
         } else {
             if ((rc = run_gemm(c, m->fc[2], P1, P0, nullptr, nb, s, nullptr, nullptr, nullptr, nullptr, chain ? 1 : 0))) return rc;
-            TapGemmParams q = m->fc[3].proto;
-            q.X = P0; q.Wp = m->fc[3].d_w; q.part = part; q.M = (int)nb; q.x_bytes = (unsigned)(4.0 * (double)nb * q.Cin);
+            TapGemmParams q;
+            if ((rc = bind_layer(c, m->fc[3], nb, "tensor", &q))) return rc;
+            q.X = P0; q.Wp = m->fc[3].d_w; q.part = part;
+            const double out_flops = 2.0 * (double)nb * m->fc[3].k_total * n_out;
             // small passes: the K segments and their reduction in ONE launch (fc_out_f32_chain_kernel: the same bits, one launch less
             // in the chain of a single-block call)
             if (c->opt_fc_out_f32 && nb <= 512 && !c->opt_time_launches) {
@@ -656,14 +665,12 @@ int fc_pass(pnn_ctx* c, Model* m, const float* d_ctx, bool ctx_is_split, long nb
                     const int nwg = (int)((nb + 15) / 16) * ((n_out + 15) / 16);      // fc_out_f32_chain_kernel's workgroups: a completion flag each
                     if (void* slot = diag_stamp_slot(c, "fc_out_f32_chain", nwg, 1200.0)) r.Xlo = slot;
                     HIPCHK(c, launch_fc_out_f32_small(r, s, take_done_signal_per_wg(c, nwg)));
-                    c->stat_gemm_launches++; c->stat_launches++;
-                    c->stat_gemm_flops += 2.0 * (double)nb * m->fc[3].k_total * n_out;
+                    count_gemm(c, out_flops);
                     return PNN_OK;
                 }
             }
             HIPCHK(c, launch_fc_out_f32(q, s, &tiles));
-            c->stat_gemm_launches++; c->stat_launches++;
-            c->stat_gemm_flops += 2.0 * (double)nb * m->fc[3].k_total * n_out;
+            count_gemm(c, out_flops);
         }
         if (tiles != segs) return fail(c, PNN_E_ARG, "output layer: %d K segments, expected %d", tiles, segs);
         HIPCHK(c, launch_fuse_reduce(part, tiles, (int)nb, n_out, m->fc[3].d_bias, 1.f, c->mean, d_out, d_dst, s, take_done_signal(c)));
@@ -697,8 +704,8 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
     // cost ~4 us each whatever they do.  Layer i of both branches goes into ONE launch (conv_cin1_pair_kernel, then
     // tapgemm_small_pair_kernel): 13 -> 9 launches for the 16x16 net, no event traffic between streams.  Same kernels' bodies,
     // same arithmetic: bit-identical to the separate launches.
-    static const bool env_profile = getenv("PNN_PROFILE") != nullptr, env_sdiag = getenv("PNN_F32S_DIAG") != nullptr;   // (not per pass: getenv walks the environment)
-    bool pair = sp && c->opt_pair && c->opt_small && c->opt_sp_cfg < 0 && !c->opt_time_launches && !env_profile &&
+    const bool timed = c->opt_time_launches || env_profile(), env_sdiag = env_f32s_diag();
+    bool pair = sp && c->opt_pair && c->opt_small && c->opt_sp_cfg < 0 && !timed &&
                 m->branch[0].size() == m->branch[1].size() && !m->branch[0].empty();
     for (size_t i = 0; pair && i < m->branch[0].size(); i++) {
         long tiles = 0;
@@ -714,10 +721,8 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
         float* Q[2][2] = {{P[0], P[1]}, {(float*)c->ws[4].p, (float*)c->ws[5].p}};
         Conv1Params f[2];
         for (int br = 0; br < 2; br++) {
-            f[br] = m->first[br].proto;
-            f[br].X = br == 0 ? d_above : d_left; f[br].W = m->first[br].d_w; f[br].bias = m->first[br].d_bias;
-            f[br].Wsp = m->first[br].d_w_sp; f[br].out_scale = m->first[br].sp_inv_scale; f[br].npad = m->first[br].npad;
-            f[br].B = (int)nb; f[br].range_flag = c->h_range; f[br].Y = Q[br][0]; f[br].split = 1;
+            f[br] = first_conv(c, m, br, nb, br == 0 ? d_above : d_left);
+            f[br].Y = Q[br][0]; f[br].split = 1;
         }
         HIPCHK(c, launch_conv_cin1_pair(f[0], f[1], s));
         c->stat_launches++;
@@ -726,20 +731,18 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
         for (size_t i = 0; i < nl; i++) {
             const bool last = i + 1 == nl;
             TapGemmParams q[2];
+            double flops = 0;
             for (int br = 0; br < 2; br++) {
                 const GemmLayer& L = m->branch[br][i];
-                q[br] = L.proto;
+                if ((rc = bind_layer(c, L, nb, "plane", &q[br]))) return rc;   // (cannot fire: opt_small_tiles caps a pair's tiles far below the bounds)
                 q[br].X = Q[br][cur]; q[br].Wp = L.d_w_sp; q[br].bias = L.d_bias; q[br].mean = c->mean; q[br].out_scale = L.sp_inv_scale;
                 q[br].range_flag = c->h_range; q[br].zero = c->d_zero;
                 if (last) q[br].Y = F[br]; else q[br].Yhi = Q[br][cur ^ 1];
-                q[br].M = (int)(nb * q[br].SH * q[br].SW);
-                q[br].x_bytes = (unsigned)(4.0 * (double)nb * q[br].IH * q[br].IW * q[br].Cin);
-                c->stat_gemm_flops += 2.0 * (double)q[br].M * L.k_total * q[br].Cout;
+                flops += 2.0 * (double)q[br].M * L.k_total * q[br].Cout;
             }
-            static const bool dbg = getenv("PNN_DEBUG") != nullptr;
-            if (dbg) fprintf(stderr, "[pnn] sp-gemm pair: branch layer %zu, M = %d / %d -> one small-kernel launch\n", i + 1, q[0].M, q[1].M);
+            if (env_debug()) fprintf(stderr, "[pnn] sp-gemm pair: branch layer %zu, M = %d / %d -> one small-kernel launch\n", i + 1, q[0].M, q[1].M);
             HIPCHK(c, launch_tapgemm_small_pair(q[0], q[1], s));
-            c->stat_gemm_launches++; c->stat_launches++;
+            count_gemm(c, flops);
             cur ^= 1;
         }
     }
@@ -749,7 +752,7 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
     bool merger_done = false, merger_chain_done = false;   // the merger ran as the tail of the branches' last pair launch (below)
     int merged_in = 0;                                // ... and left the merged map in P[merged_in]
     bool pair32 = !sp && !pair && c->opt_pair && c->opt_f32_small && c->opt_f32_cfg < 0 &&
-                  !c->opt_time_launches && !env_profile && !env_sdiag && m->branch[0].size() == m->branch[1].size() && !m->branch[0].empty();
+                  !timed && !env_sdiag && m->branch[0].size() == m->branch[1].size() && !m->branch[0].empty();
     for (size_t i = 0; pair32 && i < m->branch[0].size(); i++) {
         long tiles = 0;
         for (int br = 0; br < 2; br++) {
@@ -767,15 +770,10 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
         // the first convolutions' maps in chain order too: their consumer is the pair launch of layer 1 (both branches or neither)
         const bool first_chain = c->opt_chain_io && m->first[0].proto.Cout % 16 == 0 && m->first[1].proto.Cout % 16 == 0;
         for (int br = 0; br < 2; br++) {
-            f[br] = m->first[br].proto;
-            f[br].X = br == 0 ? d_above : d_left; f[br].W = m->first[br].d_w; f[br].bias = m->first[br].d_bias;
-            f[br].Wsp = m->first[br].d_w_sp; f[br].out_scale = m->first[br].sp_inv_scale; f[br].npad = m->first[br].npad;
-            f[br].B = (int)nb; f[br].range_flag = c->h_range; f[br].Y = Q[br][0]; f[br].split = 0;
+            f[br] = first_conv(c, m, br, nb, br == 0 ? d_above : d_left);
+            f[br].Y = Q[br][0]; f[br].split = 0;
             f[br].chain = first_chain ? 1 : 0;
-            if (!f[br].X && c->lazy.plane) {
-                f[br].plane = c->lazy.plane; f[br].tbs = reinterpret_cast<const TbDev*>(c->lazy.tbs); f[br].pel_bytes = c->lazy.pel_bytes; f[br].unit = c->lazy.unit;
-                f[br].w = m->width; f[br].branch = br; f[br].mean = c->mean;
-            }
+            if (!f[br].X && c->lazy.plane) attach_plane(c, m, br, f[br]);
         }
         HIPCHK(c, launch_conv_cin1_pair(f[0], f[1], s));
         c->stat_launches++;
@@ -790,33 +788,24 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
             bool folded[2] = {false, false};
             // ... and layer i writes that way when layer i + 1 is another launch of this kernel (the last branch layer feeds the merger: channel order)
             const bool out_chain = !last && f32_small_chain_out_ok(c, m->branch[0][i], nb) && f32_small_chain_out_ok(c, m->branch[1][i], nb);
+            double flops = 0;
             for (int br = 0; br < 2; br++) {
                 const GemmLayer& L = m->branch[br][i];
-                q[br] = L.proto;
+                if ((rc = bind_layer(c, L, nb, "tensor", &q[br]))) return rc;   // (cannot fire: opt_f32_small_tiles caps a pair's tiles far below the bounds)
                 q[br].X = Q[br][cur]; q[br].Wp = L.d_w_ch; q[br].bias = L.d_bias; q[br].mean = c->mean;
                 dst[br] = last ? F[br] : Q[br][cur ^ 1];
                 q[br].Y = dst[br];
-                q[br].M = (int)(nb * q[br].SH * q[br].SW);
-                q[br].x_bytes = (unsigned)(4.0 * (double)nb * q[br].IH * q[br].IW * q[br].Cin);
                 out_floats[br] = (size_t)nb * (size_t)L.out_per_block;
                 if (L.nseg > 1) {                     // raw sums into the branch's planes; seg_reduce below applies bias and activation
-                    DevBuf& sb = c->seg_part[br];
-                    if ((rc = dev_reserve(c, sb, (size_t)L.nseg * out_floats[br] * 4))) return rc;
-                    if (out_floats[br] >= 0xffffffffull) return fail(c, PNN_E_ARG, "batch too large for one pass");
-                    q[br].Y = (float*)sb.p; q[br].bias = (const float*)c->d_zero; q[br].act = 0; q[br].nseg = L.nseg; q[br].seg_stride = (unsigned)out_floats[br];
-                    folded[br] = c->opt_seg_fold && c->d_seg_cnt && tapgemm_f32_small_tiles(q[br]) / L.nseg <= pnn_ctx::kSegCntTiles;
-                    if (folded[br]) {                 // ... or the launch adds the planes up itself (tapgemm_f32_small_body; tile-major planes)
-                        if ((rc = dev_reserve(c, sb, (size_t)tapgemm_f32_small_tiles(q[br]) * 1024))) return rc;
-                        q[br].Y = (float*)sb.p;
-                        q[br].seg_cnt = c->d_seg_cnt + br * pnn_ctx::kSegCntTiles;
-                        q[br].seg_Y = dst[br]; q[br].bias = L.d_bias; q[br].act = L.proto.act;
-                    }
+                    if ((rc = seg_planes(c, q[br], L.nseg, out_floats[br], c->seg_part[br]))) return rc;
+                    folded[br] = launch_folds_segments(c, q[br]);   // ... or the launch adds the planes up itself (never timed: pair32)
+                    if (folded[br] && (rc = seg_planes_folded(c, q[br], L, dst[br], c->seg_part[br], br))) return rc;
                 }
                 q[br].chain_io = (in_chain ? 1 : 0) | (out_chain ? 2 : 0);
-                c->stat_gemm_flops += 2.0 * (double)q[br].M * L.k_total * q[br].Cout;
+                flops += 2.0 * (double)q[br].M * L.k_total * q[br].Cout;
                 if (void* slot = diag_stamp_slot(c, br ? "f32_small pair, left branch" : "f32_small pair, above branch", tapgemm_f32_small_tiles(q[br]), L.k_total)) q[br].Xlo = slot;
             }
-            static const bool dbg = getenv("PNN_DEBUG") != nullptr;
+            const bool dbg = env_debug();
             if (dbg) fprintf(stderr, "[pnn] f32 gemm pair: branch layer %zu, M = %d / %d -> one f32 small-kernel launch\n", i + 1, q[0].M, q[1].M);
             // the merger as the tail of the branches' LAST pair launch (SmallTail kind 1): per (block, channel group), by the last of its
             // five tiles to arrive -- where the launch is at most one workgroup per CU (the tail kernel's registers allow one)
@@ -833,14 +822,14 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
                 mtail = f32_small_merger_tail_ok(q[0], q[1], mt.m);
             }
             if (mtail) {
-                if (c->seg_cnt_dirty) { HIPCHK(c, hipMemsetAsync(c->d_seg_cnt, 0, pnn_ctx::kCntWords * 4, s)); c->seg_cnt_dirty = false; }
+                if ((rc = clear_tail_counters(c, s, false))) return rc;
                 if (dbg) fprintf(stderr, "[pnn]   ... with the merger as its tail\n");
                 HIPCHK(c, launch_tapgemm_f32_small_pair_tail(q[0], q[1], mt, s, (int)c->opt_f32_small_deep));
                 merger_done = true; merger_chain_done = mt.m.chain != 0; merged_in = cur ^ 1;
             } else {
                 HIPCHK(c, launch_tapgemm_f32_small_pair(q[0], q[1], s, (int)c->opt_f32_small_deep));
             }
-            c->stat_gemm_launches++; c->stat_launches++;
+            count_gemm(c, flops);
             for (int br = 0; br < 2; br++) {
                 const GemmLayer& L = m->branch[br][i];
                 if (L.nseg <= 1 || folded[br]) continue;
@@ -857,16 +846,12 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
     int bcur[2] = {0, 0};
     auto branch_layers = [&](int br, hipStream_t st) -> int {
         const size_t nl = m->branch[br].size();
-        Conv1Params f = m->first[br].proto;
-        f.X = br == 0 ? d_above : d_left; f.W = m->first[br].d_w; f.bias = m->first[br].d_bias;
-        f.Wsp = m->first[br].d_w_sp; f.out_scale = m->first[br].sp_inv_scale; f.npad = m->first[br].npad;
-        f.B = (int)nb; f.range_flag = c->h_range;
+        Conv1Params f = first_conv(c, m, br, nb, br == 0 ? d_above : d_left);
         f.Y = nl == 0 ? F[br] : PB[br][0];
         f.split = (sp && nl > 0) ? 1 : 0;
-        if (!f.X && !sp && c->lazy.plane) {           // exact-f32 pass straight from the picture plane (pnn_predict_tbs_device decided so)
-            f.plane = c->lazy.plane; f.tbs = reinterpret_cast<const TbDev*>(c->lazy.tbs); f.pel_bytes = c->lazy.pel_bytes; f.unit = c->lazy.unit;
-            f.w = m->width; f.branch = br; f.mean = c->mean;
-        }
+        // straight from the picture plane (pnn_predict_tbs_device decided so): an exact-f32 pass in this launch, a split one in the
+        // image kernel that absorbs it (a split convolution launched on its own never reads the plane: conv_pass_fuses_first)
+        if (!f.X && c->lazy.plane && (!sp || nl > 0)) attach_plane(c, m, br, f);
         const bool delegate = sp && nl > 0;           // run_gemm_sp of the next layer launches or absorbs this convolution
         if (!delegate) {
             HIPCHK(c, launch_conv_cin1(f, st));
@@ -916,13 +901,14 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
     tp.W = m->last.d_w; tp.Y = d_out; tp.Yi = d_dst; tp.B = (int)nb; tp.mean = c->mean;
     // the last layer as the tail of the last GEMM of the transposed stack (SmallTail kind 2; run_gemm takes it where that GEMM runs on
     // the small kernels and the shapes fit): one completion flag per block instead of the counter form
-    const bool want_ctail = !sp && nt > 0 && c->opt_tails && c->d_seg_cnt && nb <= pnn_ctx::kTailCnt && nb <= 64 && !c->opt_time_launches && !env_profile && !env_sdiag &&
+    const bool want_ctail = !sp && nt > 0 && c->opt_tails && c->d_seg_cnt && nb <= pnn_ctx::kTailCnt && nb <= 64 && !timed && !env_sdiag &&
                             f32_small_applies(c, m->tconv[nt - 1], nb, false, false);
     SmallTail ct;
     if (want_ctail) {
-        if (c->seg_cnt_dirty) { HIPCHK(c, hipMemsetAsync(c->d_seg_cnt, 0, pnn_ctx::kCntWords * 4, s)); c->seg_cnt_dirty = false; }
-        TapGemmParams probe = m->tconv[nt - 1].proto;
-        probe.M = (int)(nb * probe.SH * probe.SW); probe.Y = P[0]; probe.Yi = nullptr; probe.nseg = m->tconv[nt - 1].nseg; probe.chain_io = 0;
+        if ((rc = clear_tail_counters(c, s, false))) return rc;
+        TapGemmParams probe;
+        if ((rc = bind_layer(c, m->tconv[nt - 1], nb, "tensor", &probe))) return rc;
+        probe.Y = P[0]; probe.Yi = nullptr; probe.nseg = m->tconv[nt - 1].nseg; probe.chain_io = 0;
         TConv1Params tq = tp;
         tq.X = P[0];
         if (!f32_small_cout1_tail_ok(probe, tq)) { tp.done = take_done_signal(c); ct.kind = 0; }
@@ -972,13 +958,11 @@ int conv_pass(pnn_ctx* c, Model* m, const float* d_above, const float* d_left, l
 bool conv_pass_fuses_first(pnn_ctx* c, Model* m, long nb)
 {
     if (!m->is_fc && c->opt_fuse_gather && !pass_uses_split(c, m, nb)) return true;
-    if (m->is_fc || !c->opt_fuse_gather || !pass_uses_split(c, m, nb) || c->opt_time_launches || getenv("PNN_PROFILE")) return false;
+    if (m->is_fc || !c->opt_fuse_gather || !pass_uses_split(c, m, nb) || c->opt_time_launches || env_profile()) return false;
     for (int br = 0; br < 2; br++) {
         if (m->branch[br].empty()) return false;
-        Conv1Params f = m->first[br].proto;
-        f.W = m->first[br].d_w; f.bias = m->first[br].d_bias;
-        f.Wsp = m->first[br].d_w_sp; f.out_scale = m->first[br].sp_inv_scale; f.npad = m->first[br].npad;
-        f.B = (int)nb; f.split = 1;
+        Conv1Params f = first_conv(c, m, br, nb, nullptr);
+        f.split = 1;
         bool fuse = false;
         if (run_gemm_sp(c, m->branch[br][0], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nb, nullptr, nullptr, nullptr, nullptr, &f, false, 0, &fuse) || !fuse) return false;
     }
