@@ -73,17 +73,25 @@ SIGNATURES = {
     "pnn_block_cost_device": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp]),
     "pnn_predict_tbs_cost_device": (ci, [vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp]),
     "pnn_hevc_intra_predict": (ci, [u8p, ci, ci, ci, ci, u8p]),
+    "pnn_hevc_mode_uses_smoothing": (ci, [ci, ci]),
+    "pnn_hevc_smoothed_reference_host": (ci, [vp, ci, ci, ci, ci, vp, ctypes.POINTER(ci)]),
+    "pnn_hevc_intra_predict_hm": (ci, [u8p, ci, ci, ci, ci, ci, u8p]),
     "pnn_hevc_best_mode_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
+    "pnn_hevc_best_mode_hm_device": (ci, [vp, ci, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp]),
     "pnn_first_pass_list_size": (ci, [ci]),
     "pnn_hevc_mode_hads_host": (ci, [vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp]),
     "pnn_hevc_mode_hads_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "pnn_hevc_mode_hads_hm_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, vp, vp, vp, vp]),
+    "pnn_hevc_mode_hads_hm_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]),
     "pnn_first_pass_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "pnn_first_pass_picture_pairs_hm_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
     "pnn_ipfcns_forward_host": (ci, [ci, f32p, f32p, ci, ci, f32p]),
     "pnn_ipfcns_load": (ci, [vp, ci, f32p, ctypes.c_size_t]),
     "pnn_ipfcns_forward_device": (ci, [vp, ci, vp, ci, vp, vp]),
     "pnn_ipfcns_predict_device": (ci, [vp, ci, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
     "pnn_score_pictures_device": (ci, [vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "pnn_score_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pnn_score_picture_pairs_hm_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "pnn_score_f32_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),

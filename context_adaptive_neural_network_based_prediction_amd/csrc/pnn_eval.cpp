@@ -1,5 +1,6 @@
 // The C-ABI entries of the Python evaluator (include/pnn_hip.h; HM calls none of them): the best HEVC intra mode and the first-pass
-// Hadamard ranking on dense patterns, IPFCN-S, the scores from pictures and pairs of pictures.  Contexts, models, staging and the
+// Hadamard ranking on dense patterns (each with its *_hm sibling: HM's reference-sample smoothing as an option; the entry without the
+// suffix is the sibling called with 0), IPFCN-S, the scores from pictures and pairs of pictures.  Contexts, models, staging and the
 // predictor's entries: pnn_abi.cpp.  Each argument check is written once and composed per entry; an entry's ORDER of checks is part of
 // its behaviour (which of two bad arguments pnn_last_error names), so it is spelled out in the entry.
 #include "pnn_ctx.h"
@@ -28,6 +29,11 @@ int count_blocks(pnn_ctx* c, int images, int positions, long* n)
 {
     *n = (long)images * positions;
     return *n > 0x7fffffffL ? fail(c, PNN_E_ARG, "more than 2^31 - 1 blocks") : PNN_OK;
+}
+// the option of every *_hm entry (include/pnn_hip.h): HM's reference-sample smoothing
+int check_smoothing(pnn_ctx* c, int smoothing)
+{
+    return smoothing < 0 || smoothing > 2 ? fail(c, PNN_E_ARG, "smoothing %d is not 0 (none), 1 ([1 2 1]) or 2 (HM: strong allowed)", smoothing) : PNN_OK;
 }
 // the outputs of the first-pass ranking, dense or from pictures
 int check_hads_outputs(pnn_ctx* c, const void* d_cand_pred, const void* d_mode_hads, const void* d_cand_hads, const void* d_list_modes,
@@ -90,27 +96,28 @@ PictureBlocks picture_blocks(const uint8_t* d_channels, int height, int width_ch
 
 // Where a 35-mode kernel reads its blocks, the fields both parameter structs have (pnn_kernels.h).  Dense form: patterns and targets, no
 // picture.  Picture form: patterns == NULL, the planes in *pic and pic_targets, ph / pw = 2w + 1 - mask_h / mask_w (what the masks leave
-// of the pattern's first column and row).
+// of the pattern's first column and row).  smoothing: the checked option.
 template <typename P>
-void set_blocks(P& p, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets, long n, int width)
+void set_blocks(P& p, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets, long n, int width,
+                int smoothing)
 {
     p.patterns = patterns; p.ph = ph; p.pw = pw; p.targets = targets; p.N = (int)n; p.w = width;
-    p.pic = pic ? *pic : PictureBlocks{}; p.pic_targets = pic_targets;
+    p.pic = pic ? *pic : PictureBlocks{}; p.pic_targets = pic_targets; p.smoothing = smoothing;
 }
 HevcBestModeParams best_mode_params(const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets,
-                                    long n, int width, uint8_t* best_mode, uint32_t* best_sse, uint8_t* best_pred, uint32_t* mode_sse)
+                                    long n, int width, int smoothing, uint8_t* best_mode, uint32_t* best_sse, uint8_t* best_pred, uint32_t* mode_sse)
 {
     HevcBestModeParams p;
-    set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width);
+    set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
     p.best_mode = best_mode; p.best_sse = best_sse; p.best_pred = best_pred; p.mode_sse = mode_sse;
     return p;
 }
 HevcModeHadsParams mode_hads_params(const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets,
-                                    long n, int width, const uint8_t* cand_pred, uint32_t* mode_hads, uint32_t* cand_hads, uint8_t* list_modes,
-                                    uint32_t* list_costs)
+                                    long n, int width, int smoothing, const uint8_t* cand_pred, uint32_t* mode_hads, uint32_t* cand_hads,
+                                    uint8_t* list_modes, uint32_t* list_costs)
 {
     HevcModeHadsParams p;
-    set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width);
+    set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
     p.cand_pred = cand_pred; p.mode_hads = mode_hads; p.cand_hads = cand_hads; p.list_modes = list_modes; p.list_costs = list_costs;
     return p;
 }
@@ -131,14 +138,23 @@ int pnn_hevc_best_mode_device(pnn_ctx* c, int width, const uint8_t* d_patterns, 
                               const uint8_t* d_targets, int n, uint8_t* d_best_mode, uint32_t* d_best_sse, uint8_t* d_best_pred,
                               uint32_t* d_mode_sse, void* stream)
 {
+    // the reference's extracted predictor is HM's without the smoothing
+    return pnn_hevc_best_mode_hm_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, 0, d_best_mode, d_best_sse, d_best_pred,
+                                        d_mode_sse, stream);
+}
+
+int pnn_hevc_best_mode_hm_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
+                                 const uint8_t* d_targets, int n, int smoothing, uint8_t* d_best_mode, uint32_t* d_best_sse,
+                                 uint8_t* d_best_pred, uint32_t* d_mode_sse, void* stream)
+{
     if (!c) return PNN_E_ARG;
     int rc;
-    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) ||
+    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing)) ||
         (rc = check_some_output(c, d_best_mode || d_best_sse || d_best_pred || d_mode_sse))) return rc;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const HevcBestModeParams p = best_mode_params(d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, width, d_best_mode, d_best_sse,
-                                                  d_best_pred, d_mode_sse);
+    const HevcBestModeParams p = best_mode_params(d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, width, smoothing, d_best_mode,
+                                                  d_best_sse, d_best_pred, d_mode_sse);
     HIPCHK(c, launch_hevc_best_mode(p, (hipStream_t)stream));
     return PNN_OK;
 }
@@ -147,14 +163,22 @@ int pnn_hevc_mode_hads_device(pnn_ctx* c, int width, const uint8_t* d_patterns, 
                               int n, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes,
                               uint32_t* d_list_costs, void* stream)
 {
+    return pnn_hevc_mode_hads_hm_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, d_cand_pred, 0, d_mode_hads, d_cand_hads,
+                                        d_list_modes, d_list_costs, stream);
+}
+
+int pnn_hevc_mode_hads_hm_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets,
+                                 int n, const uint8_t* d_cand_pred, int smoothing, uint32_t* d_mode_hads, uint32_t* d_cand_hads,
+                                 uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
+{
     if (!c) return PNN_E_ARG;
     int rc;
-    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) ||
+    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing)) ||
         (rc = check_hads_outputs(c, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs))) return rc;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const HevcModeHadsParams p = mode_hads_params(d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, width, d_cand_pred, d_mode_hads,
-                                                  d_cand_hads, d_list_modes, d_list_costs);
+    const HevcModeHadsParams p = mode_hads_params(d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, width, smoothing, d_cand_pred,
+                                                  d_mode_hads, d_cand_hads, d_list_modes, d_list_costs);
     HIPCHK(c, launch_hevc_mode_hads(p, (hipStream_t)stream));
     return PNN_OK;
 }
@@ -249,11 +273,22 @@ int pnn_score_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_conte
                                    int mask_h, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
                                    uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
 {
+    return pnn_score_picture_pairs_hm_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols, positions,
+                                             mask_w, mask_h, 0, d_targets, d_pnn_u8, d_pnn_f32, d_pnn_sse, d_hevc_mode, d_hevc_sse, d_hevc_pred,
+                                             stream);
+}
+
+int pnn_score_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                      int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
+                                      int mask_h, int smoothing, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
+                                      uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
+{
     if (!c) return PNN_E_ARG;
     int rc;
     long n;
     const bool want_pnn = d_pnn_u8 || d_pnn_f32 || d_pnn_sse, want_hevc = d_hevc_mode || d_hevc_sse || d_hevc_pred;
     if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+        (rc = check_smoothing(c, smoothing)) ||
         (rc = check_some_output(c, d_targets || want_pnn || want_hevc))) return rc;
     Model* m = want_pnn ? c->models[width_index(width)] : nullptr;
     if (want_pnn && !m) return fail(c, PNN_E_ARG, "a PNN output is asked for, but no model is loaded for width %d", width);
@@ -300,7 +335,7 @@ int pnn_score_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_conte
     }
     if (want_hevc) {
         const HevcBestModeParams p = best_mode_params(nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n,
-                                                      width, d_hevc_mode, d_hevc_sse, d_hevc_pred, nullptr);
+                                                      width, smoothing, d_hevc_mode, d_hevc_sse, d_hevc_pred, nullptr);
         HIPCHK(c, launch_hevc_best_mode(p, s));
         c->stat_launches++;
     }
@@ -312,10 +347,21 @@ int pnn_first_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_
                                         int mask_h, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads,
                                         uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
 {
+    return pnn_first_pass_picture_pairs_hm_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols,
+                                                  positions, mask_w, mask_h, d_cand_pred, 0, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs,
+                                                  stream);
+}
+
+int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                           int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, uint32_t* d_mode_hads,
+                                           uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
+{
     if (!c) return PNN_E_ARG;
     int rc;
     long n;
     if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+        (rc = check_smoothing(c, smoothing)) ||
         (rc = check_hads_outputs(c, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs)) ||
         (rc = count_blocks(c, images, positions, &n))) return rc;
     if (n == 0) return PNN_OK;
@@ -325,7 +371,7 @@ int pnn_first_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_
     if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
     reset_stats(c);
     const HevcModeHadsParams p = mode_hads_params(nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n,
-                                                  width, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs);
+                                                  width, smoothing, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs);
     HIPCHK(c, launch_hevc_mode_hads(p, s));
     c->stat_launches++;
     return PNN_OK;

@@ -2,10 +2,14 @@
 // pad the pattern into a full (2w+1)^2 one, build refMain / refSide per mode (negative angles project the side reference
 // through invAngTable), predict the vertical orientation and transpose for the horizontal modes.  Same contract as the
 // reference's hevc_intraprediction (hevc/intraprediction/c++/source/extracted_hevc_intraprediction.cpp:3-134): no reference
-// sample smoothing, 8-bit luma, DC filtering and the mode 10 / 26 edge filter for w <= 16; -1 where the reference throws.
+// sample smoothing (smoothing = 0), 8-bit luma, DC filtering and the mode 10 / 26 edge filter for w <= 16; -1 where the reference throws.
 // pnn_hevc_intra.hip computes the same predictions in closed form; tests/test_gpu_hevc_intra.py checks one against the other.
 // pnn_hevc_mode_hads_host is the host twin of the first-pass ranking (hevc_mode_hads_kernel): the 35 predictions above, HM's
 // xGetHADs written from its rule, and xUpdateCandList; tests/test_gpu_mode_hads.py checks the kernel against it.
+// HM's reference-sample smoothing (TComPattern.cpp:410-478, :721-746; TComPrediction.cpp:39-55) is an option of the *_hm entries:
+// `smoothing` 0 = none (the reference's extracted predictor, what the older entries compute: they are the 0 case of the same bodies),
+// 1 = the [1 2 1] filter for the modes and sizes HM filters, 2 = HM's default, which also allows the strong (bilinear) filter on flat
+// 32 x 32 neighbourhoods.  tests/test_hevc_smoothing.py pins it to a numpy restatement, tests/test_gpu_hevc_smoothing.py the kernels to it.
 #include "../../include/pnn_hip.h"
 
 #include <cstdint>
@@ -120,6 +124,86 @@ void update_cand_list(int mode, uint32_t cost, int k, int* list_modes, uint64_t*
     list_costs[k - shift] = cost;
 }
 
+// intraFilterThreshold: a mode reads smoothed samples iff it is not DC and lies further than thr[w] from both pure directions
+bool mode_smooths(int w, int mode)
+{
+    const int thr = w == 8 ? 7 : w == 16 ? 1 : w == 32 ? 0 : 10;
+    const int dh = mode > 10 ? mode - 10 : 10 - mode, dv = mode > 26 ? mode - 26 : 26 - mode;
+    return mode != 1 && (dh < dv ? dh : dv) > thr;
+}
+
+bool smoothing_ok(int smoothing)
+{
+    if (smoothing >= 0 && smoothing <= 2) return true;
+    fprintf(stderr, "The reference-sample smoothing %d is not 0 (none), 1 (HM without StrongIntraSmoothing) or 2 (HM).\n", smoothing);
+    return false;
+}
+
+// The padding rule, its one home: line[2w + j], j in [-2w, 2w], = the corner at j = 0, left / below-left below it (first column), above /
+// above-right to the right (first row); a short row or column is extended with its last sample.
+void padded_line(const uint8_t* pat, int ph, int pw, int w, int* line)
+{
+    for (int i = 0; i <= 2 * w; i++) {
+        line[2 * w + i] = pat[i < pw ? i : pw - 1];
+        line[2 * w - i] = pat[(i < ph ? i : ph - 1) * pw];
+    }
+}
+
+// filteringIntraReferenceSamples on the padded line (HM substitutes first, filters afterwards): both ends copied; strong (w = 32,
+// `allow_strong`, both halves flat at their three anchors): the corner copied, each side bilinear between its anchors; else [1 2 1].
+bool smooth_line(const int* line, int w, bool allow_strong, int* out)
+{
+    const int* rf = line + 2 * w;
+    int* o = out + 2 * w;
+    o[-2 * w] = rf[-2 * w];
+    o[2 * w] = rf[2 * w];
+    bool strong = false;
+    if (w == 32 && allow_strong) {
+        const int bl = rf[-64], tl = rf[0], tr = rf[64], thr = 1 << (8 - 5);
+        const int dl = bl + tl - 2 * rf[-32], da = tl + tr - 2 * rf[32];
+        strong = (dl < 0 ? -dl : dl) < thr && (da < 0 ? -da : da) < thr;
+        if (strong) {
+            o[0] = tl;
+            for (int i = 1; i < 64; i++) {
+                o[-64 + i] = ((64 - i) * bl + i * tl + 32) >> 6;
+                o[i] = ((64 - i) * tl + i * tr + 32) >> 6;
+            }
+        }
+    }
+    if (!strong)
+        for (int j = -2 * w + 1; j < 2 * w; j++) o[j] = (rf[j - 1] + 2 * rf[j] + rf[j + 1] + 2) >> 2;
+    return strong;
+}
+
+// The reference samples of one pattern as predict() takes them: [0] the plain ones, [1] the ones the smoothed modes read (the same
+// when `smoothing` is 0 or no mode of this width smooths).
+struct RefSamples {
+    int top[2][2 * 64 + 1], left[2][2 * 64 + 1];
+    bool strong;
+    RefSamples(const uint8_t* pat, int ph, int pw, int w, int smoothing) : strong(false)
+    {
+        int line[2][4 * 64 + 1];
+        padded_line(pat, ph, pw, w, line[0]);
+        const bool any = smoothing != 0 && (w == 8 || w == 16 || w == 32);
+        if (any) strong = smooth_line(line[0], w, smoothing == 2, line[1]);
+        for (int s = 0; s < 2; s++)
+            for (int i = 0; i <= 2 * w; i++) {
+                top[s][i] = line[any ? s : 0][2 * w + i];
+                left[s][i] = line[any ? s : 0][2 * w - i];
+            }
+    }
+    void predict_mode(int w, int mode, int* pred) const
+    {
+        const int s = mode_smooths(w, mode) ? 1 : 0;
+        predict(top[s], left[s], w, mode, pred);
+    }
+};
+
+bool pattern_sides_ok(int pattern_h, int pattern_w, int width)
+{
+    return pattern_h >= width + 1 && pattern_h <= 2 * width + 1 && pattern_w >= width + 1 && pattern_w <= 2 * width + 1;
+}
+
 }  // namespace
 
 extern "C" int pnn_first_pass_list_size(int width)
@@ -128,29 +212,59 @@ extern "C" int pnn_first_pass_list_size(int width)
     return width <= 8 ? 8 : 3;                                                // g_aucIntraModeNumFast_UseMPM
 }
 
+extern "C" int pnn_hevc_mode_uses_smoothing(int width, int mode)
+{
+    if (log2_width(width) < 0) { fprintf(stderr, "The width of the target patch is not 4, 8, 16, 32 or 64.\n"); return PNN_E_ARG; }
+    if (mode < 0 || mode > 34) { fprintf(stderr, "The direction is not smaller than 34.\n"); return PNN_E_ARG; }
+    return mode_smooths(width, mode) ? 1 : 0;
+}
+
+extern "C" int pnn_hevc_smoothed_reference_host(const uint8_t* pattern, int pattern_h, int pattern_w, int width, int smoothing, uint8_t* line,
+                                                int* strong_used)
+{
+    if (!pattern || !line) { fprintf(stderr, "NULL pointer.\n"); return PNN_E_ARG; }
+    if (log2_width(width) < 0) { fprintf(stderr, "The width of the target patch is not 4, 8, 16, 32 or 64.\n"); return PNN_E_ARG; }
+    if (!pattern_sides_ok(pattern_h, pattern_w, width)) {
+        fprintf(stderr, "A side of the intra pattern does not belong to [%d, %d].\n", width + 1, 2 * width + 1);
+        return PNN_E_ARG;
+    }
+    if (!smoothing_ok(smoothing)) return PNN_E_ARG;
+    const RefSamples r(pattern, pattern_h, pattern_w, width, smoothing);
+    for (int i = 0; i <= 2 * width; i++) {
+        line[2 * width + i] = (uint8_t)r.top[1][i];
+        line[2 * width - i] = (uint8_t)r.left[1][i];
+    }
+    if (strong_used) *strong_used = r.strong ? 1 : 0;
+    return PNN_OK;
+}
+
 extern "C" int pnn_hevc_mode_hads_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
                                        const uint8_t* cand_pred, uint32_t* mode_hads, uint32_t* cand_hads, uint8_t* list_modes,
                                        uint32_t* list_costs)
 {
+    return pnn_hevc_mode_hads_hm_host(patterns, pattern_h, pattern_w, targets, width, n, cand_pred, 0, mode_hads, cand_hads, list_modes, list_costs);
+}
+
+extern "C" int pnn_hevc_mode_hads_hm_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                                          const uint8_t* cand_pred, int smoothing, uint32_t* mode_hads, uint32_t* cand_hads, uint8_t* list_modes,
+                                          uint32_t* list_costs)
+{
     if (log2_width(width) < 0) return PNN_E_ARG;
-    if (pattern_h < width + 1 || pattern_h > 2 * width + 1 || pattern_w < width + 1 || pattern_w > 2 * width + 1) return PNN_E_ARG;
+    if (!pattern_sides_ok(pattern_h, pattern_w, width)) return PNN_E_ARG;
     if (n < 0 || (n > 0 && (!patterns || !targets))) return PNN_E_ARG;
+    if (!smoothing_ok(smoothing)) return PNN_E_ARG;
     if (!mode_hads && !cand_hads && !list_modes && !list_costs) return PNN_E_ARG;
     if (cand_hads && !cand_pred) return PNN_E_ARG;
     const int w2 = width * width, k = width <= 8 ? 8 : 3;
     std::vector<int> pred(w2);
     for (long b = 0; b < n; b++) {
-        const uint8_t* pat = patterns + (size_t)b * pattern_h * pattern_w;
         const uint8_t* org = targets + (size_t)b * w2;
-        int top[2 * 64 + 1], left[2 * 64 + 1], modes[8];
+        const RefSamples refs(patterns + (size_t)b * pattern_h * pattern_w, pattern_h, pattern_w, width, smoothing);
+        int modes[8];
         uint64_t costs[8];
         for (int i = 0; i < k; i++) { modes[i] = 255; costs[i] = UINT64_MAX; }  // HM starts the list at MAX_DOUBLE
-        for (int i = 0; i <= 2 * width; i++) {
-            top[i] = pat[i < pattern_w ? i : pattern_w - 1];
-            left[i] = pat[(i < pattern_h ? i : pattern_h - 1) * pattern_w];
-        }
         for (int mode = 0; mode < 35; mode++) {
-            predict(top, left, width, mode, pred.data());
+            refs.predict_mode(width, mode, pred.data());
             const uint32_t c = hads(org, pred.data(), width);
             if (mode_hads) mode_hads[b * 35 + mode] = c;
             update_cand_list(mode, c, k, modes, costs);
@@ -172,6 +286,12 @@ extern "C" int pnn_hevc_mode_hads_host(const uint8_t* patterns, int pattern_h, i
 extern "C" int pnn_hevc_intra_predict(const uint8_t* intra_pattern, int pattern_h, int pattern_w, int width, int mode,
                                       uint8_t* out)
 {
+    return pnn_hevc_intra_predict_hm(intra_pattern, pattern_h, pattern_w, width, mode, 0, out);
+}
+
+extern "C" int pnn_hevc_intra_predict_hm(const uint8_t* intra_pattern, int pattern_h, int pattern_w, int width, int mode, int smoothing,
+                                         uint8_t* out)
+{
     if (!intra_pattern || !out) { fprintf(stderr, "NULL pointer.\n"); return -1; }
     if (mode < 0 || mode > 34) { fprintf(stderr, "The direction is not smaller than 34.\n"); return -1; }
     if (log2_width(width) < 0) { fprintf(stderr, "The width of the target patch is not 4, 8, 16, 32 or 64.\n"); return -1; }
@@ -183,12 +303,9 @@ extern "C" int pnn_hevc_intra_predict(const uint8_t* intra_pattern, int pattern_
         fprintf(stderr, "The width of the intra pattern does not belong to [%d, %d].\n", width + 1, 2 * width + 1);
         return -1;
     }
-    int top[2 * 64 + 1], left[2 * 64 + 1], pred[64 * 64];
-    for (int i = 0; i <= 2 * width; i++) {
-        top[i] = intra_pattern[i < pattern_w ? i : pattern_w - 1];
-        left[i] = intra_pattern[(i < pattern_h ? i : pattern_h - 1) * pattern_w];
-    }
-    predict(top, left, width, mode, pred);
+    if (!smoothing_ok(smoothing)) return PNN_E_ARG;
+    int pred[64 * 64];
+    RefSamples(intra_pattern, pattern_h, pattern_w, width, smoothing).predict_mode(width, mode, pred);
     for (int i = 0; i < width * width; i++) out[i] = (uint8_t)pred[i];
     return 0;
 }

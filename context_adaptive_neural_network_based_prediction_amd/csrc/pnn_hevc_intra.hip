@@ -1,6 +1,6 @@
 // HEVC best-intra-mode search for the evaluator's competitor (comparing_pnn_ipfcns_hevc_best_mode.py:162-322 via
 // hevc/intraprediction/intraprediction.py:231-294): for each of N blocks, all 35 luma predictions of HM's xPredIntraPlanar /
-// DC / xPredIntraAng from the block's intra pattern (no reference smoothing: the reference did not extract it), the SSE of
+// DC / xPredIntraAng from the block's intra pattern (no reference smoothing unless asked for, below: the reference did not extract it), the SSE of
 // each against the target, and the mode of smallest SSE (lowest index among ties -- the reference keeps a mode only when its
 // PSNR, strictly decreasing in the SSE, is strictly larger).  Integer VALU arithmetic only; bit-exact against the host twin
 // (pnn_hevc_intra.cpp), which builds refMain the way HM does.
@@ -20,8 +20,16 @@
 // staging and the same per-pixel mode functions, but a lane owns one T x T sub-block (T = 8, 4 at w = 4) of one block and one mode at
 // a time -- its T^2 residuals in registers, the Walsh-Hadamard butterflies of pnn_wht.h, the rounding of TComRdCost::xGetHADs -- and
 // adds the sub-block's cost into cost[block][mode] in LDS.  A candidate prediction handed in (the PNN's) is costed as index 35 in a
-// sixth round of one wave; then one lane per block builds HM's sorted candidate list (xUpdateCandList).  No reference smoothing (as
-// above) and no modeBits * sqrtLambda term: the costs are the distortions alone.
+// sixth round of one wave; then one lane per block builds HM's sorted candidate list (xUpdateCandList).  Reference smoothing as an option (as
+// below) and no modeBits * sqrtLambda term: the costs are the distortions alone.
+//
+// HM's reference-sample smoothing (include/pnn_hip.h, "smoothing") is the compile-time axis SMOOTH of both kernels, instantiated for
+// w = 8, 16, 32 only (no mode smooths at 4 and 64).  A second staging pass, stage_smoothed, filters the staged line LDS -> LDS into
+// ref_s (same stride); at w = 32 one lane per block first takes the strong-filter decision into LDS, and whether the strong filter is
+// allowed at all is the runtime field p.smoothing, one uniform branch.  In the mode rounds the mode is wave-uniform, so the wave picks
+// ref or ref_s by mode_smooths(mode) with one scalar select and runs the same pixel functions; DC and the modes 10 / 26 are not in that
+// table, so the DC value, the DC filter and the edge filter read ref by construction.  With SMOOTH = false the kernels are the code
+// they were.
 #include "pnn_kernels.h"
 #include "pnn_wht.h"
 
@@ -169,12 +177,52 @@ __device__ __forceinline__ void stage_dc(const int* ref, int* dcv, int tid)
     }
 }
 
-template <int W, bool PIC>
+// intraFilterThreshold (TComPrediction.cpp:39-55): does `mode` read the smoothed line at this width?  Never DC, never modes 10 / 26.
+template <int W>
+__device__ inline bool mode_smooths(int mode)
+{
+    constexpr int thr = W == 8 ? 7 : W == 16 ? 1 : W == 32 ? 0 : 10;
+    return mode != 1 && min(abs(mode - 10), abs(mode - 26)) > thr;
+}
+
+// filteringIntraReferenceSamples on the G staged (hence padded) lines, LDS -> LDS: ref_s has ref's layout.  Both ends are copied.
+// W = 32: one lane per block decides whether its line is strong (both halves flat at their anchors; only when `allow_strong`), then
+// every thread writes bilinear samples (corner copied) or [1 2 1] ones as its block's flag says.  Called between two barriers: ref is
+// complete on entry, the caller's next barrier publishes ref_s.
+template <int W, int G>
+__device__ __forceinline__ void stage_smoothed(const int* ref, int* ref_s, int* strong, bool allow_strong, int tid)
+{
+    constexpr int RS = 4 * W + 1;
+    if (W == 32) {
+        const int g = tid - 64;                        // the second wave: the first one is in stage_dc
+        if (g >= 0 && g < G) {
+            const int* rf = ref + g * RS + 2 * W;
+            int s = 0;
+            if (allow_strong) s = abs(rf[-64] + rf[0] - 2 * rf[-32]) < 8 && abs(rf[0] + rf[64] - 2 * rf[32]) < 8;   // 1 << (bitDepth - 5)
+            strong[g] = s;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < G * RS; i += kThreads) {
+        const int g = i / RS, j = i % RS - 2 * W;
+        const int* rf = ref + g * RS + 2 * W;
+        int v;
+        if (j == -2 * W || j == 2 * W) v = rf[j];
+        else if (W == 32 && strong[g]) v = j == 0 ? rf[0] : j < 0 ? (-j * rf[-64] + (64 + j) * rf[0] + 32) >> 6 : ((64 - j) * rf[0] + j * rf[64] + 32) >> 6;
+        else v = (rf[j - 1] + 2 * rf[j] + rf[j + 1] + 2) >> 2;
+        ref_s[i] = v;
+    }
+}
+
+template <int W, bool PIC, bool SMOOTH>
 __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBestModeParams p)
 {
     constexpr int R = W <= 8 ? W : 4, RG = W / R, G = 64 / RG;    // rows per lane, lanes per block, blocks per workgroup
     constexpr int RS = 4 * W + 1, TS = W * W + 4;                 // LDS strides, those of stage_blocks
+    static_assert(!SMOOTH || W == 8 || W == 16 || W == 32, "no mode smooths at w = 4 and 64");
     __shared__ int ref[G * RS];
+    __shared__ int ref_s[SMOOTH ? G * RS : 1];
+    __shared__ int strong[SMOOTH && W == 32 ? G : 1];
     __shared__ uint8_t tgt[G * TS];
     __shared__ unsigned sse[G * 35];
     __shared__ int dcv[G], best[G];
@@ -186,13 +234,14 @@ __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBest
     for (int i = tid; i < G * 35; i += kThreads) sse[i] = 0;
     __syncthreads();
     stage_dc<W, G>(ref, dcv, tid);
+    if (SMOOTH) stage_smoothed<W, G>(ref, ref_s, strong, p.smoothing == 2, tid);
     __syncthreads();
 
     const int lane = tid & 63, g = lane / RG, rg = lane % RG;
-    const int* rf = ref + g * RS + 2 * W;
     const uint8_t* tg = tgt + g * TS;
     for (int round = 0; round < kRounds; round++) {
         const int mode = __builtin_amdgcn_readfirstlane(round * (kThreads / 64) + tid / 64);
+        const int* rf = (SMOOTH && mode_smooths<W>(mode) ? ref_s : ref) + g * RS + 2 * W;   // the line this mode reads: a scalar select
         unsigned acc = 0;
         if (mode <= 1) {
             const int dc = dcv[g];
@@ -231,7 +280,8 @@ __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBest
         const int gg = i / (W * W), e = i % (W * W);
         if (blk0 + gg >= p.N) break;
         const int m = best[gg];
-        const int v = m < 0 ? 0 : mode_pixel<W>(ref + gg * RS + 2 * W, dcv[gg], m, e / W, e % W);
+        const int* rf = (SMOOTH && mode_smooths<W>(m) ? ref_s : ref) + gg * RS + 2 * W;    // the winner's line
+        const int v = m < 0 ? 0 : mode_pixel<W>(rf, dcv[gg], m, e / W, e % W);
         p.best_pred[blk0 * W * W + i] = (uint8_t)v;
     }
 }
@@ -262,13 +312,16 @@ __device__ __forceinline__ unsigned sub_block_hads(const uint8_t* tg, int by, in
 
 // The SATD twin of hevc_best_mode_kernel (same staging, same forms PIC).  Lane = (block g, sub-block sb) of the workgroup's G =
 // 64 / (w / T)^2 blocks; wave = one mode per round, so the mode is wave-uniform.  cost[g][0 .. 34] the modes, [35] the candidate.
-template <int W, bool PIC>
+template <int W, bool PIC, bool SMOOTH>
 __global__ __launch_bounds__(kThreads) void hevc_mode_hads_kernel(const HevcModeHadsParams p)
 {
+    static_assert(!SMOOTH || W == 8 || W == 16 || W == 32, "no mode smooths at w = 4 and 64");
     constexpr int T = W == 4 ? 4 : 8, SB = W / T, NSB = SB * SB, G = 64 / NSB;   // sub-block side, sub-blocks per side / block, blocks per workgroup
     constexpr int K = W <= 8 ? 8 : 3, NC = 36;                                  // list entries, costs per block
     constexpr int RS = 4 * W + 1, TS = W * W + 4;                               // LDS strides, those of stage_blocks
     __shared__ int ref[G * RS];
+    __shared__ int ref_s[SMOOTH ? G * RS : 1];
+    __shared__ int strong[SMOOTH && W == 32 ? G : 1];
     __shared__ __attribute__((aligned(4))) uint8_t tgt[G * TS];
     __shared__ __attribute__((aligned(4))) uint8_t cnd[G * TS];
     __shared__ unsigned cost[G * NC];
@@ -286,14 +339,15 @@ __global__ __launch_bounds__(kThreads) void hevc_mode_hads_kernel(const HevcMode
     for (int i = tid; i < G * NC; i += kThreads) cost[i] = 0;
     __syncthreads();
     stage_dc<W, G>(ref, dcv, tid);
+    if (SMOOTH) stage_smoothed<W, G>(ref, ref_s, strong, p.smoothing == 2, tid);
     __syncthreads();
 
     const int lane = tid & 63, g = lane / NSB, sb = lane % NSB;
     const int by = sb / SB * T, bx = sb % SB * T;
-    const int* rf = ref + g * RS + 2 * W;
     const uint8_t* tg = tgt + g * TS;
     for (int round = 0; round < kRounds; round++) {
         const int mode = __builtin_amdgcn_readfirstlane(round * (kThreads / 64) + tid / 64);
+        const int* rf = (SMOOTH && mode_smooths<W>(mode) ? ref_s : ref) + g * RS + 2 * W;   // the line this mode reads: a scalar select
         unsigned acc;
         if (mode == 0) {
             acc = sub_block_hads<W, T>(tg, by, bx, [&](int y, int x) { return planar_pixel<W>(rf, y, x); });
@@ -359,14 +413,20 @@ hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s)
     const dim3 grid((unsigned)((p.N + blocks_per_wg - 1) / blocks_per_wg)), block(kThreads);
     const bool pic = p.patterns == nullptr;
     if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
-#define PNN_HEVC_LAUNCH(W_) \
-    case W_: if (pic) hipLaunchKernelGGL((hevc_best_mode_kernel<W_, true>), grid, block, 0, s, p); \
-             else hipLaunchKernelGGL((hevc_best_mode_kernel<W_, false>), grid, block, 0, s, p); \
-             break;
-    switch (p.w) {
-    PNN_HEVC_LAUNCH(4) PNN_HEVC_LAUNCH(8) PNN_HEVC_LAUNCH(16) PNN_HEVC_LAUNCH(32) PNN_HEVC_LAUNCH(64)
+    if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
+#define PNN_HEVC_LAUNCH(W_, SMOOTH_) \
+    if (pic) hipLaunchKernelGGL((hevc_best_mode_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
+    else hipLaunchKernelGGL((hevc_best_mode_kernel<W_, false, SMOOTH_>), grid, block, 0, s, p);
+#define PNN_HEVC_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_HEVC_LAUNCH(W_, true) } else { PNN_HEVC_LAUNCH(W_, false) }
+    switch (p.w) {                                     // at w = 4 and 64 no mode smooths: the one instantiation for every `smoothing`
+    case 4: PNN_HEVC_LAUNCH(4, false) break;
+    case 8: PNN_HEVC_LAUNCH_SMOOTH(8) break;
+    case 16: PNN_HEVC_LAUNCH_SMOOTH(16) break;
+    case 32: PNN_HEVC_LAUNCH_SMOOTH(32) break;
+    case 64: PNN_HEVC_LAUNCH(64, false) break;
     default: return hipErrorInvalidValue;
     }
+#undef PNN_HEVC_LAUNCH_SMOOTH
 #undef PNN_HEVC_LAUNCH
     return hipGetLastError();
 }
@@ -378,14 +438,20 @@ hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s)
     const dim3 grid((unsigned)((p.N + blocks_per_wg - 1) / blocks_per_wg)), block(kThreads);
     const bool pic = p.patterns == nullptr;
     if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
-#define PNN_HADS_LAUNCH(W_) \
-    case W_: if (pic) hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, true>), grid, block, 0, s, p); \
-             else hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, false>), grid, block, 0, s, p); \
-             break;
+    if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
+#define PNN_HADS_LAUNCH(W_, SMOOTH_) \
+    if (pic) hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
+    else hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, false, SMOOTH_>), grid, block, 0, s, p);
+#define PNN_HADS_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_HADS_LAUNCH(W_, true) } else { PNN_HADS_LAUNCH(W_, false) }
     switch (p.w) {
-    PNN_HADS_LAUNCH(4) PNN_HADS_LAUNCH(8) PNN_HADS_LAUNCH(16) PNN_HADS_LAUNCH(32) PNN_HADS_LAUNCH(64)
+    case 4: PNN_HADS_LAUNCH(4, false) break;
+    case 8: PNN_HADS_LAUNCH_SMOOTH(8) break;
+    case 16: PNN_HADS_LAUNCH_SMOOTH(16) break;
+    case 32: PNN_HADS_LAUNCH_SMOOTH(32) break;
+    case 64: PNN_HADS_LAUNCH(64, false) break;
     default: return hipErrorInvalidValue;
     }
+#undef PNN_HADS_LAUNCH_SMOOTH
 #undef PNN_HADS_LAUNCH
     return hipGetLastError();
 }

@@ -268,11 +268,14 @@ struct PictureBlocks {
 // instead: the pattern's first row and column start at (row + w - 1, col + w - 1), ph and pw say how much of them is not masked.
 // The picture form has two planes of equal geometry: the reference samples are read from pic.channels (the context plane -- the
 // decoded picture of a pair), the targets from pic_targets (the original; the same pointer for single pictures).
+// smoothing: HM's reference-sample smoothing (include/pnn_hip.h), 0 none, 1 the [1 2 1] filter, 2 also the strong filter at w = 32; 1
+// and 2 launch the SMOOTH instantiations at w = 8, 16, 32 (no mode smooths at 4 and 64), where "strong allowed" is a runtime branch.
 struct HevcBestModeParams {
     const uint8_t* patterns; int ph; int pw; const uint8_t* targets; int N; int w;
     uint8_t* best_mode; uint32_t* best_sse; uint8_t* best_pred; uint32_t* mode_sse;
     PictureBlocks pic;
-    const uint8_t* pic_targets;   // last, so that the dense form's arguments keep their offsets
+    const uint8_t* pic_targets;   // behind the dense form's arguments, which keep their offsets
+    int smoothing;
 };
 hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s);
 
@@ -285,6 +288,7 @@ struct HevcModeHadsParams {
     const uint8_t* cand_pred; uint32_t* mode_hads; uint32_t* cand_hads; uint8_t* list_modes; uint32_t* list_costs;
     PictureBlocks pic;
     const uint8_t* pic_targets;
+    int smoothing;
 };
 inline int hevc_first_pass_list_size(int w) { return w <= 8 ? 8 : 3; }   // g_aucIntraModeNumFast_UseMPM for w = 4 .. 64
 hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s);

@@ -12,6 +12,9 @@ the pictures) and one download; the same dictionaries as predict_mask_vs_hevc_be
 score_masks_from_picture_pairs is the same loop on [images, H, W, 2] pairs (original, HEVC-decoded) for the pair models.
 Both take first_pass=True for one more column per mask: the PNN and the 35 modes ranked by the Hadamard cost of HM's first intra
 pass (pnn_first_pass_picture_pairs_device: one more call per mask, the same download).
+Every function with an HEVC column takes reference_smoothing (0, 1, 2: intraprediction's `smoothing`): 0, the default, is the reference's
+extracted predictor; 2 makes the HEVC columns and the first-pass ranking those of HM's own predictor, with its reference-sample
+smoothing.  A nonzero value adds the key 'reference_smoothing' to the dictionaries and changes nothing in the PNN's columns.
 """
 import ctypes
 
@@ -74,26 +77,36 @@ def compute_performance_neural_network_vs_hevc_best_mode(targets_uint8, predicti
 
 
 def predict_mask_vs_hevc_best_mode(channels_uint8, width_target, row_1sts, col_1sts, predictor, batch_size, mean_training,
-                                   tuple_width_height_masks=(0, 0)):
+                                   tuple_width_height_masks=(0, 0), reference_smoothing=0):
     """predict_mask plus its competitor, as comparing_pnn_ipfcns_hevc_best_mode.py:162-322 scores them: the intra pattern of
     every target (its first row and column start one pixel above-left of the target, i.e. at (row_1st + w - 1,
     col_1st + w - 1)) predicted by the best HEVC intra mode on the GPU.
 
     Returns the reference's dictionary_performance -- 'indices_hevc_best_mode' [N] uint8, 'psnrs_hevc_best_mode' [N],
     'psnrs_pnn' [N], 'frequency_win_pnn', 'mean_psnr_pnn' -- plus 'predictions_pnn_uint8', 'predictions_hevc_best_mode_uint8'
-    and 'targets_uint8' ([N,w,w,1] uint8), N = images x positions, image-major."""
+    and 'targets_uint8' ([N,w,w,1] uint8), N = images x positions, image-major.  reference_smoothing != 0: the HEVC modes predict with
+    HM's reference-sample smoothing, and the dictionary says so in 'reference_smoothing'."""
+    reference_smoothing = intraprediction._check_smoothing(reference_smoothing)
     pnn = predict_mask(channels_uint8, width_target, row_1sts, col_1sts, predictor, batch_size, mean_training,
                        tuple_width_height_masks)
     intra_patterns_uint8 = intraprediction.extract_intra_patterns(channels_uint8, width_target, row_1sts + width_target - 1,
                                                                   col_1sts + width_target - 1, tuple_width_height_masks)
-    indices, psnrs_hevc, predictions_hevc = intraprediction.predict_series_via_hevc_best_mode(
-        intra_patterns_uint8, pnn['targets_uint8'], device=predictor.device)
+    if reference_smoothing == 0:
+        indices, psnrs_hevc, predictions_hevc = intraprediction.predict_series_via_hevc_best_mode(
+            intra_patterns_uint8, pnn['targets_uint8'], device=predictor.device)
+    else:
+        indices, psnrs_hevc, predictions_hevc = intraprediction.predict_series_via_hevc_best_mode(
+            intra_patterns_uint8, pnn['targets_uint8'], device=predictor.device, smoothing=reference_smoothing)
     psnrs_pnn, frequency_win_pnn = compute_performance_neural_network_vs_hevc_best_mode(
         pnn['targets_uint8'], pnn['predictions_pnn_uint8'], psnrs_hevc)
-    return {'indices_hevc_best_mode': indices, 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
-            'frequency_win_pnn': frequency_win_pnn, 'mean_psnr_pnn': np.mean(psnrs_pnn).item(),
-            'predictions_pnn_uint8': pnn['predictions_pnn_uint8'], 'predictions_hevc_best_mode_uint8': predictions_hevc,
-            'targets_uint8': pnn['targets_uint8']}
+    dictionary_performance = {
+        'indices_hevc_best_mode': indices, 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
+        'frequency_win_pnn': frequency_win_pnn, 'mean_psnr_pnn': np.mean(psnrs_pnn).item(),
+        'predictions_pnn_uint8': pnn['predictions_pnn_uint8'], 'predictions_hevc_best_mode_uint8': predictions_hevc,
+        'targets_uint8': pnn['targets_uint8']}
+    if reference_smoothing:
+        dictionary_performance['reference_smoothing'] = reference_smoothing
+    return dictionary_performance
 
 
 def predict_without_mask_via_ipfcns(channels_uint8, width_target, row_1sts, col_1sts, batch_size, net_ipfcns,
@@ -136,12 +149,12 @@ def _fill_ipfcns_keys(dictionary_performance, sses, width_target, pred_u8):
 
 
 def predict_mask_vs_hevc_best_mode_and_ipfcns(channels_uint8, width_target, row_1sts, col_1sts, predictor, batch_size,
-                                              mean_training, net_ipfcns, tuple_width_height_masks=(0, 0)):
+                                              mean_training, net_ipfcns, tuple_width_height_masks=(0, 0), reference_smoothing=0):
     """The three columns of the paper's table, as comparing_pnn_ipfcns_hevc_best_mode.py:162-322 fills them:
     predict_mask_vs_hevc_best_mode's dictionary plus, when net_ipfcns is given and nothing is masked (masks == (0, 0)), the
-    IPFCN-S keys of predict_without_mask_via_ipfcns."""
+    IPFCN-S keys of predict_without_mask_via_ipfcns.  reference_smoothing: as for predict_mask_vs_hevc_best_mode."""
     dictionary_performance = predict_mask_vs_hevc_best_mode(channels_uint8, width_target, row_1sts, col_1sts, predictor,
-                                                            batch_size, mean_training, tuple_width_height_masks)
+                                                            batch_size, mean_training, tuple_width_height_masks, reference_smoothing)
     if net_ipfcns is not None and tuple(tuple_width_height_masks) == (0, 0):
         predict_without_mask_via_ipfcns(channels_uint8, width_target, row_1sts, col_1sts, batch_size, net_ipfcns,
                                         dictionary_performance)
@@ -166,7 +179,7 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 
 
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
-                              tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False):
+                              tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -186,14 +199,19 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     predictions against the targets), 'first_pass_list' uint8 [N, K] and 'first_pass_costs' uint32 [N, K] (HM's sorted candidate list,
     K = 8 for w <= 8, else 3; ascending cost, the lower index first among equal costs, 35 = the PNN),
     'frequency_pnn_in_first_pass_list' and 'frequency_pnn_first_pass_best' (float: the share of blocks whose list contains 35 / starts
-    with 35).  The costs are those of this evaluator's competitor (no reference-sample smoothing) and leave out HM's
-    modeBits * sqrtLambda term (include/pnn_hip.h).  With first_pass=False nothing changes: not a key, a call or a byte."""
+    with 35).  The costs leave out HM's modeBits * sqrtLambda term (include/pnn_hip.h); whose predictions they cost is
+    reference_smoothing's choice.  With first_pass=False nothing changes: not a key, a call or a byte.
+
+    reference_smoothing (0, 1, 2): HM's reference-sample smoothing in the HEVC modes, of the best-mode search and of the first pass alike
+    (the *_hm entries of include/pnn_hip.h).  0 reproduces the reference's extracted predictor, which has none -- the evaluator's
+    competitor; 2 is HM's default, the predictor the encoders run.  A nonzero value adds the key 'reference_smoothing' (int) to every
+    dictionary and leaves the PNN's and IPFCN-S's keys bit-identical.  With 0 nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
-                        net_ipfcns, keep_predictions, first_pass)
+                        net_ipfcns, keep_predictions, first_pass, reference_smoothing)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
-                                   tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False):
+                                   tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -205,13 +223,14 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
       original (channel 0):    'targets_uint8' and the targets of every SSE, hence of every PSNR
     The pair is de-interleaved once on the host and uploaded once; per mask ONE call and ONE download, as for single pictures.
     first_pass=True: the keys of score_masks_from_pictures; reference samples from the decoded plane, targets of the costs from the
-    original, as in the table above."""
+    original, as in the table above.  reference_smoothing: as for score_masks_from_pictures; the smoothed line is built from the decoded
+    plane's samples, as the unsmoothed one is."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
-                        tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass)
+                        tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing)
 
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                 keep_predictions, first_pass=False):
+                 keep_predictions, first_pass=False, reference_smoothing=0):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer."""
     if ch.dtype != np.uint8:
@@ -234,6 +253,9 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     w = width_target
     if w not in intraprediction.WIDTHS:
         raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    if reference_smoothing not in intraprediction.SMOOTHINGS:
+        raise ValueError('`reference_smoothing` does not belong to {0, 1, 2}.')
+    reference_smoothing = int(reference_smoothing)
     masks = [(int(m[0]), int(m[1])) for m in tuples_width_height_masks]
     rows, cols = row_1sts.astype(np.int64).ravel(), col_1sts.astype(np.int64).ravel()
     n_pos = rows.size
@@ -290,18 +312,24 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         if mask in results:
             continue
         first = i == 0
+        blocks = (predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
+                  d_rows.data_ptr(), d_cols.data_ptr(), n_pos, mask[0], mask[1])
+        scores = (ptr['targets'] if first else None, ptr['predictions_pnn'] if keep_predictions or first_pass else None, None,
+                  ptr['sses_pnn'], ptr['indices_hevc'], ptr['sses_hevc'], ptr['predictions_hevc'] if keep_predictions else None,
+                  ctypes.c_void_p(stream.cuda_stream))
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_score_picture_pairs_device(
-                predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
-                d_rows.data_ptr(), d_cols.data_ptr(), n_pos,
-                mask[0], mask[1], ptr['targets'] if first else None, ptr['predictions_pnn'] if keep_predictions or first_pass else None, None,
-                ptr['sses_pnn'], ptr['indices_hevc'], ptr['sses_hevc'], ptr['predictions_hevc'] if keep_predictions else None,
-                ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
+            if reference_smoothing == 0:
+                _lib.check(L.pnn_score_picture_pairs_device(*(blocks + scores)), predictor.ctx)
+            else:
+                _lib.check(L.pnn_score_picture_pairs_hm_device(*(blocks + (reference_smoothing,) + scores)), predictor.ctx)
             if first_pass:                                # the PNN's uint8 predictions are on the device: candidate 35
-                _lib.check(L.pnn_first_pass_picture_pairs_device(
-                    predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
-                    d_rows.data_ptr(), d_cols.data_ptr(), n_pos, mask[0], mask[1], ptr['predictions_pnn'], ptr['hads_hevc_modes'],
-                    ptr['hads_pnn'], ptr['first_pass_list'], ptr['first_pass_costs'], ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
+                ranking = (ptr['hads_hevc_modes'], ptr['hads_pnn'], ptr['first_pass_list'], ptr['first_pass_costs'],
+                           ctypes.c_void_p(stream.cuda_stream))
+                if reference_smoothing == 0:
+                    _lib.check(L.pnn_first_pass_picture_pairs_device(*(blocks + (ptr['predictions_pnn'],) + ranking)), predictor.ctx)
+                else:
+                    _lib.check(L.pnn_first_pass_picture_pairs_hm_device(
+                        *(blocks + (ptr['predictions_pnn'], reference_smoothing) + ranking)), predictor.ctx)
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
@@ -318,6 +346,8 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
             dictionary_performance['frequency_pnn_in_first_pass_list'] = \
                 float(np.count_nonzero((first_pass_list == nb_modes).any(axis=1))) / n
             dictionary_performance['frequency_pnn_first_pass_best'] = float(np.count_nonzero(first_pass_list[:, 0] == nb_modes)) / n
+        if reference_smoothing:
+            dictionary_performance['reference_smoothing'] = reference_smoothing
         if keep_predictions:
             if first:
                 targets_uint8 = view['targets'].copy()

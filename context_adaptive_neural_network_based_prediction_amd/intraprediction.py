@@ -8,6 +8,10 @@ on the GPU (pnn_hevc_best_mode_device: all 35 modes, their SSEs and the winner o
 model-less context per device; there is no CPU fallback.  PSNRs are recomputed on the host from the integer SSEs with
 the reference's float64 expression: SSE / w^2 is exactly numpy.mean of the squared differences, so they match the
 reference bit for bit.
+
+HM's reference-sample smoothing, which the reference's extracted predictor left out, is the option `smoothing` of every predictor
+here (include/pnn_hip.h): 0 (the default) reproduces the reference's predictor, 1 is HM with StrongIntraSmoothing 0, 2 is HM's
+default.  mode_uses_smoothing and smoothed_reference show the decision table and the filtered line.
 """
 import ctypes
 
@@ -84,8 +88,47 @@ def extract_intra_patterns(channels_uint8, width_target, row_refs, col_refs, tup
     return out.reshape(intra_patterns_uint8.shape)
 
 
-def predict_via_hevc_mode(intra_pattern_uint8, width_target, index_mode):
-    """interface.pyx:15-64: the [w, w, 1] uint8 prediction of mode `index_mode` from a [h, w', 1] intra pattern (host twin)."""
+SMOOTHINGS = (0, 1, 2)                          # none, HM's [1 2 1] filter, HM's default (the strong filter allowed at w = 32)
+
+
+def _check_smoothing(smoothing):
+    if smoothing not in SMOOTHINGS:
+        raise ValueError('`smoothing` does not belong to {0, 1, 2}.')
+    return int(smoothing)
+
+
+def mode_uses_smoothing(width_target, index_mode):
+    """HM's decision table (TComPrediction.cpp:39-55): does mode `index_mode` read smoothed reference samples at this width?"""
+    rc = _lib.lib().pnn_hevc_mode_uses_smoothing(int(width_target), int(index_mode))
+    if rc < 0:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64} or `index_mode` not to [0, 34].')
+    return bool(rc)
+
+
+def smoothed_reference(intra_pattern_uint8, width_target, smoothing):
+    """(line uint8 [4w + 1], strong_used bool): the reference samples of a [h, w'] or [h, w', 1] intra pattern, padded and then smoothed
+    as `smoothing` says; index 2w is the corner, the left column runs below it (towards index 0), the above row above it."""
+    if not isinstance(intra_pattern_uint8, np.ndarray) or intra_pattern_uint8.dtype != np.uint8:
+        raise TypeError('`intra_pattern_uint8` is not a `numpy.ndarray` of dtype `numpy.uint8`.')
+    pattern = intra_pattern_uint8[..., 0] if intra_pattern_uint8.ndim == 3 else intra_pattern_uint8
+    if pattern.ndim != 2:
+        raise ValueError('`intra_pattern_uint8` has neither 2 nor 3 dimensions.')
+    pattern = np.ascontiguousarray(pattern)
+    if width_target not in WIDTHS:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    line = np.zeros(4 * width_target + 1, np.uint8)
+    strong = ctypes.c_int(0)
+    rc = _lib.lib().pnn_hevc_smoothed_reference_host(pattern.ctypes.data, pattern.shape[0], pattern.shape[1], width_target,
+                                                     _check_smoothing(smoothing), line.ctypes.data, ctypes.byref(strong))
+    if rc != 0:
+        raise ValueError('pnn_hevc_smoothed_reference_host refused the arguments (pattern %dx%d, width %d).'
+                         % (pattern.shape[0], pattern.shape[1], width_target))
+    return line, bool(strong.value)
+
+
+def predict_via_hevc_mode(intra_pattern_uint8, width_target, index_mode, smoothing=0):
+    """interface.pyx:15-64: the [w, w, 1] uint8 prediction of mode `index_mode` from a [h, w', 1] intra pattern (host twin).
+    smoothing: 0 the reference's predictor, 1 / 2 HM's reference-sample smoothing (pnn_hevc_intra_predict_hm)."""
     if not isinstance(intra_pattern_uint8, np.ndarray):
         raise TypeError('Argument \'intra_pattern_uint8\' has incorrect type (expected numpy.ndarray)')
     if intra_pattern_uint8.ndim != 3:
@@ -99,9 +142,14 @@ def predict_via_hevc_mode(intra_pattern_uint8, width_target, index_mode):
     if intra_pattern_uint8.shape[2] != 1:
         raise ValueError('`intra_pattern_uint8.shape[2]` is not equal to 1.')
     prediction_uint8 = np.zeros((width_target, width_target, 1), dtype=np.uint8)
-    rc = _lib.lib().pnn_hevc_intra_predict(intra_pattern_uint8.ctypes.data_as(_lib.u8p), intra_pattern_uint8.shape[0],
-                                           intra_pattern_uint8.shape[1], width_target, int(index_mode),
-                                           prediction_uint8.ctypes.data_as(_lib.u8p))
+    if smoothing == 0:
+        rc = _lib.lib().pnn_hevc_intra_predict(intra_pattern_uint8.ctypes.data_as(_lib.u8p), intra_pattern_uint8.shape[0],
+                                               intra_pattern_uint8.shape[1], width_target, int(index_mode),
+                                               prediction_uint8.ctypes.data_as(_lib.u8p))
+    else:
+        rc = _lib.lib().pnn_hevc_intra_predict_hm(intra_pattern_uint8.ctypes.data_as(_lib.u8p), intra_pattern_uint8.shape[0],
+                                                  intra_pattern_uint8.shape[1], width_target, int(index_mode), _check_smoothing(smoothing),
+                                                  prediction_uint8.ctypes.data_as(_lib.u8p))
     if rc != 0:
         raise ValueError('hevc_intraprediction refused the arguments (pattern %dx%d, width %d, mode %d).'
                          % (intra_pattern_uint8.shape[0], intra_pattern_uint8.shape[1], width_target, index_mode))
@@ -124,11 +172,13 @@ def _context(device):
     return _contexts[device]
 
 
-def best_modes_device(intra_patterns, targets, width_target, best_pred=True, mode_sse=False, device=0):
-    """The GPU search on torch uint8 tensors already on `device`: patterns [n, h, w'] and targets [n, w, w].
+def best_modes_device(intra_patterns, targets, width_target, best_pred=True, mode_sse=False, device=0, smoothing=0):
+    """The GPU search on torch uint8 tensors already on `device`: patterns [n, h, w'] and targets [n, w, w]; smoothing != 0: over HM's
+    smoothed predictions (pnn_hevc_best_mode_hm_device).
     Returns (best index uint8 [n], best SSE int32 [n], best prediction uint8 [n, w, w] or None, SSE of every mode int32 [n, 35]
     or None), torch tensors on `device`, after the stream has finished."""
     import torch
+    smoothing = _check_smoothing(smoothing)
     n = targets.shape[0]
     dev = torch.device("cuda", device)
     index = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -137,12 +187,14 @@ def best_modes_device(intra_patterns, targets, width_target, best_pred=True, mod
     all_sse = torch.empty((n, NB_MODES), dtype=torch.int32, device=dev) if mode_sse else None
     stream = torch.cuda.current_stream(dev)
     L = _lib.lib()
+    inputs = (_context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1], intra_patterns.shape[2], targets.data_ptr(), n)
+    outputs = (index.data_ptr(), sse.data_ptr(), pred.data_ptr() if best_pred else None, all_sse.data_ptr() if mode_sse else None,
+               ctypes.c_void_p(stream.cuda_stream))
     with torch.cuda.device(dev):
-        _lib.check(L.pnn_hevc_best_mode_device(_context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1],
-                                               intra_patterns.shape[2], targets.data_ptr(), n, index.data_ptr(), sse.data_ptr(),
-                                               pred.data_ptr() if best_pred else None,
-                                               all_sse.data_ptr() if mode_sse else None,
-                                               ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        if smoothing == 0:
+            _lib.check(L.pnn_hevc_best_mode_device(*(inputs + outputs)), _context(device))
+        else:
+            _lib.check(L.pnn_hevc_best_mode_hm_device(*(inputs + (smoothing,) + outputs)), _context(device))
     stream.synchronize()
     return index, sse, pred, all_sse
 
@@ -171,13 +223,15 @@ def _check_mode_hads_arguments(intra_patterns, targets, width_target, candidate_
     return n
 
 
-def mode_hads_device(intra_patterns, targets, width_target, candidate_predictions=None, device=0):
+def mode_hads_device(intra_patterns, targets, width_target, candidate_predictions=None, device=0, smoothing=0):
     """HM's first intra pass on the GPU (pnn_hevc_mode_hads_device) on torch uint8 tensors already on `device`: patterns [n, h, w'],
     targets [n, w, w], candidate_predictions None or [n, w, w] (the PNN's uint8 predictions, candidate 35).  One launch.
     Returns numpy arrays {'hads_modes': uint32 [n, 35], 'hads_candidate': uint32 [n] or None, 'list_modes': uint8 [n, K],
     'list_costs': uint32 [n, K]}, K = first_pass_list_size(width_target); the list is in ascending cost, the lower index first among
-    equal costs.  Costs: TComRdCost::xGetHADs of this competitor's predictions (no reference smoothing), without HM's mode-bit term."""
+    equal costs.  Costs: TComRdCost::xGetHADs of the predictions `smoothing` selects (0: the reference's predictor, no reference smoothing;
+    2: HM's; pnn_hevc_mode_hads_hm_device), without HM's mode-bit term."""
     import torch
+    smoothing = _check_smoothing(smoothing)
     n = _check_mode_hads_arguments(intra_patterns, targets, width_target, candidate_predictions)
     k = first_pass_list_size(width_target)
     dev = torch.device("cuda", device)
@@ -189,20 +243,24 @@ def mode_hads_device(intra_patterns, targets, width_target, candidate_prediction
     modes = torch.empty((n, k), dtype=torch.uint8, device=dev)
     costs = torch.empty((n, k), dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev)
+    inputs = (_context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1], intra_patterns.shape[2],
+              targets.data_ptr(), n, None if candidate_predictions is None else candidate_predictions.data_ptr())
+    outputs = (hads.data_ptr(), None if cand is None else cand.data_ptr(), modes.data_ptr(), costs.data_ptr(),
+               ctypes.c_void_p(stream.cuda_stream))
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().pnn_hevc_mode_hads_device(
-            _context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1], intra_patterns.shape[2],
-            targets.data_ptr(), n, None if candidate_predictions is None else candidate_predictions.data_ptr(), hads.data_ptr(),
-            None if cand is None else cand.data_ptr(), modes.data_ptr(), costs.data_ptr(),
-            ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        if smoothing == 0:
+            _lib.check(_lib.lib().pnn_hevc_mode_hads_device(*(inputs + outputs)), _context(device))
+        else:
+            _lib.check(_lib.lib().pnn_hevc_mode_hads_hm_device(*(inputs + (smoothing,) + outputs)), _context(device))
     stream.synchronize()
     return {'hads_modes': hads.cpu().numpy().view(np.uint32), 'hads_candidate': None if cand is None else cand.cpu().numpy().view(np.uint32),
             'list_modes': modes.cpu().numpy(), 'list_costs': costs.cpu().numpy().view(np.uint32)}
 
 
-def mode_hads_host(intra_patterns, targets, width_target, candidate_predictions=None):
-    """mode_hads_device's host twin (pnn_hevc_mode_hads_host, pure host code) on numpy uint8 arrays: same arguments, same dictionary,
-    same bits."""
+def mode_hads_host(intra_patterns, targets, width_target, candidate_predictions=None, smoothing=0):
+    """mode_hads_device's host twin (pnn_hevc_mode_hads_host, pnn_hevc_mode_hads_hm_host when smoothing != 0; pure host code) on numpy
+    uint8 arrays: same arguments, same dictionary, same bits."""
+    smoothing = _check_smoothing(smoothing)
     arrays = [intra_patterns, targets] + ([] if candidate_predictions is None else [candidate_predictions])
     if any(not isinstance(a, np.ndarray) or a.dtype != np.uint8 for a in arrays):
         raise TypeError('the arrays must be `numpy.ndarray`s of dtype `numpy.uint8`.')
@@ -213,19 +271,25 @@ def mode_hads_host(intra_patterns, targets, width_target, candidate_predictions=
     hads = np.zeros((n, NB_MODES), np.uint32)
     cand = None if candidate is None else np.zeros(n, np.uint32)
     modes, costs = np.zeros((n, k), np.uint8), np.zeros((n, k), np.uint32)
-    rc = _lib.lib().pnn_hevc_mode_hads_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, width_target, n,
-                                            None if candidate is None else candidate.ctypes.data, hads.ctypes.data,
-                                            None if cand is None else cand.ctypes.data, modes.ctypes.data, costs.ctypes.data)
+    inputs = (patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, width_target, n,
+              None if candidate is None else candidate.ctypes.data)
+    outputs = (hads.ctypes.data, None if cand is None else cand.ctypes.data, modes.ctypes.data, costs.ctypes.data)
+    if smoothing == 0:
+        rc = _lib.lib().pnn_hevc_mode_hads_host(*(inputs + outputs))
+    else:
+        rc = _lib.lib().pnn_hevc_mode_hads_hm_host(*(inputs + (smoothing,) + outputs))
     if rc != 0:
         raise ValueError('pnn_hevc_mode_hads_host refused the arguments (patterns %dx%d, width %d).'
                          % (patterns.shape[1], patterns.shape[2], width_target))
     return {'hads_modes': hads, 'hads_candidate': cand, 'list_modes': modes, 'list_costs': costs}
 
 
-def predict_series_via_hevc_best_mode(intra_patterns_uint8, targets_uint8, device=0):
+def predict_series_via_hevc_best_mode(intra_patterns_uint8, targets_uint8, device=0, smoothing=0):
     """intraprediction.py:183-229 on the GPU: (indices uint8 [N], PSNRs float64 [N], predictions uint8 [N, w, w, 1]) of the
-    best HEVC intra mode per target (smallest SSE, lowest index among ties; index 0, 0 dB and zeros when no mode beats 0 dB)."""
+    best HEVC intra mode per target (smallest SSE, lowest index among ties; index 0, 0 dB and zeros when no mode beats 0 dB).
+    smoothing != 0: the modes predict with HM's reference-sample smoothing."""
     import torch
+    smoothing = _check_smoothing(smoothing)
     if targets_uint8.dtype != np.uint8:
         raise TypeError('`array_0_uint8.dtype` is not equal to `numpy.uint8`.')
     if targets_uint8.ndim != 4 or targets_uint8.shape[3] != 1:
@@ -248,7 +312,7 @@ def predict_series_via_hevc_best_mode(intra_patterns_uint8, targets_uint8, devic
     dev = torch.device("cuda", device)
     d_patterns = torch.from_numpy(np.ascontiguousarray(intra_patterns_uint8[:nb_targets, :, :, 0])).to(dev)
     d_targets = torch.from_numpy(np.ascontiguousarray(targets_uint8[:, :, :, 0])).to(dev)
-    index, sse, pred, _ = best_modes_device(d_patterns, d_targets, width_target, device=device)
+    index, sse, pred, _ = best_modes_device(d_patterns, d_targets, width_target, device=device, smoothing=smoothing)
     indices = index.cpu().numpy()
     sses = sse.cpu().numpy().view(np.uint32)
     psnrs = psnrs_from_sses(sses, width_target)
@@ -256,11 +320,11 @@ def predict_series_via_hevc_best_mode(intra_patterns_uint8, targets_uint8, devic
     return (indices, psnrs, pred.cpu().numpy()[..., None])
 
 
-def predict_via_hevc_best_mode(intra_pattern_uint8, target_uint8, device=0):
+def predict_via_hevc_best_mode(intra_pattern_uint8, target_uint8, device=0, smoothing=0):
     """intraprediction.py:231-294 on the GPU: (index int, PSNR numpy.float64, prediction uint8 [w, w, 1])."""
     if target_uint8.dtype != np.uint8:
         raise TypeError('`array_0_uint8.dtype` is not equal to `numpy.uint8`.')
     if target_uint8.ndim != 3 or intra_pattern_uint8.ndim != 3:
         raise ValueError('Buffer has wrong number of dimensions (expected 3)')
-    indices, psnrs, predictions = predict_series_via_hevc_best_mode(intra_pattern_uint8[None], target_uint8[None], device)
+    indices, psnrs, predictions = predict_series_via_hevc_best_mode(intra_pattern_uint8[None], target_uint8[None], device, smoothing)
     return (int(indices[0]), psnrs[0], predictions[0])

@@ -255,10 +255,37 @@ int pnn_predict_tbs_cost_device(pnn_ctx* ctx, int width, const void* d_plane, co
  * interface.pyx:15-64): the prediction [width][width] of HEVC intra mode `mode` (0 planar, 1 DC, 2..34 angular; 8-bit luma)
  * from a dense uint8 intra pattern [pattern_h][pattern_w] of which only the first row (corner, above, above-right) and the
  * first column (corner, left, below-left) are read; a shorter row / column is padded with its last sample.  No reference
- * sample smoothing (the reference did not extract it); DC filtering and the mode 10 / 26 edge filter for width <= 16.
+ * sample smoothing (the reference did not extract it; pnn_hevc_intra_predict_hm below has it as an option); DC filtering and the
+ * mode 10 / 26 edge filter for width <= 16.
  * Returns -1 + a line on stderr where the reference throws: NULL pointers, mode > 34, a side of the pattern outside
  * [width + 1, 2 width + 1]; also for a width other than 4, 8, 16, 32, 64 and for mode < 0.  Pure host code. */
 int pnn_hevc_intra_predict(const uint8_t* intra_pattern, int pattern_h, int pattern_w, int width, int mode, uint8_t* out);
+
+/* HM's reference-sample smoothing (filteringIntraReferenceSamples, TComPattern.cpp:410-478 and :721-746; the decision table
+ * TComPrediction.cpp:39-55; called at TEncSearch.cpp:2402-2422), the option `smoothing` of every *_hm entry of this header:
+ *   0  none: the reference's extracted predictor.  Every entry without the suffix is its *_hm sibling called with 0, same bits.
+ *   1  HM with StrongIntraSmoothing 0: the [1 2 1] filter alone.
+ *   2  HM's default (StrongIntraSmoothing 1): the strong filter where it applies, the [1 2 1] filter elsewhere.
+ * Which modes read smoothed samples: mode != 1 and min(|mode - 10|, |mode - 26|) > thr, thr = 10, 7, 1, 0, 10 for width 4 .. 64 --
+ * none at width 4 and 64, {0, 2, 18, 34} at 8, all but {1, 9, 10, 11, 25, 26, 27} at 16, all but {1, 10, 26} at 32.  DC and the modes
+ * 10 / 26 never do, so the DC filter and the edge filter always read unsmoothed samples.
+ * The smoothed line: the 4 width + 1 samples AFTER the padding rule above (HM substitutes first and filters afterwards), rf[j] for j
+ * in [-2 width, 2 width] with the corner at 0, the left column below it and the above row to the right.  rf[+-2 width] are copied;
+ * every other sample becomes (rf[j - 1] + 2 rf[j] + rf[j + 1] + 2) >> 2.  Strong filter: only width 32, only smoothing 2, only when
+ * |rf[-64] + rf[0] - 2 rf[-32]| < 8 and |rf[0] + rf[64] - 2 rf[32]| < 8 (8 = 1 << (bitDepth - 5)); then the corner and both ends are
+ * copied, rf[-64 + i] = ((64 - i) rf[-64] + i rf[0] + 32) >> 6 and rf[i] = ((64 - i) rf[0] + i rf[64] + 32) >> 6 for i = 1 .. 63.
+ * 8-bit luma, integers only.  PNN_E_ARG for a smoothing outside {0, 1, 2}.
+ *
+ * 1 if `mode` (0 .. 34) reads smoothed samples at `width`, else 0; PNN_E_ARG + a line on stderr for another width or mode. */
+int pnn_hevc_mode_uses_smoothing(int width, int mode);
+/* The line itself, so that it can be looked at: line[2 width + j] = rf[j] of `pattern` (as for pnn_hevc_intra_predict), padded and then
+ * smoothed as `smoothing` says (0, or a width of 4 or 64: the padded line); *strong_used (may be NULL) = 1 if the strong filter was
+ * applied.  PNN_E_ARG + a line on stderr for NULL pointers, a bad width, pattern side or smoothing.  Pure host code. */
+int pnn_hevc_smoothed_reference_host(const uint8_t* pattern, int pattern_h, int pattern_w, int width, int smoothing, uint8_t* line,
+                                     int* strong_used);
+/* pnn_hevc_intra_predict with `mode` reading the smoothed line where the table says so.  Same refusals, and a bad smoothing. */
+int pnn_hevc_intra_predict_hm(const uint8_t* intra_pattern, int pattern_h, int pattern_w, int width, int mode, int smoothing,
+                              uint8_t* out);
 
 /* == predict_via_hevc_best_mode (hevc/intraprediction/intraprediction.py:231-294) for n blocks at once, on the GPU.
  * Inputs: dense patterns [n][pattern_h][pattern_w] (as above) and targets [n][width][width], uint8.  For each block all 35
@@ -270,6 +297,11 @@ int pnn_hevc_intra_predict(const uint8_t* intra_pattern, int pattern_h, int patt
 int pnn_hevc_best_mode_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
                               const uint8_t* d_targets, int n, uint8_t* d_best_mode, uint32_t* d_best_sse,
                               uint8_t* d_best_pred, uint32_t* d_mode_sse, void* stream);
+/* The same search over the predictions of pnn_hevc_intra_predict_hm(.., smoothing, ..); d_best_pred is that function's prediction of
+ * d_best_mode.  PNN_E_ARG for a smoothing outside {0, 1, 2}, before any launch. */
+int pnn_hevc_best_mode_hm_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
+                                 const uint8_t* d_targets, int n, int smoothing, uint8_t* d_best_mode, uint32_t* d_best_sse,
+                                 uint8_t* d_best_pred, uint32_t* d_mode_sse, void* stream);
 
 /* ---- IPFCN-S: the evaluator's second competitor ------------------------------------------------------ */
 
@@ -346,6 +378,12 @@ int pnn_score_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_con
                                    int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
                                    int mask_w, int mask_h, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
                                    uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream);
+/* The same with the HEVC search of pnn_hevc_best_mode_hm_device: `smoothing` as above, the smoothed line built from the padded samples
+ * of the CONTEXT plane, as the unsmoothed one is.  The PNN outputs and d_targets do not depend on it. */
+int pnn_score_picture_pairs_hm_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                      int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                      int mask_w, int mask_h, int smoothing, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32,
+                                      uint32_t* d_pnn_sse, uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream);
 /* The epilogue alone, on any predictor's floats: d_pred_f32 [n][width][width] (mean-subtracted) -> d_pred_u8 = rint(clip(fl32(pred
  * + pnn_mean(ctx)), 0, 255)), half to even, and d_sse [n] against the targets in the pictures (either may be NULL, not both).
  * Same geometry, same checks and the same read-back of d_rows / d_cols as above.  The result for a non-finite prediction is
@@ -359,8 +397,9 @@ int pnn_score_f32_device(pnn_ctx* ctx, int width, const float* d_pred_f32, const
 /* The SATD twin of pnn_hevc_best_mode_device: where does a candidate prediction (the PNN's) rank among the 35 modes in the metric HM's
  * first intra pass selects by (TEncSearch.cpp:2376-2492)?
  *   Predictions.  The 35 predictions of pnn_hevc_intra_predict, from the same intra patterns.  HM also smooths the reference samples
- *     for some modes and sizes (filteringIntraReferenceSamples); the reference's extracted predictor, hence this library's competitor,
- *     does not.  THE COSTS ARE THEREFORE THOSE OF THE EVALUATOR'S COMPETITOR, not of HM's filtered predictor.
+ *     for some modes and sizes (filteringIntraReferenceSamples); the reference's extracted predictor does not.  SMOOTHING IS AN OPTION
+ *     of the *_hm entries below (see pnn_hevc_mode_uses_smoothing): 0, and every entry without the suffix, reproduces the reference's
+ *     extracted predictor, so its costs are those of the evaluator's competitor; 2 gives the costs of HM's own filtered predictor.
  *   Cost of one prediction.  TComRdCost::xGetHADs for 8-bit video (TComRdCost.cpp:1753-1824) against the width x width target: the
  *     Walsh-Hadamard transform of target - prediction per T x T sub-block, T = 8 (4 at width 4); per sub-block the sum s of the
  *     absolute coefficients, rounded (s + 2) >> 2 for T = 8 and (s + 1) >> 1 for T = 4; the (width / T)^2 sub-block sums added.
@@ -381,11 +420,20 @@ int pnn_first_pass_list_size(int width);
 int pnn_hevc_mode_hads_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
                             const uint8_t* cand_pred, uint32_t* mode_hads, uint32_t* cand_hads, uint8_t* list_modes,
                             uint32_t* list_costs);
+/* The same over the predictions of pnn_hevc_intra_predict_hm(.., smoothing, ..); in addition PNN_E_ARG (+ a line on stderr) for a
+ * smoothing outside {0, 1, 2}. */
+int pnn_hevc_mode_hads_hm_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                               const uint8_t* cand_pred, int smoothing, uint32_t* mode_hads, uint32_t* cand_hads, uint8_t* list_modes,
+                               uint32_t* list_costs);
 /* The same on the GPU, all 35 modes x cost, the candidate and the list of n blocks in one launch; device pointers, asynchronous on
  * `stream`, every argument error reported before the launch.  A context without models (pnn_create_empty) suffices. */
 int pnn_hevc_mode_hads_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
                               const uint8_t* d_targets, int n, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads,
                               uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream);
+/* pnn_hevc_mode_hads_hm_host on the GPU: bit-identical to it.  PNN_E_ARG for a smoothing outside {0, 1, 2}, before any launch. */
+int pnn_hevc_mode_hads_hm_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w,
+                                 const uint8_t* d_targets, int n, const uint8_t* d_cand_pred, int smoothing, uint32_t* d_mode_hads,
+                                 uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream);
 /* The same from the evaluator's pictures: geometry, block order (n = images * positions, image-major), masks and checks of
  * pnn_score_picture_pairs_device.  The reference samples (the intra pattern at (row + width - 1, col + width - 1), ending where the
  * mask says) come from the CONTEXT (decoded) plane, the targets from the TARGET (original) plane; d_cand_pred [n][width][width] is
@@ -397,6 +445,12 @@ int pnn_first_pass_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* 
                                         int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols,
                                         int positions, int mask_w, int mask_h, const uint8_t* d_cand_pred, uint32_t* d_mode_hads,
                                         uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream);
+/* The same with `smoothing`: the smoothed line from the padded samples of the CONTEXT plane. */
+int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols,
+                                           int positions, int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing,
+                                           uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs,
+                                           void* stream);
 
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
