@@ -93,6 +93,9 @@ SIGNATURES = {
     "pnn_score_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "pnn_score_picture_pairs_hm_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
     "pnn_score_f32_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
+    "pnn_trquant_host": (ci, [vp, vp, ci, ci, ctypes.POINTER(ci), ci, vp, vp, vp, vp]),
+    "pnn_trquant_stages_host": (ci, [vp, vp, ci, ci, vp, vp, vp, vp]),
+    "pnn_trquant_device": (ci, [vp, ci, vp, vp, ci, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

@@ -5,7 +5,7 @@
 //   pnn_passes.cpp  the launch sequences of one pass of the fully-connected / convolutional nets
 //   pnn_diag.cpp    the diagnostic switches of the environment and the stamp read-backs of the diagnostic library
 //   pnn_abi.cpp     contexts, staging, the prediction cache and the extern "C" entry points of the predictor
-//   pnn_eval.cpp    the extern "C" entry points of the Python evaluator (HEVC modes, IPFCN-S, scores from pictures)
+//   pnn_eval.cpp    the extern "C" entry points of the Python evaluator (HEVC modes, IPFCN-S, scores from pictures, transform coding)
 #pragma once
 #include "../../include/pnn_hip.h"
 #include "pnn_kernels.h"

@@ -1,6 +1,7 @@
 // The C-ABI entries of the Python evaluator (include/pnn_hip.h; HM calls none of them): the best HEVC intra mode and the first-pass
 // Hadamard ranking on dense patterns (each with its *_hm sibling: HM's reference-sample smoothing as an option; the entry without the
-// suffix is the sibling called with 0), IPFCN-S, the scores from pictures and pairs of pictures.  Contexts, models, staging and the
+// suffix is the sibling called with 0), IPFCN-S, the scores from pictures and pairs of pictures, the open-loop transform
+// coding of predictions.  Contexts, models, staging and the
 // predictor's entries: pnn_abi.cpp.  Each argument check is written once and composed per entry; an entry's ORDER of checks is part of
 // its behaviour (which of two bad arguments pnn_last_error names), so it is spelled out in the entry.
 #include "pnn_ctx.h"
@@ -120,6 +121,15 @@ HevcModeHadsParams mode_hads_params(const uint8_t* patterns, int ph, int pw, con
     set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
     p.cand_pred = cand_pred; p.mode_hads = mode_hads; p.cand_hads = cand_hads; p.list_modes = list_modes; p.list_costs = list_costs;
     return p;
+}
+
+// transform coding, everything in front of the launch: width, batch, QPs, outputs
+int check_trquant(pnn_ctx* c, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const int* qps, int nb_qps, bool any_output)
+{
+    if (const int rc = check_width(c, width)) return rc;
+    if (n < 0 || (n > 0 && (!d_predictions || !d_targets))) return fail(c, PNN_E_ARG, "bad batch size or input buffers");
+    if (!trquant::qps_ok(qps, nb_qps)) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d integers in [0, %d]", trquant::kMaxQps, trquant::kMaxQp);
+    return check_some_output(c, any_output);
 }
 
 Model* ipfcns_for(pnn_ctx* c, int width, int* rc)
@@ -373,6 +383,24 @@ int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t*
     const HevcModeHadsParams p = mode_hads_params(nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n,
                                                   width, smoothing, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs);
     HIPCHK(c, launch_hevc_mode_hads(p, s));
+    c->stat_launches++;
+    return PNN_OK;
+}
+
+int pnn_trquant_device(pnn_ctx* c, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const int* qps, int nb_qps,
+                       uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels, uint8_t* d_recon, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (const int rc = check_trquant(c, width, d_predictions, d_targets, n, qps, nb_qps,
+                                     d_sses_recon || d_nb_nonzero || d_sum_abs_levels || d_recon)) return rc;
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    TrQuantParams p;
+    p.pred = d_predictions; p.targets = d_targets; p.N = n; p.w = width; p.nb_qps = nb_qps;
+    for (int i = 0; i < trquant::kMaxQps; i++) p.qp[i] = trquant::qp_consts(trquant::log2_tu(width), qps[i < nb_qps ? i : 0]);
+    p.sse = d_sses_recon; p.nonzero = d_nb_nonzero; p.sum_abs = d_sum_abs_levels; p.recon = d_recon;
+    reset_stats(c);
+    HIPCHK(c, launch_trquant(p, (hipStream_t)stream));
     c->stat_launches++;
     return PNN_OK;
 }

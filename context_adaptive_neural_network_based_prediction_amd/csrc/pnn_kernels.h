@@ -5,6 +5,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "pnn_trquant_tables.h"
+
 namespace pnn {
 
 // see signal_done, pnn_device_common.h.  per_wg = 1 (round 6, fc_out_f32_chain_kernel): workgroup g raises host_flag[g] by itself -- no
@@ -292,6 +294,16 @@ struct HevcModeHadsParams {
 };
 inline int hevc_first_pass_list_size(int w) { return w <= 8 ? 8 : 3; }   // g_aucIntraModeNumFast_UseMPM for w = 4 .. 64
 hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s);
+
+// Open-loop transform coding (pnn_trquant.hip): N predictions and targets [N][w][w] uint8, nb_qps <= 8 QPs whose constants the host has
+// worked out (trquant::qp_consts at the unit size of w).  Outputs, each NULL or [nb_qps][N] uint32: the SSE of the reconstruction, the
+// number of nonzero levels, the sum of the quantised magnitudes; recon NULL or uint8 [nb_qps][N][w][w].
+struct TrQuantParams {
+    const uint8_t* pred; const uint8_t* targets; int N; int w; int nb_qps; trquant::QpConsts qp[trquant::kMaxQps];
+    uint32_t* sse; uint32_t* nonzero; uint32_t* sum_abs; uint8_t* recon;
+};
+int trquant_blocks_per_workgroup(int w);
+hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s);
 
 // IPFCN-S, the evaluator's second competitor (pnn_ipfcns.hip).  Blocks b0 .. b0 + nb - 1 of images x positions (image-major): the
 // two groups of 8 reference lines at line origin (rows[pos], cols[pos]) of uint8 picture `img` [H][W] -- rows [r, r + 8) x columns

@@ -1,0 +1,195 @@
+// Open-loop HEVC transform coding of predicted blocks (include/pnn_hip.h, "transform coding"): for N predictions
+// and targets [N][w][w] uint8 and up to 8 QPs, HM's residual path with RDOQ 0 -- forward core transform, quantisation, dequantisation,
+// inverse transform, reconstruction -- and per (QP, block) the number of nonzero levels, the sum of their magnitudes and the SSE of the
+// reconstruction.  Integer VALU arithmetic only, plain matrix products (HM's butterflies factorise the same integers); bit-exact against
+// the host twin (pnn_trquant.cpp), with which it shares every constant (pnn_trquant_tables.h).
+//
+// Layout.  A workgroup of 4 waves owns kElems = 1024 residual samples at a time: G = 1024 / T^2 whole blocks (64, 16, 4, 1 for T = 4, 8,
+// 16, 32) or, at w = 64, the four 32 x 32 quadrants of ONE block one after the other, whose counts add into that block's slot.  Sample e
+// = 256 j + tid (j = 0 .. 3) belongs to lane tid: unit e / T^2, row (e / T) % T, column e % T -- the four samples of a lane share their
+// column.  Every stage is "one output element per (lane, j), a T-long dot product of an LDS row or column with a matrix row or
+// column", int32 in LDS:
+//   forward 1   Y[y][k] = sum_x X[y][x] M[k][x]     X: one address per T lanes (broadcast); M: stride T + 1 across lanes
+//   forward 2   C[l][k] = sum_y Y[y][k] M[l][y]     Y: consecutive lanes, consecutive words;  M: broadcast
+//   inverse 1   Z[y][k] = sum_l M[l][y] C'[l][k]    M: broadcast; C': consecutive
+//   inverse 2   R[y][x] = sum_k M[k][x] Z[y][k]     M: consecutive; Z: broadcast
+// so the only strided access is M's in the first stage, and the matrix's LDS copy has the odd row stride T + 1 for it; the data arrays
+// are dense (units of T^2 words side by side: lanes of one wave never meet in a bank on another word).  The forward transform of a unit
+// is computed once and stays in LDS; the chain quantise -> dequantise -> inverse -> reconstruct -> reduce runs per QP, two barriers
+// each.  The three sums go by wave shuffles over the lanes of one unit (64, or 16 at T = 4), then one LDS add per unit and wave.  The QP's
+// constants come ready in the argument block (qp_consts on the host).  Blocks past N in the last workgroup carry a zero residual and are
+// never stored.
+#include "pnn_kernels.h"
+#include "pnn_trquant_tables.h"
+
+namespace pnn {
+namespace {
+
+constexpr int kTqThreads = 256;
+constexpr int kElems = 1024;                      // residual samples a workgroup holds: one 32 x 32 unit, or G smaller blocks
+constexpr int kPerLane = kElems / kTqThreads;
+
+template <int W>
+__global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams p)
+{
+    using namespace trquant;
+    constexpr int T = W < 32 ? W : 32, L = W == 4 ? 2 : W == 8 ? 3 : W == 16 ? 4 : 5, TT = T * T;
+    constexpr int U = W / T, NQ = U * U;          // units per block side; units a workgroup walks one after the other
+    constexpr int G = kElems / TT;                // units side by side = blocks per workgroup (one at w = 64)
+    constexpr int MS = T + 1;                     // the matrix's row stride in LDS
+    constexpr int SEG = TT < 64 ? TT : 64;        // lanes of one wave that share a unit
+    __shared__ int mat[T * MS];
+    __shared__ int buf_a[kElems], buf_b[kElems], coef[kElems];
+    __shared__ unsigned sums[kMaxQps][3][G];      // [qp][sse, nonzero, sum of magnitudes][block]
+
+    const int tid = threadIdx.x;
+    for (int i = tid; i < TT; i += kTqThreads) mat[(i / T) * MS + i % T] = matrix_coeff(L, i / T, i % T);
+    for (int i = tid; i < kMaxQps * 3 * G; i += kTqThreads) (&sums[0][0][0])[i] = 0;
+
+    const int col = tid % T;                      // e % T of all four samples
+    int row[kPerLane], base[kPerLane], pred[kPerLane], tgt[kPerLane];
+    long blk[kPerLane];                           // the sample's block; -1 past N
+    const long blk0 = (long)blockIdx.x * G;
+#pragma unroll
+    for (int j = 0; j < kPerLane; j++) {
+        const int e = j * kTqThreads + tid;
+        row[j] = (e / T) % T;
+        base[j] = e / TT * TT;
+        const long b = blk0 + e / TT;
+        blk[j] = b < p.N ? b : -1;
+    }
+
+#pragma unroll 1
+    for (int q = 0; q < NQ; q++) {
+        const int uy = q / U, ux = q % U;
+        // residual of the unit(s): target - prediction
+#pragma unroll
+        for (int j = 0; j < kPerLane; j++) {
+            pred[j] = 0; tgt[j] = 0;
+            if (blk[j] >= 0) {
+                const size_t at = ((size_t)blk[j] * W + uy * T + row[j]) * W + ux * T + col;
+                pred[j] = p.pred[at]; tgt[j] = p.targets[at];
+            }
+            buf_a[j * kTqThreads + tid] = tgt[j] - pred[j];
+        }
+        __syncthreads();                          // (also: mat and sums are written)
+        {   // forward, first stage: rows
+            int acc[kPerLane] = {};
+#pragma unroll 8
+            for (int x = 0; x < T; x++) {
+                const int m = mat[col * MS + x];
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) acc[j] += buf_a[base[j] + row[j] * T + x] * m;
+            }
+#pragma unroll
+            for (int j = 0; j < kPerLane; j++) buf_b[j * kTqThreads + tid] = (acc[j] + (1 << (fwd_shift1(L) - 1))) >> fwd_shift1(L);
+        }
+        __syncthreads();
+        {   // forward, second stage: columns
+            int acc[kPerLane] = {};
+#pragma unroll 8
+            for (int y = 0; y < T; y++)
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) acc[j] += buf_b[base[j] + y * T + col] * mat[row[j] * MS + y];
+#pragma unroll
+            for (int j = 0; j < kPerLane; j++) coef[j * kTqThreads + tid] = (acc[j] + (1 << (fwd_shift2(L) - 1))) >> fwd_shift2(L);
+        }
+        // (each lane reads back only the coefficients it wrote: no barrier)
+#pragma unroll 1
+        for (int qi = 0; qi < p.nb_qps; qi++) {
+            const QpConsts qc = p.qp[qi];
+            unsigned nonzero[kPerLane], sum_abs[kPerLane], sse[kPerLane];
+#pragma unroll
+            for (int j = 0; j < kPerLane; j++) {
+                int mag;
+                const int level = quant_level(coef[j * kTqThreads + tid], qc, &mag);
+                nonzero[j] = level != 0;
+                sum_abs[j] = (unsigned)mag;
+                buf_a[j * kTqThreads + tid] = dequant_level(level, qc);
+            }
+            __syncthreads();
+            {   // inverse, first stage: columns
+                int acc[kPerLane] = {};
+#pragma unroll 8
+                for (int l = 0; l < T; l++)
+#pragma unroll
+                    for (int j = 0; j < kPerLane; j++) acc[j] += mat[l * MS + row[j]] * buf_a[base[j] + l * T + col];
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) buf_b[j * kTqThreads + tid] = clip16((acc[j] + (1 << (kInvShift1 - 1))) >> kInvShift1);
+            }
+            __syncthreads();
+            {   // inverse, second stage: rows; reconstruction
+                int acc[kPerLane] = {};
+#pragma unroll 8
+                for (int k = 0; k < T; k++) {
+                    const int m = mat[k * MS + col];
+#pragma unroll
+                    for (int j = 0; j < kPerLane; j++) acc[j] += m * buf_b[base[j] + row[j] * T + k];
+                }
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) {
+                    const int r = clip16((acc[j] + (1 << (kInvShift2 - 1))) >> kInvShift2);
+                    const int rec = min(max(pred[j] + r, 0), 255), d = rec - tgt[j];
+                    sse[j] = (unsigned)(d * d);
+                    if (p.recon && blk[j] >= 0)
+                        p.recon[(((size_t)qi * p.N + blk[j]) * W + uy * T + row[j]) * W + ux * T + col] = (uint8_t)rec;
+                }
+            }
+            // the three sums of each unit: at T = 32 the lane's four samples are one unit's, otherwise one unit per j
+            if (G == 1) {
+#pragma unroll
+                for (int j = 1; j < kPerLane; j++) { sse[0] += sse[j]; nonzero[0] += nonzero[j]; sum_abs[0] += sum_abs[j]; }
+            }
+#pragma unroll
+            for (int j = 0; j < (G == 1 ? 1 : kPerLane); j++) {
+#pragma unroll
+                for (int d = SEG / 2; d > 0; d >>= 1) {
+                    sse[j] += __shfl_xor(sse[j], d);
+                    nonzero[j] += __shfl_xor(nonzero[j], d);
+                    sum_abs[j] += __shfl_xor(sum_abs[j], d);
+                }
+                if (tid % SEG == 0) {
+                    const int g = (j * kTqThreads + tid) / TT;
+                    atomicAdd(&sums[qi][0][g], sse[j]);
+                    atomicAdd(&sums[qi][1][g], nonzero[j]);
+                    atomicAdd(&sums[qi][2][g], sum_abs[j]);
+                }
+            }
+            // the next QP (or unit) writes buf_a, which no lane reads after the barrier above; its own first barrier orders buf_b
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < p.nb_qps * G; i += kTqThreads) {
+        const int qi = i / G, g = i % G;
+        const long b = blk0 + g;
+        if (b < p.N) {
+            const size_t at = (size_t)qi * p.N + b;
+            if (p.sse) p.sse[at] = sums[qi][0][g];
+            if (p.nonzero) p.nonzero[at] = sums[qi][1][g];
+            if (p.sum_abs) p.sum_abs[at] = sums[qi][2][g];
+        }
+    }
+}
+
+}  // namespace
+
+int trquant_blocks_per_workgroup(int w) { return w >= 32 ? 1 : kElems / (w * w); }
+
+hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    if (!p.pred || !p.targets || p.nb_qps < 1 || p.nb_qps > trquant::kMaxQps) return hipErrorInvalidValue;
+    if (trquant::log2_tu(p.w) < 0) return hipErrorInvalidValue;
+    const int g = trquant_blocks_per_workgroup(p.w);
+    const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kTqThreads);
+    switch (p.w) {
+    case 4: hipLaunchKernelGGL(trquant_kernel<4>, grid, block, 0, s, p); break;
+    case 8: hipLaunchKernelGGL(trquant_kernel<8>, grid, block, 0, s, p); break;
+    case 16: hipLaunchKernelGGL(trquant_kernel<16>, grid, block, 0, s, p); break;
+    case 32: hipLaunchKernelGGL(trquant_kernel<32>, grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL(trquant_kernel<64>, grid, block, 0, s, p); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace pnn

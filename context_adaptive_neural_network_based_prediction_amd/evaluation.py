@@ -15,6 +15,9 @@ pass (pnn_first_pass_picture_pairs_device: one more call per mask, the same down
 Every function with an HEVC column takes reference_smoothing (0, 1, 2: intraprediction's `smoothing`): 0, the default, is the reference's
 extracted predictor; 2 makes the HEVC columns and the first-pass ranking those of HM's own predictor, with its reference-sample
 smoothing.  A nonzero value adds the key 'reference_smoothing' to the dictionaries and changes nothing in the PNN's columns.
+Both also take transform_qps, a list of 1 to 8 QPs, for the transform-domain column: what is left of the PNN's prediction and of the best
+HEVC mode's after HM's residual path with RDOQ 0 (intraprediction.transform_code; two more pnn_trquant_device calls per mask, the same
+download).
 """
 import ctypes
 
@@ -179,7 +182,8 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 
 
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
-                              tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0):
+                              tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
+                              transform_qps=()):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -205,13 +209,24 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     reference_smoothing (0, 1, 2): HM's reference-sample smoothing in the HEVC modes, of the best-mode search and of the first pass alike
     (the *_hm entries of include/pnn_hip.h).  0 reproduces the reference's extracted predictor, which has none -- the evaluator's
     competitor; 2 is HM's default, the predictor the encoders run.  A nonzero value adds the key 'reference_smoothing' (int) to every
-    dictionary and leaves the PNN's and IPFCN-S's keys bit-identical.  With 0 nothing changes: not a key, a call or a byte."""
+    dictionary and leaves the PNN's and IPFCN-S's keys bit-identical.  With 0 nothing changes: not a key, a call or a byte.
+
+    transform_qps (1 to 8 integers in [0, 51]; ValueError otherwise, before anything touches the GPU) adds the transform-domain column,
+    open-loop: per mask TWO more calls behind the score call (and the first-pass call), pnn_trquant_device on the PNN's uint8 predictions
+    and on the best HEVC mode's (the smoothed ones when reference_smoothing says so), both against the targets the first mask left on
+    the device; HM's residual path with RDOQ 0 as include/pnn_hip.h defines it (no RDOQ, sign-data hiding, transform skip or rate; at
+    w = 64 the four 32 x 32 quadrants of the one prediction).  Their results join the one download.  New keys: 'transform_qps' (tuple),
+    'sses_recon_pnn', 'nb_nonzero_levels_pnn', 'sum_abs_levels_pnn' (uint32 [nb_qps, N]), 'psnrs_recon_pnn' (float64 [nb_qps, N]), the same
+    four with '_hevc_best_mode' in place of '_pnn', and 'frequency_recon_win_pnn' (one float per QP: the share of blocks whose PNN
+    reconstruction PSNR is strictly higher).  Equal to intraprediction.transform_code on the dictionary's own predictions and targets.
+    With transform_qps=() nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
-                        net_ipfcns, keep_predictions, first_pass, reference_smoothing)
+                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
-                                   tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0):
+                                   tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
+                                   transform_qps=()):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -224,13 +239,14 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
     The pair is de-interleaved once on the host and uploaded once; per mask ONE call and ONE download, as for single pictures.
     first_pass=True: the keys of score_masks_from_pictures; reference samples from the decoded plane, targets of the costs from the
     original, as in the table above.  reference_smoothing: as for score_masks_from_pictures; the smoothed line is built from the decoded
-    plane's samples, as the unsmoothed one is."""
+    plane's samples, as the unsmoothed one is.  transform_qps: as for score_masks_from_pictures; the predictions that get coded are the
+    ones made from the decoded plane, the residual's and the SSE's targets come from the original, as in the table above."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
-                        tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing)
+                        tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps)
 
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                 keep_predictions, first_pass=False, reference_smoothing=0):
+                 keep_predictions, first_pass=False, reference_smoothing=0, transform_qps=()):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer."""
     if ch.dtype != np.uint8:
@@ -256,6 +272,8 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     if reference_smoothing not in intraprediction.SMOOTHINGS:
         raise ValueError('`reference_smoothing` does not belong to {0, 1, 2}.')
     reference_smoothing = int(reference_smoothing)
+    if not (isinstance(transform_qps, (tuple, list)) and len(transform_qps) == 0):
+        transform_qps = intraprediction._check_qps(transform_qps)
     masks = [(int(m[0]), int(m[1])) for m in tuples_width_height_masks]
     rows, cols = row_1sts.astype(np.int64).ravel(), col_1sts.astype(np.int64).ravel()
     n_pos = rows.size
@@ -297,6 +315,10 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         nb_list = intraprediction.first_pass_list_size(w)
         sections += [('hads_hevc_modes', np.uint32, (n, nb_modes)), ('hads_pnn', np.uint32, (n,)),
                      ('first_pass_costs', np.uint32, (n, nb_list)), ('first_pass_list', np.uint8, (n, nb_list))]
+    nb_qps = len(transform_qps)
+    coded = (('pnn', 'predictions_pnn'), ('hevc_best_mode', 'predictions_hevc')) if nb_qps else ()
+    for column, _ in coded:
+        sections += [('%s_%s' % (name, column), np.uint32, (nb_qps, n)) for name in ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels')]
     sections += [(name, np.uint8, (n, w, w, 1)) for name in ('predictions_pnn', 'predictions_hevc', 'targets')]
     begin, end, offset = {}, {}, 0
     for name, dtype, shape in sections:
@@ -306,6 +328,7 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     d_out = torch.empty(end['targets'], dtype=torch.uint8, device=dev)       # the last section
     ptr = {name: d_out.data_ptr() + begin[name] for name in begin}
     stream = torch.cuda.current_stream(dev)
+    c_qps = (ctypes.c_int * max(nb_qps, 1))(*transform_qps)
     results = {}
     targets_uint8 = None
     for i, mask in enumerate(masks):
@@ -314,8 +337,8 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         first = i == 0
         blocks = (predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
                   d_rows.data_ptr(), d_cols.data_ptr(), n_pos, mask[0], mask[1])
-        scores = (ptr['targets'] if first else None, ptr['predictions_pnn'] if keep_predictions or first_pass else None, None,
-                  ptr['sses_pnn'], ptr['indices_hevc'], ptr['sses_hevc'], ptr['predictions_hevc'] if keep_predictions else None,
+        scores = (ptr['targets'] if first else None, ptr['predictions_pnn'] if keep_predictions or first_pass or nb_qps else None, None,
+                  ptr['sses_pnn'], ptr['indices_hevc'], ptr['sses_hevc'], ptr['predictions_hevc'] if keep_predictions or nb_qps else None,
                   ctypes.c_void_p(stream.cuda_stream))
         with torch.cuda.device(dev):
             if reference_smoothing == 0:
@@ -330,6 +353,10 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                 else:
                     _lib.check(L.pnn_first_pass_picture_pairs_hm_device(
                         *(blocks + (ptr['predictions_pnn'], reference_smoothing) + ranking)), predictor.ctx)
+            for column, predictions in coded:             # both predictions are on the device, and so are the first mask's targets
+                _lib.check(L.pnn_trquant_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, c_qps, nb_qps,
+                                                ptr['sses_recon_' + column], ptr['nb_nonzero_levels_' + column],
+                                                ptr['sum_abs_levels_' + column], None, ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
@@ -348,6 +375,15 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
             dictionary_performance['frequency_pnn_first_pass_best'] = float(np.count_nonzero(first_pass_list[:, 0] == nb_modes)) / n
         if reference_smoothing:
             dictionary_performance['reference_smoothing'] = reference_smoothing
+        if nb_qps:
+            dictionary_performance['transform_qps'] = transform_qps
+            for column, _ in coded:
+                for name in ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels'):
+                    dictionary_performance['%s_%s' % (name, column)] = view['%s_%s' % (name, column)].copy()
+                dictionary_performance['psnrs_recon_' + column] = intraprediction.psnrs_from_sses(view['sses_recon_' + column], w)
+            dictionary_performance['frequency_recon_win_pnn'] = [
+                float(np.count_nonzero(dictionary_performance['psnrs_recon_pnn'][q] - dictionary_performance['psnrs_recon_hevc_best_mode'][q] > 0.)) / n
+                for q in range(nb_qps)]
         if keep_predictions:
             if first:
                 targets_uint8 = view['targets'].copy()

@@ -328,3 +328,98 @@ def predict_via_hevc_best_mode(intra_pattern_uint8, target_uint8, device=0, smoo
         raise ValueError('Buffer has wrong number of dimensions (expected 3)')
     indices, psnrs, predictions = predict_series_via_hevc_best_mode(intra_pattern_uint8[None], target_uint8[None], device, smoothing)
     return (int(indices[0]), psnrs[0], predictions[0])
+
+
+MAX_TRANSFORM_QPS = 8
+
+
+def _check_qps(qps):
+    """The QP list of the transform coding as a tuple of ints; ValueError unless it holds 1 to 8 integers in [0, 51]."""
+    try:
+        qps = tuple(qps)
+    except TypeError:
+        raise ValueError('`qps` is not a sequence of 1 to 8 integers.')
+    if not 1 <= len(qps) <= MAX_TRANSFORM_QPS:
+        raise ValueError('`qps` does not hold 1 to 8 quantisation parameters.')
+    if any(isinstance(q, (bool, np.bool_)) or not isinstance(q, (int, np.integer)) for q in qps):
+        raise ValueError('a quantisation parameter is not an integer.')
+    if any(q < 0 or q > 51 for q in qps):
+        raise ValueError('a quantisation parameter does not belong to [0, 51].')
+    return tuple(int(q) for q in qps)
+
+
+def _blocks_uint8(array_uint8, name):
+    """A uint8 [N, w, w] or [N, w, w, 1] numpy array as contiguous [N, w, w]."""
+    if not isinstance(array_uint8, np.ndarray) or array_uint8.dtype != np.uint8:
+        raise TypeError('`%s` is not a `numpy.ndarray` of dtype `numpy.uint8`.' % name)
+    if array_uint8.ndim == 4 and array_uint8.shape[3] == 1:
+        array_uint8 = array_uint8[..., 0]
+    if array_uint8.ndim != 3 or array_uint8.shape[1] != array_uint8.shape[2] or array_uint8.shape[1] not in WIDTHS:
+        raise ValueError('`%s` is not [N, w, w] or [N, w, w, 1] with w in {4, 8, 16, 32, 64}.' % name)
+    return np.ascontiguousarray(array_uint8)
+
+
+def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reconstructions=False):
+    """Open-loop HEVC transform coding of N predictions against their targets (uint8 [N, w, w] or [N, w, w, 1]) at the 1 to 8 QPs of
+    `qps` (integers in [0, 51]): HM's residual path with RDOQ 0 -- forward transform, quantisation, dequantisation, inverse transform,
+    reconstruction -- as include/pnn_hip.h defines it (T = w up to 32, the four 32 x 32 quadrants of the one prediction at w = 64; no
+    RDOQ, sign-data hiding, transform skip or rate).  device=None runs the host twin (pnn_trquant_host), an int that GPU
+    (pnn_trquant_device: one launch for all blocks and QPs); the bits are the same.
+    Returns {'sses_recon', 'nb_nonzero_levels', 'sum_abs_levels': uint32 [nb_qps, N], 'psnrs_recon': float64 [nb_qps, N] (psnrs_from_sses)}
+    and, with keep_reconstructions, 'reconstructions_uint8' [nb_qps, N, w, w]."""
+    qps = _check_qps(qps)
+    predictions, targets = _blocks_uint8(predictions_uint8, 'predictions_uint8'), _blocks_uint8(targets_uint8, 'targets_uint8')
+    if predictions.shape != targets.shape:
+        raise ValueError('`predictions_uint8.shape` is not equal to `targets_uint8.shape`.')
+    n, w = targets.shape[0], targets.shape[1]
+    nq = len(qps)
+    c_qps = (ctypes.c_int * nq)(*qps)
+    L = _lib.lib()
+    if device is None:
+        sses, nonzero, sum_abs = (np.zeros((nq, n), np.uint32) for _ in range(3))
+        recon = np.zeros((nq, n, w, w), np.uint8) if keep_reconstructions else None
+        rc = L.pnn_trquant_host(predictions.ctypes.data, targets.ctypes.data, w, n, c_qps, nq, sses.ctypes.data, nonzero.ctypes.data,
+                                sum_abs.ctypes.data, None if recon is None else recon.ctypes.data)
+        if rc != 0:
+            raise ValueError('pnn_trquant_host refused the arguments (width %d, %d blocks).' % (w, n))
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        d_pred, d_tg = torch.from_numpy(predictions).to(dev), torch.from_numpy(targets).to(dev)
+        d_counts = torch.zeros((3, nq, n), dtype=torch.int32, device=dev)
+        d_recon = torch.zeros((nq, n, w, w), dtype=torch.uint8, device=dev) if keep_reconstructions else None
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.pnn_trquant_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, c_qps, nq, d_counts[0].data_ptr(),
+                                            d_counts[1].data_ptr(), d_counts[2].data_ptr(), None if d_recon is None else d_recon.data_ptr(),
+                                            ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        sses, nonzero, sum_abs = d_counts.cpu().numpy().view(np.uint32)      # (waits for the stream)
+        recon = None if d_recon is None else d_recon.cpu().numpy()
+    result = {'sses_recon': sses, 'nb_nonzero_levels': nonzero, 'sum_abs_levels': sum_abs, 'psnrs_recon': psnrs_from_sses(sses, w)}
+    if keep_reconstructions:
+        result['reconstructions_uint8'] = recon
+    return result
+
+
+def transform_stages(prediction_uint8, target_uint8, qp):
+    """Every stage of transform_code for ONE block (uint8 [w, w] or [w, w, 1]) at one QP, host code (pnn_trquant_stages_host):
+    {'coeffs', 'levels', 'dequant', 'residual'}, int32 [w, w] -- the forward transform's coefficients, the quantised levels, the
+    dequantised coefficients, the inverse transform's residual; at w = 64 each 32 x 32 unit's array lies where the unit lies."""
+    (qp,) = _check_qps((qp,))
+    blocks = []
+    for name, block in (('prediction_uint8', prediction_uint8), ('target_uint8', target_uint8)):
+        if isinstance(block, np.ndarray) and block.ndim == 3 and block.shape[2] == 1:
+            block = block[..., 0]
+        if not isinstance(block, np.ndarray) or block.ndim != 2:
+            raise ValueError('`%s` is not a [w, w] or [w, w, 1] `numpy.ndarray`.' % name)
+        blocks.append(_blocks_uint8(block[None], name)[0])
+    prediction, target = blocks
+    if prediction.shape != target.shape:
+        raise ValueError('`prediction_uint8.shape` is not equal to `target_uint8.shape`.')
+    w = target.shape[0]
+    stages = {name: np.zeros((w, w), np.int32) for name in ('coeffs', 'levels', 'dequant', 'residual')}
+    rc = _lib.lib().pnn_trquant_stages_host(prediction.ctypes.data, target.ctypes.data, w, qp, stages['coeffs'].ctypes.data,
+                                            stages['levels'].ctypes.data, stages['dequant'].ctypes.data, stages['residual'].ctypes.data)
+    if rc != 0:
+        raise ValueError('pnn_trquant_stages_host refused the arguments (width %d, QP %d).' % (w, qp))
+    return stages

@@ -452,6 +452,50 @@ int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* ctx, int width, const uint8_
                                            uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs,
                                            void* stream);
 
+/* ---- open-loop transform coding: what is left of a prediction after HM's residual path ------------------ */
+
+/* Every column above judges a PREDICTION; HM keeps what the residual leaves after transform, quantisation, dequantisation and inverse
+ * transform.  These entries code the residual target - prediction of n blocks at up to 8 QPs the way HM does with RDOQ 0 (xTrMxN, the
+ * non-RDOQ branch of xQuant, the no-scaling-list branch of xDeQuant, xITrMxN of TComTrQuant.cpp; the decoder half is normative HEVC).
+ * 8-bit luma, intra, I slice, coefficients of 15 bits + sign.  OPEN-LOOP: the prediction is given, nothing is predicted again from a
+ * reconstruction.  LEFT OUT, because each needs entropy-coder state that does not exist open-loop (as modeBits * sqrtLambda above):
+ * RDOQ, sign-data hiding, transform skip, the CABAC rate.
+ *   Transform units.  T = width up to 32.  At width 64 the units are the four 32 x 32 quadrants of the ONE 64 x 64 prediction, in
+ *     raster order (HEVC has no 64-point transform).  That the quadrants are not predicted again one by one, as HM would, is THIS
+ *     PROJECT'S DEFINITION.  L = log2 T.
+ *   Matrices.  M = the T-point HEVC core transform matrix of H.265 8.6.4.2; at T = 4 the 4 x 4 DST-VII {29 55 74 84; 74 74 0 -74;
+ *     84 -29 -74 55; 55 -84 74 -29} (intra luma 4 x 4 always uses it).  HM's butterflies are exact integer factorisations: the plain
+ *     products below give the same integers, every intermediate within int32 (at most 32 * 90 * 2^15).
+ *   Forward.  X = target - prediction, rows y, columns x; >> is the arithmetic shift of a signed value.
+ *     Y[y][k] = (sum_x X[y][x] M[k][x] + (1 << (s1 - 1))) >> s1, s1 = L - 1;  C[l][k] = (sum_y Y[y][k] M[l][y] + (1 << (s2 - 1))) >> s2, s2 = L + 6.
+ *   Quantisation at QP q in [0, 51].  per = q / 6, rem = q % 6, scale = {26214, 23302, 20560, 18396, 16384, 14564}[rem], ts = 7 - L,
+ *     qbits = 14 + per + ts, add = 171 << (qbits - 9) (171: the I-slice value);  mag = (|C| scale + add) >> qbits in 64 bits;
+ *     level = clip(sign(C) mag, -32768, 32767).  sum_abs_levels = sum of mag (HM's uiAbsSum, before the clip), nb_nonzero = number of
+ *     levels != 0, both over the block (over its four units at width 64).
+ *   Dequantisation.  inv = {40, 45, 51, 57, 64, 72}[rem], rs = 6 - (ts + per);  C' = (level inv + (1 << (rs - 1))) >> rs if rs > 0, else
+ *     (level inv) << -rs;  clipped to [-32768, 32767].
+ *   Inverse.  Vertical first: Z[y][k] = clip16((sum_l M[l][y] C'[l][k] + 64) >> 7);  then R[y][x] = clip16((sum_k M[k][x] Z[y][k] + 2048) >> 12).
+ *   Reconstruction.  rec = clip(prediction + R, 0, 255);  sse_recon = sum (rec - target)^2, uint32 (at most 2.7e8 at width 64).
+ *
+ * The host twin: pure host code, the zero-tolerance yardstick of the device entry and what a CPU-only user calls.  predictions and
+ * targets dense uint8 [n][width][width]; qps: nb_qps (1 .. 8) host ints in [0, 51].  Outputs, each NULL or: sses_recon, nb_nonzero,
+ * sum_abs_levels uint32 [nb_qps][n]; recon uint8 [nb_qps][n][width][width].  n == 0 does nothing.  PNN_E_ARG + a line on stderr for a
+ * width outside {4, 8, 16, 32, 64}, n < 0, NULL inputs with n > 0, a bad QP list, every output NULL. */
+int pnn_trquant_host(const uint8_t* predictions, const uint8_t* targets, int width, int n, const int* qps, int nb_qps,
+                     uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon);
+/* One block, every stage, so that each can be looked at: coeffs = C, levels, dequant = C', residual = R, each NULL (not all) or int32
+ * [width][width]; at width 64 each unit's 32 x 32 array lies where the unit lies in the block.  Same refusals; pure host code. */
+int pnn_trquant_stages_host(const uint8_t* prediction, const uint8_t* target, int width, int qp, int32_t* coeffs, int32_t* levels,
+                            int32_t* dequant, int32_t* residual);
+/* pnn_trquant_host on the GPU, all n blocks and all QPs in ONE launch (the forward transform of a unit once, the rest per QP);
+ * bit-identical to it.  d_* are device pointers, qps is a HOST array; asynchronous on `stream`; every argument error (those of the host
+ * twin) is reported before the launch.  A context without models (pnn_create_empty) suffices.
+ * Pairs: hand in the predictions the score call made from the decoded plane and the targets it copied from the original plane
+ * (pnn_score_picture_pairs_device's d_pnn_u8 / d_hevc_pred and d_targets): residual and SSE are then against the original, the table
+ * of that entry. */
+int pnn_trquant_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const int* qps, int nb_qps,
+                       uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels, uint8_t* d_recon, void* stream);
+
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
 int pnn_last_call_stats(const pnn_ctx* ctx, int* n_gemm_launches, double* gemm_flops, int* n_launches);
