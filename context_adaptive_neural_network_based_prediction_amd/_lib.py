@@ -96,6 +96,9 @@ SIGNATURES = {
     "pnn_trquant_host": (ci, [vp, vp, ci, ci, ctypes.POINTER(ci), ci, vp, vp, vp, vp]),
     "pnn_trquant_stages_host": (ci, [vp, vp, ci, ci, vp, vp, vp, vp]),
     "pnn_trquant_device": (ci, [vp, ci, vp, vp, ci, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp]),
+    "pnn_trquant_rate_host": (ci, [vp, vp, ci, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp]),
+    "pnn_cabac_rate_levels_host": (ci, [vp, ci, ci, ci, ctypes.POINTER(ctypes.c_uint64)]),
+    "pnn_trquant_rate_device": (ci, [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

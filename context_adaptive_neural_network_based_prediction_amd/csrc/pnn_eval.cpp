@@ -390,15 +390,29 @@ int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t*
 int pnn_trquant_device(pnn_ctx* c, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const int* qps, int nb_qps,
                        uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels, uint8_t* d_recon, void* stream)
 {
+    return pnn_trquant_rate_device(c, width, d_predictions, d_targets, n, nullptr, qps, nb_qps, d_sses_recon, d_nb_nonzero, d_sum_abs_levels,
+                                   d_recon, nullptr, stream);
+}
+
+int pnn_trquant_rate_device(pnn_ctx* c, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
+                            const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
+                            uint8_t* d_recon, uint64_t* d_rate, void* stream)
+{
     if (!c) return PNN_E_ARG;
     if (const int rc = check_trquant(c, width, d_predictions, d_targets, n, qps, nb_qps,
-                                     d_sses_recon || d_nb_nonzero || d_sum_abs_levels || d_recon)) return rc;
+                                     d_sses_recon || d_nb_nonzero || d_sum_abs_levels || d_recon || d_rate)) return rc;
+    if (d_modes && !d_rate) return fail(c, PNN_E_ARG, "intra modes without a rate output");
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
     TrQuantParams p;
     p.pred = d_predictions; p.targets = d_targets; p.N = n; p.w = width; p.nb_qps = nb_qps;
-    for (int i = 0; i < trquant::kMaxQps; i++) p.qp[i] = trquant::qp_consts(trquant::log2_tu(width), qps[i < nb_qps ? i : 0]);
+    for (int i = 0; i < trquant::kMaxQps; i++) {
+        const int qp = qps[i < nb_qps ? i : 0];
+        p.qp[i] = trquant::qp_consts(trquant::log2_tu(width), qp);
+        for (int k = 0; k < cabac::kNumCtx; k++) p.init_states[i][k] = (uint8_t)cabac::init_state(qp, cabac::init_value(k));
+    }
     p.sse = d_sses_recon; p.nonzero = d_nb_nonzero; p.sum_abs = d_sum_abs_levels; p.recon = d_recon;
+    p.rate = d_rate; p.modes = d_modes;
     reset_stats(c);
     HIPCHK(c, launch_trquant(p, (hipStream_t)stream));
     c->stat_launches++;

@@ -5,6 +5,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "pnn_cabac_tables.h"
 #include "pnn_trquant_tables.h"
 
 namespace pnn {
@@ -297,10 +298,13 @@ hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s);
 
 // Open-loop transform coding (pnn_trquant.hip): N predictions and targets [N][w][w] uint8, nb_qps <= 8 QPs whose constants the host has
 // worked out (trquant::qp_consts at the unit size of w).  Outputs, each NULL or [nb_qps][N] uint32: the SSE of the reconstruction, the
-// number of nonzero levels, the sum of the quantised magnitudes; recon NULL or uint8 [nb_qps][N][w][w].
+// number of nonzero levels, the sum of the quantised magnitudes; recon NULL or uint8 [nb_qps][N][w][w].  rate NULL (the kernel without
+// the rate) or uint64 [nb_qps][N], the CABAC rate of the levels in 2^-15 bit; with it modes NULL (diagonal scan) or uint8 [N], the intra
+// mode that picks a block's scan (a value above 34 scans diagonally), and init_states, the context states each QP starts a unit with.
 struct TrQuantParams {
     const uint8_t* pred; const uint8_t* targets; int N; int w; int nb_qps; trquant::QpConsts qp[trquant::kMaxQps];
     uint32_t* sse; uint32_t* nonzero; uint32_t* sum_abs; uint8_t* recon;
+    uint64_t* rate; const uint8_t* modes; uint8_t init_states[trquant::kMaxQps][cabac::kNumCtx];
 };
 int trquant_blocks_per_workgroup(int w);
 hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s);

@@ -19,6 +19,14 @@
 // each.  The three sums go by wave shuffles over the lanes of one unit (64, or 16 at T = 4), then one LDS add per unit and wave.  The QP's
 // constants come ready in the argument block (qp_consts on the host).  Blocks past N in the last workgroup carry a zero residual and are
 // never stored.
+//
+// RATE: the instantiations with RATE also keep the levels of the current QP in LDS (dense per unit, as every
+// other array) and, behind the QP's first barrier, ONE LANE PER UNIT -- lane g of the workgroup for unit g: 64 lanes at T = 4, one at
+// T = 32 -- walks its unit's levels with cabac::unit_rate, the very lines the host twin compiles (pnn_cabac_tables.h), its 80 context
+// states and the two tables in LDS.  The other lanes go on to the inverse transform and wait at its barrier, so the levels stay until
+// the walk is over; the next QP overwrites them only behind that barrier.  The bits of a block's units add in a 64-bit LDS slot.  The
+// instantiations without RATE are the kernel as it was: no statement of theirs mentions the rate's arrays.
+#include "pnn_cabac_tables.h"
 #include "pnn_kernels.h"
 #include "pnn_trquant_tables.h"
 
@@ -29,7 +37,7 @@ constexpr int kTqThreads = 256;
 constexpr int kElems = 1024;                      // residual samples a workgroup holds: one 32 x 32 unit, or G smaller blocks
 constexpr int kPerLane = kElems / kTqThreads;
 
-template <int W>
+template <int W, bool RATE>
 __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams p)
 {
     using namespace trquant;
@@ -42,7 +50,21 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
     __shared__ int buf_a[kElems], buf_b[kElems], coef[kElems];
     __shared__ unsigned sums[kMaxQps][3][G];      // [qp][sse, nonzero, sum of magnitudes][block]
 
+    // the rate's arrays exist in the RATE instantiations only
+    int* lev = nullptr; int* ebits = nullptr; uint8_t* lps = nullptr; uint8_t* states = nullptr; unsigned long long* bits = nullptr;
+    if constexpr (RATE) {
+        __shared__ int lev_s[kElems], ebits_s[128];
+        __shared__ uint8_t lps_s[64], states_s[G * cabac::kNumCtx];
+        __shared__ unsigned long long bits_s[kMaxQps * G];
+        lev = lev_s; ebits = ebits_s; lps = lps_s; states = states_s; bits = bits_s;
+    }
+
     const int tid = threadIdx.x;
+    if constexpr (RATE) {
+        if (tid < 128) ebits[tid] = cabac::entropy_bits_table()[tid];
+        if (tid < 64) lps[tid] = cabac::trans_idx_lps_table()[tid];
+        for (int i = tid; i < kMaxQps * G; i += kTqThreads) bits[i] = 0;
+    }
     for (int i = tid; i < TT; i += kTqThreads) mat[(i / T) * MS + i % T] = matrix_coeff(L, i / T, i % T);
     for (int i = tid; i < kMaxQps * 3 * G; i += kTqThreads) (&sums[0][0][0])[i] = 0;
 
@@ -106,8 +128,16 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
                 nonzero[j] = level != 0;
                 sum_abs[j] = (unsigned)mag;
                 buf_a[j * kTqThreads + tid] = dequant_level(level, qc);
+                if constexpr (RATE) lev[j * kTqThreads + tid] = level;
             }
             __syncthreads();
+            if constexpr (RATE) {
+                if (tid < G && blk0 + tid < p.N) {    // lane g codes unit g (units past N have no slot to add to)
+                    const int scan = p.modes ? cabac::scan_of_mode(L, p.modes[blk0 + tid]) : cabac::kScanDiag;
+                    bits[qi * G + tid] += cabac::unit_rate<L>(lev + tid * TT, scan, p.init_states[qi], states + tid * cabac::kNumCtx,
+                                                              cabac::Tables{ebits, lps});
+                }
+            }
             {   // inverse, first stage: columns
                 int acc[kPerLane] = {};
 #pragma unroll 8
@@ -167,6 +197,7 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
             if (p.sse) p.sse[at] = sums[qi][0][g];
             if (p.nonzero) p.nonzero[at] = sums[qi][1][g];
             if (p.sum_abs) p.sum_abs[at] = sums[qi][2][g];
+            if constexpr (RATE) p.rate[at] = bits[qi * G + g];
         }
     }
 }
@@ -182,12 +213,22 @@ hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s)
     if (trquant::log2_tu(p.w) < 0) return hipErrorInvalidValue;
     const int g = trquant_blocks_per_workgroup(p.w);
     const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kTqThreads);
+    if (p.rate) {
+        switch (p.w) {
+        case 4: hipLaunchKernelGGL((trquant_kernel<4, true>), grid, block, 0, s, p); break;
+        case 8: hipLaunchKernelGGL((trquant_kernel<8, true>), grid, block, 0, s, p); break;
+        case 16: hipLaunchKernelGGL((trquant_kernel<16, true>), grid, block, 0, s, p); break;
+        case 32: hipLaunchKernelGGL((trquant_kernel<32, true>), grid, block, 0, s, p); break;
+        default: hipLaunchKernelGGL((trquant_kernel<64, true>), grid, block, 0, s, p); break;
+        }
+        return hipGetLastError();
+    }
     switch (p.w) {
-    case 4: hipLaunchKernelGGL(trquant_kernel<4>, grid, block, 0, s, p); break;
-    case 8: hipLaunchKernelGGL(trquant_kernel<8>, grid, block, 0, s, p); break;
-    case 16: hipLaunchKernelGGL(trquant_kernel<16>, grid, block, 0, s, p); break;
-    case 32: hipLaunchKernelGGL(trquant_kernel<32>, grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL(trquant_kernel<64>, grid, block, 0, s, p); break;
+    case 4: hipLaunchKernelGGL((trquant_kernel<4, false>), grid, block, 0, s, p); break;
+    case 8: hipLaunchKernelGGL((trquant_kernel<8, false>), grid, block, 0, s, p); break;
+    case 16: hipLaunchKernelGGL((trquant_kernel<16, false>), grid, block, 0, s, p); break;
+    case 32: hipLaunchKernelGGL((trquant_kernel<32, false>), grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL((trquant_kernel<64, false>), grid, block, 0, s, p); break;
     }
     return hipGetLastError();
 }

@@ -183,7 +183,7 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                               tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
-                              transform_qps=()):
+                              transform_qps=(), transform_rate=False):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -219,14 +219,23 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     'sses_recon_pnn', 'nb_nonzero_levels_pnn', 'sum_abs_levels_pnn' (uint32 [nb_qps, N]), 'psnrs_recon_pnn' (float64 [nb_qps, N]), the same
     four with '_hevc_best_mode' in place of '_pnn', and 'frequency_recon_win_pnn' (one float per QP: the share of blocks whose PNN
     reconstruction PSNR is strictly higher).  Equal to intraprediction.transform_code on the dictionary's own predictions and targets.
-    With transform_qps=() nothing changes: not a key, a call or a byte."""
+    With transform_qps=() nothing changes: not a key, a call or a byte.
+
+    transform_rate=True (with transform_qps; ValueError without, before anything touches the GPU) makes the two transform calls
+    pnn_trquant_rate_device: the CABAC rate of each residual's levels, the bits HM's counter reports from the I-slice initial contexts of
+    the QP (include/pnn_hip.h, "the CABAC rate of the coded levels"; cbf, mode bits and any lambda left out).  The best mode's call gets
+    the mode array the score call left on the device (the mode picks the scan at w = 4 and 8), the PNN's gets none: its blocks are coded
+    under the diagonal scan, this project's definition.  The results join the one download.  New keys: 'rate_bits_pnn',
+    'rate_bits_hevc_best_mode' (float64 [nb_qps, N], bits) and 'frequency_rate_win_pnn' (one float per QP: the share of blocks whose PNN
+    residual costs strictly fewer bits).  Equal to intraprediction.transform_code(rate=True, modes=...) on the dictionary's own
+    predictions, targets and modes.  With transform_rate=False nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
-                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps)
+                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                                    tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
-                                   transform_qps=()):
+                                   transform_qps=(), transform_rate=False):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -240,13 +249,15 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
     first_pass=True: the keys of score_masks_from_pictures; reference samples from the decoded plane, targets of the costs from the
     original, as in the table above.  reference_smoothing: as for score_masks_from_pictures; the smoothed line is built from the decoded
     plane's samples, as the unsmoothed one is.  transform_qps: as for score_masks_from_pictures; the predictions that get coded are the
-    ones made from the decoded plane, the residual's and the SSE's targets come from the original, as in the table above."""
+    ones made from the decoded plane, the residual's and the SSE's targets come from the original, as in the table above.
+    transform_rate: as for score_masks_from_pictures."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
-                        tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps)
+                        tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps,
+                        transform_rate)
 
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                 keep_predictions, first_pass=False, reference_smoothing=0, transform_qps=()):
+                 keep_predictions, first_pass=False, reference_smoothing=0, transform_qps=(), transform_rate=False):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer."""
     if ch.dtype != np.uint8:
@@ -274,6 +285,8 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     reference_smoothing = int(reference_smoothing)
     if not (isinstance(transform_qps, (tuple, list)) and len(transform_qps) == 0):
         transform_qps = intraprediction._check_qps(transform_qps)
+    if transform_rate and len(transform_qps) == 0:
+        raise ValueError('`transform_rate` is set without `transform_qps`.')
     masks = [(int(m[0]), int(m[1])) for m in tuples_width_height_masks]
     rows, cols = row_1sts.astype(np.int64).ravel(), col_1sts.astype(np.int64).ravel()
     n_pos = rows.size
@@ -319,6 +332,8 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     coded = (('pnn', 'predictions_pnn'), ('hevc_best_mode', 'predictions_hevc')) if nb_qps else ()
     for column, _ in coded:
         sections += [('%s_%s' % (name, column), np.uint32, (nb_qps, n)) for name in ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels')]
+        if transform_rate:
+            sections.append(('rate_' + column, np.uint64, (nb_qps, n)))
     sections += [(name, np.uint8, (n, w, w, 1)) for name in ('predictions_pnn', 'predictions_hevc', 'targets')]
     begin, end, offset = {}, {}, 0
     for name, dtype, shape in sections:
@@ -354,9 +369,14 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                     _lib.check(L.pnn_first_pass_picture_pairs_hm_device(
                         *(blocks + (ptr['predictions_pnn'], reference_smoothing) + ranking)), predictor.ctx)
             for column, predictions in coded:             # both predictions are on the device, and so are the first mask's targets
-                _lib.check(L.pnn_trquant_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, c_qps, nb_qps,
-                                                ptr['sses_recon_' + column], ptr['nb_nonzero_levels_' + column],
-                                                ptr['sum_abs_levels_' + column], None, ctypes.c_void_p(stream.cuda_stream)), predictor.ctx)
+                counts = (ptr['sses_recon_' + column], ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None)
+                if transform_rate:                        # the best mode's scan follows its mode, which the score call left; the PNN has none
+                    modes = ptr['indices_hevc'] if column == 'hevc_best_mode' else None
+                    _lib.check(L.pnn_trquant_rate_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps,
+                                                         *(counts + (ptr['rate_' + column], ctypes.c_void_p(stream.cuda_stream)))), predictor.ctx)
+                else:
+                    _lib.check(L.pnn_trquant_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, c_qps, nb_qps,
+                                                    *(counts + (ctypes.c_void_p(stream.cuda_stream),))), predictor.ctx)
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
@@ -383,6 +403,12 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                 dictionary_performance['psnrs_recon_' + column] = intraprediction.psnrs_from_sses(view['sses_recon_' + column], w)
             dictionary_performance['frequency_recon_win_pnn'] = [
                 float(np.count_nonzero(dictionary_performance['psnrs_recon_pnn'][q] - dictionary_performance['psnrs_recon_hevc_best_mode'][q] > 0.)) / n
+                for q in range(nb_qps)]
+        if transform_rate:
+            for column, _ in coded:
+                dictionary_performance['rate_bits_' + column] = view['rate_' + column].astype(np.float64) / 32768.
+            dictionary_performance['frequency_rate_win_pnn'] = [
+                float(np.count_nonzero(dictionary_performance['rate_bits_pnn'][q] < dictionary_performance['rate_bits_hevc_best_mode'][q])) / n
                 for q in range(nb_qps)]
         if keep_predictions:
             if first:

@@ -359,14 +359,19 @@ def _blocks_uint8(array_uint8, name):
     return np.ascontiguousarray(array_uint8)
 
 
-def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reconstructions=False):
+def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reconstructions=False, modes=None, rate=False):
     """Open-loop HEVC transform coding of N predictions against their targets (uint8 [N, w, w] or [N, w, w, 1]) at the 1 to 8 QPs of
     `qps` (integers in [0, 51]): HM's residual path with RDOQ 0 -- forward transform, quantisation, dequantisation, inverse transform,
     reconstruction -- as include/pnn_hip.h defines it (T = w up to 32, the four 32 x 32 quadrants of the one prediction at w = 64; no
     RDOQ, sign-data hiding, transform skip or rate).  device=None runs the host twin (pnn_trquant_host), an int that GPU
     (pnn_trquant_device: one launch for all blocks and QPs); the bits are the same.
     Returns {'sses_recon', 'nb_nonzero_levels', 'sum_abs_levels': uint32 [nb_qps, N], 'psnrs_recon': float64 [nb_qps, N] (psnrs_from_sses)}
-    and, with keep_reconstructions, 'reconstructions_uint8' [nb_qps, N, w, w]."""
+    and, with keep_reconstructions, 'reconstructions_uint8' [nb_qps, N, w, w].
+    rate=True adds 'rate_bits', float64 [nb_qps, N]: the bits HM's CABAC counter reports for the levels of each block's transform
+    unit(s) from the I-slice initial contexts of the QP (include/pnn_hip.h, "the CABAC rate of the coded levels"; cbf_luma and mode bits
+    not counted) -- the uint64 count of pnn_trquant_rate_host / _device over 32768.  modes (with rate only): uint8 [N] intra modes in
+    [0, 34] that pick each block's scan at w = 4 and 8; None codes every block under the diagonal scan.  With rate=False the dictionary
+    is the one above."""
     qps = _check_qps(qps)
     predictions, targets = _blocks_uint8(predictions_uint8, 'predictions_uint8'), _blocks_uint8(targets_uint8, 'targets_uint8')
     if predictions.shape != targets.shape:
@@ -375,6 +380,10 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     nq = len(qps)
     c_qps = (ctypes.c_int * nq)(*qps)
     L = _lib.lib()
+    if rate:
+        return _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_reconstructions, modes)
+    if modes is not None:
+        raise ValueError('`modes` is given without `rate`.')
     if device is None:
         sses, nonzero, sum_abs = (np.zeros((nq, n), np.uint32) for _ in range(3))
         recon = np.zeros((nq, n, w, w), np.uint8) if keep_reconstructions else None
@@ -399,6 +408,75 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     if keep_reconstructions:
         result['reconstructions_uint8'] = recon
     return result
+
+
+def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_reconstructions, modes):
+    """transform_code(rate=True) behind its argument checks: the entries with the rate, host or device."""
+    n, w, nq = targets.shape[0], targets.shape[1], len(qps)
+    if modes is not None:
+        modes = np.asarray(modes)
+        if modes.shape != (n,) or not np.issubdtype(modes.dtype, np.integer):
+            raise ValueError('`modes` is not an integer array of shape [N].')
+        if n and (modes.min() < 0 or modes.max() > 34):
+            raise ValueError('`modes` has a value outside [0, 34].')
+        modes = np.ascontiguousarray(modes.astype(np.uint8))
+    if device is None:
+        sses, nonzero, sum_abs = (np.zeros((nq, n), np.uint32) for _ in range(3))
+        bits = np.zeros((nq, n), np.uint64)
+        recon = np.zeros((nq, n, w, w), np.uint8) if keep_reconstructions else None
+        rc = L.pnn_trquant_rate_host(predictions.ctypes.data, targets.ctypes.data, w, n, None if modes is None else modes.ctypes.data, c_qps,
+                                     nq, sses.ctypes.data, nonzero.ctypes.data, sum_abs.ctypes.data,
+                                     None if recon is None else recon.ctypes.data, bits.ctypes.data)
+        if rc != 0:
+            raise ValueError('pnn_trquant_rate_host refused the arguments (width %d, %d blocks).' % (w, n))
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        d_pred, d_tg = torch.from_numpy(predictions).to(dev), torch.from_numpy(targets).to(dev)
+        d_modes = None if modes is None else torch.from_numpy(modes).to(dev)
+        d_counts = torch.zeros((3, nq, n), dtype=torch.int32, device=dev)
+        d_bits = torch.zeros((nq, n), dtype=torch.int64, device=dev)
+        d_recon = torch.zeros((nq, n, w, w), dtype=torch.uint8, device=dev) if keep_reconstructions else None
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.pnn_trquant_rate_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n,
+                                                 None if d_modes is None else d_modes.data_ptr(), c_qps, nq, d_counts[0].data_ptr(),
+                                                 d_counts[1].data_ptr(), d_counts[2].data_ptr(),
+                                                 None if d_recon is None else d_recon.data_ptr(), d_bits.data_ptr(),
+                                                 ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        sses, nonzero, sum_abs = d_counts.cpu().numpy().view(np.uint32)      # (waits for the stream)
+        bits = d_bits.cpu().numpy().view(np.uint64)
+        recon = None if d_recon is None else d_recon.cpu().numpy()
+    result = {'sses_recon': sses, 'nb_nonzero_levels': nonzero, 'sum_abs_levels': sum_abs, 'psnrs_recon': psnrs_from_sses(sses, w),
+              'rate_bits': bits.astype(np.float64) / 32768.}
+    if keep_reconstructions:
+        result['reconstructions_uint8'] = recon
+    return result
+
+
+SCANS = {'diagonal': 0, 'horizontal': 1, 'vertical': 2}
+
+
+def cabac_rate_of_levels(levels, scan, qp):
+    """The CABAC rate, in units of 2^-15 bit (a Python int), of ONE transform unit given its levels -- an integer [T, T] array, T in
+    {4, 8, 16, 32}, each level in [-32768, 32767] -- under scan 0 / 'diagonal', 1 / 'horizontal' or 2 / 'vertical' (diagonal only at
+    T = 16 and 32) at QP `qp`: pnn_cabac_rate_levels_host, the definition at include/pnn_hip.h.  0 for an all-zero unit."""
+    (qp,) = _check_qps((qp,))
+    scan = SCANS.get(scan, scan)
+    levels = np.asarray(levels)
+    if levels.ndim != 2 or levels.shape[0] != levels.shape[1] or levels.shape[0] not in (4, 8, 16, 32) or \
+            not np.issubdtype(levels.dtype, np.integer):
+        raise ValueError('`levels` is not an integer [T, T] array with T in {4, 8, 16, 32}.')
+    if levels.size and (levels.min() < -32768 or levels.max() > 32767):
+        raise ValueError('`levels` has a value outside [-32768, 32767].')
+    if scan not in (0, 1, 2):
+        raise ValueError('`scan` is not 0, 1, 2 or their names.')
+    levels = np.ascontiguousarray(levels.astype(np.int32))
+    bits = ctypes.c_uint64(0)
+    rc = _lib.lib().pnn_cabac_rate_levels_host(levels.ctypes.data, levels.shape[0], int(scan), qp, ctypes.byref(bits))
+    if rc != 0:
+        raise ValueError('pnn_cabac_rate_levels_host refused the arguments (T %d, scan %s, QP %d).' % (levels.shape[0], scan, qp))
+    return int(bits.value)
 
 
 def transform_stages(prediction_uint8, target_uint8, qp):

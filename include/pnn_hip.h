@@ -458,8 +458,9 @@ int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* ctx, int width, const uint8_
  * transform.  These entries code the residual target - prediction of n blocks at up to 8 QPs the way HM does with RDOQ 0 (xTrMxN, the
  * non-RDOQ branch of xQuant, the no-scaling-list branch of xDeQuant, xITrMxN of TComTrQuant.cpp; the decoder half is normative HEVC).
  * 8-bit luma, intra, I slice, coefficients of 15 bits + sign.  OPEN-LOOP: the prediction is given, nothing is predicted again from a
- * reconstruction.  LEFT OUT, because each needs entropy-coder state that does not exist open-loop (as modeBits * sqrtLambda above):
- * RDOQ, sign-data hiding, transform skip, the CABAC rate.
+ * reconstruction.  LEFT OUT, because each needs the running entropy-coder state, which does not exist open-loop (as modeBits *
+ * sqrtLambda above): RDOQ, sign-data hiding, transform skip.  (The CABAC rate of the levels, counted from the state a slice STARTS
+ * with, is the next group of entries.)
  *   Transform units.  T = width up to 32.  At width 64 the units are the four 32 x 32 quadrants of the ONE 64 x 64 prediction, in
  *     raster order (HEVC has no 64-point transform).  That the quadrants are not predicted again one by one, as HM would, is THIS
  *     PROJECT'S DEFINITION.  L = log2 T.
@@ -495,6 +496,58 @@ int pnn_trquant_stages_host(const uint8_t* prediction, const uint8_t* target, in
  * of that entry. */
 int pnn_trquant_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const int* qps, int nb_qps,
                        uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels, uint8_t* d_recon, void* stream);
+
+/* ---- the CABAC rate of the coded levels, HM's bit counter ----------------------------------------------- */
+
+/* The entries above report how many levels survive and how large they are; HM decides by bits.  These report, per (QP, block), THE
+ * FRACTIONAL BITS THAT HM-16.15's TEncSbac::codeCoeffNxN ADDS TO A TEncBinCABACCounter (m_fracBits) FOR THE LEVELS OF THE TRANSFORM
+ * UNIT, WERE THE UNIT THE FIRST RESIDUAL OF AN I SLICE OF THAT QP: every context model starts each unit at its initial state
+ * (ContextModel::init, H.265 9.3.2.2, initType 0, SliceQpY = the QP).  That is well defined open-loop; the running state of a slice is
+ * not.  Unit: 2^-15 bit, uint64.  Luma, intra, 8-bit video, maxLog2TrDynamicRange 15; sign-data hiding, transform skip, transquant
+ * bypass, extended precision, persistent Rice adaptation and CABAC bypass alignment are all OFF.  NOT COUNTED: cbf_luma (its context
+ * depends on a transform tree that does not exist here), mode bits, lambda; no RDOQ.
+ *   Units.  The transform units of the entries above: T = width up to 32; at width 64 the four 32 x 32 quadrants, each coded as a unit
+ *     of its own (all contexts at their initial states again), bits added.  A unit whose levels are all zero costs 0.
+ *   Scan.  0 diagonal, 1 horizontal, 2 vertical, generated as HM's initROM does (4 x 4 groups in scan order, the scan again inside a
+ *     group).  From the block's intra mode by TComTU::getCoefScanIdx with MDCS_ANGLE_LIMIT 4: at T = 4 and T = 8 modes 22 .. 30
+ *     (vertical +- 4) scan horizontally, modes 6 .. 14 (horizontal +- 4) vertically, every other mode diagonally; at T = 16 and 32
+ *     always diagonally.  Without a mode array: diagonally.  The PNN has no mode: that its blocks are coded under the diagonal scan is
+ *     THIS PROJECT'S DEFINITION.
+ *   Bins, in codeCoeffNxN's order.  (1) The last significant position (x and y swapped under the vertical scan): per coordinate,
+ *     group g = {0,1,2,3,4,4,5,5,6,6,6,6,7,7,7,7,8 x 8,9 x 8}[pos]: g bins 1 and, if g < the group of T - 1, a bin 0, bin k on context
+ *     offset + (k >> shift), offset = 3 (L - 2) + ((L - 1) >> 2), shift = (L + 1) >> 2, of the lastX / lastY set; then (g - 2) >> 1
+ *     bypass bins per coordinate with g > 3.  (2) Per 4 x 4 group from the last one back to the first: coded_sub_block_flag when the
+ *     group is neither the last nor the first, on context (right or lower group coded ? 1 : 0); in a coded group (the first always
+ *     counts as coded) the sig_coeff_flags from the position before the last one (from 15 in other groups) down to 0, the flag at 0
+ *     inferred when the group was flagged and nothing else in it is set; context 0 at DC, else at T = 4 ctxIdxMap {0 1 4 5; 2 3 4 5;
+ *     6 6 8 8; 7 7 8 8}, else first + (group is not the first ? 3 : 0) + cnt, first = 9 at T = 8 diagonal, 15 at T = 8 otherwise, 21
+ *     above, cnt from the pattern right + 2 lower of the coded neighbour groups and the position (x, y) inside the group: pattern 0:
+ *     x + y >= 3 ? 0 : x + y >= 1 ? 1 : 2; 1: y >= 2 ? 0 : y >= 1 ? 1 : 2; 2: the same of x; 3: 2.  Then for the first 8 levels of the
+ *     group in coding order a greater-than-1 flag on context 4 set + c1, set = (group is not the first ? 2 : 0) + (the previous group
+ *     with levels ended with c1 == 0), c1 = 1 at the group's start, 0 after a flag 1, else + 1 up to 3; one greater-than-2 flag, for
+ *     the first level above 1, on context `set`; one bypass bin per sign; coeff_abs_level_remaining for every level >= its base (3
+ *     until a level >= 2 has passed, then 2; 1 from the ninth level on) by xWriteCoefRemainExGolomb: value v = |level| - base at Rice
+ *     parameter r: v < 3 << r: (v >> r) + 1 + r bypass bins, else 4 + 2 l - r with l = floor(log2(v - (3 << r) + (1 << r))); r starts
+ *     each group at 0 and goes up by one, to 4 at most, after a level > 3 << r.
+ *   Cost.  A context-coded bin costs entropyBits[state ^ bin] (HM's ContextModel::m_entropyBits, the FAST_BIT_EST table) and moves its
+ *     context by H.265 table 9-41, as TEncBinCABACCounter::encodeBin does; a bypass bin costs 32768.
+ * The numbers live in csrc/pnn_cabac_tables.h, whose lines host and device both compile.
+ *
+ * pnn_trquant_host with the rate: modes NULL or uint8 [n], each in [0, 34] (0 planar, 1 DC, 2 .. 34 angular); rate NULL or uint64
+ * [nb_qps][n].  Every other argument and refusal as there; also PNN_E_ARG for a mode above 34, for modes without rate, and `every
+ * output NULL` now counts rate.  Pure host code, the zero-tolerance yardstick of the device entry. */
+int pnn_trquant_rate_host(const uint8_t* predictions, const uint8_t* targets, int width, int n, const uint8_t* modes, const int* qps,
+                          int nb_qps, uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon, uint64_t* rate);
+/* The rate of ONE unit given its levels: int32 [t][t], t in {4, 8, 16, 32}, each level in [-32768, 32767]; scan 0, 1 or 2 (0 only at
+ * t = 16 and 32); qp in [0, 51].  *rate in 2^-15 bit.  PNN_E_ARG + a line on stderr otherwise.  Pure host code. */
+int pnn_cabac_rate_levels_host(const int32_t* levels, int t, int scan, int qp, uint64_t* rate);
+/* pnn_trquant_rate_host on the GPU, in the ONE launch of pnn_trquant_device (which is this call with d_modes and d_rate NULL and
+ * launches the kernel without the rate, bit-identical to what it was); bit-identical to the host twin.  d_modes NULL or a device uint8
+ * [n] -- pnn_score_pictures_device's d_hevc_mode as it lies; the array is NOT read back, a value above 34 scans diagonally.  d_rate NULL
+ * or device uint64 [nb_qps][n].  PNN_E_ARG before the launch for everything the host twin refuses but the mode values. */
+int pnn_trquant_rate_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
+                            const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
+                            uint8_t* d_recon, uint64_t* d_rate, void* stream);
 
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */

@@ -8,7 +8,13 @@
   Before anything is timed every output of the kernel, reconstructions included, is compared with the host twin on the first blocks:
   faster and different is not faster.
 
-    python tools/trquant_rate.py           # on the GPU box
+  The rate column: pnn_trquant_rate_device with the CABAC rate as a fifth output, without modes (TQ+R) and with
+  a mode array that takes every scan (TQ+R modes), in the same alternation, compared with the host twin first, reported as a multiple
+  of the no-rate call of the same run.  With --parent-lib, a libpnn_hip.so built from the parent commit joins the alternation (its own
+  context, the same buffers): the no-rate call must lie inside the min .. max spread of the parent's samples, or the kernel without
+  the rate was disturbed.  The results are APPENDED to profiles/trquant_rate.txt.
+
+    python tools/trquant_rate.py [--parent-lib /path/to/parent/libpnn_hip.so]          # on the GPU box
 """
 import argparse
 import ctypes
@@ -32,6 +38,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--calls", type=int, default=20, help="back-to-back calls per timed sample")
+    ap.add_argument("--parent-lib", default=None, help="libpnn_hip.so of the parent commit, for the no-rate comparison")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trquant_rate.txt"))
     args = ap.parse_args()
     import torch
@@ -44,16 +51,31 @@ def main():
     sp = ctypes.c_void_p(s.cuda_stream)
     nq = len(QPS)
     c_qps = (ctypes.c_int * nq)(*QPS)
+    parent = parent_ctx = None
+    if args.parent_lib:
+        parent = ctypes.CDLL(args.parent_lib)
+        parent.pnn_trquant_device.restype, parent.pnn_trquant_device.argtypes = _lib.SIGNATURES["pnn_trquant_device"]
+        parent.pnn_create_empty.restype, parent.pnn_create_empty.argtypes = _lib.SIGNATURES["pnn_create_empty"]
+        parent_ctx = ctypes.c_void_p()
+        assert parent.pnn_create_empty(ctypes.byref(parent_ctx), ctypes.c_float(0.), 0) == 0
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
+    legend = "# TQ+R = pnn_trquant_rate_device"
+    text = open(args.out).read() if os.path.exists(args.out) else ""
+    fresh, known = not text, legend in text               # a file with the legend gets a run line and rows only, an older one the legend too
+    with open(args.out, "a") as f:
         def out(line):
             print(line, flush=True)
             f.write(line + "\n")
-        out("# tools/trquant_rate.py on one %s: %d warm-up + %d timed samples each, alternating; a sample = %d back-to-back calls between"
-            % (torch.cuda.get_device_name(0), args.warmup, args.reps, args.calls))
-        out("# two HIP events; us per call (median [min .. max]); TQ = pnn_trquant_device at the %d QPs %s (SSE, nonzero levels, sum of magnitudes;" % (nq, QPS))
-        out("# no reconstructions stored), SSE = pnn_hevc_best_mode_device (index + SSE) on blocks of the same size: a size reference")
-        out("%-3s %8s %26s %12s %14s %26s %12s" % ("w", "N", "TQ us/call", "blocks/s", "block-QPs/s", "SSE us/call", "x SSE search"))
+        if fresh:
+            out("# tools/trquant_rate.py on one %s: %d warm-up + %d timed samples each, alternating; a sample = %d back-to-back calls between"
+                % (torch.cuda.get_device_name(0), args.warmup, args.reps, args.calls))
+            out("# two HIP events; us per call (median [min .. max]); TQ = pnn_trquant_device at the %d QPs %s (SSE, nonzero levels, sum of magnitudes;" % (nq, QPS))
+            out("# no reconstructions stored), SSE = pnn_hevc_best_mode_device (index + SSE) on blocks of the same size: a size reference")
+        if not known:
+            out(legend + ", the same call with the CABAC rate as a fifth output (diagonal scan); TQ+R modes = with a mode")
+            out("# array that takes every scan; x TQ = its median over TQ's of this run; parent = pnn_trquant_device of the parent commit's library")
+            out("%-3s %8s %26s %12s %14s %26s %12s" % ("w", "N", "TQ us/call", "blocks/s", "block-QPs/s", "SSE us/call", "x SSE search"))
+        out("# run: %s, %d warm-up + %d timed samples of %d calls" % (torch.cuda.get_device_name(0), args.warmup, args.reps, args.calls))
         for w, n in SHAPES:
             patterns, targets, candidate = blocks(w, n, 50 + w)
             d_p, d_t, d_c = (torch.from_numpy(a).cuda() for a in (patterns, targets, candidate))
@@ -65,9 +87,19 @@ def main():
             def code(d_recon=None):
                 return L.pnn_trquant_device(ctx, w, d_c.data_ptr(), d_t.data_ptr(), n, c_qps, nq, counts[0].data_ptr(), counts[1].data_ptr(),
                                             counts[2].data_ptr(), d_recon, sp)
-            calls = {"tq": code,
+            bits = torch.empty((nq, n), dtype=torch.int64, device="cuda")
+            modes = (np.arange(n) % 35).astype(np.uint8)
+            d_modes = torch.from_numpy(modes).cuda()
+
+            def code_rate(d_m=None):
+                return L.pnn_trquant_rate_device(ctx, w, d_c.data_ptr(), d_t.data_ptr(), n, d_m, c_qps, nq, counts[0].data_ptr(),
+                                                 counts[1].data_ptr(), counts[2].data_ptr(), None, bits.data_ptr(), sp)
+            calls = {"tq": code, "tq_rate": code_rate, "tq_rate_modes": lambda: code_rate(d_modes.data_ptr()),
                      "sse": lambda: L.pnn_hevc_best_mode_device(ctx, w, d_p.data_ptr(), 2 * w + 1, 2 * w + 1, d_t.data_ptr(), n, index.data_ptr(),
                                                                 sse.data_ptr(), None, None, sp)}
+            if parent is not None:
+                calls["parent"] = lambda: parent.pnn_trquant_device(parent_ctx, w, d_c.data_ptr(), d_t.data_ptr(), n, c_qps, nq,
+                                                                    counts[0].data_ptr(), counts[1].data_ptr(), counts[2].data_ptr(), None, sp)
             # results first
             assert code(recon.data_ptr()) == 0
             torch.cuda.synchronize()
@@ -77,9 +109,24 @@ def main():
             for k, name in enumerate(("sses_recon", "nb_nonzero_levels", "sum_abs_levels")):
                 assert np.array_equal(got[k], host[name]), "w %d: %s differs from the host twin" % (w, name)
             assert np.array_equal(recon[:, :m].cpu().numpy(), host["reconstructions_uint8"]), "w %d: reconstructions differ from the host twin" % w
+            mean_bits = {}
+            for name, d_m, host_modes in (("tq_rate", None, None), ("tq_rate_modes", d_modes.data_ptr(), modes[:m])):
+                assert code_rate(d_m) == 0
+                torch.cuda.synchronize()
+                host = ip.transform_code(candidate[:m], targets[:m], QPS, modes=host_modes, rate=True)
+                assert np.array_equal(bits[:, :m].cpu().numpy().astype(np.float64) / 32768., host["rate_bits"]), "w %d: the rate differs from the host twin" % w
+                got = counts[:, :, :m].cpu().numpy().view(np.uint32)
+                for k, key in enumerate(("sses_recon", "nb_nonzero_levels", "sum_abs_levels")):
+                    assert np.array_equal(got[k], host[key]), "w %d: %s differs from the host twin beside the rate" % (w, key)
+                mean_bits[name] = float(bits.cpu().numpy().mean()) / 32768.
             times = {name: [] for name in calls}
             for i in range(args.warmup + args.reps):
-                for name in calls:
+                order = list(calls)
+                if parent is not None:                    # the two no-rate calls side by side, each first in turn: what runs in front of
+                    order.remove("parent")                # a sample (and leaves its data in the caches) is then the same for both
+                    order.remove("tq")
+                    order = (["tq", "parent"] if i % 2 == 0 else ["parent", "tq"]) + order
+                for name in order:
                     t = sample(torch, s, calls[name], args.calls)
                     if i >= args.warmup:
                         times[name].append(t)
@@ -87,6 +134,11 @@ def main():
             fmt = lambda name: "%.1f [%.1f .. %.1f]" % (med[name], min(times[name]), max(times[name]))
             out("%-3d %8d %26s %12.4g %14.4g %26s %11.2fx" % (w, n, fmt("tq"), n / med["tq"] * 1e6, n * nq / med["tq"] * 1e6, fmt("sse"),
                                                                med["tq"] / med["sse"]))
+            for name, label in (("tq_rate", "TQ+R"), ("tq_rate_modes", "TQ+R modes")):
+                out("    %-12s %26s  %5.2fx TQ   (%.1f bits per block and QP on average)" % (label, fmt(name), med[name] / med["tq"], mean_bits[name]))
+            if parent is not None:
+                inside = min(times["parent"]) <= med["tq"] <= max(times["parent"])
+                out("    %-12s %26s  TQ's median %.1f lies %s the parent's min .. max" % ("parent TQ", fmt("parent"), med["tq"], "INSIDE" if inside else "OUTSIDE"))
 
 
 if __name__ == "__main__":
