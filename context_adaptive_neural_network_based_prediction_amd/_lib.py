@@ -99,6 +99,11 @@ SIGNATURES = {
     "pnn_trquant_rate_host": (ci, [vp, vp, ci, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp]),
     "pnn_cabac_rate_levels_host": (ci, [vp, ci, ci, ci, ctypes.POINTER(ctypes.c_uint64)]),
     "pnn_trquant_rate_device": (ci, [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, vp]),
+    "pnn_sign_hide_unit_host": (ci, [vp, vp, vp, ci, ci]),
+    "pnn_trquant_sdh_host": (ci, [vp, vp, ci, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, ci]),
+    "pnn_trquant_stages_sdh_host": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "pnn_cabac_rate_levels_sdh_host": (ci, [vp, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_uint64)]),
+    "pnn_trquant_sdh_device": (ci, [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, ci, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

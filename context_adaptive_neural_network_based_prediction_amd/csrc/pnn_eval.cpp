@@ -398,10 +398,18 @@ int pnn_trquant_rate_device(pnn_ctx* c, int width, const uint8_t* d_predictions,
                             const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
                             uint8_t* d_recon, uint64_t* d_rate, void* stream)
 {
+    return pnn_trquant_sdh_device(c, width, d_predictions, d_targets, n, d_modes, qps, nb_qps, d_sses_recon, d_nb_nonzero, d_sum_abs_levels,
+                                  d_recon, d_rate, 0, stream);
+}
+
+int pnn_trquant_sdh_device(pnn_ctx* c, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
+                           const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
+                           uint8_t* d_recon, uint64_t* d_rate, int sign_data_hiding, void* stream)
+{
     if (!c) return PNN_E_ARG;
     if (const int rc = check_trquant(c, width, d_predictions, d_targets, n, qps, nb_qps,
                                      d_sses_recon || d_nb_nonzero || d_sum_abs_levels || d_recon || d_rate)) return rc;
-    if (d_modes && !d_rate) return fail(c, PNN_E_ARG, "intra modes without a rate output");
+    if (d_modes && !d_rate && !sign_data_hiding) return fail(c, PNN_E_ARG, "intra modes without a rate output or sign-data hiding");
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
     TrQuantParams p;
@@ -412,7 +420,7 @@ int pnn_trquant_rate_device(pnn_ctx* c, int width, const uint8_t* d_predictions,
         for (int k = 0; k < cabac::kNumCtx; k++) p.init_states[i][k] = (uint8_t)cabac::init_state(qp, cabac::init_value(k));
     }
     p.sse = d_sses_recon; p.nonzero = d_nb_nonzero; p.sum_abs = d_sum_abs_levels; p.recon = d_recon;
-    p.rate = d_rate; p.modes = d_modes;
+    p.rate = d_rate; p.modes = d_modes; p.sdh = sign_data_hiding != 0;
     reset_stats(c);
     HIPCHK(c, launch_trquant(p, (hipStream_t)stream));
     c->stat_launches++;

@@ -301,10 +301,13 @@ hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s);
 // number of nonzero levels, the sum of the quantised magnitudes; recon NULL or uint8 [nb_qps][N][w][w].  rate NULL (the kernel without
 // the rate) or uint64 [nb_qps][N], the CABAC rate of the levels in 2^-15 bit; with it modes NULL (diagonal scan) or uint8 [N], the intra
 // mode that picks a block's scan (a value above 34 scans diagonally), and init_states, the context states each QP starts a unit with.
+// sdh nonzero: the kernels with HM's sign-data hiding between quantisation and dequantisation; modes is then read
+// with or without rate.
 struct TrQuantParams {
     const uint8_t* pred; const uint8_t* targets; int N; int w; int nb_qps; trquant::QpConsts qp[trquant::kMaxQps];
     uint32_t* sse; uint32_t* nonzero; uint32_t* sum_abs; uint8_t* recon;
     uint64_t* rate; const uint8_t* modes; uint8_t init_states[trquant::kMaxQps][cabac::kNumCtx];
+    int sdh;
 };
 int trquant_blocks_per_workgroup(int w);
 hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s);

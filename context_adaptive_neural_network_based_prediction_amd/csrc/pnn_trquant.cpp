@@ -3,9 +3,11 @@
 // scaling lists), inverse transform (xITrMxN), reconstruction -- for 8-bit luma intra blocks, per transform unit: T = w up to 32, the
 // four 32 x 32 quadrants of the one prediction at w = 64 (this project's definition; HM would predict each quadrant again).  The
 // definition is restated at the declarations in include/pnn_hip.h; the constants live in pnn_trquant_tables.h.  HM's butterflies are
-// exact integer factorisations of the matrix products written here, so the integers are the same.  No RDOQ, sign-data hiding, transform
-// skip: all need the running entropy-coder state, which does not exist open-loop.  The CABAC rate of the levels
-// is counted from the state a slice STARTS with: pnn_cabac_tables.h, whose lines the kernel compiles too.
+// exact integer factorisations of the matrix products written here, so the integers are the same.  No RDOQ (nor its own sign hiding),
+// no transform skip: they need bit estimates from the running entropy-coder state, which does not exist open-loop.  Sign-data hiding as
+// xQuant does it with RDOQ 0 (signBitHidingHDQ) reads coefficients, levels, remainders and the scan only: it is
+// here, behind a flag.  The CABAC rate of the levels is counted from the state a slice STARTS with:
+// pnn_cabac_tables.h, whose lines the kernel compiles too.
 // pnn_trquant.hip computes the same on the GPU; tests/test_gpu_trquant.py checks one against the other, tests/test_trquant.py pins this
 // file to a numpy restatement and to recorded outputs of HM's own transforms.
 #include "../../include/pnn_hip.h"
@@ -21,6 +23,10 @@ namespace {
 using namespace pnn::trquant;
 
 bool width_ok(int w) { return w == 4 || w == 8 || w == 16 || w == 32 || w == 64; }
+bool unit_size_ok(int t) { return t == 4 || t == 8 || t == 16 || t == 32; }
+// 0, 1 or 2, and diagonal where the unit is above 8 x 8
+bool scan_ok(int scan, int t) { return scan >= 0 && scan <= 2 && (t <= 8 || scan == pnn::cabac::kScanDiag); }
+const char* const kBadScan = "The scan is not 0 (diagonal), 1 (horizontal) or 2 (vertical), or not diagonal above 8 x 8.\n";
 
 // M[k][x] of one unit size, dense
 struct Matrix {
@@ -70,16 +76,69 @@ void inverse(const Matrix& M, const int* dequant, int* residual)
         }
 }
 
-// quantise -> dequantise -> inverse of one unit's coefficients at one QP; the counts ADD into *nb_nonzero / *sum_abs
-void code_unit(const Matrix& M, const int* coeffs, const QpConsts& q, int* levels, int* dequant, int* residual, uint32_t* nb_nonzero,
-               uint32_t* sum_abs)
+// HM's signBitHidingHDQ over one unit (levels, coeffs, delta_u dense [t][t]), line for line: the groups from the highest scan index
+// down; the first one met with a level is the "last group", whose candidates start at its last level.  (HM's minPos = -1 cannot
+// occur and its uiAbsSum >= 2 guard never decides: include/pnn_hip.h.)
+template <int L>
+void sign_hide_unit(int* levels, const int* coeffs, const int* delta_u, int scan)
 {
-    for (int i = 0; i < M.t * M.t; i++) {
+    constexpr int T = 1 << L, LG = L - 2, NG = 1 << LG;
+    bool last_group = true;                                                // no group with a level has been met yet
+    for (int c = NG * NG - 1; c >= 0; c--) {
+        int cx, cy, pos[16];
+        pnn::cabac::scan_position<LG>(scan, c, &cx, &cy);
+        for (int n = 0; n < 16; n++) {
+            int x, y;
+            pnn::cabac::scan_position<2>(scan, n, &x, &y);
+            pos[n] = (cy * 4 + y) * T + cx * 4 + x;
+        }
+        int first = 16, last = -1, abs_sum = 0;
+        for (int n = 15; n >= 0; n--)
+            if (levels[pos[n]]) { last = n; break; }
+        for (int n = 0; n < 16; n++)
+            if (levels[pos[n]]) { first = n; break; }
+        for (int n = first; n <= last; n++) abs_sum += levels[pos[n]];
+        if (last < 0) continue;
+        if (last - first >= kSbhThreshold) {
+            const int signbit = levels[pos[first]] > 0 ? 0 : 1;
+            if (signbit != (abs_sum & 1)) {
+                int min_cost = kSdhForbidden, min_n = -1, final_change = 0;
+                for (int n = last_group ? last : 15; n >= 0; n--) {
+                    int change;
+                    const int cost = sdh_cost(levels[pos[n]], coeffs[pos[n]], delta_u[pos[n]], n, first, signbit, &change);
+                    if (cost < min_cost) { min_cost = cost; final_change = change; min_n = n; }
+                }
+                levels[pos[min_n]] = sdh_changed_level(levels[pos[min_n]], coeffs[pos[min_n]], final_change);
+            }
+        }
+        last_group = false;
+    }
+}
+void sign_hide_unit(int log2_t, int* levels, const int* coeffs, const int* delta_u, int scan)
+{
+    switch (log2_t) {
+    case 2: sign_hide_unit<2>(levels, coeffs, delta_u, scan); break;
+    case 3: sign_hide_unit<3>(levels, coeffs, delta_u, scan); break;
+    case 4: sign_hide_unit<4>(levels, coeffs, delta_u, scan); break;
+    default: sign_hide_unit<5>(levels, coeffs, delta_u, scan); break;
+    }
+}
+
+// quantise -> (hide signs) -> dequantise -> inverse of one unit's coefficients at one QP; the counts ADD into *nb_nonzero / *sum_abs.
+// levels: as quantised; hidden: what is dequantised (the same array may serve for both; equal without sdh)
+void code_unit(const Matrix& M, const int* coeffs, const QpConsts& q, int scan, bool sdh, int* levels, int* delta_u, int* hidden, int* dequant,
+               int* residual, uint32_t* nb_nonzero, uint32_t* sum_abs)
+{
+    const int tt = M.t * M.t;
+    for (int i = 0; i < tt; i++) {
         int mag;
-        levels[i] = quant_level(coeffs[i], q, &mag);
-        dequant[i] = dequant_level(levels[i], q);
-        *nb_nonzero += levels[i] != 0;
-        *sum_abs += (uint32_t)mag;
+        hidden[i] = levels[i] = quant_level(coeffs[i], q, &mag, &delta_u[i]);
+        *sum_abs += (uint32_t)mag;                                             // HM's uiAbsSum: before the clip, before the hiding
+    }
+    if (sdh) sign_hide_unit(M.log2_t, hidden, coeffs, delta_u, scan);
+    for (int i = 0; i < tt; i++) {
+        dequant[i] = dequant_level(hidden[i], q);
+        *nb_nonzero += hidden[i] != 0;
     }
     inverse(M, dequant, residual);
 }
@@ -102,10 +161,17 @@ struct InitStates {
         for (int i = 0; i < pnn::cabac::kNumCtx; i++) s[i] = (uint8_t)pnn::cabac::init_state(qp, pnn::cabac::init_value(i));
     }
 };
-uint64_t unit_rate(int log2_t, const int* levels, int scan, const InitStates& init)
+uint64_t unit_rate(int log2_t, const int* levels, int scan, const InitStates& init, bool sdh)
 {
     using namespace pnn::cabac;
     uint8_t state[kNumCtx];
+    if (sdh)
+        switch (log2_t) {
+        case 2: return pnn::cabac::unit_rate<2, true>(levels, scan, init.s, state, rom_tables());
+        case 3: return pnn::cabac::unit_rate<3, true>(levels, scan, init.s, state, rom_tables());
+        case 4: return pnn::cabac::unit_rate<4, true>(levels, scan, init.s, state, rom_tables());
+        default: return pnn::cabac::unit_rate<5, true>(levels, scan, init.s, state, rom_tables());
+        }
     switch (log2_t) {
     case 2: return pnn::cabac::unit_rate<2>(levels, scan, init.s, state, rom_tables());
     case 3: return pnn::cabac::unit_rate<3>(levels, scan, init.s, state, rom_tables());
@@ -126,11 +192,19 @@ extern "C" int pnn_trquant_rate_host(const uint8_t* predictions, const uint8_t* 
                                      int nb_qps, uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon,
                                      uint64_t* rate)
 {
+    return pnn_trquant_sdh_host(predictions, targets, width, n, modes, qps, nb_qps, sses_recon, nb_nonzero, sum_abs_levels, recon, rate, 0);
+}
+
+extern "C" int pnn_trquant_sdh_host(const uint8_t* predictions, const uint8_t* targets, int width, int n, const uint8_t* modes, const int* qps,
+                                    int nb_qps, uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon,
+                                    uint64_t* rate, int sign_data_hiding)
+{
+    const bool sdh = sign_data_hiding != 0;
     if (!width_ok(width)) { fprintf(stderr, "The width of the target patch is not 4, 8, 16, 32 or 64.\n"); return PNN_E_ARG; }
     if (n < 0 || (n > 0 && (!predictions || !targets))) { fprintf(stderr, "Bad batch size or NULL inputs.\n"); return PNN_E_ARG; }
     if (!qps_ok(qps, nb_qps)) { fprintf(stderr, "The QPs are not 1 to 8 integers in [0, 51].\n"); return PNN_E_ARG; }
     if (!sses_recon && !nb_nonzero && !sum_abs_levels && !recon && !rate) { fprintf(stderr, "Every output is NULL.\n"); return PNN_E_ARG; }
-    if (modes && !rate) { fprintf(stderr, "Intra modes without a rate output.\n"); return PNN_E_ARG; }
+    if (modes && !rate && !sdh) { fprintf(stderr, "Intra modes without a rate output or sign-data hiding.\n"); return PNN_E_ARG; }
     for (long b = 0; modes && b < n; b++)
         if (modes[b] > 34) { fprintf(stderr, "An intra mode is above 34.\n"); return PNN_E_ARG; }
     const Matrix M(log2_tu(width));
@@ -138,7 +212,7 @@ extern "C" int pnn_trquant_rate_host(const uint8_t* predictions, const uint8_t* 
     const size_t w2 = (size_t)width * width;
     std::vector<InitStates> init;
     for (int qi = 0; rate && qi < nb_qps; qi++) init.emplace_back(qps[qi]);
-    int residual[32 * 32], coeffs[32 * 32], levels[32 * 32], dequant[32 * 32], decoded[32 * 32];
+    int residual[32 * 32], coeffs[32 * 32], levels[32 * 32], delta_u[32 * 32], dequant[32 * 32], decoded[32 * 32];
     for (long b = 0; b < n; b++) {
         const uint8_t* prediction = predictions + b * w2;
         const uint8_t* target = targets + b * w2;
@@ -150,8 +224,9 @@ extern "C" int pnn_trquant_rate_host(const uint8_t* predictions, const uint8_t* 
                 unit_residual(prediction, target, width, t, uy, ux, residual);
                 forward(M, residual, coeffs);                                  // once per unit, whatever the number of QPs
                 for (int qi = 0; qi < nb_qps; qi++) {
-                    code_unit(M, coeffs, qp_consts(M.log2_t, qps[qi]), levels, dequant, decoded, &nonzero[qi], &sum_abs[qi]);
-                    if (rate) bits[qi] += unit_rate(M.log2_t, levels, scan, init[qi]);
+                    code_unit(M, coeffs, qp_consts(M.log2_t, qps[qi]), scan, sdh, levels, delta_u, levels, dequant, decoded, &nonzero[qi],
+                              &sum_abs[qi]);
+                    if (rate) bits[qi] += unit_rate(M.log2_t, levels, scan, init[qi], sdh);
                     for (int y = 0; y < t; y++)
                         for (int x = 0; x < t; x++) {
                             const size_t i = (size_t)(uy * t + y) * width + ux * t + x;
@@ -174,38 +249,61 @@ extern "C" int pnn_trquant_rate_host(const uint8_t* predictions, const uint8_t* 
 
 extern "C" int pnn_cabac_rate_levels_host(const int32_t* levels, int t, int scan, int qp, uint64_t* rate)
 {
-    if (t != 4 && t != 8 && t != 16 && t != 32) { fprintf(stderr, "The unit size is not 4, 8, 16 or 32.\n"); return PNN_E_ARG; }
+    return pnn_cabac_rate_levels_sdh_host(levels, t, scan, qp, 0, rate);
+}
+
+extern "C" int pnn_cabac_rate_levels_sdh_host(const int32_t* levels, int t, int scan, int qp, int sign_data_hiding, uint64_t* rate)
+{
+    if (!unit_size_ok(t)) { fprintf(stderr, "The unit size is not 4, 8, 16 or 32.\n"); return PNN_E_ARG; }
     if (!levels || !rate) { fprintf(stderr, "NULL pointer.\n"); return PNN_E_ARG; }
-    if (scan < 0 || scan > 2 || (t > 8 && scan != pnn::cabac::kScanDiag)) {
-        fprintf(stderr, "The scan is not 0 (diagonal), 1 (horizontal) or 2 (vertical), or not diagonal above 8 x 8.\n");
-        return PNN_E_ARG;
-    }
+    if (!scan_ok(scan, t)) { fprintf(stderr, kBadScan); return PNN_E_ARG; }
     if (!qps_ok(&qp, 1)) { fprintf(stderr, "The QP does not belong to [0, 51].\n"); return PNN_E_ARG; }
     for (int i = 0; i < t * t; i++)
         if (levels[i] < -32768 || levels[i] > 32767) { fprintf(stderr, "A level is outside [-32768, 32767].\n"); return PNN_E_ARG; }
-    *rate = unit_rate(log2_tu(t), levels, scan, InitStates(qp));
+    *rate = unit_rate(log2_tu(t), levels, scan, InitStates(qp), sign_data_hiding != 0);
+    return PNN_OK;
+}
+
+extern "C" int pnn_sign_hide_unit_host(int32_t* levels, const int32_t* coeffs, const int32_t* delta_u, int t, int scan)
+{
+    if (!unit_size_ok(t)) { fprintf(stderr, "The unit size is not 4, 8, 16 or 32.\n"); return PNN_E_ARG; }
+    if (!levels || !coeffs || !delta_u) { fprintf(stderr, "NULL pointer.\n"); return PNN_E_ARG; }
+    if (!scan_ok(scan, t)) { fprintf(stderr, kBadScan); return PNN_E_ARG; }
+    for (int i = 0; i < t * t; i++) {
+        if (levels[i] < -32768 || levels[i] > 32767) { fprintf(stderr, "A level is outside [-32768, 32767].\n"); return PNN_E_ARG; }
+        if (delta_u[i] == INT32_MIN) { fprintf(stderr, "A remainder cannot be negated.\n"); return PNN_E_ARG; }
+    }
+    sign_hide_unit(log2_tu(t), levels, coeffs, delta_u, scan);
     return PNN_OK;
 }
 
 extern "C" int pnn_trquant_stages_host(const uint8_t* prediction, const uint8_t* target, int width, int qp, int32_t* coeffs, int32_t* levels,
                                        int32_t* dequant, int32_t* residual)
 {
+    return pnn_trquant_stages_sdh_host(prediction, target, width, qp, 0, 0, coeffs, levels, nullptr, nullptr, dequant, residual);
+}
+
+extern "C" int pnn_trquant_stages_sdh_host(const uint8_t* prediction, const uint8_t* target, int width, int qp, int scan, int sign_data_hiding,
+                                           int32_t* coeffs, int32_t* levels, int32_t* delta_u, int32_t* levels_hidden, int32_t* dequant,
+                                           int32_t* residual)
+{
     if (!width_ok(width)) { fprintf(stderr, "The width of the target patch is not 4, 8, 16, 32 or 64.\n"); return PNN_E_ARG; }
     if (!prediction || !target) { fprintf(stderr, "NULL pointer.\n"); return PNN_E_ARG; }
     if (!qps_ok(&qp, 1)) { fprintf(stderr, "The QP does not belong to [0, 51].\n"); return PNN_E_ARG; }
-    if (!coeffs && !levels && !dequant && !residual) { fprintf(stderr, "Every output is NULL.\n"); return PNN_E_ARG; }
+    if (!scan_ok(scan, width)) { fprintf(stderr, kBadScan); return PNN_E_ARG; }
+    if (!coeffs && !levels && !delta_u && !levels_hidden && !dequant && !residual) { fprintf(stderr, "Every output is NULL.\n"); return PNN_E_ARG; }
     const Matrix M(log2_tu(width));
     const int t = M.t, units = width / t;
     const QpConsts q = qp_consts(M.log2_t, qp);
-    int in[32 * 32], stage[4][32 * 32];
-    int32_t* const outs[4] = {coeffs, levels, dequant, residual};
+    int in[32 * 32], stage[6][32 * 32];
+    int32_t* const outs[6] = {coeffs, levels, delta_u, levels_hidden, dequant, residual};
     for (int uy = 0; uy < units; uy++)
         for (int ux = 0; ux < units; ux++) {
             uint32_t nonzero = 0, sum_abs = 0;
             unit_residual(prediction, target, width, t, uy, ux, in);
             forward(M, in, stage[0]);
-            code_unit(M, stage[0], q, stage[1], stage[2], stage[3], &nonzero, &sum_abs);
-            for (int s = 0; s < 4; s++)                                        // each unit's arrays where the unit lies in the block
+            code_unit(M, stage[0], q, scan, sign_data_hiding != 0, stage[1], stage[2], stage[3], stage[4], stage[5], &nonzero, &sum_abs);
+            for (int s = 0; s < 6; s++)                                        // each unit's arrays where the unit lies in the block
                 if (outs[s])
                     for (int y = 0; y < t; y++)
                         for (int x = 0; x < t; x++) outs[s][(size_t)(uy * t + y) * width + ux * t + x] = stage[s][y * t + x];

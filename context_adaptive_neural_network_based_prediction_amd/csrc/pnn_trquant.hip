@@ -26,6 +26,17 @@
 // states and the two tables in LDS.  The other lanes go on to the inverse transform and wait at its barrier, so the levels stay until
 // the walk is over; the next QP overwrites them only behind that barrier.  The bits of a block's units add in a 64-bit LDS slot.  The
 // instantiations without RATE are the kernel as it was: no statement of theirs mentions the rate's arrays.
+//
+// SDH: the instantiations with SDH put HM's sign-data hiding (signBitHidingHDQ) between quantisation and
+// dequantisation.  The levels and the remainders deltaU of the current QP go to LDS, dense per unit; then ONE LANE PER SCAN POSITION,
+// 16 consecutive lanes per 4 x 4 group (the workgroup's 1024 positions in four rounds of 256 lanes): a lane looks its block position
+// up in its unit's scan once, at the kernel's start, and per QP reads its level, coefficient and remainder from there.  first, last,
+// the parity and the sign bit of a group are ballots cut to the group's 16 bits; the unit's last group is the highest group with a
+// level -- of the wave's ballot where a unit fits a wave (T <= 8), else one LDS max per unit and a barrier; the winner is a 16-lane min
+// (__shfl_xor below 16) over the key (cost + 256) << 4 | (15 - n) -- the costs lie in [-170, 170], the tie goes to the highest n -- and
+// the winning lane rewrites its one level in LDS.  Behind a barrier every lane reads back the levels of its own samples, counts the
+// nonzero ones and dequantises; from there on the kernel is the one above (the rate walk with the SDH rule of unit_rate).  The
+// instantiations without SDH are the kernels as they were: no statement of theirs mentions the hiding's arrays.
 #include "pnn_cabac_tables.h"
 #include "pnn_kernels.h"
 #include "pnn_trquant_tables.h"
@@ -37,7 +48,7 @@ constexpr int kTqThreads = 256;
 constexpr int kElems = 1024;                      // residual samples a workgroup holds: one 32 x 32 unit, or G smaller blocks
 constexpr int kPerLane = kElems / kTqThreads;
 
-template <int W, bool RATE>
+template <int W, bool RATE, bool SDH>
 __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams p)
 {
     using namespace trquant;
@@ -57,6 +68,17 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
         __shared__ uint8_t lps_s[64], states_s[G * cabac::kNumCtx];
         __shared__ unsigned long long bits_s[kMaxQps * G];
         lev = lev_s; ebits = ebits_s; lps = lps_s; states = states_s; bits = bits_s;
+    }
+
+    // the hiding's arrays exist in the SDH instantiations only (the levels are the rate's array where there is one)
+    int* du = nullptr; int* lastg = nullptr;
+    if constexpr (SDH) {
+        __shared__ int du_s[kElems], lastg_s[G];
+        du = du_s; lastg = lastg_s;
+        if constexpr (!RATE) {
+            __shared__ int lev_sdh[kElems];
+            lev = lev_sdh;
+        }
     }
 
     const int tid = threadIdx.x;
@@ -79,6 +101,21 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
         base[j] = e / TT * TT;
         const long b = blk0 + e / TT;
         blk[j] = b < p.N ? b : -1;
+    }
+
+    // SDH: lane tid of round j is scan position (256 j + tid) % TT of unit (256 j + tid) / TT; where that lies in LDS
+    [[maybe_unused]] int hide_at[kPerLane];
+    if constexpr (SDH) {
+#pragma unroll
+        for (int j = 0; j < kPerLane; j++) {
+            const int s = j * kTqThreads + tid, u = s / TT, i = s % TT;
+            const long b = blk0 + u;
+            const int scan = p.modes && b < p.N ? cabac::scan_of_mode(L, p.modes[b]) : cabac::kScanDiag;
+            int cx, cy, x, y;
+            cabac::scan_position<L - 2>(scan, i >> 4, &cx, &cy);
+            cabac::scan_position<2>(scan, i & 15, &x, &y);
+            hide_at[j] = u * TT + (cy * 4 + y) * T + cx * 4 + x;
+        }
     }
 
 #pragma unroll 1
@@ -121,20 +158,72 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
         for (int qi = 0; qi < p.nb_qps; qi++) {
             const QpConsts qc = p.qp[qi];
             unsigned nonzero[kPerLane], sum_abs[kPerLane], sse[kPerLane];
+            if constexpr (SDH) {
 #pragma unroll
-            for (int j = 0; j < kPerLane; j++) {
-                int mag;
-                const int level = quant_level(coef[j * kTqThreads + tid], qc, &mag);
-                nonzero[j] = level != 0;
-                sum_abs[j] = (unsigned)mag;
-                buf_a[j * kTqThreads + tid] = dequant_level(level, qc);
-                if constexpr (RATE) lev[j * kTqThreads + tid] = level;
+                for (int j = 0; j < kPerLane; j++) {
+                    int mag, delta_u;
+                    lev[j * kTqThreads + tid] = quant_level(coef[j * kTqThreads + tid], qc, &mag, &delta_u);
+                    du[j * kTqThreads + tid] = delta_u;
+                    sum_abs[j] = (unsigned)mag;                    // HM's uiAbsSum: before the hiding
+                }
+                if (TT > 64 && tid < G) lastg[tid] = -1;
+                __syncthreads();
+                // one lane per scan position: 16 consecutive lanes are one group, n = tid % 16
+                const int n = tid & 15, shift = tid & 48;
+                int lv[kPerLane], cf[kPerLane], dl[kPerLane];
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) {
+                    lv[j] = lev[hide_at[j]]; cf[j] = coef[hide_at[j]]; dl[j] = du[hide_at[j]];
+                    if (TT > 64) {                                 // the unit's last group: the highest one with a level
+                        const unsigned long long any = __ballot(lv[j] != 0);
+                        if (any && (tid & 63) == 0)
+                            atomicMax(&lastg[(j * kTqThreads + tid) / TT], ((j * kTqThreads + tid) % TT >> 4) + ((63 - __builtin_clzll(any)) >> 4));
+                    }
+                }
+                if (TT > 64) __syncthreads();
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) {
+                    const unsigned long long any = __ballot(lv[j] != 0);
+                    const unsigned nz = (unsigned)(any >> shift) & 0xffffu, neg = (unsigned)(__ballot(lv[j] < 0) >> shift) & 0xffffu;
+                    const unsigned odd = (unsigned)(__ballot(lv[j] & 1) >> shift) & 0xffffu;
+                    const int first = nz ? __builtin_ctz(nz) : 16, last = nz ? 31 - __builtin_clz(nz) : -1;
+                    const int signbit = (int)(neg >> (first & 15)) & 1;
+                    const int c = (j * kTqThreads + tid) % TT >> 4;
+                    const bool last_group = TT == 16 ? true : TT == 64 ? c == (63 - __builtin_clzll(any | 1)) >> 4
+                                                                       : c == lastg[(j * kTqThreads + tid) / TT];
+                    int key = kSdhForbidden, change = 0;
+                    if (last - first >= kSbhThreshold && signbit != (__builtin_popcount(odd) & 1) && n <= (last_group ? last : 15)) {
+                        const int cost = sdh_cost(lv[j], cf[j], dl[j], n, first, signbit, &change);
+                        if (cost != kSdhForbidden) key = ((cost + 256) << 4) | (15 - n);
+                    }
+                    int best = key;
+#pragma unroll
+                    for (int d = 8; d > 0; d >>= 1) best = min(best, __shfl_xor(best, d));
+                    if (key == best && key != kSdhForbidden) lev[hide_at[j]] = sdh_changed_level(lv[j], cf[j], change);
+                }
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) {
+                    const int level = lev[j * kTqThreads + tid];
+                    nonzero[j] = level != 0;
+                    buf_a[j * kTqThreads + tid] = dequant_level(level, qc);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) {
+                    int mag;
+                    const int level = quant_level(coef[j * kTqThreads + tid], qc, &mag);
+                    nonzero[j] = level != 0;
+                    sum_abs[j] = (unsigned)mag;
+                    buf_a[j * kTqThreads + tid] = dequant_level(level, qc);
+                    if constexpr (RATE) lev[j * kTqThreads + tid] = level;
+                }
             }
             __syncthreads();
             if constexpr (RATE) {
                 if (tid < G && blk0 + tid < p.N) {    // lane g codes unit g (units past N have no slot to add to)
                     const int scan = p.modes ? cabac::scan_of_mode(L, p.modes[blk0 + tid]) : cabac::kScanDiag;
-                    bits[qi * G + tid] += cabac::unit_rate<L>(lev + tid * TT, scan, p.init_states[qi], states + tid * cabac::kNumCtx,
+                    bits[qi * G + tid] += cabac::unit_rate<L, SDH>(lev + tid * TT, scan, p.init_states[qi], states + tid * cabac::kNumCtx,
                                                               cabac::Tables{ebits, lps});
                 }
             }
@@ -202,6 +291,19 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
     }
 }
 
+template <bool RATE, bool SDH>
+hipError_t launch_width(const TrQuantParams& p, dim3 grid, dim3 block, hipStream_t s)
+{
+    switch (p.w) {
+    case 4: hipLaunchKernelGGL((trquant_kernel<4, RATE, SDH>), grid, block, 0, s, p); break;
+    case 8: hipLaunchKernelGGL((trquant_kernel<8, RATE, SDH>), grid, block, 0, s, p); break;
+    case 16: hipLaunchKernelGGL((trquant_kernel<16, RATE, SDH>), grid, block, 0, s, p); break;
+    case 32: hipLaunchKernelGGL((trquant_kernel<32, RATE, SDH>), grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL((trquant_kernel<64, RATE, SDH>), grid, block, 0, s, p); break;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
 
 int trquant_blocks_per_workgroup(int w) { return w >= 32 ? 1 : kElems / (w * w); }
@@ -213,24 +315,8 @@ hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s)
     if (trquant::log2_tu(p.w) < 0) return hipErrorInvalidValue;
     const int g = trquant_blocks_per_workgroup(p.w);
     const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kTqThreads);
-    if (p.rate) {
-        switch (p.w) {
-        case 4: hipLaunchKernelGGL((trquant_kernel<4, true>), grid, block, 0, s, p); break;
-        case 8: hipLaunchKernelGGL((trquant_kernel<8, true>), grid, block, 0, s, p); break;
-        case 16: hipLaunchKernelGGL((trquant_kernel<16, true>), grid, block, 0, s, p); break;
-        case 32: hipLaunchKernelGGL((trquant_kernel<32, true>), grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL((trquant_kernel<64, true>), grid, block, 0, s, p); break;
-        }
-        return hipGetLastError();
-    }
-    switch (p.w) {
-    case 4: hipLaunchKernelGGL((trquant_kernel<4, false>), grid, block, 0, s, p); break;
-    case 8: hipLaunchKernelGGL((trquant_kernel<8, false>), grid, block, 0, s, p); break;
-    case 16: hipLaunchKernelGGL((trquant_kernel<16, false>), grid, block, 0, s, p); break;
-    case 32: hipLaunchKernelGGL((trquant_kernel<32, false>), grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL((trquant_kernel<64, false>), grid, block, 0, s, p); break;
-    }
-    return hipGetLastError();
+    if (p.rate) return p.sdh ? launch_width<true, true>(p, grid, block, s) : launch_width<true, false>(p, grid, block, s);
+    return p.sdh ? launch_width<false, true>(p, grid, block, s) : launch_width<false, false>(p, grid, block, s);
 }
 
 }  // namespace pnn

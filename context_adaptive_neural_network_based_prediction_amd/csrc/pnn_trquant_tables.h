@@ -85,6 +85,43 @@ PNN_TQ_HD inline int quant_level(int coeff, const QpConsts& q, int* mag)
     return clip16(coeff < 0 ? -*mag : *mag);
 }
 
+// the same with xQuant's rounding remainder, which sign-data hiding costs its changes by:
+//   deltaU = (|C| scale - (mag << qbits)) >> (qbits - 8), in 64 bits; qbits - 8 >= 8 for every unit size and QP.
+// mag 2^qbits <= |C| scale + add < (mag + 1) 2^qbits and add = 171 * 2^(qbits - 9), so deltaU lies in [-86, 170]
+constexpr int kDeltaUMin = -86, kDeltaUMax = 170;
+PNN_TQ_HD inline int quant_level(int coeff, const QpConsts& q, int* mag, int* delta_u)
+{
+    const int a = coeff < 0 ? -coeff : coeff;
+    const long long tmp = (long long)a * q.scale;
+    *mag = (int)((tmp + q.add) >> q.qbits);
+    *delta_u = (int)((tmp - ((long long)*mag << q.qbits)) >> (q.qbits - 8));
+    return clip16(coeff < 0 ? -*mag : *mag);
+}
+
+// Sign-data hiding (TComTrQuant::signBitHidingHDQ): a 4 x 4 group whose first and last nonzero scan positions are at least
+// kSbhThreshold apart hides the sign of the first one in the parity of its levels.  What changing position n of such a group costs and
+// which way it goes (the table of include/pnn_hip.h): first = the group's lowest nonzero position, signbit = the sign to hide.
+constexpr int kSbhThreshold = 4;
+constexpr int kSdhForbidden = 0x7fffffff;
+PNN_TQ_HD inline int sdh_cost(int level, int coeff, int delta_u, int n, int first, int signbit, int* change)
+{
+    *change = 1;
+    if (level != 0) {
+        if (delta_u > 0) return -delta_u;
+        if (n == first && (level == 1 || level == -1)) return kSdhForbidden;
+        *change = -1;
+        return delta_u;
+    }
+    if (n < first && (coeff >= 0 ? 0 : 1) != signbit) return kSdhForbidden;
+    return -delta_u;
+}
+// the winner's new level: +-32767 / -32768 can only come down
+PNN_TQ_HD inline int sdh_changed_level(int level, int coeff, int change)
+{
+    if (level == 32767 || level == -32768) change = -1;
+    return coeff >= 0 ? level + change : level - change;
+}
+
 PNN_TQ_HD inline int dequant_level(int level, const QpConsts& q)
 {
     const int v = level * q.inv;          // |v| <= 32768 * 72

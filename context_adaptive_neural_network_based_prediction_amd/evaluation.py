@@ -183,7 +183,7 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                               tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
-                              transform_qps=(), transform_rate=False):
+                              transform_qps=(), transform_rate=False, transform_sign_hiding=False):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -228,14 +228,22 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     under the diagonal scan, this project's definition.  The results join the one download.  New keys: 'rate_bits_pnn',
     'rate_bits_hevc_best_mode' (float64 [nb_qps, N], bits) and 'frequency_rate_win_pnn' (one float per QP: the share of blocks whose PNN
     residual costs strictly fewer bits).  Equal to intraprediction.transform_code(rate=True, modes=...) on the dictionary's own
-    predictions, targets and modes.  With transform_rate=False nothing changes: not a key, a call or a byte."""
+    predictions, targets and modes.  With transform_rate=False nothing changes: not a key, a call or a byte.
+
+    transform_sign_hiding=True (with transform_qps; ValueError without, before anything touches the GPU) makes the two transform calls
+    pnn_trquant_sdh_device with the flag set, whether or not transform_rate is: HM's sign-data hiding as its quantiser does it with
+    RDOQ 0 and SignHideFlag 1, HM's default (include/pnn_hip.h, "sign-data hiding").  The best mode's call gets the mode array the score
+    call left on the device (the scan now shapes the levels), the PNN's gets none.  Same keys, computed from the levels after hiding
+    ('sum_abs_levels_*' stays the sum before it; 'rate_bits_*' does not charge the hidden signs), plus 'transform_sign_hiding': True.
+    Equal to intraprediction.transform_code(sign_data_hiding=True, modes=...) on the dictionary's own predictions, targets and modes.
+    With transform_sign_hiding=False nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
-                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate)
+                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                                    tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
-                                   transform_qps=(), transform_rate=False):
+                                   transform_qps=(), transform_rate=False, transform_sign_hiding=False):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -250,14 +258,15 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
     original, as in the table above.  reference_smoothing: as for score_masks_from_pictures; the smoothed line is built from the decoded
     plane's samples, as the unsmoothed one is.  transform_qps: as for score_masks_from_pictures; the predictions that get coded are the
     ones made from the decoded plane, the residual's and the SSE's targets come from the original, as in the table above.
-    transform_rate: as for score_masks_from_pictures."""
+    transform_rate, transform_sign_hiding: as for score_masks_from_pictures."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
                         tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps,
-                        transform_rate)
+                        transform_rate, transform_sign_hiding)
 
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                 keep_predictions, first_pass=False, reference_smoothing=0, transform_qps=(), transform_rate=False):
+                 keep_predictions, first_pass=False, reference_smoothing=0, transform_qps=(), transform_rate=False,
+                 transform_sign_hiding=False):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer."""
     if ch.dtype != np.uint8:
@@ -287,6 +296,8 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         transform_qps = intraprediction._check_qps(transform_qps)
     if transform_rate and len(transform_qps) == 0:
         raise ValueError('`transform_rate` is set without `transform_qps`.')
+    if transform_sign_hiding and len(transform_qps) == 0:
+        raise ValueError('`transform_sign_hiding` is set without `transform_qps`.')
     masks = [(int(m[0]), int(m[1])) for m in tuples_width_height_masks]
     rows, cols = row_1sts.astype(np.int64).ravel(), col_1sts.astype(np.int64).ravel()
     n_pos = rows.size
@@ -370,7 +381,12 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                         *(blocks + (ptr['predictions_pnn'], reference_smoothing) + ranking)), predictor.ctx)
             for column, predictions in coded:             # both predictions are on the device, and so are the first mask's targets
                 counts = (ptr['sses_recon_' + column], ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None)
-                if transform_rate:                        # the best mode's scan follows its mode, which the score call left; the PNN has none
+                if transform_sign_hiding:                 # the scan shapes the levels: the best mode's array, with or without the rate
+                    modes = ptr['indices_hevc'] if column == 'hevc_best_mode' else None
+                    _lib.check(L.pnn_trquant_sdh_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps,
+                                                        *(counts + (ptr['rate_' + column] if transform_rate else None, 1,
+                                                                    ctypes.c_void_p(stream.cuda_stream)))), predictor.ctx)
+                elif transform_rate:                      # the best mode's scan follows its mode, which the score call left; the PNN has none
                     modes = ptr['indices_hevc'] if column == 'hevc_best_mode' else None
                     _lib.check(L.pnn_trquant_rate_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps,
                                                          *(counts + (ptr['rate_' + column], ctypes.c_void_p(stream.cuda_stream)))), predictor.ctx)
@@ -410,6 +426,8 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
             dictionary_performance['frequency_rate_win_pnn'] = [
                 float(np.count_nonzero(dictionary_performance['rate_bits_pnn'][q] < dictionary_performance['rate_bits_hevc_best_mode'][q])) / n
                 for q in range(nb_qps)]
+        if transform_sign_hiding:
+            dictionary_performance['transform_sign_hiding'] = True
         if keep_predictions:
             if first:
                 targets_uint8 = view['targets'].copy()

@@ -359,7 +359,8 @@ def _blocks_uint8(array_uint8, name):
     return np.ascontiguousarray(array_uint8)
 
 
-def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reconstructions=False, modes=None, rate=False):
+def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reconstructions=False, modes=None, rate=False,
+                   sign_data_hiding=False):
     """Open-loop HEVC transform coding of N predictions against their targets (uint8 [N, w, w] or [N, w, w, 1]) at the 1 to 8 QPs of
     `qps` (integers in [0, 51]): HM's residual path with RDOQ 0 -- forward transform, quantisation, dequantisation, inverse transform,
     reconstruction -- as include/pnn_hip.h defines it (T = w up to 32, the four 32 x 32 quadrants of the one prediction at w = 64; no
@@ -371,7 +372,11 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     unit(s) from the I-slice initial contexts of the QP (include/pnn_hip.h, "the CABAC rate of the coded levels"; cbf_luma and mode bits
     not counted) -- the uint64 count of pnn_trquant_rate_host / _device over 32768.  modes (with rate only): uint8 [N] intra modes in
     [0, 34] that pick each block's scan at w = 4 and 8; None codes every block under the diagonal scan.  With rate=False the dictionary
-    is the one above."""
+    is the one above.
+    sign_data_hiding=True codes the way HM does with SignHideFlag 1 (its default) and RDOQ 0: signBitHidingHDQ between quantisation and
+    dequantisation (include/pnn_hip.h, "sign-data hiding"; pnn_trquant_sdh_host / _device).  Same keys; nb_nonzero_levels, the
+    reconstruction, sses_recon and rate_bits follow the levels after hiding (the hidden signs cost no bin), sum_abs_levels stays the
+    sum before it.  `modes` is then allowed without `rate`: the scan shapes the levels.  With False nothing changes."""
     qps = _check_qps(qps)
     predictions, targets = _blocks_uint8(predictions_uint8, 'predictions_uint8'), _blocks_uint8(targets_uint8, 'targets_uint8')
     if predictions.shape != targets.shape:
@@ -380,8 +385,8 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     nq = len(qps)
     c_qps = (ctypes.c_int * nq)(*qps)
     L = _lib.lib()
-    if rate:
-        return _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_reconstructions, modes)
+    if rate or sign_data_hiding:
+        return _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_reconstructions, modes, rate, bool(sign_data_hiding))
     if modes is not None:
         raise ValueError('`modes` is given without `rate`.')
     if device is None:
@@ -410,8 +415,9 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     return result
 
 
-def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_reconstructions, modes):
-    """transform_code(rate=True) behind its argument checks: the entries with the rate, host or device."""
+def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_reconstructions, modes, rate=True, sign_data_hiding=False):
+    """transform_code(rate=True) and transform_code(sign_data_hiding=True) behind their argument checks: the entries with the rate (and
+    with the flag, when it is set), host or device."""
     n, w, nq = targets.shape[0], targets.shape[1], len(qps)
     if modes is not None:
         modes = np.asarray(modes)
@@ -422,33 +428,40 @@ def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_recon
         modes = np.ascontiguousarray(modes.astype(np.uint8))
     if device is None:
         sses, nonzero, sum_abs = (np.zeros((nq, n), np.uint32) for _ in range(3))
-        bits = np.zeros((nq, n), np.uint64)
+        bits = np.zeros((nq, n), np.uint64) if rate else None
         recon = np.zeros((nq, n, w, w), np.uint8) if keep_reconstructions else None
-        rc = L.pnn_trquant_rate_host(predictions.ctypes.data, targets.ctypes.data, w, n, None if modes is None else modes.ctypes.data, c_qps,
-                                     nq, sses.ctypes.data, nonzero.ctypes.data, sum_abs.ctypes.data,
-                                     None if recon is None else recon.ctypes.data, bits.ctypes.data)
+        outputs = (sses.ctypes.data, nonzero.ctypes.data, sum_abs.ctypes.data, None if recon is None else recon.ctypes.data,
+                   None if bits is None else bits.ctypes.data)
+        blocks = (predictions.ctypes.data, targets.ctypes.data, w, n, None if modes is None else modes.ctypes.data, c_qps, nq)
+        if sign_data_hiding:
+            rc = L.pnn_trquant_sdh_host(*(blocks + outputs + (1,)))
+        else:
+            rc = L.pnn_trquant_rate_host(*(blocks + outputs))
         if rc != 0:
-            raise ValueError('pnn_trquant_rate_host refused the arguments (width %d, %d blocks).' % (w, n))
+            raise ValueError('pnn_trquant_%s_host refused the arguments (width %d, %d blocks).' % ('sdh' if sign_data_hiding else 'rate', w, n))
     else:
         import torch
         dev = torch.device("cuda", device)
         d_pred, d_tg = torch.from_numpy(predictions).to(dev), torch.from_numpy(targets).to(dev)
         d_modes = None if modes is None else torch.from_numpy(modes).to(dev)
         d_counts = torch.zeros((3, nq, n), dtype=torch.int32, device=dev)
-        d_bits = torch.zeros((nq, n), dtype=torch.int64, device=dev)
+        d_bits = torch.zeros((nq, n), dtype=torch.int64, device=dev) if rate else None
         d_recon = torch.zeros((nq, n, w, w), dtype=torch.uint8, device=dev) if keep_reconstructions else None
         stream = torch.cuda.current_stream(dev)
+        blocks = (_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, None if d_modes is None else d_modes.data_ptr(), c_qps, nq,
+                  d_counts[0].data_ptr(), d_counts[1].data_ptr(), d_counts[2].data_ptr(), None if d_recon is None else d_recon.data_ptr(),
+                  None if d_bits is None else d_bits.data_ptr())
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_trquant_rate_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n,
-                                                 None if d_modes is None else d_modes.data_ptr(), c_qps, nq, d_counts[0].data_ptr(),
-                                                 d_counts[1].data_ptr(), d_counts[2].data_ptr(),
-                                                 None if d_recon is None else d_recon.data_ptr(), d_bits.data_ptr(),
-                                                 ctypes.c_void_p(stream.cuda_stream)), _context(device))
+            if sign_data_hiding:
+                _lib.check(L.pnn_trquant_sdh_device(*(blocks + (1, ctypes.c_void_p(stream.cuda_stream)))), _context(device))
+            else:
+                _lib.check(L.pnn_trquant_rate_device(*(blocks + (ctypes.c_void_p(stream.cuda_stream),))), _context(device))
         sses, nonzero, sum_abs = d_counts.cpu().numpy().view(np.uint32)      # (waits for the stream)
-        bits = d_bits.cpu().numpy().view(np.uint64)
+        bits = None if d_bits is None else d_bits.cpu().numpy().view(np.uint64)
         recon = None if d_recon is None else d_recon.cpu().numpy()
-    result = {'sses_recon': sses, 'nb_nonzero_levels': nonzero, 'sum_abs_levels': sum_abs, 'psnrs_recon': psnrs_from_sses(sses, w),
-              'rate_bits': bits.astype(np.float64) / 32768.}
+    result = {'sses_recon': sses, 'nb_nonzero_levels': nonzero, 'sum_abs_levels': sum_abs, 'psnrs_recon': psnrs_from_sses(sses, w)}
+    if rate:
+        result['rate_bits'] = bits.astype(np.float64) / 32768.
     if keep_reconstructions:
         result['reconstructions_uint8'] = recon
     return result
@@ -457,10 +470,44 @@ def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_recon
 SCANS = {'diagonal': 0, 'horizontal': 1, 'vertical': 2}
 
 
-def cabac_rate_of_levels(levels, scan, qp):
+def _unit_array(array, name, dtype_check=True):
+    """An integer [T, T] array, T in {4, 8, 16, 32}, as contiguous int32."""
+    array = np.asarray(array)
+    if array.ndim != 2 or array.shape[0] != array.shape[1] or array.shape[0] not in (4, 8, 16, 32) or \
+            not np.issubdtype(array.dtype, np.integer):
+        raise ValueError('`%s` is not an integer [T, T] array with T in {4, 8, 16, 32}.' % name)
+    if array.size and (array.min() < -2 ** 31 + 1 or array.max() > 2 ** 31 - 1):
+        raise ValueError('`%s` has a value that does not fit 32 bits.' % name)
+    return np.ascontiguousarray(array.astype(np.int32))
+
+
+def sign_hide_levels(levels, coeffs, delta_u, scan):
+    """HM's TComTrQuant::signBitHidingHDQ on ONE transform unit (pnn_sign_hide_unit_host; include/pnn_hip.h, "sign-data hiding"): the
+    levels after hiding, int32 [T, T], given the levels (each in [-32768, 32767]), the coefficients and the rounding remainders deltaU
+    -- integer [T, T] arrays, T in {4, 8, 16, 32} -- under scan 0 / 'diagonal', 1 / 'horizontal' or 2 / 'vertical' (diagonal only at
+    T = 16 and 32).  The inputs are left as they are."""
+    scan = SCANS.get(scan, scan)
+    hidden, coeffs, delta_u = _unit_array(levels, 'levels'), _unit_array(coeffs, 'coeffs'), _unit_array(delta_u, 'delta_u')
+    if hidden is levels:
+        hidden = hidden.copy()
+    if not hidden.shape == coeffs.shape == delta_u.shape:
+        raise ValueError('`levels`, `coeffs` and `delta_u` differ in shape.')
+    if hidden.min() < -32768 or hidden.max() > 32767:
+        raise ValueError('`levels` has a value outside [-32768, 32767].')
+    if scan not in (0, 1, 2):
+        raise ValueError('`scan` is not 0, 1, 2 or their names.')
+    rc = _lib.lib().pnn_sign_hide_unit_host(hidden.ctypes.data, coeffs.ctypes.data, delta_u.ctypes.data, hidden.shape[0], int(scan))
+    if rc != 0:
+        raise ValueError('pnn_sign_hide_unit_host refused the arguments (T %d, scan %s).' % (hidden.shape[0], scan))
+    return hidden
+
+
+def cabac_rate_of_levels(levels, scan, qp, sign_data_hiding=False):
     """The CABAC rate, in units of 2^-15 bit (a Python int), of ONE transform unit given its levels -- an integer [T, T] array, T in
     {4, 8, 16, 32}, each level in [-32768, 32767] -- under scan 0 / 'diagonal', 1 / 'horizontal' or 2 / 'vertical' (diagonal only at
-    T = 16 and 32) at QP `qp`: pnn_cabac_rate_levels_host, the definition at include/pnn_hip.h.  0 for an all-zero unit."""
+    T = 16 and 32) at QP `qp`: pnn_cabac_rate_levels_host, the definition at include/pnn_hip.h.  0 for an all-zero unit.
+    sign_data_hiding=True: the rate when the hidden signs are not coded (pnn_cabac_rate_levels_sdh_host) -- one bypass bin fewer per
+    group whose first and last nonzero scan positions are at least 4 apart."""
     (qp,) = _check_qps((qp,))
     scan = SCANS.get(scan, scan)
     levels = np.asarray(levels)
@@ -473,16 +520,22 @@ def cabac_rate_of_levels(levels, scan, qp):
         raise ValueError('`scan` is not 0, 1, 2 or their names.')
     levels = np.ascontiguousarray(levels.astype(np.int32))
     bits = ctypes.c_uint64(0)
-    rc = _lib.lib().pnn_cabac_rate_levels_host(levels.ctypes.data, levels.shape[0], int(scan), qp, ctypes.byref(bits))
+    if sign_data_hiding:
+        rc = _lib.lib().pnn_cabac_rate_levels_sdh_host(levels.ctypes.data, levels.shape[0], int(scan), qp, 1, ctypes.byref(bits))
+    else:
+        rc = _lib.lib().pnn_cabac_rate_levels_host(levels.ctypes.data, levels.shape[0], int(scan), qp, ctypes.byref(bits))
     if rc != 0:
         raise ValueError('pnn_cabac_rate_levels_host refused the arguments (T %d, scan %s, QP %d).' % (levels.shape[0], scan, qp))
     return int(bits.value)
 
 
-def transform_stages(prediction_uint8, target_uint8, qp):
+def transform_stages(prediction_uint8, target_uint8, qp, sign_data_hiding=False, scan=0):
     """Every stage of transform_code for ONE block (uint8 [w, w] or [w, w, 1]) at one QP, host code (pnn_trquant_stages_host):
     {'coeffs', 'levels', 'dequant', 'residual'}, int32 [w, w] -- the forward transform's coefficients, the quantised levels, the
-    dequantised coefficients, the inverse transform's residual; at w = 64 each 32 x 32 unit's array lies where the unit lies."""
+    dequantised coefficients, the inverse transform's residual; at w = 64 each 32 x 32 unit's array lies where the unit lies.
+    sign_data_hiding=True (pnn_trquant_stages_sdh_host) hides signs under `scan` (0, 1, 2 or their names; diagonal only at w >= 16) and
+    adds 'delta_u', xQuant's rounding remainders, and 'levels_hidden', the levels after hiding, from which 'dequant' and 'residual'
+    then come; 'levels' stays the quantiser's output.  `scan` is read with the flag only."""
     (qp,) = _check_qps((qp,))
     blocks = []
     for name, block in (('prediction_uint8', prediction_uint8), ('target_uint8', target_uint8)):
@@ -495,6 +548,17 @@ def transform_stages(prediction_uint8, target_uint8, qp):
     if prediction.shape != target.shape:
         raise ValueError('`prediction_uint8.shape` is not equal to `target_uint8.shape`.')
     w = target.shape[0]
+    if sign_data_hiding:
+        scan = SCANS.get(scan, scan)
+        if scan not in (0, 1, 2):
+            raise ValueError('`scan` is not 0, 1, 2 or their names.')
+        names = ('coeffs', 'levels', 'delta_u', 'levels_hidden', 'dequant', 'residual')
+        stages = {name: np.zeros((w, w), np.int32) for name in names}
+        rc = _lib.lib().pnn_trquant_stages_sdh_host(prediction.ctypes.data, target.ctypes.data, w, qp, int(scan), 1,
+                                                    *(stages[name].ctypes.data for name in names))
+        if rc != 0:
+            raise ValueError('pnn_trquant_stages_sdh_host refused the arguments (width %d, QP %d, scan %d).' % (w, qp, scan))
+        return stages
     stages = {name: np.zeros((w, w), np.int32) for name in ('coeffs', 'levels', 'dequant', 'residual')}
     rc = _lib.lib().pnn_trquant_stages_host(prediction.ctypes.data, target.ctypes.data, w, qp, stages['coeffs'].ctypes.data,
                                             stages['levels'].ctypes.data, stages['dequant'].ctypes.data, stages['residual'].ctypes.data)

@@ -458,9 +458,10 @@ int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* ctx, int width, const uint8_
  * transform.  These entries code the residual target - prediction of n blocks at up to 8 QPs the way HM does with RDOQ 0 (xTrMxN, the
  * non-RDOQ branch of xQuant, the no-scaling-list branch of xDeQuant, xITrMxN of TComTrQuant.cpp; the decoder half is normative HEVC).
  * 8-bit luma, intra, I slice, coefficients of 15 bits + sign.  OPEN-LOOP: the prediction is given, nothing is predicted again from a
- * reconstruction.  LEFT OUT, because each needs the running entropy-coder state, which does not exist open-loop (as modeBits *
- * sqrtLambda above): RDOQ, sign-data hiding, transform skip.  (The CABAC rate of the levels, counted from the state a slice STARTS
- * with, is the next group of entries.)
+ * reconstruction.  LEFT OUT, because each needs bit estimates from the running entropy-coder state, which does not exist open-loop
+ * (as modeBits * sqrtLambda above): RDOQ with its own sign hiding, transform skip.  (The CABAC rate of the levels, counted from the
+ * state a slice STARTS with, is the next group of entries; the sign-data hiding xQuant does with RDOQ 0, which needs no such state,
+ * the group after it.)
  *   Transform units.  T = width up to 32.  At width 64 the units are the four 32 x 32 quadrants of the ONE 64 x 64 prediction, in
  *     raster order (HEVC has no 64-point transform).  That the quadrants are not predicted again one by one, as HM would, is THIS
  *     PROJECT'S DEFINITION.  L = log2 T.
@@ -503,8 +504,9 @@ int pnn_trquant_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, co
  * FRACTIONAL BITS THAT HM-16.15's TEncSbac::codeCoeffNxN ADDS TO A TEncBinCABACCounter (m_fracBits) FOR THE LEVELS OF THE TRANSFORM
  * UNIT, WERE THE UNIT THE FIRST RESIDUAL OF AN I SLICE OF THAT QP: every context model starts each unit at its initial state
  * (ContextModel::init, H.265 9.3.2.2, initType 0, SliceQpY = the QP).  That is well defined open-loop; the running state of a slice is
- * not.  Unit: 2^-15 bit, uint64.  Luma, intra, 8-bit video, maxLog2TrDynamicRange 15; sign-data hiding, transform skip, transquant
- * bypass, extended precision, persistent Rice adaptation and CABAC bypass alignment are all OFF.  NOT COUNTED: cbf_luma (its context
+ * not.  Unit: 2^-15 bit, uint64.  Luma, intra, 8-bit video, maxLog2TrDynamicRange 15; sign-data hiding (OFF in these entries, a flag
+ * of the next group's), transform skip, transquant bypass, extended precision, persistent Rice adaptation and CABAC bypass alignment
+ * are all OFF.  NOT COUNTED: cbf_luma (its context
  * depends on a transform tree that does not exist here), mode bits, lambda; no RDOQ.
  *   Units.  The transform units of the entries above: T = width up to 32; at width 64 the four 32 x 32 quadrants, each coded as a unit
  *     of its own (all contexts at their initial states again), bits added.  A unit whose levels are all zero costs 0.
@@ -548,6 +550,67 @@ int pnn_cabac_rate_levels_host(const int32_t* levels, int t, int scan, int qp, u
 int pnn_trquant_rate_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
                             const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
                             uint8_t* d_recon, uint64_t* d_rate, void* stream);
+
+/* ---- sign-data hiding, as HM's quantiser does it with RDOQ 0 -------------------------------------------- */
+
+/* With SignHideFlag 1 (HM's default) and RDOQ 0, xQuant hands every unit to TComTrQuant::signBitHidingHDQ, which reads the unit's
+ * coefficients, its levels, the rounding remainders deltaU and the scan -- no context model, no lambda, no bit estimate (only the
+ * variant inside xRateDistOptQuant needs those: it stays out, with RDOQ).  The entries below are the ones above with a flag
+ * sign_data_hiding; with the flag 0 they ARE the ones above.  Everything of the two groups above holds unless changed here.
+ *   Terms.  A group is a 4 x 4 coefficient group; `scan` is the unit's grouped scan as above (from the block's intra mode; diagonal
+ *     without a mode array, hence for the PNN: this project's definition); position n = 0 .. 15 of group c is block position
+ *     scan[16 c + n].
+ *   Remainder.  tmp = |C| scale (64 bits), mag = (tmp + add) >> qbits, deltaU = (int32)((tmp - ((int64)mag << qbits)) >> (qbits - 8)):
+ *     xQuant's line; qbits - 8 >= 8 for every T and QP.  (mag 2^qbits <= tmp + add < (mag + 1) 2^qbits and add = 171 2^(qbits - 9), so
+ *     deltaU lies in [-86, 170].)
+ *   Hiding, signBitHidingHDQ line for line.  Groups are visited from the highest scan index down.  In a group, last / first = the
+ *     highest / lowest n with a nonzero level (last = -1: none), absSum = the signed sum of the levels from first to last (only its low
+ *     bit is used).  The LAST GROUP is the first group met, going down, that has a nonzero level.  A group takes part when last - first
+ *     >= 4 (SBH_THRESHOLD).  signbit = (level at first > 0 ? 0 : 1).  If signbit == (absSum & 1) nothing changes.  Otherwise every
+ *     candidate n -- from last down to 0 in the last group, from 15 down to 0 in every other -- gets a cost and a change:
+ *       nonzero level, deltaU > 0:                                    cost -deltaU, change +1
+ *       nonzero level, deltaU <= 0, n == first and |level| == 1:      not allowed (cost INT32_MAX)
+ *       nonzero level, deltaU <= 0, otherwise:                        cost deltaU, change -1
+ *       zero level, n < first, (C >= 0 ? 0 : 1) != signbit:           not allowed
+ *       zero level, any other case:                                   cost -deltaU, change +1
+ *     The winner is the smallest cost under a strict < while n descends: of equal costs the HIGHEST n wins.  A level of 32767 or
+ *     -32768 at the winner forces the change to -1.  The winner's level becomes level + change when C >= 0, level - change otherwise.
+ *     (1) A participating group always has an allowed candidate: its position `last` holds a nonzero level and is not `first`, so
+ *     neither forbidden row applies to it; HM's minPos = -1 cannot occur.  (2) HM's guard uiAbsSum >= 2 never changes a result: a
+ *     group needs two nonzero levels to take part, and then uiAbsSum >= 2; the guard is not computed.
+ *   What follows the levels.  nb_nonzero, the dequantisation, the reconstruction, sse_recon and the rate use the levels AFTER hiding.
+ *     sum_abs_levels stays HM's uiAbsSum, the sum of mag BEFORE hiding and before the clip: HM does not update it either.
+ *   Rate (codeCoeffNxN with beValid; transform skip, transquant bypass and RDPCM are off, so beValid is the flag): in every group
+ *     whose FINAL levels have last - first >= 4 the sign of the level at `first`, the last one in coding order, is not coded: one bypass
+ *     bin (32768) fewer.  Nothing else changes.
+ *   Width 64: each 32 x 32 quadrant is hidden and rated as a unit of its own.
+ *   Pinned to HM's own signBitHidingHDQ by recorded calls (tests/golden/hm_sign_hiding.npz); the deltaU line and the sign rule of the
+ *   rate rest on the reading of the source.
+ *
+ * signBitHidingHDQ on ONE unit: levels int32 [t][t] in and out (each in [-32768, 32767]), coeffs and delta_u int32 [t][t] (delta_u from
+ * the caller, any value but INT32_MIN), t in {4, 8, 16, 32}, scan 0, 1 or 2 (0 only at t = 16 and 32).  PNN_E_ARG + a line on stderr
+ * otherwise and for a NULL pointer.  Pure host code. */
+int pnn_sign_hide_unit_host(int32_t* levels, const int32_t* coeffs, const int32_t* delta_u, int t, int scan);
+/* pnn_trquant_rate_host with the flag.  sign_data_hiding 0: that entry.  Nonzero: as defined above; modes are then allowed without
+ * rate (the scan shapes the levels).  Every other refusal as there.  Pure host code, the zero-tolerance yardstick of the device entry. */
+int pnn_trquant_sdh_host(const uint8_t* predictions, const uint8_t* targets, int width, int n, const uint8_t* modes, const int* qps,
+                         int nb_qps, uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon, uint64_t* rate,
+                         int sign_data_hiding);
+/* pnn_trquant_stages_host under scan `scan` (0, 1, 2; 0 only at width >= 16) with the flag: also delta_u and levels_hidden, the levels
+ * after hiding (equal to levels with the flag 0); dequant and residual come from levels_hidden.  Each output NULL (not all) or int32
+ * [width][width].  Same refusals, and PNN_E_ARG for a bad scan. */
+int pnn_trquant_stages_sdh_host(const uint8_t* prediction, const uint8_t* target, int width, int qp, int scan, int sign_data_hiding,
+                                int32_t* coeffs, int32_t* levels, int32_t* delta_u, int32_t* levels_hidden, int32_t* dequant,
+                                int32_t* residual);
+/* pnn_cabac_rate_levels_host with the flag: the rate of the given levels when the hidden signs are not coded. */
+int pnn_cabac_rate_levels_sdh_host(const int32_t* levels, int t, int scan, int qp, int sign_data_hiding, uint64_t* rate);
+/* pnn_trquant_sdh_host on the GPU, in ONE launch; bit-identical to the host twin.  pnn_trquant_rate_device is this call with the flag 0
+ * and launches the kernels it launched before, unchanged.  With the flag, the hiding runs one lane per scan position, 16 lanes per
+ * group, between quantisation and dequantisation of each QP.  d_modes is then read with or without d_rate (a value above 34 scans
+ * diagonally).  PNN_E_ARG before the launch for everything the host twin refuses but the mode values. */
+int pnn_trquant_sdh_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
+                           const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
+                           uint8_t* d_recon, uint64_t* d_rate, int sign_data_hiding, void* stream);
 
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */

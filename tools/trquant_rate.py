@@ -14,6 +14,10 @@
   context, the same buffers): the no-rate call must lie inside the min .. max spread of the parent's samples, or the kernel without
   the rate was disturbed.  The results are APPENDED to profiles/trquant_rate.txt.
 
+  Sign-data hiding: pnn_trquant_sdh_device with the flag set, without the rate (TQ+H) and with it (TQ+R+H), in
+  the same alternation, every output compared with the host twin first, each reported as a multiple of the same call without hiding
+  (TQ, TQ+R) of the same run; the share of blocks in which hiding changed the reconstruction at some QP is printed beside it.
+
     python tools/trquant_rate.py [--parent-lib /path/to/parent/libpnn_hip.so]          # on the GPU box
 """
 import argparse
@@ -94,7 +98,12 @@ def main():
             def code_rate(d_m=None):
                 return L.pnn_trquant_rate_device(ctx, w, d_c.data_ptr(), d_t.data_ptr(), n, d_m, c_qps, nq, counts[0].data_ptr(),
                                                  counts[1].data_ptr(), counts[2].data_ptr(), None, bits.data_ptr(), sp)
-            calls = {"tq": code, "tq_rate": code_rate, "tq_rate_modes": lambda: code_rate(d_modes.data_ptr()),
+
+            def code_sdh(d_bits=None, d_recon=None):
+                return L.pnn_trquant_sdh_device(ctx, w, d_c.data_ptr(), d_t.data_ptr(), n, None, c_qps, nq, counts[0].data_ptr(),
+                                                counts[1].data_ptr(), counts[2].data_ptr(), d_recon, d_bits, 1, sp)
+            calls = {"tq": code, "tq_sdh": code_sdh, "tq_rate": code_rate, "tq_rate_sdh": lambda: code_sdh(bits.data_ptr()),
+                     "tq_rate_modes": lambda: code_rate(d_modes.data_ptr()),
                      "sse": lambda: L.pnn_hevc_best_mode_device(ctx, w, d_p.data_ptr(), 2 * w + 1, 2 * w + 1, d_t.data_ptr(), n, index.data_ptr(),
                                                                 sse.data_ptr(), None, None, sp)}
             if parent is not None:
@@ -119,6 +128,19 @@ def main():
                 for k, key in enumerate(("sses_recon", "nb_nonzero_levels", "sum_abs_levels")):
                     assert np.array_equal(got[k], host[key]), "w %d: %s differs from the host twin beside the rate" % (w, key)
                 mean_bits[name] = float(bits.cpu().numpy().mean()) / 32768.
+            plain_recon = recon[:, :m].cpu().numpy()
+            for with_rate in (False, True):               # sign-data hiding: every output against the host twin
+                assert code_sdh(bits.data_ptr() if with_rate else None, recon.data_ptr()) == 0
+                torch.cuda.synchronize()
+                host = ip.transform_code(candidate[:m], targets[:m], QPS, keep_reconstructions=True, rate=with_rate, sign_data_hiding=True)
+                got = counts[:, :, :m].cpu().numpy().view(np.uint32)
+                for k, key in enumerate(("sses_recon", "nb_nonzero_levels", "sum_abs_levels")):
+                    assert np.array_equal(got[k], host[key]), "w %d: %s differs from the host twin under sign-data hiding" % (w, key)
+                assert np.array_equal(recon[:, :m].cpu().numpy(), host["reconstructions_uint8"]), "w %d: hidden reconstructions differ" % w
+                if with_rate:
+                    assert np.array_equal(bits[:, :m].cpu().numpy().astype(np.float64) / 32768., host["rate_bits"]), "w %d: the hidden rate differs" % w
+                    mean_bits["tq_rate_sdh"] = float(bits.cpu().numpy().mean()) / 32768.
+            hidden_share = float((host["reconstructions_uint8"] != plain_recon).any(axis=(0, 2, 3)).mean())
             times = {name: [] for name in calls}
             for i in range(args.warmup + args.reps):
                 order = list(calls)
@@ -136,6 +158,10 @@ def main():
                                                                med["tq"] / med["sse"]))
             for name, label in (("tq_rate", "TQ+R"), ("tq_rate_modes", "TQ+R modes")):
                 out("    %-12s %26s  %5.2fx TQ   (%.1f bits per block and QP on average)" % (label, fmt(name), med[name] / med["tq"], mean_bits[name]))
+            out("    %-12s %26s  %5.2fx TQ   (hiding changed the reconstruction of %.0f %% of the blocks)"
+                % ("TQ+H", fmt("tq_sdh"), med["tq_sdh"] / med["tq"], 100 * hidden_share))
+            out("    %-12s %26s  %5.2fx TQ+R (%.1f bits per block and QP on average)"
+                % ("TQ+R+H", fmt("tq_rate_sdh"), med["tq_rate_sdh"] / med["tq_rate"], mean_bits["tq_rate_sdh"]))
             if parent is not None:
                 inside = min(times["parent"]) <= med["tq"] <= max(times["parent"])
                 out("    %-12s %26s  TQ's median %.1f lies %s the parent's min .. max" % ("parent TQ", fmt("parent"), med["tq"], "INSIDE" if inside else "OUTSIDE"))
