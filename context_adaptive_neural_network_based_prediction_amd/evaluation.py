@@ -11,13 +11,15 @@ GPU: per mask one pnn_score_pictures_device call (descriptors, PNN pass, uint8 e
 the pictures) and one download; the same dictionaries as predict_mask_vs_hevc_best_mode[_and_ipfcns], bit for bit.
 score_masks_from_picture_pairs is the same loop on [images, H, W, 2] pairs (original, HEVC-decoded) for the pair models.
 Both take first_pass=True for one more column per mask: the PNN and the 35 modes ranked by the Hadamard cost of HM's first intra
-pass (pnn_first_pass_picture_pairs_device: one more call per mask, the same download).
+pass (pnn_first_pass_picture_pairs_hm_device: one more call per mask, the same download).
 Every function with an HEVC column takes reference_smoothing (0, 1, 2: intraprediction's `smoothing`): 0, the default, is the reference's
 extracted predictor; 2 makes the HEVC columns and the first-pass ranking those of HM's own predictor, with its reference-sample
 smoothing.  A nonzero value adds the key 'reference_smoothing' to the dictionaries and changes nothing in the PNN's columns.
 Both also take transform_qps, a list of 1 to 8 QPs, for the transform-domain column: what is left of the PNN's prediction and of the best
-HEVC mode's after HM's residual path with RDOQ 0 (intraprediction.transform_code; two more pnn_trquant_device calls per mask, the same
-download).
+HEVC mode's after HM's residual path with RDOQ 0 (intraprediction.transform_code; two more pnn_trquant_sdh_device calls per mask, the
+same download).
+Options travel as arguments: every call of the mask loop goes to the widest entry of its operation (*_hm_device, pnn_trquant_sdh_device) with 0
+or NULL for an option that is off; the narrower entries of include/pnn_hip.h forward to these with those values: the same kernel launch.
 """
 import ctypes
 
@@ -94,12 +96,8 @@ def predict_mask_vs_hevc_best_mode(channels_uint8, width_target, row_1sts, col_1
                        tuple_width_height_masks)
     intra_patterns_uint8 = intraprediction.extract_intra_patterns(channels_uint8, width_target, row_1sts + width_target - 1,
                                                                   col_1sts + width_target - 1, tuple_width_height_masks)
-    if reference_smoothing == 0:
-        indices, psnrs_hevc, predictions_hevc = intraprediction.predict_series_via_hevc_best_mode(
-            intra_patterns_uint8, pnn['targets_uint8'], device=predictor.device)
-    else:
-        indices, psnrs_hevc, predictions_hevc = intraprediction.predict_series_via_hevc_best_mode(
-            intra_patterns_uint8, pnn['targets_uint8'], device=predictor.device, smoothing=reference_smoothing)
+    indices, psnrs_hevc, predictions_hevc = intraprediction.predict_series_via_hevc_best_mode(
+        intra_patterns_uint8, pnn['targets_uint8'], device=predictor.device, smoothing=reference_smoothing)
     psnrs_pnn, frequency_win_pnn = compute_performance_neural_network_vs_hevc_best_mode(
         pnn['targets_uint8'], pnn['predictions_pnn_uint8'], psnrs_hevc)
     dictionary_performance = {
@@ -189,16 +187,15 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
 
     channels_uint8 [images, H, W, 1], row_1sts / col_1sts (the contexts' top-left corners) are uploaded once.  Per mask ONE
-    pnn_score_pictures_device call (made as pnn_score_picture_pairs_device with one plane in both places) -- the descriptors of
+    pnn_score_pictures_device call (made as pnn_score_picture_pairs_hm_device with one plane in both places) -- the descriptors of
     context_descriptor_fields, the PNN pass, the uint8 cast and its integer SSE, the best HEVC mode searched in the pictures
-    themselves -- and ONE download; PSNRs from the SSEs by
-    intraprediction.psnrs_from_sses (equal to compute_psnr), 0 dB where no HEVC mode beats the reference's start value.
-    keep_predictions=False leaves out (and never downloads) 'predictions_*_uint8' and 'targets_uint8'.
-    Argument errors are those of context.extract_context_portions_targets_from_channels_plus_preprocessing, raised before
-    anything touches the GPU.
+    themselves -- and ONE download; PSNRs from the SSEs by intraprediction.psnrs_from_sses (equal to compute_psnr), 0 dB where no
+    HEVC mode beats the reference's start value.  keep_predictions=False leaves out (and never downloads) 'predictions_*_uint8' and
+    'targets_uint8'.  Argument errors are those of context.extract_context_portions_targets_from_channels_plus_preprocessing, raised
+    before anything touches the GPU.
 
     first_pass=True adds, per mask, the ranking of HM's first intra pass (TEncSearch.cpp:2376-2492) by ONE more call,
-    pnn_first_pass_picture_pairs_device, with the uint8 PNN predictions the score call left on the device as candidate 35; its results
+    pnn_first_pass_picture_pairs_hm_device, with the uint8 PNN predictions the score call left on the device as candidate 35; its results
     join the one download.  New keys: 'hads_pnn' uint32 [N] and 'hads_hevc_modes' uint32 [N, 35] (TComRdCost::xGetHADs of the
     predictions against the targets), 'first_pass_list' uint8 [N, K] and 'first_pass_costs' uint32 [N, K] (HM's sorted candidate list,
     K = 8 for w <= 8, else 3; ascending cost, the lower index first among equal costs, 35 = the PNN),
@@ -207,12 +204,13 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     reference_smoothing's choice.  With first_pass=False nothing changes: not a key, a call or a byte.
 
     reference_smoothing (0, 1, 2): HM's reference-sample smoothing in the HEVC modes, of the best-mode search and of the first pass alike
-    (the *_hm entries of include/pnn_hip.h).  0 reproduces the reference's extracted predictor, which has none -- the evaluator's
-    competitor; 2 is HM's default, the predictor the encoders run.  A nonzero value adds the key 'reference_smoothing' (int) to every
-    dictionary and leaves the PNN's and IPFCN-S's keys bit-identical.  With 0 nothing changes: not a key, a call or a byte.
+    (the `smoothing` argument of the *_hm entries of include/pnn_hip.h, which every call goes through).  0 reproduces the reference's
+    extracted predictor, which has none -- the evaluator's competitor; 2 is HM's default, the predictor the encoders run.  A nonzero
+    value adds the key 'reference_smoothing' (int) to every dictionary and leaves the PNN's and IPFCN-S's keys bit-identical.  With 0
+    nothing changes: not a key, a call or a byte (the entries without _hm pass that 0 on: the same kernel launch under either name).
 
     transform_qps (1 to 8 integers in [0, 51]; ValueError otherwise, before anything touches the GPU) adds the transform-domain column,
-    open-loop: per mask TWO more calls behind the score call (and the first-pass call), pnn_trquant_device on the PNN's uint8 predictions
+    open-loop: per mask TWO more calls behind the score call (and the first-pass call), pnn_trquant_sdh_device on the PNN's uint8 predictions
     and on the best HEVC mode's (the smoothed ones when reference_smoothing says so), both against the targets the first mask left on
     the device; HM's residual path with RDOQ 0 as include/pnn_hip.h defines it (no RDOQ, sign-data hiding, transform skip or rate; at
     w = 64 the four 32 x 32 quadrants of the one prediction).  Their results join the one download.  New keys: 'transform_qps' (tuple),
@@ -221,22 +219,22 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     reconstruction PSNR is strictly higher).  Equal to intraprediction.transform_code on the dictionary's own predictions and targets.
     With transform_qps=() nothing changes: not a key, a call or a byte.
 
-    transform_rate=True (with transform_qps; ValueError without, before anything touches the GPU) makes the two transform calls
-    pnn_trquant_rate_device: the CABAC rate of each residual's levels, the bits HM's counter reports from the I-slice initial contexts of
-    the QP (include/pnn_hip.h, "the CABAC rate of the coded levels"; cbf, mode bits and any lambda left out).  The best mode's call gets
-    the mode array the score call left on the device (the mode picks the scan at w = 4 and 8), the PNN's gets none: its blocks are coded
-    under the diagonal scan, this project's definition.  The results join the one download.  New keys: 'rate_bits_pnn',
-    'rate_bits_hevc_best_mode' (float64 [nb_qps, N], bits) and 'frequency_rate_win_pnn' (one float per QP: the share of blocks whose PNN
-    residual costs strictly fewer bits).  Equal to intraprediction.transform_code(rate=True, modes=...) on the dictionary's own
-    predictions, targets and modes.  With transform_rate=False nothing changes: not a key, a call or a byte.
+    transform_rate=True (with transform_qps; ValueError without, before anything touches the GPU) gives the two transform calls a rate
+    pointer (NULL without it, as pnn_trquant_device passes): the CABAC rate of each residual's levels, the bits HM's counter reports
+    from the I-slice initial contexts of the QP (include/pnn_hip.h, "the CABAC rate of the coded levels"; cbf, mode bits and any lambda
+    left out).  The best mode's call gets the mode array the score call left on the device (the mode picks the scan at w = 4 and 8),
+    the PNN's gets none: its blocks are coded under the diagonal scan, this project's definition.  The results join the one download.
+    New keys: 'rate_bits_pnn', 'rate_bits_hevc_best_mode' (float64 [nb_qps, N], bits) and 'frequency_rate_win_pnn' (one float per QP:
+    the share of blocks whose PNN residual costs strictly fewer bits).  Equal to intraprediction.transform_code(rate=True, modes=...)
+    on the dictionary's own predictions, targets and modes.  With transform_rate=False nothing changes: not a key, a call or a byte.
 
-    transform_sign_hiding=True (with transform_qps; ValueError without, before anything touches the GPU) makes the two transform calls
-    pnn_trquant_sdh_device with the flag set, whether or not transform_rate is: HM's sign-data hiding as its quantiser does it with
-    RDOQ 0 and SignHideFlag 1, HM's default (include/pnn_hip.h, "sign-data hiding").  The best mode's call gets the mode array the score
-    call left on the device (the scan now shapes the levels), the PNN's gets none.  Same keys, computed from the levels after hiding
-    ('sum_abs_levels_*' stays the sum before it; 'rate_bits_*' does not charge the hidden signs), plus 'transform_sign_hiding': True.
-    Equal to intraprediction.transform_code(sign_data_hiding=True, modes=...) on the dictionary's own predictions, targets and modes.
-    With transform_sign_hiding=False nothing changes: not a key, a call or a byte."""
+    transform_sign_hiding=True (with transform_qps; ValueError without, before anything touches the GPU) sets the flag of the two
+    transform calls (0 without it, as pnn_trquant_rate_device passes), whether or not transform_rate is set: HM's sign-data hiding as
+    its quantiser does it with RDOQ 0 and SignHideFlag 1, HM's default (include/pnn_hip.h, "sign-data hiding").  The best mode's call
+    gets the mode array the score call left on the device (the scan now shapes the levels), the PNN's gets none.  Same keys, computed
+    from the levels after hiding ('sum_abs_levels_*' stays the sum before it; 'rate_bits_*' does not charge the hidden signs), plus
+    'transform_sign_hiding': True.  Equal to intraprediction.transform_code(sign_data_hiding=True, modes=...) on the dictionary's own
+    predictions, targets and modes.  With transform_sign_hiding=False nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
                         net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding)
 
@@ -248,7 +246,7 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
 
-    Which plane feeds what (pnn_score_picture_pairs_device):
+    Which plane feeds what (pnn_score_picture_pairs_hm_device):
       decoded (last channel):  the PNN's contexts (sets/common.py reads them there), the intra pattern of the HEVC search (this
                                project's definition -- the reference's extract_intra_patterns has no pair form; the decoded
                                neighbourhood is what an encoder holds), the reference lines of IPFCN-S (ipfcns.py:60-65)
@@ -263,12 +261,10 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
                         tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps,
                         transform_rate, transform_sign_hiding)
 
-
-def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                 keep_predictions, first_pass=False, reference_smoothing=0, transform_qps=(), transform_rate=False,
-                 transform_sign_hiding=False):
-    """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
-    everything a predictor reads from the last channel; with one plane the two are the same device buffer."""
+def _check_score_masks_arguments(ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
+                                 reference_smoothing, transform_qps, transform_rate, transform_sign_hiding):
+    """The argument checks of _score_masks, all before anything touches the GPU; the library is first used by the last, the predictor's mean.
+    Returns (masks as int pairs, rows and cols as flat int64 arrays, reference_smoothing as int, transform_qps as a tuple of ints or ())."""
     if ch.dtype != np.uint8:
         raise TypeError('`channels_single_or_pair_uint8.dtype` is not equal to `numpy.uint8`.')
     if not np.issubdtype(row_1sts.dtype, np.integer):
@@ -286,12 +282,10 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         raise ValueError('`channels_uint8.shape[3]` is not equal to 1 (pairs of channels: context.py).')
     if nb_planes == 2 and nb_channels != 2:
         raise ValueError('`channels_pair_uint8.shape[3]` is not equal to 2 (single pictures: score_masks_from_pictures).')
-    w = width_target
     if w not in intraprediction.WIDTHS:
         raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
     if reference_smoothing not in intraprediction.SMOOTHINGS:
         raise ValueError('`reference_smoothing` does not belong to {0, 1, 2}.')
-    reference_smoothing = int(reference_smoothing)
     if not (isinstance(transform_qps, (tuple, list)) and len(transform_qps) == 0):
         transform_qps = intraprediction._check_qps(transform_qps)
     if transform_rate and len(transform_qps) == 0:
@@ -300,9 +294,7 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         raise ValueError('`transform_sign_hiding` is set without `transform_qps`.')
     masks = [(int(m[0]), int(m[1])) for m in tuples_width_height_masks]
     rows, cols = row_1sts.astype(np.int64).ravel(), col_1sts.astype(np.int64).ravel()
-    n_pos = rows.size
-    n = nb_images * n_pos
-    if n == 0:
+    if nb_images * rows.size == 0:
         raise ValueError('there is no target: no image or no position.')
     for mask in masks:
         context_descriptor_fields(w, height, width, nb_images - 1, rows[-1], cols[-1], mask)
@@ -319,30 +311,27 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
             raise ValueError('the net is the width-%d IPFCN-S, not the width-%d one' % (net_ipfcns.width_target, w))
         if net_ipfcns.device != predictor.device:
             raise ValueError('the IPFCN-S and the predictor are on different devices')
-    L = _lib.lib()
-    ctx_mean = ctypes.c_float(L.pnn_mean(predictor.ctx)).value
+    ctx_mean = ctypes.c_float(_lib.lib().pnn_mean(predictor.ctx)).value
     if abs(ctx_mean - np.float32(mean_training)) > 1e-6:
         raise ValueError("`mean_training` differs from the predictor's mean")
+    return masks, rows, cols, int(reference_smoothing), tuple(transform_qps)
 
-    import torch
-    dev = torch.device('cuda', predictor.device)
-    w2 = w * w
-    d_planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(ch, 3, 0))).to(dev)      # [planes, images, H, W]: one copy, one upload
-    d_target_channels, d_context_channels = d_planes[0], d_planes[nb_planes - 1]
-    d_rows = torch.from_numpy(rows.astype(np.int32)).to(dev)
-    d_cols = torch.from_numpy(cols.astype(np.int32)).to(dev)
-    # Every output of a call in ONE buffer, described once as (name, dtype, shape): the small results first, then the uint8 blocks
-    # of the PNN, of HEVC and the targets; a download is a prefix of it.  Each section starts at a multiple of its item size.
+
+_CODED_COLUMNS = (('pnn', 'predictions_pnn'), ('hevc_best_mode', 'predictions_hevc'))      # (key suffix, section) of what transform_qps codes
+_COUNTS = ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels')                            # per coded column, uint32 [nb_qps, n]
+
+
+def _output_layout(n, w, first_pass, nb_qps, transform_rate):
+    """Every output of a mask's calls in ONE buffer, described once as (name, dtype, shape): the small results first, then the uint8
+    blocks of the PNN, of HEVC and the targets; a download is a prefix of it.  Each section starts at a multiple of its item size.
+    Returns (sections, begin, end), the last two the byte offsets by name; end['targets'] is the size of the buffer."""
     sections = [('sses_pnn', np.uint32, (n,)), ('sses_hevc', np.uint32, (n,)), ('indices_hevc', np.uint8, (n,))]
-    nb_modes = intraprediction.NB_MODES
     if first_pass:
         nb_list = intraprediction.first_pass_list_size(w)
-        sections += [('hads_hevc_modes', np.uint32, (n, nb_modes)), ('hads_pnn', np.uint32, (n,)),
+        sections += [('hads_hevc_modes', np.uint32, (n, intraprediction.NB_MODES)), ('hads_pnn', np.uint32, (n,)),
                      ('first_pass_costs', np.uint32, (n, nb_list)), ('first_pass_list', np.uint8, (n, nb_list))]
-    nb_qps = len(transform_qps)
-    coded = (('pnn', 'predictions_pnn'), ('hevc_best_mode', 'predictions_hevc')) if nb_qps else ()
-    for column, _ in coded:
-        sections += [('%s_%s' % (name, column), np.uint32, (nb_qps, n)) for name in ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels')]
+    for column, _ in _CODED_COLUMNS if nb_qps else ():
+        sections += [('%s_%s' % (name, column), np.uint32, (nb_qps, n)) for name in _COUNTS]
         if transform_rate:
             sections.append(('rate_' + column, np.uint64, (nb_qps, n)))
     sections += [(name, np.uint8, (n, w, w, 1)) for name in ('predictions_pnn', 'predictions_hevc', 'targets')]
@@ -351,83 +340,93 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         size = np.dtype(dtype).itemsize
         begin[name] = (offset + size - 1) // size * size
         end[name] = offset = begin[name] + size * int(np.prod(shape))
+    return sections, begin, end
+
+
+def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding):
+    """One mask's dictionary_performance, but for the uint8 blocks, from `view`: the downloaded sections by name."""
+    psnrs_pnn = intraprediction.psnrs_from_sses(view['sses_pnn'], w)
+    psnrs_hevc = intraprediction.psnrs_from_sses(view['sses_hevc'], w)
+    psnrs_hevc[view['sses_hevc'] == 65025 * w * w] = 0.   # the reference's start value, never beaten
+    d = {'indices_hevc_best_mode': view['indices_hevc'].copy(), 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
+         'frequency_win_pnn': float(np.count_nonzero(psnrs_pnn - psnrs_hevc > 0.)) / n, 'mean_psnr_pnn': np.mean(psnrs_pnn).item()}
+    if first_pass:
+        d.update({key: view[key].copy() for key in ('hads_pnn', 'hads_hevc_modes', 'first_pass_list', 'first_pass_costs')})
+        is_pnn = d['first_pass_list'] == intraprediction.NB_MODES
+        d['frequency_pnn_in_first_pass_list'] = float(np.count_nonzero(is_pnn.any(axis=1))) / n
+        d['frequency_pnn_first_pass_best'] = float(np.count_nonzero(is_pnn[:, 0])) / n
+    if reference_smoothing:
+        d['reference_smoothing'] = reference_smoothing
+    if transform_qps:
+        d['transform_qps'] = transform_qps
+        for column, _ in _CODED_COLUMNS:
+            d.update({key: view[key].copy() for key in ('%s_%s' % (name, column) for name in _COUNTS)})
+            d['psnrs_recon_' + column] = intraprediction.psnrs_from_sses(view['sses_recon_' + column], w)
+        d['frequency_recon_win_pnn'] = [float(np.count_nonzero(pnn - hevc > 0.)) / n                   # one float per QP
+                                        for pnn, hevc in zip(d['psnrs_recon_pnn'], d['psnrs_recon_hevc_best_mode'])]
+    if transform_rate:
+        for column, _ in _CODED_COLUMNS:
+            d['rate_bits_' + column] = view['rate_' + column].astype(np.float64) / 32768.
+        d['frequency_rate_win_pnn'] = [float(np.count_nonzero(pnn < hevc)) / n
+                                       for pnn, hevc in zip(d['rate_bits_pnn'], d['rate_bits_hevc_best_mode'])]
+    if transform_sign_hiding:
+        d['transform_sign_hiding'] = True
+    return d
+
+
+def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
+                 keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding):
+    """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
+    everything a predictor reads from the last channel; with one plane the two are the same device buffer.  Every option is an argument
+    of the one entry its call has (the smoothing; the mode pointer, the rate pointer and the flag), 0 or NULL when off."""
+    w = width_target
+    masks, rows, cols, reference_smoothing, transform_qps = _check_score_masks_arguments(
+        ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns, reference_smoothing,
+        transform_qps, transform_rate, transform_sign_hiding)
+    nb_images, height, width = ch.shape[:3]
+    n_pos, nb_qps = rows.size, len(transform_qps)
+    n = nb_images * n_pos
+    L = _lib.lib()
+
+    import torch
+    dev = torch.device('cuda', predictor.device)
+    d_planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(ch, 3, 0))).to(dev)      # [planes, images, H, W]: one copy, one upload
+    d_target_channels, d_context_channels = d_planes[0], d_planes[nb_planes - 1]
+    d_rows, d_cols = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (rows, cols))
+    sections, begin, end = _output_layout(n, w, first_pass, nb_qps, transform_rate)
     d_out = torch.empty(end['targets'], dtype=torch.uint8, device=dev)       # the last section
     ptr = {name: d_out.data_ptr() + begin[name] for name in begin}
-    stream = torch.cuda.current_stream(dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     c_qps = (ctypes.c_int * max(nb_qps, 1))(*transform_qps)
-    results = {}
-    targets_uint8 = None
+    results, targets_uint8 = {}, None
     for i, mask in enumerate(masks):
         if mask in results:
             continue
         first = i == 0
         blocks = (predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
                   d_rows.data_ptr(), d_cols.data_ptr(), n_pos, mask[0], mask[1])
-        scores = (ptr['targets'] if first else None, ptr['predictions_pnn'] if keep_predictions or first_pass or nb_qps else None, None,
-                  ptr['sses_pnn'], ptr['indices_hevc'], ptr['sses_hevc'], ptr['predictions_hevc'] if keep_predictions or nb_qps else None,
-                  ctypes.c_void_p(stream.cuda_stream))
         with torch.cuda.device(dev):
-            if reference_smoothing == 0:
-                _lib.check(L.pnn_score_picture_pairs_device(*(blocks + scores)), predictor.ctx)
-            else:
-                _lib.check(L.pnn_score_picture_pairs_hm_device(*(blocks + (reference_smoothing,) + scores)), predictor.ctx)
+            _lib.check(L.pnn_score_picture_pairs_hm_device(
+                *blocks, reference_smoothing, ptr['targets'] if first else None,
+                ptr['predictions_pnn'] if keep_predictions or first_pass or nb_qps else None, None, ptr['sses_pnn'], ptr['indices_hevc'],
+                ptr['sses_hevc'], ptr['predictions_hevc'] if keep_predictions or nb_qps else None, stream), predictor.ctx)
             if first_pass:                                # the PNN's uint8 predictions are on the device: candidate 35
-                ranking = (ptr['hads_hevc_modes'], ptr['hads_pnn'], ptr['first_pass_list'], ptr['first_pass_costs'],
-                           ctypes.c_void_p(stream.cuda_stream))
-                if reference_smoothing == 0:
-                    _lib.check(L.pnn_first_pass_picture_pairs_device(*(blocks + (ptr['predictions_pnn'],) + ranking)), predictor.ctx)
-                else:
-                    _lib.check(L.pnn_first_pass_picture_pairs_hm_device(
-                        *(blocks + (ptr['predictions_pnn'], reference_smoothing) + ranking)), predictor.ctx)
-            for column, predictions in coded:             # both predictions are on the device, and so are the first mask's targets
-                counts = (ptr['sses_recon_' + column], ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None)
-                if transform_sign_hiding:                 # the scan shapes the levels: the best mode's array, with or without the rate
-                    modes = ptr['indices_hevc'] if column == 'hevc_best_mode' else None
-                    _lib.check(L.pnn_trquant_sdh_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps,
-                                                        *(counts + (ptr['rate_' + column] if transform_rate else None, 1,
-                                                                    ctypes.c_void_p(stream.cuda_stream)))), predictor.ctx)
-                elif transform_rate:                      # the best mode's scan follows its mode, which the score call left; the PNN has none
-                    modes = ptr['indices_hevc'] if column == 'hevc_best_mode' else None
-                    _lib.check(L.pnn_trquant_rate_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps,
-                                                         *(counts + (ptr['rate_' + column], ctypes.c_void_p(stream.cuda_stream)))), predictor.ctx)
-                else:
-                    _lib.check(L.pnn_trquant_device(predictor.ctx, w, ptr[predictions], ptr['targets'], n, c_qps, nb_qps,
-                                                    *(counts + (ctypes.c_void_p(stream.cuda_stream),))), predictor.ctx)
+                _lib.check(L.pnn_first_pass_picture_pairs_hm_device(
+                    *blocks, ptr['predictions_pnn'], reference_smoothing, ptr['hads_hevc_modes'], ptr['hads_pnn'], ptr['first_pass_list'],
+                    ptr['first_pass_costs'], stream), predictor.ctx)
+            for column, predictions in _CODED_COLUMNS if nb_qps else ():
+                # both predictions and the first mask's targets are on the device.  Where the scan is read (by the rate, by the hiding), the
+                # best mode's follows its mode, which the score call left there; the PNN has no mode: the diagonal scan
+                modes = ptr['indices_hevc'] if column == 'hevc_best_mode' and (transform_rate or transform_sign_hiding) else None
+                _lib.check(L.pnn_trquant_sdh_device(
+                    predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps, ptr['sses_recon_' + column],
+                    ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None, ptr['rate_' + column] if transform_rate else None,
+                    int(bool(transform_sign_hiding)), stream), predictor.ctx)
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
-        psnrs_pnn = intraprediction.psnrs_from_sses(view['sses_pnn'], w)
-        psnrs_hevc = intraprediction.psnrs_from_sses(view['sses_hevc'], w)
-        psnrs_hevc[view['sses_hevc'] == 65025 * w2] = 0.  # the reference's start value, never beaten
-        dictionary_performance = {
-            'indices_hevc_best_mode': view['indices_hevc'].copy(), 'psnrs_hevc_best_mode': psnrs_hevc, 'psnrs_pnn': psnrs_pnn,
-            'frequency_win_pnn': float(np.count_nonzero(psnrs_pnn - psnrs_hevc > 0.)) / n, 'mean_psnr_pnn': np.mean(psnrs_pnn).item()}
-        if first_pass:
-            for key in ('hads_pnn', 'hads_hevc_modes', 'first_pass_list', 'first_pass_costs'):
-                dictionary_performance[key] = view[key].copy()
-            first_pass_list = dictionary_performance['first_pass_list']
-            dictionary_performance['frequency_pnn_in_first_pass_list'] = \
-                float(np.count_nonzero((first_pass_list == nb_modes).any(axis=1))) / n
-            dictionary_performance['frequency_pnn_first_pass_best'] = float(np.count_nonzero(first_pass_list[:, 0] == nb_modes)) / n
-        if reference_smoothing:
-            dictionary_performance['reference_smoothing'] = reference_smoothing
-        if nb_qps:
-            dictionary_performance['transform_qps'] = transform_qps
-            for column, _ in coded:
-                for name in ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels'):
-                    dictionary_performance['%s_%s' % (name, column)] = view['%s_%s' % (name, column)].copy()
-                dictionary_performance['psnrs_recon_' + column] = intraprediction.psnrs_from_sses(view['sses_recon_' + column], w)
-            dictionary_performance['frequency_recon_win_pnn'] = [
-                float(np.count_nonzero(dictionary_performance['psnrs_recon_pnn'][q] - dictionary_performance['psnrs_recon_hevc_best_mode'][q] > 0.)) / n
-                for q in range(nb_qps)]
-        if transform_rate:
-            for column, _ in coded:
-                dictionary_performance['rate_bits_' + column] = view['rate_' + column].astype(np.float64) / 32768.
-            dictionary_performance['frequency_rate_win_pnn'] = [
-                float(np.count_nonzero(dictionary_performance['rate_bits_pnn'][q] < dictionary_performance['rate_bits_hevc_best_mode'][q])) / n
-                for q in range(nb_qps)]
-        if transform_sign_hiding:
-            dictionary_performance['transform_sign_hiding'] = True
+        dictionary_performance = _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate,
+                                                         transform_sign_hiding)
         if keep_predictions:
             if first:
                 targets_uint8 = view['targets'].copy()

@@ -3,8 +3,8 @@ hevc/intraprediction/intraprediction.py (extract_intra_pattern(s), predict_via_h
 predict_series_via_hevc_best_mode) and interface.pyx (predict_via_hevc_mode): same names, arguments, return
 dtypes and shapes, same exceptions for bad arguments.
 
-predict_via_hevc_mode is the per-block host twin (pnn_hevc_intra_predict, pure host code).  The best-mode search runs
-on the GPU (pnn_hevc_best_mode_device: all 35 modes, their SSEs and the winner of n blocks in one launch) through a
+predict_via_hevc_mode is the per-block host twin (pnn_hevc_intra_predict_hm, pure host code).  The best-mode search runs
+on the GPU (pnn_hevc_best_mode_hm_device: all 35 modes, their SSEs and the winner of n blocks in one launch) through a
 model-less context per device; there is no CPU fallback.  PSNRs are recomputed on the host from the integer SSEs with
 the reference's float64 expression: SSE / w^2 is exactly numpy.mean of the squared differences, so they match the
 reference bit for bit.
@@ -12,6 +12,10 @@ reference bit for bit.
 HM's reference-sample smoothing, which the reference's extracted predictor left out, is the option `smoothing` of every predictor
 here (include/pnn_hip.h): 0 (the default) reproduces the reference's predictor, 1 is HM with StrongIntraSmoothing 0, 2 is HM's
 default.  mode_uses_smoothing and smoothed_reference show the decision table and the filtered line.
+
+Every option (`smoothing`, `rate`, `modes`, `sign_data_hiding`) travels as an argument of ONE C entry per operation, the widest one
+(*_hm_*, *_sdh_*), with 0 or NULL for "off"; the narrower entries of include/pnn_hip.h forward to the same bodies with those very
+values and are for integrators.
 """
 import ctypes
 
@@ -22,6 +26,13 @@ from . import _lib
 NB_MODES = 35
 WIDTHS = (4, 8, 16, 32, 64)
 _contexts = {}                                  # device -> model-less pnn_ctx
+
+
+def _address(buffer):
+    """The address of a numpy array or a torch tensor; None (a NULL pointer) for None."""
+    if buffer is None:
+        return None
+    return buffer.ctypes.data if isinstance(buffer, np.ndarray) else buffer.data_ptr()
 
 
 def extract_intra_pattern(channel_uint8, width_target, row_ref, col_ref, tuple_width_height_masks):
@@ -128,7 +139,7 @@ def smoothed_reference(intra_pattern_uint8, width_target, smoothing):
 
 def predict_via_hevc_mode(intra_pattern_uint8, width_target, index_mode, smoothing=0):
     """interface.pyx:15-64: the [w, w, 1] uint8 prediction of mode `index_mode` from a [h, w', 1] intra pattern (host twin).
-    smoothing: 0 the reference's predictor, 1 / 2 HM's reference-sample smoothing (pnn_hevc_intra_predict_hm)."""
+    smoothing: 0 the reference's predictor, 1 / 2 HM's reference-sample smoothing (the argument of pnn_hevc_intra_predict_hm)."""
     if not isinstance(intra_pattern_uint8, np.ndarray):
         raise TypeError('Argument \'intra_pattern_uint8\' has incorrect type (expected numpy.ndarray)')
     if intra_pattern_uint8.ndim != 3:
@@ -142,14 +153,9 @@ def predict_via_hevc_mode(intra_pattern_uint8, width_target, index_mode, smoothi
     if intra_pattern_uint8.shape[2] != 1:
         raise ValueError('`intra_pattern_uint8.shape[2]` is not equal to 1.')
     prediction_uint8 = np.zeros((width_target, width_target, 1), dtype=np.uint8)
-    if smoothing == 0:
-        rc = _lib.lib().pnn_hevc_intra_predict(intra_pattern_uint8.ctypes.data_as(_lib.u8p), intra_pattern_uint8.shape[0],
-                                               intra_pattern_uint8.shape[1], width_target, int(index_mode),
-                                               prediction_uint8.ctypes.data_as(_lib.u8p))
-    else:
-        rc = _lib.lib().pnn_hevc_intra_predict_hm(intra_pattern_uint8.ctypes.data_as(_lib.u8p), intra_pattern_uint8.shape[0],
-                                                  intra_pattern_uint8.shape[1], width_target, int(index_mode), _check_smoothing(smoothing),
-                                                  prediction_uint8.ctypes.data_as(_lib.u8p))
+    rc = _lib.lib().pnn_hevc_intra_predict_hm(intra_pattern_uint8.ctypes.data_as(_lib.u8p), intra_pattern_uint8.shape[0],
+                                              intra_pattern_uint8.shape[1], width_target, int(index_mode), _check_smoothing(smoothing),
+                                              prediction_uint8.ctypes.data_as(_lib.u8p))
     if rc != 0:
         raise ValueError('hevc_intraprediction refused the arguments (pattern %dx%d, width %d, mode %d).'
                          % (intra_pattern_uint8.shape[0], intra_pattern_uint8.shape[1], width_target, index_mode))
@@ -173,8 +179,8 @@ def _context(device):
 
 
 def best_modes_device(intra_patterns, targets, width_target, best_pred=True, mode_sse=False, device=0, smoothing=0):
-    """The GPU search on torch uint8 tensors already on `device`: patterns [n, h, w'] and targets [n, w, w]; smoothing != 0: over HM's
-    smoothed predictions (pnn_hevc_best_mode_hm_device).
+    """The GPU search (pnn_hevc_best_mode_hm_device) on torch uint8 tensors already on `device`: patterns [n, h, w'] and targets
+    [n, w, w]; smoothing != 0: over HM's smoothed predictions.
     Returns (best index uint8 [n], best SSE int32 [n], best prediction uint8 [n, w, w] or None, SSE of every mode int32 [n, 35]
     or None), torch tensors on `device`, after the stream has finished."""
     import torch
@@ -186,15 +192,11 @@ def best_modes_device(intra_patterns, targets, width_target, best_pred=True, mod
     pred = torch.empty((n, width_target, width_target), dtype=torch.uint8, device=dev) if best_pred else None
     all_sse = torch.empty((n, NB_MODES), dtype=torch.int32, device=dev) if mode_sse else None
     stream = torch.cuda.current_stream(dev)
-    L = _lib.lib()
-    inputs = (_context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1], intra_patterns.shape[2], targets.data_ptr(), n)
-    outputs = (index.data_ptr(), sse.data_ptr(), pred.data_ptr() if best_pred else None, all_sse.data_ptr() if mode_sse else None,
-               ctypes.c_void_p(stream.cuda_stream))
     with torch.cuda.device(dev):
-        if smoothing == 0:
-            _lib.check(L.pnn_hevc_best_mode_device(*(inputs + outputs)), _context(device))
-        else:
-            _lib.check(L.pnn_hevc_best_mode_hm_device(*(inputs + (smoothing,) + outputs)), _context(device))
+        _lib.check(_lib.lib().pnn_hevc_best_mode_hm_device(
+            _context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1], intra_patterns.shape[2], targets.data_ptr(), n,
+            smoothing, index.data_ptr(), sse.data_ptr(), _address(pred), _address(all_sse), ctypes.c_void_p(stream.cuda_stream)),
+            _context(device))
     stream.synchronize()
     return index, sse, pred, all_sse
 
@@ -224,12 +226,12 @@ def _check_mode_hads_arguments(intra_patterns, targets, width_target, candidate_
 
 
 def mode_hads_device(intra_patterns, targets, width_target, candidate_predictions=None, device=0, smoothing=0):
-    """HM's first intra pass on the GPU (pnn_hevc_mode_hads_device) on torch uint8 tensors already on `device`: patterns [n, h, w'],
+    """HM's first intra pass on the GPU (pnn_hevc_mode_hads_hm_device) on torch uint8 tensors already on `device`: patterns [n, h, w'],
     targets [n, w, w], candidate_predictions None or [n, w, w] (the PNN's uint8 predictions, candidate 35).  One launch.
     Returns numpy arrays {'hads_modes': uint32 [n, 35], 'hads_candidate': uint32 [n] or None, 'list_modes': uint8 [n, K],
     'list_costs': uint32 [n, K]}, K = first_pass_list_size(width_target); the list is in ascending cost, the lower index first among
     equal costs.  Costs: TComRdCost::xGetHADs of the predictions `smoothing` selects (0: the reference's predictor, no reference smoothing;
-    2: HM's; pnn_hevc_mode_hads_hm_device), without HM's mode-bit term."""
+    2: HM's), without HM's mode-bit term."""
     import torch
     smoothing = _check_smoothing(smoothing)
     n = _check_mode_hads_arguments(intra_patterns, targets, width_target, candidate_predictions)
@@ -243,23 +245,19 @@ def mode_hads_device(intra_patterns, targets, width_target, candidate_prediction
     modes = torch.empty((n, k), dtype=torch.uint8, device=dev)
     costs = torch.empty((n, k), dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev)
-    inputs = (_context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1], intra_patterns.shape[2],
-              targets.data_ptr(), n, None if candidate_predictions is None else candidate_predictions.data_ptr())
-    outputs = (hads.data_ptr(), None if cand is None else cand.data_ptr(), modes.data_ptr(), costs.data_ptr(),
-               ctypes.c_void_p(stream.cuda_stream))
     with torch.cuda.device(dev):
-        if smoothing == 0:
-            _lib.check(_lib.lib().pnn_hevc_mode_hads_device(*(inputs + outputs)), _context(device))
-        else:
-            _lib.check(_lib.lib().pnn_hevc_mode_hads_hm_device(*(inputs + (smoothing,) + outputs)), _context(device))
+        _lib.check(_lib.lib().pnn_hevc_mode_hads_hm_device(
+            _context(device), width_target, intra_patterns.data_ptr(), intra_patterns.shape[1], intra_patterns.shape[2], targets.data_ptr(), n,
+            _address(candidate_predictions), smoothing, hads.data_ptr(), _address(cand), modes.data_ptr(), costs.data_ptr(),
+            ctypes.c_void_p(stream.cuda_stream)), _context(device))
     stream.synchronize()
     return {'hads_modes': hads.cpu().numpy().view(np.uint32), 'hads_candidate': None if cand is None else cand.cpu().numpy().view(np.uint32),
             'list_modes': modes.cpu().numpy(), 'list_costs': costs.cpu().numpy().view(np.uint32)}
 
 
 def mode_hads_host(intra_patterns, targets, width_target, candidate_predictions=None, smoothing=0):
-    """mode_hads_device's host twin (pnn_hevc_mode_hads_host, pnn_hevc_mode_hads_hm_host when smoothing != 0; pure host code) on numpy
-    uint8 arrays: same arguments, same dictionary, same bits."""
+    """mode_hads_device's host twin (pnn_hevc_mode_hads_hm_host; pure host code) on numpy uint8 arrays: same arguments, same dictionary,
+    same bits."""
     smoothing = _check_smoothing(smoothing)
     arrays = [intra_patterns, targets] + ([] if candidate_predictions is None else [candidate_predictions])
     if any(not isinstance(a, np.ndarray) or a.dtype != np.uint8 for a in arrays):
@@ -271,13 +269,9 @@ def mode_hads_host(intra_patterns, targets, width_target, candidate_predictions=
     hads = np.zeros((n, NB_MODES), np.uint32)
     cand = None if candidate is None else np.zeros(n, np.uint32)
     modes, costs = np.zeros((n, k), np.uint8), np.zeros((n, k), np.uint32)
-    inputs = (patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, width_target, n,
-              None if candidate is None else candidate.ctypes.data)
-    outputs = (hads.ctypes.data, None if cand is None else cand.ctypes.data, modes.ctypes.data, costs.ctypes.data)
-    if smoothing == 0:
-        rc = _lib.lib().pnn_hevc_mode_hads_host(*(inputs + outputs))
-    else:
-        rc = _lib.lib().pnn_hevc_mode_hads_hm_host(*(inputs + (smoothing,) + outputs))
+    rc = _lib.lib().pnn_hevc_mode_hads_hm_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, width_target, n,
+                                               _address(candidate), smoothing, hads.ctypes.data, _address(cand), modes.ctypes.data,
+                                               costs.ctypes.data)
     if rc != 0:
         raise ValueError('pnn_hevc_mode_hads_host refused the arguments (patterns %dx%d, width %d).'
                          % (patterns.shape[1], patterns.shape[2], width_target))
@@ -364,17 +358,19 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     """Open-loop HEVC transform coding of N predictions against their targets (uint8 [N, w, w] or [N, w, w, 1]) at the 1 to 8 QPs of
     `qps` (integers in [0, 51]): HM's residual path with RDOQ 0 -- forward transform, quantisation, dequantisation, inverse transform,
     reconstruction -- as include/pnn_hip.h defines it (T = w up to 32, the four 32 x 32 quadrants of the one prediction at w = 64; no
-    RDOQ, sign-data hiding, transform skip or rate).  device=None runs the host twin (pnn_trquant_host), an int that GPU
-    (pnn_trquant_device: one launch for all blocks and QPs); the bits are the same.
+    RDOQ, sign-data hiding, transform skip or rate).  device=None runs the host twin (pnn_trquant_sdh_host), an int that GPU
+    (pnn_trquant_sdh_device: one launch for all blocks and QPs); the bits are the same.  The options below are arguments of these two
+    entries -- the rate pointer, the mode pointer, the flag -- NULL or 0 when off, which is what pnn_trquant_host / _device and
+    pnn_trquant_rate_host / _device forward to them.
     Returns {'sses_recon', 'nb_nonzero_levels', 'sum_abs_levels': uint32 [nb_qps, N], 'psnrs_recon': float64 [nb_qps, N] (psnrs_from_sses)}
     and, with keep_reconstructions, 'reconstructions_uint8' [nb_qps, N, w, w].
     rate=True adds 'rate_bits', float64 [nb_qps, N]: the bits HM's CABAC counter reports for the levels of each block's transform
     unit(s) from the I-slice initial contexts of the QP (include/pnn_hip.h, "the CABAC rate of the coded levels"; cbf_luma and mode bits
-    not counted) -- the uint64 count of pnn_trquant_rate_host / _device over 32768.  modes (with rate only): uint8 [N] intra modes in
+    not counted) -- the uint64 count the entry writes through its rate pointer, over 32768.  modes (with rate only): uint8 [N] intra modes in
     [0, 34] that pick each block's scan at w = 4 and 8; None codes every block under the diagonal scan.  With rate=False the dictionary
     is the one above.
     sign_data_hiding=True codes the way HM does with SignHideFlag 1 (its default) and RDOQ 0: signBitHidingHDQ between quantisation and
-    dequantisation (include/pnn_hip.h, "sign-data hiding"; pnn_trquant_sdh_host / _device).  Same keys; nb_nonzero_levels, the
+    dequantisation (include/pnn_hip.h, "sign-data hiding"; the entries' flag).  Same keys; nb_nonzero_levels, the
     reconstruction, sses_recon and rate_bits follow the levels after hiding (the hidden signs cost no bin), sum_abs_levels stays the
     sum before it.  `modes` is then allowed without `rate`: the scan shapes the levels.  With False nothing changes."""
     qps = _check_qps(qps)
@@ -385,41 +381,11 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     nq = len(qps)
     c_qps = (ctypes.c_int * nq)(*qps)
     L = _lib.lib()
-    if rate or sign_data_hiding:
-        return _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_reconstructions, modes, rate, bool(sign_data_hiding))
-    if modes is not None:
-        raise ValueError('`modes` is given without `rate`.')
-    if device is None:
-        sses, nonzero, sum_abs = (np.zeros((nq, n), np.uint32) for _ in range(3))
-        recon = np.zeros((nq, n, w, w), np.uint8) if keep_reconstructions else None
-        rc = L.pnn_trquant_host(predictions.ctypes.data, targets.ctypes.data, w, n, c_qps, nq, sses.ctypes.data, nonzero.ctypes.data,
-                                sum_abs.ctypes.data, None if recon is None else recon.ctypes.data)
-        if rc != 0:
-            raise ValueError('pnn_trquant_host refused the arguments (width %d, %d blocks).' % (w, n))
-    else:
-        import torch
-        dev = torch.device("cuda", device)
-        d_pred, d_tg = torch.from_numpy(predictions).to(dev), torch.from_numpy(targets).to(dev)
-        d_counts = torch.zeros((3, nq, n), dtype=torch.int32, device=dev)
-        d_recon = torch.zeros((nq, n, w, w), dtype=torch.uint8, device=dev) if keep_reconstructions else None
-        stream = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.pnn_trquant_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, c_qps, nq, d_counts[0].data_ptr(),
-                                            d_counts[1].data_ptr(), d_counts[2].data_ptr(), None if d_recon is None else d_recon.data_ptr(),
-                                            ctypes.c_void_p(stream.cuda_stream)), _context(device))
-        sses, nonzero, sum_abs = d_counts.cpu().numpy().view(np.uint32)      # (waits for the stream)
-        recon = None if d_recon is None else d_recon.cpu().numpy()
-    result = {'sses_recon': sses, 'nb_nonzero_levels': nonzero, 'sum_abs_levels': sum_abs, 'psnrs_recon': psnrs_from_sses(sses, w)}
-    if keep_reconstructions:
-        result['reconstructions_uint8'] = recon
-    return result
-
-
-def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_reconstructions, modes, rate=True, sign_data_hiding=False):
-    """transform_code(rate=True) and transform_code(sign_data_hiding=True) behind their argument checks: the entries with the rate (and
-    with the flag, when it is set), host or device."""
-    n, w, nq = targets.shape[0], targets.shape[1], len(qps)
-    if modes is not None:
+    flag = int(bool(sign_data_hiding))
+    if not (rate or flag):
+        if modes is not None:
+            raise ValueError('`modes` is given without `rate`.')
+    elif modes is not None:
         modes = np.asarray(modes)
         if modes.shape != (n,) or not np.issubdtype(modes.dtype, np.integer):
             raise ValueError('`modes` is not an integer array of shape [N].')
@@ -430,15 +396,11 @@ def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_recon
         sses, nonzero, sum_abs = (np.zeros((nq, n), np.uint32) for _ in range(3))
         bits = np.zeros((nq, n), np.uint64) if rate else None
         recon = np.zeros((nq, n, w, w), np.uint8) if keep_reconstructions else None
-        outputs = (sses.ctypes.data, nonzero.ctypes.data, sum_abs.ctypes.data, None if recon is None else recon.ctypes.data,
-                   None if bits is None else bits.ctypes.data)
-        blocks = (predictions.ctypes.data, targets.ctypes.data, w, n, None if modes is None else modes.ctypes.data, c_qps, nq)
-        if sign_data_hiding:
-            rc = L.pnn_trquant_sdh_host(*(blocks + outputs + (1,)))
-        else:
-            rc = L.pnn_trquant_rate_host(*(blocks + outputs))
-        if rc != 0:
-            raise ValueError('pnn_trquant_%s_host refused the arguments (width %d, %d blocks).' % ('sdh' if sign_data_hiding else 'rate', w, n))
+        rc = L.pnn_trquant_sdh_host(predictions.ctypes.data, targets.ctypes.data, w, n, _address(modes), c_qps, nq, sses.ctypes.data,
+                                    nonzero.ctypes.data, sum_abs.ctypes.data, _address(recon), _address(bits), flag)
+        if rc != 0:                                       # (named as the ABI names the call with these options)
+            raise ValueError('pnn_trquant_%shost refused the arguments (width %d, %d blocks).'
+                             % ('sdh_' if flag else 'rate_' if rate else '', w, n))
     else:
         import torch
         dev = torch.device("cuda", device)
@@ -448,14 +410,10 @@ def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_recon
         d_bits = torch.zeros((nq, n), dtype=torch.int64, device=dev) if rate else None
         d_recon = torch.zeros((nq, n, w, w), dtype=torch.uint8, device=dev) if keep_reconstructions else None
         stream = torch.cuda.current_stream(dev)
-        blocks = (_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, None if d_modes is None else d_modes.data_ptr(), c_qps, nq,
-                  d_counts[0].data_ptr(), d_counts[1].data_ptr(), d_counts[2].data_ptr(), None if d_recon is None else d_recon.data_ptr(),
-                  None if d_bits is None else d_bits.data_ptr())
         with torch.cuda.device(dev):
-            if sign_data_hiding:
-                _lib.check(L.pnn_trquant_sdh_device(*(blocks + (1, ctypes.c_void_p(stream.cuda_stream)))), _context(device))
-            else:
-                _lib.check(L.pnn_trquant_rate_device(*(blocks + (ctypes.c_void_p(stream.cuda_stream),))), _context(device))
+            _lib.check(L.pnn_trquant_sdh_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, _address(d_modes), c_qps, nq,
+                                                d_counts[0].data_ptr(), d_counts[1].data_ptr(), d_counts[2].data_ptr(), _address(d_recon),
+                                                _address(d_bits), flag, ctypes.c_void_p(stream.cuda_stream)), _context(device))
         sses, nonzero, sum_abs = d_counts.cpu().numpy().view(np.uint32)      # (waits for the stream)
         bits = None if d_bits is None else d_bits.cpu().numpy().view(np.uint64)
         recon = None if d_recon is None else d_recon.cpu().numpy()
@@ -470,13 +428,27 @@ def _transform_code_rate(L, predictions, targets, qps, c_qps, device, keep_recon
 SCANS = {'diagonal': 0, 'horizontal': 1, 'vertical': 2}
 
 
-def _unit_array(array, name, dtype_check=True):
-    """An integer [T, T] array, T in {4, 8, 16, 32}, as contiguous int32."""
+def _check_scan(scan):
+    """A scan, 0, 1, 2 or one of the names of SCANS, as its number."""
+    scan = SCANS.get(scan, scan)
+    if scan not in (0, 1, 2):
+        raise ValueError('`scan` is not 0, 1, 2 or their names.')
+    return scan
+
+
+def _square_integer_array(array, name):
+    """An integer [T, T] array, T in {4, 8, 16, 32}, as a numpy array of the dtype it came in."""
     array = np.asarray(array)
     if array.ndim != 2 or array.shape[0] != array.shape[1] or array.shape[0] not in (4, 8, 16, 32) or \
             not np.issubdtype(array.dtype, np.integer):
         raise ValueError('`%s` is not an integer [T, T] array with T in {4, 8, 16, 32}.' % name)
-    if array.size and (array.min() < -2 ** 31 + 1 or array.max() > 2 ** 31 - 1):
+    return array
+
+
+def _unit_array(array, name):
+    """An integer [T, T] array, T in {4, 8, 16, 32}, as contiguous int32."""
+    array = _square_integer_array(array, name)
+    if array.min() < -2 ** 31 + 1 or array.max() > 2 ** 31 - 1:
         raise ValueError('`%s` has a value that does not fit 32 bits.' % name)
     return np.ascontiguousarray(array.astype(np.int32))
 
@@ -486,7 +458,6 @@ def sign_hide_levels(levels, coeffs, delta_u, scan):
     levels after hiding, int32 [T, T], given the levels (each in [-32768, 32767]), the coefficients and the rounding remainders deltaU
     -- integer [T, T] arrays, T in {4, 8, 16, 32} -- under scan 0 / 'diagonal', 1 / 'horizontal' or 2 / 'vertical' (diagonal only at
     T = 16 and 32).  The inputs are left as they are."""
-    scan = SCANS.get(scan, scan)
     hidden, coeffs, delta_u = _unit_array(levels, 'levels'), _unit_array(coeffs, 'coeffs'), _unit_array(delta_u, 'delta_u')
     if hidden is levels:
         hidden = hidden.copy()
@@ -494,8 +465,7 @@ def sign_hide_levels(levels, coeffs, delta_u, scan):
         raise ValueError('`levels`, `coeffs` and `delta_u` differ in shape.')
     if hidden.min() < -32768 or hidden.max() > 32767:
         raise ValueError('`levels` has a value outside [-32768, 32767].')
-    if scan not in (0, 1, 2):
-        raise ValueError('`scan` is not 0, 1, 2 or their names.')
+    scan = _check_scan(scan)
     rc = _lib.lib().pnn_sign_hide_unit_host(hidden.ctypes.data, coeffs.ctypes.data, delta_u.ctypes.data, hidden.shape[0], int(scan))
     if rc != 0:
         raise ValueError('pnn_sign_hide_unit_host refused the arguments (T %d, scan %s).' % (hidden.shape[0], scan))
@@ -505,37 +475,31 @@ def sign_hide_levels(levels, coeffs, delta_u, scan):
 def cabac_rate_of_levels(levels, scan, qp, sign_data_hiding=False):
     """The CABAC rate, in units of 2^-15 bit (a Python int), of ONE transform unit given its levels -- an integer [T, T] array, T in
     {4, 8, 16, 32}, each level in [-32768, 32767] -- under scan 0 / 'diagonal', 1 / 'horizontal' or 2 / 'vertical' (diagonal only at
-    T = 16 and 32) at QP `qp`: pnn_cabac_rate_levels_host, the definition at include/pnn_hip.h.  0 for an all-zero unit.
-    sign_data_hiding=True: the rate when the hidden signs are not coded (pnn_cabac_rate_levels_sdh_host) -- one bypass bin fewer per
-    group whose first and last nonzero scan positions are at least 4 apart."""
+    T = 16 and 32) at QP `qp`: pnn_cabac_rate_levels_sdh_host, the definition at include/pnn_hip.h.  0 for an all-zero unit.
+    sign_data_hiding=True (the entry's flag; False is what pnn_cabac_rate_levels_host passes): the rate when the hidden signs are not
+    coded -- one bypass bin fewer per group whose first and last nonzero scan positions are at least 4 apart."""
     (qp,) = _check_qps((qp,))
-    scan = SCANS.get(scan, scan)
-    levels = np.asarray(levels)
-    if levels.ndim != 2 or levels.shape[0] != levels.shape[1] or levels.shape[0] not in (4, 8, 16, 32) or \
-            not np.issubdtype(levels.dtype, np.integer):
-        raise ValueError('`levels` is not an integer [T, T] array with T in {4, 8, 16, 32}.')
-    if levels.size and (levels.min() < -32768 or levels.max() > 32767):
+    levels = _square_integer_array(levels, 'levels')
+    if levels.min() < -32768 or levels.max() > 32767:     # (before the cast: a value that overflows 32 bits is outside this range too)
         raise ValueError('`levels` has a value outside [-32768, 32767].')
-    if scan not in (0, 1, 2):
-        raise ValueError('`scan` is not 0, 1, 2 or their names.')
+    scan = _check_scan(scan)
     levels = np.ascontiguousarray(levels.astype(np.int32))
     bits = ctypes.c_uint64(0)
-    if sign_data_hiding:
-        rc = _lib.lib().pnn_cabac_rate_levels_sdh_host(levels.ctypes.data, levels.shape[0], int(scan), qp, 1, ctypes.byref(bits))
-    else:
-        rc = _lib.lib().pnn_cabac_rate_levels_host(levels.ctypes.data, levels.shape[0], int(scan), qp, ctypes.byref(bits))
+    rc = _lib.lib().pnn_cabac_rate_levels_sdh_host(levels.ctypes.data, levels.shape[0], int(scan), qp, int(bool(sign_data_hiding)),
+                                                   ctypes.byref(bits))
     if rc != 0:
         raise ValueError('pnn_cabac_rate_levels_host refused the arguments (T %d, scan %s, QP %d).' % (levels.shape[0], scan, qp))
     return int(bits.value)
 
 
 def transform_stages(prediction_uint8, target_uint8, qp, sign_data_hiding=False, scan=0):
-    """Every stage of transform_code for ONE block (uint8 [w, w] or [w, w, 1]) at one QP, host code (pnn_trquant_stages_host):
+    """Every stage of transform_code for ONE block (uint8 [w, w] or [w, w, 1]) at one QP, host code (pnn_trquant_stages_sdh_host):
     {'coeffs', 'levels', 'dequant', 'residual'}, int32 [w, w] -- the forward transform's coefficients, the quantised levels, the
     dequantised coefficients, the inverse transform's residual; at w = 64 each 32 x 32 unit's array lies where the unit lies.
-    sign_data_hiding=True (pnn_trquant_stages_sdh_host) hides signs under `scan` (0, 1, 2 or their names; diagonal only at w >= 16) and
+    sign_data_hiding=True (the entry's flag) hides signs under `scan` (0, 1, 2 or their names; diagonal only at w >= 16) and
     adds 'delta_u', xQuant's rounding remainders, and 'levels_hidden', the levels after hiding, from which 'dequant' and 'residual'
-    then come; 'levels' stays the quantiser's output.  `scan` is read with the flag only."""
+    then come; 'levels' stays the quantiser's output.  `scan` is read with the flag only: without it the entry gets scan 0, the flag 0
+    and NULL for the two added arrays, as pnn_trquant_stages_host passes them."""
     (qp,) = _check_qps((qp,))
     blocks = []
     for name, block in (('prediction_uint8', prediction_uint8), ('target_uint8', target_uint8)):
@@ -548,20 +512,17 @@ def transform_stages(prediction_uint8, target_uint8, qp, sign_data_hiding=False,
     if prediction.shape != target.shape:
         raise ValueError('`prediction_uint8.shape` is not equal to `target_uint8.shape`.')
     w = target.shape[0]
-    if sign_data_hiding:
-        scan = SCANS.get(scan, scan)
-        if scan not in (0, 1, 2):
-            raise ValueError('`scan` is not 0, 1, 2 or their names.')
-        names = ('coeffs', 'levels', 'delta_u', 'levels_hidden', 'dequant', 'residual')
-        stages = {name: np.zeros((w, w), np.int32) for name in names}
-        rc = _lib.lib().pnn_trquant_stages_sdh_host(prediction.ctypes.data, target.ctypes.data, w, qp, int(scan), 1,
-                                                    *(stages[name].ctypes.data for name in names))
-        if rc != 0:
-            raise ValueError('pnn_trquant_stages_sdh_host refused the arguments (width %d, QP %d, scan %d).' % (w, qp, scan))
-        return stages
-    stages = {name: np.zeros((w, w), np.int32) for name in ('coeffs', 'levels', 'dequant', 'residual')}
-    rc = _lib.lib().pnn_trquant_stages_host(prediction.ctypes.data, target.ctypes.data, w, qp, stages['coeffs'].ctypes.data,
-                                            stages['levels'].ctypes.data, stages['dequant'].ctypes.data, stages['residual'].ctypes.data)
+    flag = int(bool(sign_data_hiding))
+    scan = _check_scan(scan) if flag else 0
+    hiding = ('delta_u', 'levels_hidden')
+    stages = {name: np.zeros((w, w), np.int32) for name in ('coeffs', 'levels') + (hiding if flag else ()) + ('dequant', 'residual')}
+    rc = _lib.lib().pnn_trquant_stages_sdh_host(prediction.ctypes.data, target.ctypes.data, w, qp, int(scan), flag,
+                                                stages['coeffs'].ctypes.data, stages['levels'].ctypes.data,
+                                                *[_address(stages.get(name)) for name in hiding + ('dequant', 'residual')])
     if rc != 0:
+        if flag:
+            raise ValueError('pnn_trquant_stages_sdh_host refused the arguments (width %d, QP %d, scan %d).' % (w, qp, scan))
         raise ValueError('pnn_trquant_stages_host refused the arguments (width %d, QP %d).' % (w, qp))
     return stages
+
+

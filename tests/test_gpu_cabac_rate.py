@@ -12,24 +12,13 @@ from context_adaptive_neural_network_based_prediction_amd import _lib, evaluatio
 from context_adaptive_neural_network_based_prediction_amd import intraprediction as ip
 from tests import trquant_cases as cases
 from tests import util
-from tests.util import assert_same_dictionary, dev, picture_pairs, positions, stream
+from tests.trquant_cases import MODES, blocks_per_workgroup, specs_of
+from tests.util import PNN_E_ARG, assert_same_dictionary, dev, make_net, picture_pairs, positions, ptr, untouched
 
 pytestmark = pytest.mark.gpu
 
-PNN_E_ARG = -1
-GUARD, PAD = 0xC5, 256
 QP_LISTS = {1: (27,), 4: (0, 22, 37, 51), 8: (0, 5, 17, 22, 30, 37, 46, 51)}
 OUTPUTS = ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels', 'reconstructions_uint8', 'rate')
-# all three scans and both ends of each angle window (6 .. 14 vertical scan, 22 .. 30 horizontal scan) with their outer neighbours
-MODES = (5, 6, 14, 15, 21, 22, 30, 31, 0, 1, 10, 26, 2, 34, 18)
-
-
-def blocks_per_workgroup(w):
-    return 1 if w >= 32 else 1024 // (w * w)              # trquant_blocks_per_workgroup of csrc/pnn_trquant.hip
-
-
-def specs_of(w, n, nq):
-    return [(np.uint32, (nq, n))] * 3 + [(np.uint8, (nq, n, w, w)), (np.uint64, (nq, n))]
 
 
 def host_call(w, predictions, targets, qps, modes):
@@ -43,26 +32,18 @@ def host_call(w, predictions, targets, qps, modes):
 
 
 def device_call(w, predictions, targets, qps, modes, wanted=(True,) * 5, plain=False):
-    """Raw ABI call of pnn_trquant_rate_device (plain: of pnn_trquant_device, which has neither modes nor rate); every output between PAD
-    guard bytes.  Returns (rc, the outputs as numpy or None, guards intact)."""
-    import torch
+    """Raw ABI call of pnn_trquant_rate_device (plain: of pnn_trquant_device, which has neither modes nor rate: its four outputs, None
+    for the rate); every output between guard bytes.  Returns (rc, the outputs as numpy or None, guards intact)."""
     n, nq = predictions.shape[0], len(qps)
     specs = specs_of(w, n, nq)
-    bufs = [torch.full((2 * PAD + int(np.prod(s)) * np.dtype(t).itemsize,), GUARD, dtype=torch.uint8, device="cuda") for t, s in specs]
     d_p, d_t = dev(predictions), dev(targets)
     d_m = None if modes is None else dev(modes)
-    pointers = [b.data_ptr() + PAD if want else None for b, want in zip(bufs, wanted)]
+    blocks = (ip._context(0), w, d_p.data_ptr(), d_t.data_ptr(), n)
     c_qps = (ctypes.c_int * max(nq, 1))(*qps)
     if plain:
-        rc = _lib.lib().pnn_trquant_device(ip._context(0), w, d_p.data_ptr(), d_t.data_ptr(), n, c_qps, nq, *pointers[:4], stream())
-    else:
-        rc = _lib.lib().pnn_trquant_rate_device(ip._context(0), w, d_p.data_ptr(), d_t.data_ptr(), n, None if d_m is None else d_m.data_ptr(),
-                                                c_qps, nq, *pointers, stream())
-    torch.cuda.synchronize()
-    raw = [b.cpu().numpy() for b in bufs]
-    intact = all((r[:PAD] == GUARD).all() and (r[-PAD:] == GUARD).all() and (want or (r == GUARD).all()) for r, want in zip(raw, wanted))
-    outs = [r[PAD:-PAD].view(t).reshape(s) if want else None for r, want, (t, s) in zip(raw, wanted, specs)]
-    return rc, outs, intact
+        rc, outs, intact = util.call("pnn_trquant_device", blocks + (c_qps, nq), (), specs[:4], wanted[:4])
+        return rc, outs + [None], intact
+    return util.call("pnn_trquant_rate_device", blocks + (ptr(d_m), c_qps, nq), (), specs, wanted)
 
 
 def blocks_of(w, n, nb_qps):
@@ -126,17 +107,12 @@ def test_device_argument_errors():
     for wanted, mode_array, word in (((True,) * 4 + (False,), modes, b"modes"), ((False,) * 5, None, b"NULL")):
         rc, outs, intact = device_call(w, predictions, targets, (22,), mode_array, wanted=wanted)
         assert rc == PNN_E_ARG and intact
-        assert all(o is None or (o.view(np.uint8) == GUARD).all() for o in outs)
+        assert untouched(outs)
         assert word in _lib.lib().pnn_last_error(ip._context(0))
     with pytest.raises(ValueError):
         ip.transform_code(predictions, targets, (22,), device=0, modes=modes)
     with pytest.raises(ValueError):
         ip.transform_code(predictions, targets, (22,), device=0, modes=np.array([0, 35, 1]), rate=True)
-
-
-def make_net(w, is_fc, batch):
-    import context_adaptive_neural_network_based_prediction_amd as P
-    return P.PredictionNeuralNetwork(batch, w, is_fc, params=util.make_params(w, is_fc, seed=70 + w, out_gain=util.out_gain(w, is_fc)))
 
 
 RATE_KEYS = {'rate_bits_pnn', 'rate_bits_hevc_best_mode', 'frequency_rate_win_pnn'}

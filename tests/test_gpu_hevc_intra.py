@@ -11,7 +11,7 @@ import pytest
 from context_adaptive_neural_network_based_prediction_amd import _lib, evaluation
 from context_adaptive_neural_network_based_prediction_amd import intraprediction as ip
 from tests import util
-from tests.util import dev
+from tests.util import PNN_E_ARG, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +19,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 NATURAL = os.path.join(ROOT, "oracle", "_ref", "natural_luma.npz")
 WIDTHS = (4, 8, 16, 32, 64)
-PNN_E_ARG = -1                       # include/pnn_hip.h
 
 
 @pytest.fixture(scope="module")

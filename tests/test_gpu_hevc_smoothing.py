@@ -15,15 +15,13 @@ from context_adaptive_neural_network_based_prediction_amd import intraprediction
 from tests import hevc_smoothing_cases as cases
 from tests import test_gpu_mode_hads as base
 from tests import util
-from tests.util import dev, picture_pairs, positions, stream
+from tests.util import PNN_E_ARG, call, dev, picture_pairs, positions, ptr, untouched
 
 pytestmark = pytest.mark.gpu
 
-PNN_E_ARG = -1                       # include/pnn_hip.h
 WIDTHS = (4, 8, 16, 32, 64)
 HADS_N = {4: 64 + 3, 8: 64 + 3, 16: 16 + 3, 32: 4 + 3, 64: 3}        # the SATD kernel's G + 3 (1 + 2 at w = 64)
 SSE_N = {4: 64 + 3, 8: 64 + 3, 16: 16 + 3, 32: 8 + 3, 64: 4 + 3}     # the SSE search groups 64 / (w / rows per lane) blocks: its own G + 3
-GUARD, PAD = 0xC5, 256
 HOST_KEYS = base.HOST_KEYS
 
 
@@ -33,32 +31,6 @@ def hads_specs(n, w):
 
 def sse_specs(n, w):
     return [(np.uint8, (n,)), (np.uint32, (n,)), (np.uint8, (n, w, w)), (np.uint32, (n, 35))]
-
-
-def guarded(specs):
-    import torch
-    return [torch.full((2 * PAD + int(np.prod(s)) * np.dtype(t).itemsize,), GUARD, dtype=torch.uint8, device="cuda") for t, s in specs]
-
-
-def collect(bufs, wanted, specs):
-    """(the outputs as numpy, None where not asked for; whether every byte outside the asked-for outputs still is the guard)"""
-    import torch
-    torch.cuda.synchronize()
-    raw = [b.cpu().numpy() for b in bufs]
-    intact = all((r[:PAD] == GUARD).all() and (r[-PAD:] == GUARD).all() and (want or (r == GUARD).all()) for r, want in zip(raw, wanted))
-    return [r[PAD:-PAD].view(t).reshape(s) if want else None for r, want, (t, s) in zip(raw, wanted, specs)], intact
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def call(entry, front, back, specs, wanted):
-    """entry(*front, <output pointers>, stream) -- or, with `back` (the smoothing), entry(*front, *back, <outputs>, stream)."""
-    bufs = guarded(specs)
-    rc = getattr(_lib.lib(), entry)(*front, *back, *[b.data_ptr() + PAD if want else None for b, want in zip(bufs, wanted)], stream())
-    outs, intact = collect(bufs, wanted, specs)
-    return rc, outs, intact
 
 
 def hads_dense(ctx, w, d_patterns, sides, d_targets, n, d_cand, smoothing, wanted=(True,) * 4, blocks=None):
@@ -320,9 +292,6 @@ def test_bad_arguments_are_refused_before_any_launch():
     ctx = ip._context(0)
     d_context, d_target = dev(pair[..., 1]), dev(pair[..., 0])
     d_cand = dev(np.zeros((6, w, w), np.uint8))
-
-    def untouched(outs):
-        return all(g is None or (g.view(np.uint8) == GUARD).all() for g in outs)
 
     def first_pass_refused(planes=(d_context, d_target), rows=rows, cols=cols, shape=(images, H, W), mask=mask, wanted=(True,) * 4, w=w, cand=d_cand,
                            smoothing=2, ctx=ctx):

@@ -14,17 +14,15 @@ import pytest
 from context_adaptive_neural_network_based_prediction_amd import _lib, evaluation
 from context_adaptive_neural_network_based_prediction_amd import intraprediction as ip
 from tests import util
-from tests.util import dev, picture_pairs, positions, stream
+from tests.util import PNN_E_ARG, call, dev, picture_pairs, positions, ptr, untouched
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-PNN_E_ARG = -1                       # include/pnn_hip.h
 DENSE_N = {4: 64 + 3, 8: 64 + 3, 16: 16 + 3, 32: 4 + 3, 64: 3}
 OUTPUTS = ("mode_hads", "cand_hads", "list_modes", "list_costs")
 HOST_KEYS = ("hads_modes", "hads_candidate", "list_modes", "list_costs")
-GUARD, PAD = 0xC5, 256                             # guard bytes in front of and behind every output
 
 
 def dense_blocks(w, n, sides, seed):
@@ -50,45 +48,19 @@ def output_specs(n, w):
     return [(np.uint32, (n, 35)), (np.uint32, (n,)), (np.uint8, (n, k)), (np.uint32, (n, k))]
 
 
-def guarded(n, w):
-    import torch
-    return [torch.full((2 * PAD + int(np.prod(s)) * np.dtype(t).itemsize,), GUARD, dtype=torch.uint8, device="cuda") for t, s in output_specs(n, w)]
-
-
-def collect(bufs, wanted, n, w):
-    """(the four outputs as numpy, None where not asked for; whether every byte outside the asked-for outputs still is the guard)"""
-    import torch
-    torch.cuda.synchronize()
-    raw = [b.cpu().numpy() for b in bufs]
-    intact = all((r[:PAD] == GUARD).all() and (r[-PAD:] == GUARD).all() and (want or (r == GUARD).all()) for r, want in zip(raw, wanted))
-    return [r[PAD:-PAD].view(t).reshape(s) if want else None for r, want, (t, s) in zip(raw, wanted, output_specs(n, w))], intact
-
-
 def dense_call(ctx, w, d_patterns, sides, d_targets, n, d_cand, wanted=(True,) * 4, blocks=None):
-    bufs = guarded(blocks if blocks is not None else n, w)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    rc = _lib.lib().pnn_hevc_mode_hads_device(ctx, w, ptr(d_patterns), sides[0], sides[1], ptr(d_targets), n, ptr(d_cand),
-                                              *[b.data_ptr() + PAD if want else None for b, want in zip(bufs, wanted)], stream())
-    outs, intact = collect(bufs, wanted, blocks if blocks is not None else n, w)
-    return rc, outs, intact
+    """Raw call of pnn_hevc_mode_hads_device, every output between guard bytes: (rc, the four outputs or None, guards intact)."""
+    front = (ctx, w, ptr(d_patterns), sides[0], sides[1], ptr(d_targets), n, ptr(d_cand))
+    return call("pnn_hevc_mode_hads_device", front, (), output_specs(blocks if blocks is not None else n, w), wanted)
 
 
 def picture_call(ctx, w, planes, rows, cols, mask, d_cand, shape, wanted=(True,) * 4, blocks=None):
     """Raw call of pnn_first_pass_picture_pairs_device; `planes` = (context, target) device tensors or None."""
     images, H, W = shape
     n = blocks if blocks is not None else images * len(rows)
-    bufs = guarded(n, w)
     d_r, d_c = dev(np.asarray(rows, np.int32)), dev(np.asarray(cols, np.int32))
-    ptr = lambda t: None if t is None else t.data_ptr()
-    rc = _lib.lib().pnn_first_pass_picture_pairs_device(ctx, w, ptr(planes[0]), ptr(planes[1]), images, H, W, d_r.data_ptr(), d_c.data_ptr(),
-                                                        len(rows), mask[0], mask[1], ptr(d_cand),
-                                                        *[b.data_ptr() + PAD if want else None for b, want in zip(bufs, wanted)], stream())
-    outs, intact = collect(bufs, wanted, n, w)
-    return rc, outs, intact
-
-
-def untouched(outs):
-    return all(g is None or (g.view(np.uint8) == GUARD).all() for g in outs)
+    front = (ctx, w, ptr(planes[0]), ptr(planes[1]), images, H, W, d_r.data_ptr(), d_c.data_ptr(), len(rows), mask[0], mask[1], ptr(d_cand))
+    return call("pnn_first_pass_picture_pairs_device", front, (), output_specs(n, w), wanted)
 
 
 def assert_equal_host(got, host, wanted, label):

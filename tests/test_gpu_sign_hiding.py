@@ -18,26 +18,15 @@ from context_adaptive_neural_network_based_prediction_amd import intraprediction
 from tests import cabac_rate_cases as cabac
 from tests import sign_hiding_cases as cases
 from tests import util
-from tests.util import assert_same_dictionary, dev, picture_pairs, positions, stream
+from tests.trquant_cases import MODES, blocks_per_workgroup, specs_of
+from tests.util import PNN_E_ARG, assert_same_dictionary, dev, make_net, picture_pairs, positions, ptr, untouched
 
 pytestmark = pytest.mark.gpu
 
-PNN_E_ARG = -1
-GUARD, PAD = 0xC5, 256
 # low QPs: dense levels, whose groups have the wrong parity about half the time
 QP_LISTS = {1: (12,), 4: (0, 10, 22, 27), 8: (0, 4, 8, 12, 17, 22, 27, 32)}
 OUTPUTS = ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels', 'reconstructions_uint8', 'rate')
-# all three scans and both ends of each angle window (6 .. 14 vertical scan, 22 .. 30 horizontal scan) with their outer neighbours
-MODES = (5, 6, 14, 15, 21, 22, 30, 31, 0, 1, 10, 26, 2, 34, 18)
 TAKEN = {}                                                # rows of the cost table the host twin took, over the whole file
-
-
-def blocks_per_workgroup(w):
-    return 1 if w >= 32 else 1024 // (w * w)              # trquant_blocks_per_workgroup of csrc/pnn_trquant.hip
-
-
-def specs_of(w, n, nq):
-    return [(np.uint32, (nq, n))] * 3 + [(np.uint8, (nq, n, w, w)), (np.uint64, (nq, n))]
 
 
 def host_call(w, predictions, targets, qps, modes, flag=1, wanted=(True,) * 5):
@@ -51,26 +40,15 @@ def host_call(w, predictions, targets, qps, modes, flag=1, wanted=(True,) * 5):
 
 
 def device_call(w, predictions, targets, qps, modes, flag=1, wanted=(True,) * 5, entry="sdh"):
-    """Raw ABI call of pnn_trquant_sdh_device (entry "rate": of pnn_trquant_rate_device, which has no flag); every output between PAD
-    guard bytes.  Returns (rc, the outputs as numpy or None, guards intact)."""
-    import torch
+    """Raw ABI call of pnn_trquant_sdh_device (entry "rate": of pnn_trquant_rate_device, which has no flag); every output between guard
+    bytes.  Returns (rc, the outputs as numpy or None, guards intact)."""
     n, nq = predictions.shape[0], len(qps)
-    specs = specs_of(w, n, nq)
-    bufs = [torch.full((2 * PAD + int(np.prod(s)) * np.dtype(t).itemsize,), GUARD, dtype=torch.uint8, device="cuda") for t, s in specs]
     d_p, d_t = dev(predictions), dev(targets)
     d_m = None if modes is None else dev(modes)
-    pointers = [b.data_ptr() + PAD if want else None for b, want in zip(bufs, wanted)]
-    c_qps = (ctypes.c_int * max(nq, 1))(*qps)
-    front = (ip._context(0), w, d_p.data_ptr(), d_t.data_ptr(), n, None if d_m is None else d_m.data_ptr(), c_qps, nq)
+    front = (ip._context(0), w, d_p.data_ptr(), d_t.data_ptr(), n, ptr(d_m), (ctypes.c_int * max(nq, 1))(*qps), nq)
     if entry == "rate":
-        rc = _lib.lib().pnn_trquant_rate_device(*front, *pointers, stream())
-    else:
-        rc = _lib.lib().pnn_trquant_sdh_device(*front, *pointers, flag, stream())
-    torch.cuda.synchronize()
-    raw = [b.cpu().numpy() for b in bufs]
-    intact = all((r[:PAD] == GUARD).all() and (r[-PAD:] == GUARD).all() and (want or (r == GUARD).all()) for r, want in zip(raw, wanted))
-    outs = [r[PAD:-PAD].view(t).reshape(s) if want else None for r, want, (t, s) in zip(raw, wanted, specs)]
-    return rc, outs, intact
+        return util.call("pnn_trquant_rate_device", front, (), specs_of(w, n, nq), wanted)
+    return util.call("pnn_trquant_sdh_device", front, (), specs_of(w, n, nq), wanted, after=(flag,))
 
 
 def blocks_of(w, n):
@@ -162,7 +140,7 @@ def test_device_argument_errors():
     for wanted, mode_array, flag, word in ((no_rate, modes, 0, b"modes"), ((False,) * 5, None, 1, b"NULL")):
         rc, outs, intact = device_call(w, predictions, targets, (22,), mode_array, flag=flag, wanted=wanted)
         assert rc == PNN_E_ARG and intact
-        assert all(o is None or (o.view(np.uint8) == GUARD).all() for o in outs)
+        assert untouched(outs)
         assert word in _lib.lib().pnn_last_error(ip._context(0))
     rc, outs, intact = device_call(w, predictions, targets, (22,), modes, wanted=no_rate)
     assert rc == 0 and intact
@@ -170,11 +148,6 @@ def test_device_argument_errors():
                                              None) == PNN_E_ARG
     with pytest.raises(ValueError):
         ip.transform_code(predictions, targets, (22,), device=0, modes=np.array([0, 35, 1]), sign_data_hiding=True)
-
-
-def make_net(w, is_fc, batch):
-    import context_adaptive_neural_network_based_prediction_amd as P
-    return P.PredictionNeuralNetwork(batch, w, is_fc, params=util.make_params(w, is_fc, seed=70 + w, out_gain=util.out_gain(w, is_fc)))
 
 
 COLUMN_KEYS = ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels', 'psnrs_recon')

@@ -11,40 +11,28 @@ from context_adaptive_neural_network_based_prediction_amd import _lib, evaluatio
 from context_adaptive_neural_network_based_prediction_amd import intraprediction as ip
 from tests import trquant_cases as cases
 from tests import util
-from tests.util import assert_same_dictionary, dev, picture_pairs, positions, stream
+from tests.util import PNN_E_ARG, assert_same_dictionary, dev, make_net, picture_pairs, positions, stream, untouched
 
 pytestmark = pytest.mark.gpu
 
-PNN_E_ARG = -1
-GUARD, PAD = 0xC5, 256
-BLOCKS_PER_WORKGROUP = {4: 64, 8: 16, 16: 4, 32: 1, 64: 1}      # G of csrc/pnn_trquant.hip
 QP_LISTS = {1: (27,), 4: (22, 27, 32, 37), 8: (0, 5, 17, 22, 30, 37, 46, 51)}
 OUTPUTS = ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels', 'reconstructions_uint8')
 
 
 def device_call(w, predictions, targets, qps, wanted=(True,) * 4, n=None, ctx=None):
-    """Raw ABI call; every output between PAD guard bytes.  Returns (rc, the four outputs as numpy or None, guards intact)."""
-    import torch
+    """Raw ABI call; every output between guard bytes.  Returns (rc, the four outputs as numpy or None, guards intact)."""
     n = predictions.shape[0] if n is None else n
     nq = len(qps)
-    specs = [(np.uint32, (nq, max(n, 0)))] * 3 + [(np.uint8, (nq, max(n, 0), w, w))]
-    bufs = [torch.full((2 * PAD + int(np.prod(s)) * np.dtype(t).itemsize,), GUARD, dtype=torch.uint8, device="cuda") for t, s in specs]
     d_p, d_t = dev(predictions), dev(targets)
-    rc = _lib.lib().pnn_trquant_device(ip._context(0) if ctx is None else ctx, w, d_p.data_ptr(), d_t.data_ptr(), n,
-                                       (ctypes.c_int * max(nq, 1))(*qps), nq,
-                                       *[b.data_ptr() + PAD if want else None for b, want in zip(bufs, wanted)], stream())
-    torch.cuda.synchronize()
-    raw = [b.cpu().numpy() for b in bufs]
-    intact = all((r[:PAD] == GUARD).all() and (r[-PAD:] == GUARD).all() and (want or (r == GUARD).all()) for r, want in zip(raw, wanted))
-    outs = [r[PAD:-PAD].view(t).reshape(s) if want else None for r, want, (t, s) in zip(raw, wanted, specs)]
-    return rc, outs, intact
+    front = (ip._context(0) if ctx is None else ctx, w, d_p.data_ptr(), d_t.data_ptr(), n, (ctypes.c_int * max(nq, 1))(*qps), nq)
+    return util.call("pnn_trquant_device", front, (), cases.specs_of(w, max(n, 0), nq)[:4], wanted)
 
 
 @pytest.mark.parametrize("nb_qps", (1, 4, 8))
 @pytest.mark.parametrize("w", cases.WIDTHS)
 def test_kernel_against_host_twin(w, nb_qps):
     """n = 2 G + 1 blocks: two full workgroups and a ragged one; the extremes and a zero residual share the first with random blocks."""
-    n = 2 * BLOCKS_PER_WORKGROUP[w] + 1
+    n = 2 * cases.blocks_per_workgroup(w) + 1
     qps = QP_LISTS[nb_qps]
     predictions, targets = cases.mixed_pairs(w, max(n, 4), 700 + w)
     predictions, targets = predictions[:n], targets[:n]
@@ -100,7 +88,7 @@ def test_device_argument_errors():
         args.update(kwargs)
         rc, outs, intact = device_call(args['w'], predictions, targets, args['qps'], wanted=args['wanted'], n=args['n'])
         assert rc == PNN_E_ARG and intact, kwargs
-        assert all(o is None or (o.view(np.uint8) == GUARD).all() for o in outs), kwargs
+        assert untouched(outs), kwargs
         assert word in L.pnn_last_error(ctx), (kwargs, L.pnn_last_error(ctx))
     out = dev(np.zeros(3, np.uint32))
     good = (ctypes.c_int * 1)(22)
@@ -110,11 +98,6 @@ def test_device_argument_errors():
     assert L.pnn_trquant_device(ctx, w, None, None, 0, good, 1, out.data_ptr(), None, None, None, stream()) == 0       # n == 0 does nothing
     with pytest.raises(ValueError):
         ip.transform_code(predictions, targets, (52,), device=0)
-
-
-def make_net(w, is_fc, batch):
-    import context_adaptive_neural_network_based_prediction_amd as P
-    return P.PredictionNeuralNetwork(batch, w, is_fc, params=util.make_params(w, is_fc, seed=70 + w, out_gain=util.out_gain(w, is_fc)))
 
 
 TRANSFORM_KEYS = {'transform_qps', 'frequency_recon_win_pnn'} | {

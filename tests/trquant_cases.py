@@ -152,3 +152,18 @@ def mixed_pairs(w, n, seed):
     k = min(4, n)
     pr[:k], tr[:k] = p0[:k], t0[:k]
     return pr, tr
+
+
+# What the GPU tests of the three transform-coding entries (tests/test_gpu_trquant.py, _cabac_rate.py, _sign_hiding.py) share.
+# MODES: all three scans and both ends of each angle window (6 .. 14 vertical scan, 22 .. 30 horizontal scan) with their outer neighbours
+MODES = (5, 6, 14, 15, 21, 22, 30, 31, 0, 1, 10, 26, 2, 34, 18)
+
+
+def blocks_per_workgroup(w):
+    return 1 if w >= 32 else 1024 // (w * w)              # trquant_blocks_per_workgroup of csrc/pnn_trquant.hip
+
+
+def specs_of(w, n, nq):
+    """(dtype, shape) of the five outputs: sses_recon, nb_nonzero_levels, sum_abs_levels, the reconstructions, the rate (the entry
+    without the rate has the first four)"""
+    return [(np.uint32, (nq, n))] * 3 + [(np.uint8, (nq, n, w, w)), (np.uint64, (nq, n))]

@@ -145,6 +145,53 @@ def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def make_net(w, is_fc, batch, seed=None):
+    """A PredictionNeuralNetwork of seeded weights (seed 70 + w unless given) whose predictions sweep the whole 0..255 range."""
+    import context_adaptive_neural_network_based_prediction_amd as P
+    return P.PredictionNeuralNetwork(batch, w, is_fc, params=make_params(w, is_fc, seed=70 + w if seed is None else seed,
+                                                                         out_gain=out_gain(w, is_fc)))
+
+
+# The guarded raw call of a C-ABI device entry: every output lies in a buffer of its own between PAD guard bytes, so a write in front
+# of, behind or into an output that was not asked for shows.  `specs` lists the outputs as (dtype, shape), `wanted` says which get a
+# pointer (the others get NULL).
+PNN_E_ARG = -1                                     # include/pnn_hip.h
+GUARD, PAD = 0xC5, 256
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def guarded(specs):
+    import torch
+    return [torch.full((2 * PAD + int(np.prod(s)) * np.dtype(t).itemsize,), GUARD, dtype=torch.uint8, device="cuda") for t, s in specs]
+
+
+def collect(bufs, wanted, specs):
+    """(the outputs as numpy, None where not asked for; whether every byte outside the asked-for outputs still is the guard)"""
+    import torch
+    torch.cuda.synchronize()
+    raw = [b.cpu().numpy() for b in bufs]
+    intact = all((r[:PAD] == GUARD).all() and (r[-PAD:] == GUARD).all() and (want or (r == GUARD).all()) for r, want in zip(raw, wanted))
+    return [r[PAD:-PAD].view(t).reshape(s) if want else None for r, want, (t, s) in zip(raw, wanted, specs)], intact
+
+
+def call(entry, front, back, specs, wanted, after=()):
+    """entry(*front, *back, <output pointers>, *after, stream): `back` is what an entry takes between its inputs and its outputs (the
+    smoothing), `after` what it takes behind them (the sign-hiding flag).  Returns (rc, outputs, intact) as collect gives them."""
+    from context_adaptive_neural_network_based_prediction_amd import _lib
+    bufs = guarded(specs)
+    rc = getattr(_lib.lib(), entry)(*front, *back, *[b.data_ptr() + PAD if want else None for b, want in zip(bufs, wanted)], *after, stream())
+    outs, intact = collect(bufs, wanted, specs)
+    return rc, outs, intact
+
+
+def untouched(outs):
+    """No asked-for output of a guarded call was written: each still holds the guard."""
+    return all(g is None or (g.view(np.uint8) == GUARD).all() for g in outs)
+
+
 def assert_same_dictionary(got, want, label):
     """Same keys; arrays equal in dtype, shape and bytes; everything else equal in type and value."""
     assert set(got) == set(want), label
