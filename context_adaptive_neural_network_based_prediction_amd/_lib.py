@@ -104,6 +104,13 @@ SIGNATURES = {
     "pnn_trquant_stages_sdh_host": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
     "pnn_cabac_rate_levels_sdh_host": (ci, [vp, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_uint64)]),
     "pnn_trquant_sdh_device": (ci, [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, ci, vp]),
+    "pnn_hm_intra_lambda": (ctypes.c_double, [ci]),
+    "pnn_rd_pass_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci] + [vp] * 7),
+    "pnn_rd_pass_workspace_bytes": (ctypes.c_size_t, [ci, ci, ci]),
+    "pnn_rd_pass_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci] + [vp] * 8 +
+                           [ctypes.c_size_t, vp]),
+    "pnn_rd_pass_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(ci), ci,
+                                              ctypes.POINTER(ctypes.c_double), ci] + [vp] * 8 + [ctypes.c_size_t, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

@@ -1,7 +1,7 @@
 // The C-ABI entries of the Python evaluator (include/pnn_hip.h; HM calls none of them): the best HEVC intra mode and the first-pass
 // Hadamard ranking on dense patterns (each with its *_hm sibling: HM's reference-sample smoothing as an option; the entry without the
 // suffix is the sibling called with 0), IPFCN-S, the scores from pictures and pairs of pictures, the open-loop transform
-// coding of predictions.  Contexts, models, staging and the
+// coding of predictions, HM's second intra pass over the first-pass candidates.  Contexts, models, staging and the
 // predictor's entries: pnn_abi.cpp.  Each argument check is written once and composed per entry; an entry's ORDER of checks is part of
 // its behaviour (which of two bad arguments pnn_last_error names), so it is spelled out in the entry.
 #include "pnn_ctx.h"
@@ -130,6 +130,90 @@ int check_trquant(pnn_ctx* c, int width, const uint8_t* d_predictions, const uin
     if (n < 0 || (n > 0 && (!d_predictions || !d_targets))) return fail(c, PNN_E_ARG, "bad batch size or input buffers");
     if (!trquant::qps_ok(qps, nb_qps)) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d integers in [0, %d]", trquant::kMaxQps, trquant::kMaxQp);
     return check_some_output(c, any_output);
+}
+
+// the launch's inputs: the QPs' constants and initial context states, worked out here; the outputs are the caller's to set
+TrQuantParams trquant_params(int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes, const int* qps,
+                             int nb_qps, int sign_data_hiding)
+{
+    TrQuantParams p;
+    p.pred = d_predictions; p.targets = d_targets; p.N = n; p.w = width; p.nb_qps = nb_qps;
+    for (int i = 0; i < trquant::kMaxQps; i++) {
+        const int qp = qps[i < nb_qps ? i : 0];
+        p.qp[i] = trquant::qp_consts(trquant::log2_tu(width), qp);
+        for (int k = 0; k < cabac::kNumCtx; k++) p.init_states[i][k] = (uint8_t)cabac::init_state(qp, cabac::init_value(k));
+    }
+    p.sse = nullptr; p.nonzero = nullptr; p.sum_abs = nullptr; p.recon = nullptr; p.rate = nullptr;
+    p.modes = d_modes; p.sdh = sign_data_hiding != 0;
+    return p;
+}
+
+// The caller's scratch of the second intra pass, n (K + 1) slots: per-slot rate and SSE [nb_qps][slots], the slots' predictions and
+// replicated targets [slots][w][w], their modes [slots], the first-pass list [n][K]; every section at a multiple of 256 bytes.
+struct RdWorkspace { uint64_t* rate; uint32_t* sse; uint8_t* pred; uint8_t* targets; uint8_t* modes; uint8_t* list; size_t bytes; };
+RdWorkspace rd_workspace(void* base, int width, long n, int nb_qps)
+{
+    const int k = hevc_first_pass_list_size(width);
+    const size_t slots = (size_t)n * (k + 1), w2 = (size_t)width * width;
+    size_t at = 0;
+    const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
+    RdWorkspace ws;
+    ws.rate = (uint64_t*)take(slots * nb_qps * 8);
+    ws.sse = (uint32_t*)take(slots * nb_qps * 4);
+    ws.pred = take(slots * w2);
+    ws.targets = take(slots * w2);
+    ws.modes = take(slots);
+    ws.list = take((size_t)n * k);
+    ws.bytes = at;
+    return ws;
+}
+
+// what both forms of the second intra pass check behind their blocks (the width is checked): candidate, QPs, lambdas, outputs, scratch
+int check_rd_pass(pnn_ctx* c, int width, int n, const uint8_t* d_cand_pred, const int* qps, int nb_qps, const double* lambdas, bool any_output,
+                  const void* d_workspace, size_t workspace_bytes)
+{
+    if (n > 0 && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_pred is NULL");
+    if ((long)n * (hevc_first_pass_list_size(width) + 1) > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 candidate slots");
+    if (!trquant::qps_ok(qps, nb_qps)) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d integers in [0, %d]", trquant::kMaxQps, trquant::kMaxQp);
+    for (int i = 0; lambdas && i < nb_qps; i++)
+        if (!(lambdas[i] >= 0. && lambdas[i] <= 1.7976931348623157e308)) return fail(c, PNN_E_ARG, "lambda %d is negative or not finite", i);
+    if (const int rc = check_some_output(c, any_output)) return rc;
+    if (n == 0) return PNN_OK;
+    const size_t need = rd_workspace(nullptr, width, n, nb_qps).bytes;
+    if (!d_workspace || (uintptr_t)d_workspace % 8) return fail(c, PNN_E_ARG, "d_workspace is NULL or not aligned to 8 bytes");
+    if (workspace_bytes < need) return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_rd_pass_workspace_bytes asks for %zu", workspace_bytes, need);
+    return PNN_OK;
+}
+
+// The four launches of the second intra pass, either form (dense: patterns and targets; pictures: *pic and pic_targets), everything
+// checked: the first-pass list into the scratch, the candidates' predictions, the transform coding of the n (K + 1) slots -- the
+// launch of pnn_trquant_sdh_device with the slots' modes as its mode array --, the decision.
+int rd_pass_launches(pnn_ctx* c, int width, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic,
+                     const uint8_t* pic_targets, long n, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                     const double* lambdas, int sign_data_hiding, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode,
+                     uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, hipStream_t s)
+{
+    const RdWorkspace ws = rd_workspace(d_workspace, width, n, nb_qps);
+    const int k1 = hevc_first_pass_list_size(width) + 1;
+    const HevcModeHadsParams h = mode_hads_params(patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing, d_cand_pred, nullptr, nullptr,
+                                                  ws.list, nullptr);
+    HIPCHK(c, launch_hevc_mode_hads(h, s));
+    RdCandidatesParams r;
+    set_blocks(r, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
+    r.cand_pred = d_cand_pred; r.list_modes = ws.list; r.cand_modes = d_cand_modes ? d_cand_modes : ws.modes;
+    r.slot_pred = ws.pred; r.slot_targets = ws.targets;
+    HIPCHK(c, launch_rd_candidates(r, s));
+    TrQuantParams t = trquant_params(width, ws.pred, ws.targets, (int)(n * k1), r.cand_modes, qps, nb_qps, sign_data_hiding);
+    t.sse = ws.sse; t.rate = ws.rate;
+    HIPCHK(c, launch_trquant(t, s));
+    RdDecideParams d;
+    d.sse = ws.sse; d.rate = ws.rate; d.cand_modes = r.cand_modes; d.N = (int)n; d.w = width; d.nb_qps = nb_qps;
+    for (int i = 0; i < trquant::kMaxQps; i++) d.lambda[i] = i >= nb_qps ? 0. : lambdas ? lambdas[i] : pnn_hm_intra_lambda(qps[i]);
+    d.cand_costs = d_cand_costs; d.best_mode = d_best_mode; d.best_slot = d_best_slot; d.best_cost = d_best_cost; d.best_sse = d_best_sse;
+    d.best_rate = d_best_rate;
+    HIPCHK(c, launch_rd_decide(d, s));
+    c->stat_launches += 4;
+    return PNN_OK;
 }
 
 Model* ipfcns_for(pnn_ctx* c, int width, int* rc)
@@ -412,19 +496,63 @@ int pnn_trquant_sdh_device(pnn_ctx* c, int width, const uint8_t* d_predictions, 
     if (d_modes && !d_rate && !sign_data_hiding) return fail(c, PNN_E_ARG, "intra modes without a rate output or sign-data hiding");
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    TrQuantParams p;
-    p.pred = d_predictions; p.targets = d_targets; p.N = n; p.w = width; p.nb_qps = nb_qps;
-    for (int i = 0; i < trquant::kMaxQps; i++) {
-        const int qp = qps[i < nb_qps ? i : 0];
-        p.qp[i] = trquant::qp_consts(trquant::log2_tu(width), qp);
-        for (int k = 0; k < cabac::kNumCtx; k++) p.init_states[i][k] = (uint8_t)cabac::init_state(qp, cabac::init_value(k));
-    }
-    p.sse = d_sses_recon; p.nonzero = d_nb_nonzero; p.sum_abs = d_sum_abs_levels; p.recon = d_recon;
-    p.rate = d_rate; p.modes = d_modes; p.sdh = sign_data_hiding != 0;
+    TrQuantParams p = trquant_params(width, d_predictions, d_targets, n, d_modes, qps, nb_qps, sign_data_hiding);
+    p.sse = d_sses_recon; p.nonzero = d_nb_nonzero; p.sum_abs = d_sum_abs_levels; p.recon = d_recon; p.rate = d_rate;
     reset_stats(c);
     HIPCHK(c, launch_trquant(p, (hipStream_t)stream));
     c->stat_launches++;
     return PNN_OK;
+}
+
+size_t pnn_rd_pass_workspace_bytes(int width, int n, int nb_qps)
+{
+    if (width_index(width) < 0 || n < 0 || nb_qps < 1 || nb_qps > trquant::kMaxQps) return 0;
+    return rd_workspace(nullptr, width, n, nb_qps).bytes;
+}
+
+int pnn_rd_pass_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                       const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                       uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
+                       uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing)) ||
+        (rc = check_rd_pass(c, width, n, d_cand_pred, qps, nb_qps, lambdas,
+                            d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate, d_workspace,
+                            workspace_bytes))) return rc;
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    reset_stats(c);
+    return rd_pass_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
+                            lambdas, sign_data_hiding, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
+                            d_workspace, (hipStream_t)stream);
+}
+
+int pnn_rd_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                     int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
+                                     int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas,
+                                     int sign_data_hiding, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode,
+                                     uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace,
+                                     size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    long n;
+    if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+        (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n)) ||
+        (rc = check_rd_pass(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas,
+                            d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate, d_workspace,
+                            workspace_bytes))) return rc;
+    if (n == 0) return PNN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
+    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
+    reset_stats(c);
+    return rd_pass_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
+                            smoothing, qps, nb_qps, lambdas, sign_data_hiding, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost,
+                            d_best_sse, d_best_rate, d_workspace, s);
 }
 
 int pnn_score_f32_device(pnn_ctx* c, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,

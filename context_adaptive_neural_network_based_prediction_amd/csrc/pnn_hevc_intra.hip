@@ -131,8 +131,8 @@ __device__ inline size_t picture_corner(const PictureBlocks& pic, long b)
 // bytes) of the workgroup's G blocks, zeros for blocks past p.N; `Params` is either kernel's.  PIC = false: reference samples from dense
 // intra patterns, targets from their own array; true: both from pictures -- the reference samples from the context plane (p.pic.channels),
 // the targets from the target plane (p.pic_targets), which have one geometry and so share each block's offset `corner`.  For single
-// pictures the two pointers are equal.
-template <int W, int G, bool PIC, typename Params>
+// pictures the two pointers are equal.  NT: the threads of the calling workgroup (rd_candidates_kernel has 256).
+template <int W, int G, bool PIC, int NT = kThreads, typename Params>
 __device__ __forceinline__ void stage_blocks(const Params& p, long blk0, int tid, int* ref, uint8_t* tgt, size_t* corner)
 {
     constexpr int RS = 4 * W + 1, TS = W * W + 4;                 // LDS strides (odd in dwords: lanes of different blocks spread over banks)
@@ -140,7 +140,7 @@ __device__ __forceinline__ void stage_blocks(const Params& p, long blk0, int tid
         if (tid < G && blk0 + tid < p.N) corner[tid] = picture_corner(p.pic, blk0 + tid);
         __syncthreads();
     }
-    for (int i = tid; i < G * RS; i += kThreads) {
+    for (int i = tid; i < G * RS; i += NT) {
         const int g = i / RS, j = i % RS - 2 * W;
         int v = 0;
         if (blk0 + g < p.N) {
@@ -154,7 +154,7 @@ __device__ __forceinline__ void stage_blocks(const Params& p, long blk0, int tid
         }
         ref[i] = v;
     }
-    for (int i = tid; i < G * W * W; i += kThreads) {
+    for (int i = tid; i < G * W * W; i += NT) {
         const int g = i / (W * W), e = i % (W * W);
         int v = 0;
         if (blk0 + g < p.N) {
@@ -189,7 +189,7 @@ __device__ inline bool mode_smooths(int mode)
 // W = 32: one lane per block decides whether its line is strong (both halves flat at their anchors; only when `allow_strong`), then
 // every thread writes bilinear samples (corner copied) or [1 2 1] ones as its block's flag says.  Called between two barriers: ref is
 // complete on entry, the caller's next barrier publishes ref_s.
-template <int W, int G>
+template <int W, int G, int NT = kThreads>
 __device__ __forceinline__ void stage_smoothed(const int* ref, int* ref_s, int* strong, bool allow_strong, int tid)
 {
     constexpr int RS = 4 * W + 1;
@@ -203,7 +203,7 @@ __device__ __forceinline__ void stage_smoothed(const int* ref, int* ref_s, int* 
         }
         __syncthreads();
     }
-    for (int i = tid; i < G * RS; i += kThreads) {
+    for (int i = tid; i < G * RS; i += NT) {
         const int g = i / RS, j = i % RS - 2 * W;
         const int* rf = ref + g * RS + 2 * W;
         int v;
@@ -404,7 +404,147 @@ __global__ __launch_bounds__(kThreads) void hevc_mode_hads_kernel(const HevcMode
     }
 }
 
+// Candidates of HM's second intra pass: the predictions the RD choice codes.  A workgroup of 4 waves takes G
+// blocks -- as many as trquant_kernel, which codes what this kernel writes -- stages them as the kernels above do, and one lane per
+// block turns the block's first-pass list (K modes a launch of hevc_mode_hads_kernel left on the device) into K + 1 slots: the list in
+// order, then 35 if the list lacks it, else 255.  Then the G (K + 1) w^2 output pixels, one after the other over the workgroup: slot
+// s of block g gets mode_pixel of its mode from the line that mode reads (modes 0 .. 34), the candidate's own pixel (35) or the target
+// (255, and any value above 35: a zero residual), and the target beside it.  Outputs are dense per workgroup: consecutive lanes,
+// consecutive bytes.
+constexpr int kRdThreads = 256;
+
+template <int W, bool PIC, bool SMOOTH>
+__global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandidatesParams p)
+{
+    static_assert(!SMOOTH || W == 8 || W == 16 || W == 32, "no mode smooths at w = 4 and 64");
+    constexpr int G = W >= 32 ? 1 : 1024 / (W * W);                // blocks per workgroup: trquant_kernel's
+    constexpr int K = W <= 8 ? 8 : 3, K1 = K + 1;                  // list entries, slots
+    constexpr int RS = 4 * W + 1, TS = W * W + 4;                  // LDS strides, those of stage_blocks
+    __shared__ int ref[G * RS];
+    __shared__ int ref_s[SMOOTH ? G * RS : 1];
+    __shared__ int strong[SMOOTH && W == 32 ? G : 1];
+    __shared__ uint8_t tgt[G * TS];
+    __shared__ int dcv[G], slot_mode[G * K1];
+    __shared__ size_t corner[PIC ? G : 1];
+    const int tid = threadIdx.x;
+    const long blk0 = (long)blockIdx.x * G;
+
+    stage_blocks<W, G, PIC, kRdThreads>(p, blk0, tid, ref, tgt, corner);
+    __syncthreads();
+    stage_dc<W, G>(ref, dcv, tid);
+    if (SMOOTH) stage_smoothed<W, G, kRdThreads>(ref, ref_s, strong, p.smoothing == 2, tid);
+    if (tid < G && blk0 + tid < p.N) {
+        bool listed = false;
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const int m = p.list_modes[(blk0 + tid) * K + j];
+            listed = listed || m == 35;
+            slot_mode[tid * K1 + j] = m > 35 ? kRdUnusedSlot : m;
+        }
+        slot_mode[tid * K1 + K] = listed ? kRdUnusedSlot : 35;
+#pragma unroll
+        for (int j = 0; j < K1; j++) p.cand_modes[(blk0 + tid) * K1 + j] = (uint8_t)slot_mode[tid * K1 + j];
+    }
+    __syncthreads();
+
+    const size_t out0 = (size_t)blk0 * K1 * W * W;
+    for (int i = tid; i < G * K1 * W * W; i += kRdThreads) {
+        const int g = i / (K1 * W * W), e = i % (W * W);
+        if (blk0 + g >= p.N) break;
+        const int m = slot_mode[g * K1 + i / (W * W) % K1];
+        const int t = tgt[g * TS + e];
+        int v = t;
+        if (m == 35) {
+            v = p.cand_pred[(size_t)(blk0 + g) * W * W + e];
+        } else if (m < 35) {
+            const int* rf = (SMOOTH && mode_smooths<W>(m) ? ref_s : ref) + g * RS + 2 * W;
+            v = mode_pixel<W>(rf, dcv[g], m, e / W, e % W);
+        }
+        p.slot_pred[out0 + i] = (uint8_t)v;
+        p.slot_targets[out0 + i] = (uint8_t)t;
+    }
+}
+
+// J = D + lambda R: one IEEE multiply and one IEEE add, each rounded once -- the host twin's two operations.  HIP's __dmul_rn and
+// __dadd_rn are a plain * and + whose results the compiler may still contract into one v_fma_f64 (it did); the pragma is what forbids
+// that, so the two operations stand here as themselves.
+__device__ inline double rd_cost(uint32_t d, uint64_t r, double lambda)
+{
+#pragma clang fp contract(off)
+    const double bits = lambda * (double)(r >> 15);
+    return (double)d + bits;
+}
+
+// The costs and the winner, one lane per (QP, block); the K + 1 slots in order.
+template <int K1>
+__global__ __launch_bounds__(kRdThreads) void rd_decide_kernel(const RdDecideParams p)
+{
+    const long i = (long)blockIdx.x * kRdThreads + threadIdx.x;
+    if (i >= (long)p.nb_qps * p.N) return;
+    const int qi = (int)(i / p.N);
+    const long b = i - (long)qi * p.N;
+    const double lambda = p.lambda[qi];
+    const size_t slot0 = (size_t)b * K1, at0 = (size_t)qi * p.N * K1 + slot0;
+    double best = __builtin_inf();
+    int best_slot = kRdUnusedSlot, best_mode = kRdUnusedSlot;
+    uint32_t best_sse = 0;
+    uint64_t best_rate = 0;
+#pragma unroll
+    for (int s = 0; s < K1; s++) {
+        const int m = p.cand_modes[slot0 + s];
+        const uint32_t d = p.sse[at0 + s];
+        const uint64_t r = p.rate[at0 + s];
+        const double j = m == kRdUnusedSlot ? __builtin_inf() : rd_cost(d, r, lambda);
+        if (p.cand_costs) p.cand_costs[at0 + s] = j;
+        if (j < best) { best = j; best_slot = s; best_mode = m; best_sse = d; best_rate = r; }
+    }
+    if (p.best_mode) p.best_mode[i] = (uint8_t)best_mode;
+    if (p.best_slot) p.best_slot[i] = (uint8_t)best_slot;
+    if (p.best_cost) p.best_cost[i] = best;
+    if (p.best_sse) p.best_sse[i] = best_sse;
+    if (p.best_rate) p.best_rate[i] = best_rate;
+}
+
 }  // namespace
+
+int rd_candidates_blocks_per_workgroup(int w) { return w >= 32 ? 1 : 1024 / (w * w); }
+
+hipError_t launch_rd_candidates(const RdCandidatesParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    const int g = rd_candidates_blocks_per_workgroup(p.w);
+    const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kRdThreads);
+    const bool pic = p.patterns == nullptr;
+    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+    if (!p.cand_pred || !p.list_modes || !p.cand_modes || !p.slot_pred || !p.slot_targets) return hipErrorInvalidValue;
+    if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
+#define PNN_RD_LAUNCH(W_, SMOOTH_) \
+    if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
+    else hipLaunchKernelGGL((rd_candidates_kernel<W_, false, SMOOTH_>), grid, block, 0, s, p);
+#define PNN_RD_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_RD_LAUNCH(W_, true) } else { PNN_RD_LAUNCH(W_, false) }
+    switch (p.w) {                                     // at w = 4 and 64 no mode smooths: the one instantiation for every `smoothing`
+    case 4: PNN_RD_LAUNCH(4, false) break;
+    case 8: PNN_RD_LAUNCH_SMOOTH(8) break;
+    case 16: PNN_RD_LAUNCH_SMOOTH(16) break;
+    case 32: PNN_RD_LAUNCH_SMOOTH(32) break;
+    case 64: PNN_RD_LAUNCH(64, false) break;
+    default: return hipErrorInvalidValue;
+    }
+#undef PNN_RD_LAUNCH_SMOOTH
+#undef PNN_RD_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_rd_decide(const RdDecideParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    if (!p.sse || !p.rate || !p.cand_modes || p.nb_qps < 1 || p.nb_qps > trquant::kMaxQps) return hipErrorInvalidValue;
+    const long total = (long)p.nb_qps * p.N;
+    const dim3 grid((unsigned)((total + kRdThreads - 1) / kRdThreads)), block(kRdThreads);
+    if (p.w <= 8) hipLaunchKernelGGL((rd_decide_kernel<9>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((rd_decide_kernel<4>), grid, block, 0, s, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s)
 {

@@ -296,6 +296,31 @@ struct HevcModeHadsParams {
 inline int hevc_first_pass_list_size(int w) { return w <= 8 ? 8 : 3; }   // g_aucIntraModeNumFast_UseMPM for w = 4 .. 64
 hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s);
 
+// Candidates of HM's second intra pass (pnn_hevc_intra.hip): the same inputs in the same two forms, the
+// candidate's predictions cand_pred [N][w][w] and the first-pass list list_modes [N][K] a launch_hevc_mode_hads call left on the
+// device.  Per block K + 1 slots: the list's modes in order, then 35 if the list lacks it, else 255 (unused).  Outputs, all required:
+// cand_modes [N][K + 1], slot_pred [N][K + 1][w][w] (a mode's prediction, cand_pred for 35, the target for 255: a zero residual) and
+// slot_targets, the block's target once per slot -- what launch_trquant codes as N (K + 1) blocks with cand_modes as its mode array.
+struct RdCandidatesParams {
+    const uint8_t* patterns; int ph; int pw; const uint8_t* targets; int N; int w;
+    const uint8_t* cand_pred; const uint8_t* list_modes; uint8_t* cand_modes; uint8_t* slot_pred; uint8_t* slot_targets;
+    PictureBlocks pic;
+    const uint8_t* pic_targets;
+    int smoothing;
+};
+constexpr int kRdUnusedSlot = 255;                 // cand_modes of a slot that holds no candidate
+int rd_candidates_blocks_per_workgroup(int w);
+hipError_t launch_rd_candidates(const RdCandidatesParams& p, hipStream_t s);
+// The decision: J = D + lambda R per (QP, block, slot) -- D = sse [nb_qps][N (K + 1)], R = rate >> 15 of rate [nb_qps][N (K + 1)], one
+// IEEE multiply and one IEEE add in double, lambda[qi] as the host computed it -- +inf in an unused slot, and the least J over the
+// slots in order under a strict <.  Outputs, each NULL or: cand_costs [nb_qps][N][K + 1]; best_* [nb_qps][N] (mode and slot 255, cost
+// +inf, sse and rate 0 where no slot is below +inf).
+struct RdDecideParams {
+    const uint32_t* sse; const uint64_t* rate; const uint8_t* cand_modes; int N; int w; int nb_qps; double lambda[trquant::kMaxQps];
+    double* cand_costs; uint8_t* best_mode; uint8_t* best_slot; double* best_cost; uint32_t* best_sse; uint64_t* best_rate;
+};
+hipError_t launch_rd_decide(const RdDecideParams& p, hipStream_t s);
+
 // Open-loop transform coding (pnn_trquant.hip): N predictions and targets [N][w][w] uint8, nb_qps <= 8 QPs whose constants the host has
 // worked out (trquant::qp_consts at the unit size of w).  Outputs, each NULL or [nb_qps][N] uint32: the SSE of the reconstruction, the
 // number of nonzero levels, the sum of the quantised magnitudes; recon NULL or uint8 [nb_qps][N][w][w].  rate NULL (the kernel without

@@ -18,6 +18,8 @@ smoothing.  A nonzero value adds the key 'reference_smoothing' to the dictionari
 Both also take transform_qps, a list of 1 to 8 QPs, for the transform-domain column: what is left of the PNN's prediction and of the best
 HEVC mode's after HM's residual path with RDOQ 0 (intraprediction.transform_code; two more pnn_trquant_sdh_device calls per mask, the
 same download).
+rd_pass=True (with first_pass and transform_qps) adds HM's second intra pass: the choice by D + lambda R among the first-pass candidates
+and the PNN (pnn_rd_pass_picture_pairs_device: one more call per mask, the same download).
 Options travel as arguments: every call of the mask loop goes to the widest entry of its operation (*_hm_device, pnn_trquant_sdh_device) with 0
 or NULL for an option that is off; the narrower entries of include/pnn_hip.h forward to these with those values: the same kernel launch.
 """
@@ -181,7 +183,7 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                               tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
-                              transform_qps=(), transform_rate=False, transform_sign_hiding=False):
+                              transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -234,14 +236,26 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     gets the mode array the score call left on the device (the scan now shapes the levels), the PNN's gets none.  Same keys, computed
     from the levels after hiding ('sum_abs_levels_*' stays the sum before it; 'rate_bits_*' does not charge the hidden signs), plus
     'transform_sign_hiding': True.  Equal to intraprediction.transform_code(sign_data_hiding=True, modes=...) on the dictionary's own
-    predictions, targets and modes.  With transform_sign_hiding=False nothing changes: not a key, a call or a byte."""
+    predictions, targets and modes.  With transform_sign_hiding=False nothing changes: not a key, a call or a byte.
+
+    rd_pass=True (with first_pass=True and transform_qps; ValueError without either, before anything touches the GPU) adds HM's second
+    intra pass (include/pnn_hip.h, "the second intra pass"; TEncSearch.cpp:2476-2605): per block and QP the choice by D + lambda R among
+    the first-pass candidates and the PNN, which is appended as 35 where the list lacks it -- ONE more call per mask,
+    pnn_rd_pass_picture_pairs_device, behind the others, with the PNN's uint8 predictions on the device as the candidate, HM's lambda of
+    each QP, reference_smoothing as the candidates' smoothing and transform_sign_hiding as its flag; its results join the one
+    download, its scratch is allocated once.  New keys: 'rd_pass_candidates' uint8 [N, K + 1] (the slots' modes, 255 = unused),
+    'rd_pass_costs' float64 [nb_qps, N, K + 1] (inf in an unused slot), 'rd_pass_modes' uint8, 'rd_pass_sses' uint32, 'rd_pass_rate_bits'
+    float64 (bits), 'psnrs_recon_rd_pass' float64 (each [nb_qps, N], of the winner) and 'frequency_rd_pass_win_pnn' (one float per QP:
+    the share of blocks whose winner is 35 -- how often the encoder would pick the PNN).  Equal to intraprediction.rd_pass on the
+    dictionary's own patterns, targets and PNN predictions.  Mode bits, RDOQ and the missing most probable modes are left out, as the
+    header says.  With rd_pass=False nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
-                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding)
+                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                                    tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
-                                   transform_qps=(), transform_rate=False, transform_sign_hiding=False):
+                                   transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -259,10 +273,10 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
     transform_rate, transform_sign_hiding: as for score_masks_from_pictures."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
                         tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps,
-                        transform_rate, transform_sign_hiding)
+                        transform_rate, transform_sign_hiding, rd_pass)
 
 def _check_score_masks_arguments(ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                                 reference_smoothing, transform_qps, transform_rate, transform_sign_hiding):
+                                 reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False):
     """The argument checks of _score_masks, all before anything touches the GPU; the library is first used by the last, the predictor's mean.
     Returns (masks as int pairs, rows and cols as flat int64 arrays, reference_smoothing as int, transform_qps as a tuple of ints or ())."""
     if ch.dtype != np.uint8:
@@ -292,6 +306,8 @@ def _check_score_masks_arguments(ch, nb_planes, w, row_1sts, col_1sts, predictor
         raise ValueError('`transform_rate` is set without `transform_qps`.')
     if transform_sign_hiding and len(transform_qps) == 0:
         raise ValueError('`transform_sign_hiding` is set without `transform_qps`.')
+    if rd_pass and len(transform_qps) == 0:
+        raise ValueError('`rd_pass` is set without `transform_qps`.')
     masks = [(int(m[0]), int(m[1])) for m in tuples_width_height_masks]
     rows, cols = row_1sts.astype(np.int64).ravel(), col_1sts.astype(np.int64).ravel()
     if nb_images * rows.size == 0:
@@ -321,7 +337,11 @@ _CODED_COLUMNS = (('pnn', 'predictions_pnn'), ('hevc_best_mode', 'predictions_he
 _COUNTS = ('sses_recon', 'nb_nonzero_levels', 'sum_abs_levels')                            # per coded column, uint32 [nb_qps, n]
 
 
-def _output_layout(n, w, first_pass, nb_qps, transform_rate):
+_RD_PASS_SECTIONS = ('rd_pass_candidates', 'rd_pass_costs', 'rd_pass_modes', 'rd_pass_slots', 'rd_pass_best_costs', 'rd_pass_sses',
+                     'rd_pass_rates')                                                      # intraprediction.RD_PASS_OUTPUTS, in the entry's order
+
+
+def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False):
     """Every output of a mask's calls in ONE buffer, described once as (name, dtype, shape): the small results first, then the uint8
     blocks of the PNN, of HEVC and the targets; a download is a prefix of it.  Each section starts at a multiple of its item size.
     Returns (sections, begin, end), the last two the byte offsets by name; end['targets'] is the size of the buffer."""
@@ -334,6 +354,9 @@ def _output_layout(n, w, first_pass, nb_qps, transform_rate):
         sections += [('%s_%s' % (name, column), np.uint32, (nb_qps, n)) for name in _COUNTS]
         if transform_rate:
             sections.append(('rate_' + column, np.uint64, (nb_qps, n)))
+    if rd_pass:
+        sections += [(name, dtype, shape) for name, (_, dtype), shape in zip(_RD_PASS_SECTIONS, intraprediction.RD_PASS_OUTPUTS,
+                                                                             intraprediction.rd_pass_shapes(n, nb_qps, w))]
     sections += [(name, np.uint8, (n, w, w, 1)) for name in ('predictions_pnn', 'predictions_hevc', 'targets')]
     begin, end, offset = {}, {}, 0
     for name, dtype, shape in sections:
@@ -343,7 +366,7 @@ def _output_layout(n, w, first_pass, nb_qps, transform_rate):
     return sections, begin, end
 
 
-def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding):
+def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False):
     """One mask's dictionary_performance, but for the uint8 blocks, from `view`: the downloaded sections by name."""
     psnrs_pnn = intraprediction.psnrs_from_sses(view['sses_pnn'], w)
     psnrs_hevc = intraprediction.psnrs_from_sses(view['sses_hevc'], w)
@@ -371,18 +394,25 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
                                        for pnn, hevc in zip(d['rate_bits_pnn'], d['rate_bits_hevc_best_mode'])]
     if transform_sign_hiding:
         d['transform_sign_hiding'] = True
+    if rd_pass:
+        d.update({key: view[key].copy() for key in ('rd_pass_candidates', 'rd_pass_costs', 'rd_pass_modes', 'rd_pass_sses')})
+        d['rd_pass_rate_bits'] = view['rd_pass_rates'].astype(np.float64) / 32768.
+        d['psnrs_recon_rd_pass'] = intraprediction.psnrs_from_sses(view['rd_pass_sses'], w)
+        d['frequency_rd_pass_win_pnn'] = [float(np.count_nonzero(modes == intraprediction.NB_MODES)) / n for modes in d['rd_pass_modes']]
     return d
 
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                 keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding):
+                 keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer.  Every option is an argument
     of the one entry its call has (the smoothing; the mode pointer, the rate pointer and the flag), 0 or NULL when off."""
     w = width_target
     masks, rows, cols, reference_smoothing, transform_qps = _check_score_masks_arguments(
         ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns, reference_smoothing,
-        transform_qps, transform_rate, transform_sign_hiding)
+        transform_qps, transform_rate, transform_sign_hiding, rd_pass)
+    if rd_pass and not first_pass:
+        raise ValueError('`rd_pass` is set without `first_pass`.')
     nb_images, height, width = ch.shape[:3]
     n_pos, nb_qps = rows.size, len(transform_qps)
     n = nb_images * n_pos
@@ -393,11 +423,14 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     d_planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(ch, 3, 0))).to(dev)      # [planes, images, H, W]: one copy, one upload
     d_target_channels, d_context_channels = d_planes[0], d_planes[nb_planes - 1]
     d_rows, d_cols = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (rows, cols))
-    sections, begin, end = _output_layout(n, w, first_pass, nb_qps, transform_rate)
+    sections, begin, end = _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass)
     d_out = torch.empty(end['targets'], dtype=torch.uint8, device=dev)       # the last section
     ptr = {name: d_out.data_ptr() + begin[name] for name in begin}
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     c_qps = (ctypes.c_int * max(nb_qps, 1))(*transform_qps)
+    if rd_pass:                                           # the entry's scratch, the caller's: once for all masks
+        nb_scratch = L.pnn_rd_pass_workspace_bytes(w, n, nb_qps)
+        d_scratch = torch.empty(nb_scratch, dtype=torch.uint8, device=dev)
     results, targets_uint8 = {}, None
     for i, mask in enumerate(masks):
         if mask in results:
@@ -422,11 +455,15 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                     predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps, ptr['sses_recon_' + column],
                     ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None, ptr['rate_' + column] if transform_rate else None,
                     int(bool(transform_sign_hiding)), stream), predictor.ctx)
+            if rd_pass:                                   # the candidate is the PNN's uint8 prediction; NULL lambdas: HM's of each QP
+                _lib.check(L.pnn_rd_pass_picture_pairs_device(
+                    *blocks, ptr['predictions_pnn'], reference_smoothing, c_qps, nb_qps, None, int(bool(transform_sign_hiding)),
+                    *[ptr[name] for name in _RD_PASS_SECTIONS], d_scratch.data_ptr(), nb_scratch, stream), predictor.ctx)
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
         dictionary_performance = _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate,
-                                                         transform_sign_hiding)
+                                                         transform_sign_hiding, rd_pass)
         if keep_predictions:
             if first:
                 targets_uint8 = view['targets'].copy()

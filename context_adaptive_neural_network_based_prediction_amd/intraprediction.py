@@ -13,6 +13,9 @@ HM's reference-sample smoothing, which the reference's extracted predictor left 
 here (include/pnn_hip.h): 0 (the default) reproduces the reference's predictor, 1 is HM with StrongIntraSmoothing 0, 2 is HM's
 default.  mode_uses_smoothing and smoothed_reference show the decision table and the filtered line.
 
+rd_pass is HM's second intra pass over the first-pass candidates and a candidate prediction (pnn_rd_pass_host / _device): the transform
+coding of every candidate and the choice by D + lambda R, hm_intra_lambda its lambda.
+
 Every option (`smoothing`, `rate`, `modes`, `sign_data_hiding`) travels as an argument of ONE C entry per operation, the widest one
 (*_hm_*, *_sdh_*), with 0 or NULL for "off"; the narrower entries of include/pnn_hip.h forward to the same bodies with those very
 values and are for integrators.
@@ -422,6 +425,83 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
         result['rate_bits'] = bits.astype(np.float64) / 32768.
     if keep_reconstructions:
         result['reconstructions_uint8'] = recon
+    return result
+
+
+def hm_intra_lambda(qp):
+    """HM's lambda of an I slice at QP `qp` (pnn_hm_intra_lambda): 0.57 * 2^((qp - 12) / 3), TEncSlice::calculateLambda for GOP size 1,
+    8-bit video, no modifier."""
+    return float(_lib.lib().pnn_hm_intra_lambda(int(qp)))
+
+
+RD_PASS_OUTPUTS = (('candidates', np.uint8), ('costs', np.float64), ('modes', np.uint8), ('slots', np.uint8), ('best_costs', np.float64),
+                   ('sses', np.uint32), ('rates', np.uint64))     # the outputs of pnn_rd_pass_*, in the entries' order
+
+
+def rd_pass_shapes(n, nb_qps, width_target):
+    """The shapes of RD_PASS_OUTPUTS for n blocks: candidates [n, K + 1], costs [nb_qps, n, K + 1], the others [nb_qps, n]."""
+    k1 = first_pass_list_size(width_target) + 1
+    return ((n, k1), (nb_qps, n, k1)) + ((nb_qps, n),) * 5
+
+
+def _check_lambdas(lambdas, nb_qps):
+    """None (HM's lambda per QP: a NULL pointer) or nb_qps finite floats >= 0 as a ctypes array."""
+    if lambdas is None:
+        return None
+    values = np.asarray(lambdas, dtype=np.float64).ravel()
+    if values.size != nb_qps or not np.all(np.isfinite(values)) or np.any(values < 0.):
+        raise ValueError('`lambdas` does not hold one finite value >= 0 per quantisation parameter.')
+    return (ctypes.c_double * nb_qps)(*values)
+
+
+def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoothing=0, sign_data_hiding=False, lambdas=None, device=None):
+    """HM's second intra pass as include/pnn_hip.h defines it ("the second intra pass"): per block and QP the RD choice among the
+    first-pass candidates (mode_hads_*'s list with the candidate prediction competing as 35) and the candidate itself, appended if the
+    list lacks it.  numpy uint8 arrays: patterns [n, h, w'], targets and candidate_predictions [n, w, w]; qps: 1 to 8 integers in
+    [0, 51]; lambdas None (hm_intra_lambda of each QP) or one finite value >= 0 per QP.  device=None runs the host twin
+    (pnn_rd_pass_host), an int that GPU (pnn_rd_pass_device); the bits are the same.
+    Returns {'candidates': uint8 [n, K + 1] (the slots' modes, 255 = unused), 'costs': float64 [nb_qps, n, K + 1] (J = D + lambda R, inf in
+    an unused slot), 'modes', 'slots': uint8 [nb_qps, n] (the winner), 'best_costs': float64, 'sses': uint32 (the winner's sse_recon),
+    'rates': uint64 (its rate in 2^-15 bit), 'rate_bits': float64 (the same in bits), 'psnrs_recon': float64 (psnrs_from_sses of
+    'sses'), each [nb_qps, n], and 'lambdas': float64 [nb_qps], the values used}."""
+    smoothing = _check_smoothing(reference_smoothing)
+    qps = _check_qps(qps)
+    arrays = (intra_patterns, targets, candidate_predictions)
+    if any(not isinstance(a, np.ndarray) or a.dtype != np.uint8 for a in arrays):
+        raise TypeError('the arrays must be `numpy.ndarray`s of dtype `numpy.uint8`.')
+    if len(targets.shape) != 3 or targets.shape[1] not in WIDTHS:
+        raise ValueError('the target patches are not [n, w, w] with w in {4, 8, 16, 32, 64}.')
+    w, nq = targets.shape[1], len(qps)
+    n = _check_mode_hads_arguments(intra_patterns, targets, w, candidate_predictions)
+    patterns, targets, candidate = (np.ascontiguousarray(a) for a in arrays)
+    c_qps, c_lambdas = (ctypes.c_int * nq)(*qps), _check_lambdas(lambdas, nq)
+    flag = int(bool(sign_data_hiding))
+    shapes = rd_pass_shapes(n, nq, w)
+    L = _lib.lib()
+    if device is None or n == 0:                          # (no block: nothing to launch, the empty arrays)
+        outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
+        rc = L.pnn_rd_pass_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
+                                smoothing, c_qps, nq, c_lambdas, flag, *[o.ctypes.data for o in outs])
+        if rc != 0:
+            raise ValueError('pnn_rd_pass_host refused the arguments (patterns %dx%d, width %d).' % (patterns.shape[1], patterns.shape[2], w))
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        d_in = [torch.from_numpy(a).to(dev) for a in (patterns, targets, candidate)]
+        d_outs = [torch.zeros(int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=torch.uint8, device=dev)
+                  for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
+        nb_bytes = L.pnn_rd_pass_workspace_bytes(w, n, nq)
+        d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.pnn_rd_pass_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(), n,
+                                            d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, *[o.data_ptr() for o in d_outs],
+                                            d_ws.data_ptr(), nb_bytes, ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, RD_PASS_OUTPUTS, shapes)]   # (waits)
+    result = {name: out for (name, _), out in zip(RD_PASS_OUTPUTS, outs)}
+    result['rate_bits'] = result['rates'].astype(np.float64) / 32768.
+    result['psnrs_recon'] = psnrs_from_sses(result['sses'], w)
+    result['lambdas'] = np.array([hm_intra_lambda(q) for q in qps]) if c_lambdas is None else np.array(list(c_lambdas))
     return result
 
 

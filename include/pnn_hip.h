@@ -507,7 +507,8 @@ int pnn_trquant_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, co
  * not.  Unit: 2^-15 bit, uint64.  Luma, intra, 8-bit video, maxLog2TrDynamicRange 15; sign-data hiding (OFF in these entries, a flag
  * of the next group's), transform skip, transquant bypass, extended precision, persistent Rice adaptation and CABAC bypass alignment
  * are all OFF.  NOT COUNTED: cbf_luma (its context
- * depends on a transform tree that does not exist here), mode bits, lambda; no RDOQ.
+ * depends on a transform tree that does not exist here), mode bits; no RDOQ.  No lambda here either: these entries report bits; the
+ * lambda and the cost D + lambda R over them are the second intra pass's, the last group of evaluator entries below.
  *   Units.  The transform units of the entries above: T = width up to 32; at width 64 the four 32 x 32 quadrants, each coded as a unit
  *     of its own (all contexts at their initial states again), bits added.  A unit whose levels are all zero costs 0.
  *   Scan.  0 diagonal, 1 horizontal, 2 vertical, generated as HM's initROM does (4 x 4 groups in scan order, the scan again inside a
@@ -611,6 +612,74 @@ int pnn_cabac_rate_levels_sdh_host(const int32_t* levels, int t, int scan, int q
 int pnn_trquant_sdh_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
                            const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
                            uint8_t* d_recon, uint64_t* d_rate, int sign_data_hiding, void* stream);
+
+/* ---- HM's second intra pass: the RD choice among the first-pass candidates and the PNN ------------------- */
+
+/* The groups above each answer one of HM's questions about a prediction.  This one puts them together the way the encoder does: the
+ * reference's hm_16_15_switch takes the first-pass list, appends the PNN as mode 35 if it is absent (TEncSearch.cpp:2476-2491),
+ * transform-codes EVERY candidate and keeps the one of least distortion + lambda bits under a strict < in list order
+ * (TEncSearch.cpp:2546-2605).  Per block and per QP:
+ *   Candidates.  The list of pnn_hevc_mode_hads_hm_* called WITH the candidate prediction (35 competes on Hadamard cost): K =
+ *     pnn_first_pass_list_size(width) entries in list order, slots 0 .. K - 1.  If 35 is not among them it is appended as slot K.
+ *     K or K + 1 candidates in K + 1 slots; an unused slot K carries mode 255, cost +inf, and never wins.  HM also appends the most
+ *     probable modes that are missing; they depend on the neighbours' coded modes, do not exist open-loop and ARE LEFT OUT, as
+ *     modeBits * sqrtLambda is in the first pass.
+ *   Prediction.  Modes 0 .. 34: pnn_hevc_intra_predict_hm(.., mode, smoothing, ..).  Mode 35: the given candidate prediction.
+ *   Coding.  pnn_trquant_sdh_* exactly as it stands, that prediction against the target at every QP of the list, sign_data_hiding as
+ *     given; the scan follows the candidate's mode, mode 35 scans diagonally.  D = sse_recon, R = rate >> 15: HM's whole written bits.
+ *   Lambda.  lambda(QP) = 0.57 * 2^((QP - 12) / 3): TEncSlice::calculateLambda for an I slice, GOP size 1, 8-bit, no modifier -- what
+ *     an all-intra configuration gives.  pnn_hm_intra_lambda computes it on the HOST in double; it travels in the kernel's argument
+ *     block, so host twin and kernel use the same 64 bits.  lambdas: NULL (HM's) or the caller's own [nb_qps], each finite and >= 0.
+ *   Cost.  J = (double) D + lambda * (double) R, TComRdCost::calcRdCost with DF_DEFAULT: one IEEE multiply and one IEEE add, each
+ *     rounded once, never contracted into an FMA (contraction is switched off around the two operations in the kernel -- HIP's
+ *     __dmul_rn / __dadd_rn alone do not prevent it -- and for the host twin's translation unit).
+ *   Winner.  Slots 0 .. K in order under a strict <, starting from +inf: of equal costs the earlier slot wins, so an appended 35 loses
+ *     every tie.  Where no cost is below +inf (a caller's lambda so large that every lambda R overflows) there is no winner: mode and
+ *     slot 255, cost +inf, sse and rate 0.
+ * STILL LEFT OUT: mode bits, cbf_luma and split flags; RDOQ (campaigns run RDOQ 1 -- this is HM's pass with RDOQ 0); transform skip;
+ * the transform quadtree (one unit per block, four quadrants at width 64, as in the transform-coding group); chroma; and the contexts
+ * start cold for every candidate, as in the rate group.
+ *
+ * The lambda above; any int is accepted (the formula has no bound of its own). */
+double pnn_hm_intra_lambda(int qp);
+/* The host twin: pure host code composed of the host twins above plus the decision; the zero-tolerance yardstick of the device
+ * entries.  patterns [n][pattern_h][pattern_w], targets and cand_pred [n][width][width], uint8; qps: nb_qps (1 .. 8) ints in [0, 51].
+ * Outputs, each NULL (not all) or:
+ *   cand_modes  uint8  [n][K + 1]             the slots' modes
+ *   cand_costs  double [nb_qps][n][K + 1]     J per slot, +inf in an unused slot
+ *   best_mode, best_slot  uint8 [nb_qps][n];  best_cost  double [nb_qps][n]
+ *   best_sse    uint32 [nb_qps][n]            D of the winner
+ *   best_rate   uint64 [nb_qps][n]            the winner's rate in 2^-15 bit, as pnn_trquant_sdh_host reports it (not shifted)
+ * n == 0 does nothing.  PNN_E_ARG + a line on stderr for what the entries it is made of refuse (width, pattern sides, n < 0, NULL inputs
+ * with n > 0, smoothing, QP list), for cand_pred NULL, every output NULL, a lambdas entry that is negative or not finite. */
+int pnn_rd_pass_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                     const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                     uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode, uint8_t* best_slot, double* best_cost, uint32_t* best_sse,
+                     uint64_t* best_rate);
+/* The scratch of the device entries comes from the caller: the candidates' predictions, the replicated targets, the slots' modes, the
+ * first-pass list and the per-slot SSE and rate.  Its size in bytes for n blocks (0 for a bad width, n < 0 or nb_qps outside 1 .. 8);
+ * the pointer must be a multiple of 8.  The entries neither allocate nor keep anything. */
+size_t pnn_rd_pass_workspace_bytes(int width, int n, int nb_qps);
+/* pnn_rd_pass_host on the GPU, bit-identical to it; d_* are device pointers, qps and lambdas HOST arrays; asynchronous on `stream`;
+ * every argument error (the host twin's; also d_workspace NULL, misaligned or workspace_bytes below pnn_rd_pass_workspace_bytes)
+ * is reported before any launch.  Four launches: the first-pass kernel of pnn_hevc_mode_hads_hm_device (its list into the scratch),
+ * rd_candidates_kernel (reads that list, writes the K + 1 predictions per block, the target once per slot and the slots' modes; an
+ * unused slot gets the target as its prediction: a zero residual), the UNCHANGED launch of pnn_trquant_sdh_device on the n (K + 1) slots
+ * with the slots' modes as its mode array, rd_decide_kernel.  A context without models (pnn_create_empty) suffices. */
+int pnn_rd_pass_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                       const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                       uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
+                       uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The same from the evaluator's pictures: geometry, block order, masks, planes, checks and the read-back of d_rows / d_cols of
+ * pnn_first_pass_picture_pairs_hm_device (reference samples from the CONTEXT plane, targets from the TARGET plane); d_cand_pred
+ * [n][width][width] is what pnn_score_picture_pairs_device's d_pnn_u8 holds.  Equal to pnn_rd_pass_host on the dense patterns and
+ * targets of the same blocks. */
+int pnn_rd_pass_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                     int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                     int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                     const double* lambdas, int sign_data_hiding, uint8_t* d_cand_modes, double* d_cand_costs,
+                                     uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                                     uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
