@@ -535,6 +535,10 @@ int pnn_trquant_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, co
  *   Cost.  A context-coded bin costs entropyBits[state ^ bin] (HM's ContextModel::m_entropyBits, the FAST_BIT_EST table) and moves its
  *     context by H.265 table 9-41, as TEncBinCABACCounter::encodeBin does; a bypass bin costs 32768.
  * The numbers live in csrc/pnn_cabac_tables.h, whose lines host and device both compile.
+ * Pinned to HM: the tables and context-selection functions piece by piece (tests/golden/hm_cabac_rate.npz); the whole of the above --
+ * levels, scan of the mode, order of the bins, bits -- to HM's own transformNxN / getCoefScanIdx / codeCoeffNxN / invTransformNxN on
+ * whole units (tests/golden/hm_unit_coding.npz), which host twin and kernel are each compared with.  Not pinned: cbf_luma, mode bits,
+ * the running contexts of a slice, RDOQ.
  *
  * pnn_trquant_host with the rate: modes NULL or uint8 [n], each in [0, 34] (0 planar, 1 DC, 2 .. 34 angular); rate NULL or uint64
  * [nb_qps][n].  Every other argument and refusal as there; also PNN_E_ARG for a mode above 34, for modes without rate, and `every
@@ -585,8 +589,9 @@ int pnn_trquant_rate_device(pnn_ctx* ctx, int width, const uint8_t* d_prediction
  *     whose FINAL levels have last - first >= 4 the sign of the level at `first`, the last one in coding order, is not coded: one bypass
  *     bin (32768) fewer.  Nothing else changes.
  *   Width 64: each 32 x 32 quadrant is hidden and rated as a unit of its own.
- *   Pinned to HM's own signBitHidingHDQ by recorded calls (tests/golden/hm_sign_hiding.npz); the deltaU line and the sign rule of the
- *   rate rest on the reading of the source.
+ *   Pinned to HM's own signBitHidingHDQ by recorded calls (tests/golden/hm_sign_hiding.npz), and -- the deltaU line, the hand-over
+ *   from xQuant and the sign rule of the rate included -- to HM's own transformNxN and codeCoeffNxN on whole units with
+ *   SignDataHidingEnabledFlag 1 (tests/golden/hm_unit_coding.npz).
  *
  * signBitHidingHDQ on ONE unit: levels int32 [t][t] in and out (each in [-32768, 32767]), coeffs and delta_u int32 [t][t] (delta_u from
  * the caller, any value but INT32_MIN), t in {4, 8, 16, 32}, scan 0, 1 or 2 (0 only at t = 16 and 32).  PNN_E_ARG + a line on stderr
@@ -632,7 +637,9 @@ int pnn_trquant_sdh_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions
  *     block, so host twin and kernel use the same 64 bits.  lambdas: NULL (HM's) or the caller's own [nb_qps], each finite and >= 0.
  *   Cost.  J = (double) D + lambda * (double) R, TComRdCost::calcRdCost with DF_DEFAULT: one IEEE multiply and one IEEE add, each
  *     rounded once, never contracted into an FMA (contraction is switched off around the two operations in the kernel -- HIP's
- *     __dmul_rn / __dadd_rn alone do not prevent it -- and for the host twin's translation unit).
+ *     __dmul_rn / __dadd_rn alone do not prevent it -- and for the host twin's translation unit).  Pinned to calcRdCost's own bit
+ *     patterns, triples that differ under an FMA included (tests/golden/hm_unit_coding.npz); lambda itself stays restated:
+ *     calculateLambda cannot be called alone.
  *   Winner.  Slots 0 .. K in order under a strict <, starting from +inf: of equal costs the earlier slot wins, so an appended 35 loses
  *     every tie.  Where no cost is below +inf (a caller's lambda so large that every lambda R overflows) there is no winner: mode and
  *     slot 255, cost +inf, sse and rate 0.

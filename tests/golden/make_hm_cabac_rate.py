@@ -10,10 +10,11 @@ the fixture.  Only the fixture is kept: recorded numbers, no code.
 WHAT IS PINNED.  The pieces of codeCoeffNxN that HM exposes without a coding unit: ContextModel::init -> getEntropyBits / update along
 200-bin sequences that reach all 126 states (per QP 0, 22, 37, 51 and each of the 80 luma contexts, from its I-slice init value, which is recorded too), the scan
 tables of initROM, getSigCtxInc over every position, pattern and scan, getSigCoeffGroupCtxInc and calcPatternSigCtx over 4 x 4 group
-maps, g_uiGroupIdx and getLastSignificantContextParameters.  WHAT IS NOT: the bits of a whole TEncSbac::codeCoeffNxN call on a
-TEncBinCABACCounter -- that needs a TComSPS / TComPPS / TComSlice and a one-CU TComDataCU / TComTU stood up around it.  The ORDER in
-which codeCoeffNxN strings these pieces together (which flags are coded or inferred, the c1 walk, the Rice parameter, the escape codes)
-rests on the restatement of tests/cabac_rate_cases.py alone."""
+maps, g_uiGroupIdx and getLastSignificantContextParameters.  WHAT IS NOT, HERE: the bits of a whole TEncSbac::codeCoeffNxN call on a
+TEncBinCABACCounter -- that needs a TComSPS / TComPPS / TComSlice and a one-CU TComDataCU / TComTU stood up around it.  That is what
+tests/golden/make_hm_unit_coding.py does: the ORDER in which codeCoeffNxN strings these pieces together (which flags are coded or
+inferred, the c1 walk, the Rice parameter, the escape codes, the hidden sign) is pinned by its fixture, to which the restatement of
+tests/cabac_rate_cases.py is held as well.  Still pinned nowhere: cbf_luma, mode bits, the running contexts of a slice, RDOQ."""
 import os
 import subprocess
 import sys

@@ -15,8 +15,8 @@ quantiser: the function takes them as they come, and so must the host entry.  Th
   remainders <= 0 (the first level must not go to zero); a unit whose first group -- not the last one, a later group has a level --
   has its cheapest change at a zero of a high position; levels of 32767 and -32768, which may only come down.
 
-WHAT IS PINNED: signBitHidingHDQ itself.  WHAT IS NOT: the line of xQuant that makes deltaU and codeCoeffNxN's rule that the hidden
-sign is not coded; both rest on the reading of the source (include/pnn_hip.h)."""
+WHAT IS PINNED: signBitHidingHDQ itself.  WHAT IS NOT, HERE: the line of xQuant that makes deltaU and codeCoeffNxN's rule that the hidden
+sign is not coded; both are pinned by tests/golden/make_hm_unit_coding.py, which runs transformNxN and codeCoeffNxN on whole units."""
 import os
 import subprocess
 import sys
