@@ -111,6 +111,17 @@ SIGNATURES = {
                            [ctypes.c_size_t, vp]),
     "pnn_rd_pass_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(ci), ci,
                                               ctypes.POINTER(ctypes.c_double), ci] + [vp] * 8 + [ctypes.c_size_t, vp]),
+    "pnn_trquant_rdoq_host": (ci, [vp, vp, ci, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, ci, ci, ctypes.POINTER(ctypes.c_double)]),
+    "pnn_trquant_stages_rdoq_host": (ci, [vp, vp, ci, ci, ci, ci, ci, ctypes.c_double, ci, vp, vp, vp, vp, vp, vp]),
+    "pnn_rdoq_unit_host": (ci, [vp, ci, ci, ci, ctypes.c_double, ci, ci, vp, ctypes.POINTER(ctypes.c_int32)]),
+    "pnn_rdoq_est_bits_host": (ci, [ci, ci, vp]),
+    "pnn_trquant_rdoq_device": (ci, [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, ci, ci, ctypes.POINTER(ctypes.c_double),
+                                     vp]),
+    "pnn_rd_pass_rdoq_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci] + [vp] * 7),
+    "pnn_rd_pass_rdoq_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci] +
+                                [vp] * 8 + [ctypes.c_size_t, vp]),
+    "pnn_rd_pass_rdoq_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(ci), ci,
+                                                   ctypes.POINTER(ctypes.c_double), ci, ci] + [vp] * 8 + [ctypes.c_size_t, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

@@ -134,7 +134,7 @@ int check_trquant(pnn_ctx* c, int width, const uint8_t* d_predictions, const uin
 
 // the launch's inputs: the QPs' constants and initial context states, worked out here; the outputs are the caller's to set
 TrQuantParams trquant_params(int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes, const int* qps,
-                             int nb_qps, int sign_data_hiding)
+                             int nb_qps, int sign_data_hiding, int rdoq, const double* lambdas)
 {
     TrQuantParams p;
     p.pred = d_predictions; p.targets = d_targets; p.N = n; p.w = width; p.nb_qps = nb_qps;
@@ -145,7 +145,24 @@ TrQuantParams trquant_params(int width, const uint8_t* d_predictions, const uint
     }
     p.sse = nullptr; p.nonzero = nullptr; p.sum_abs = nullptr; p.recon = nullptr; p.rate = nullptr;
     p.modes = d_modes; p.sdh = sign_data_hiding != 0;
+    // RDOQ: lambda, error scale and rdFactor of each QP in double, here, so that twin and kernel use the same bits
+    p.rdoq = rdoq != 0; p.cbf_ctx = width == 8 || width == 16 || width == 32 ? 1 : 0;
+    for (int i = 0; i < trquant::kMaxQps; i++) {          // (zero without the option and behind the last QP: never read)
+        p.rd[i] = rdoq::Consts{0., 0., 0};
+        p.cbf_states[i][0] = p.cbf_states[i][1] = 0;
+        if (!rdoq || i >= nb_qps) continue;
+        p.rd[i] = rdoq::consts(trquant::log2_tu(width), qps[i], lambdas ? lambdas[i] : pnn_hm_intra_lambda(qps[i]));
+        for (int k = 0; k < 2; k++) p.cbf_states[i][k] = (uint8_t)cabac::init_state(qps[i], rdoq::kCbfInit[k]);
+    }
     return p;
+}
+
+// the option rdoq of the transform coding and of the second pass: with it a caller's lambda is finite and above 0 (rdFactor divides by it)
+int check_rdoq_lambdas(pnn_ctx* c, int rdoq, const double* lambdas, int nb_qps)
+{
+    for (int i = 0; rdoq && lambdas && i < nb_qps; i++)
+        if (!(lambdas[i] > 0. && lambdas[i] <= 1.7976931348623157e308)) return fail(c, PNN_E_ARG, "RDOQ with lambda %d not finite or not above 0", i);
+    return PNN_OK;
 }
 
 // The caller's scratch of the second intra pass, n (K + 1) slots: per-slot rate and SSE [nb_qps][slots], the slots' predictions and
@@ -190,7 +207,7 @@ int check_rd_pass(pnn_ctx* c, int width, int n, const uint8_t* d_cand_pred, cons
 // launch of pnn_trquant_sdh_device with the slots' modes as its mode array --, the decision.
 int rd_pass_launches(pnn_ctx* c, int width, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic,
                      const uint8_t* pic_targets, long n, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
-                     const double* lambdas, int sign_data_hiding, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode,
+                     const double* lambdas, int sign_data_hiding, int rdoq, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode,
                      uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, hipStream_t s)
 {
     const RdWorkspace ws = rd_workspace(d_workspace, width, n, nb_qps);
@@ -203,7 +220,7 @@ int rd_pass_launches(pnn_ctx* c, int width, const uint8_t* patterns, int ph, int
     r.cand_pred = d_cand_pred; r.list_modes = ws.list; r.cand_modes = d_cand_modes ? d_cand_modes : ws.modes;
     r.slot_pred = ws.pred; r.slot_targets = ws.targets;
     HIPCHK(c, launch_rd_candidates(r, s));
-    TrQuantParams t = trquant_params(width, ws.pred, ws.targets, (int)(n * k1), r.cand_modes, qps, nb_qps, sign_data_hiding);
+    TrQuantParams t = trquant_params(width, ws.pred, ws.targets, (int)(n * k1), r.cand_modes, qps, nb_qps, sign_data_hiding, rdoq, lambdas);
     t.sse = ws.sse; t.rate = ws.rate;
     HIPCHK(c, launch_trquant(t, s));
     RdDecideParams d;
@@ -490,13 +507,22 @@ int pnn_trquant_sdh_device(pnn_ctx* c, int width, const uint8_t* d_predictions, 
                            const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
                            uint8_t* d_recon, uint64_t* d_rate, int sign_data_hiding, void* stream)
 {
+    return pnn_trquant_rdoq_device(c, width, d_predictions, d_targets, n, d_modes, qps, nb_qps, d_sses_recon, d_nb_nonzero, d_sum_abs_levels,
+                                   d_recon, d_rate, sign_data_hiding, 0, nullptr, stream);
+}
+
+int pnn_trquant_rdoq_device(pnn_ctx* c, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
+                            const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
+                            uint8_t* d_recon, uint64_t* d_rate, int sign_data_hiding, int rdoq, const double* lambdas, void* stream)
+{
     if (!c) return PNN_E_ARG;
     if (const int rc = check_trquant(c, width, d_predictions, d_targets, n, qps, nb_qps,
                                      d_sses_recon || d_nb_nonzero || d_sum_abs_levels || d_recon || d_rate)) return rc;
-    if (d_modes && !d_rate && !sign_data_hiding) return fail(c, PNN_E_ARG, "intra modes without a rate output or sign-data hiding");
+    if (d_modes && !d_rate && !sign_data_hiding && !rdoq) return fail(c, PNN_E_ARG, "intra modes without a rate output, sign-data hiding or RDOQ");
+    if (const int rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps)) return rc;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    TrQuantParams p = trquant_params(width, d_predictions, d_targets, n, d_modes, qps, nb_qps, sign_data_hiding);
+    TrQuantParams p = trquant_params(width, d_predictions, d_targets, n, d_modes, qps, nb_qps, sign_data_hiding, rdoq, lambdas);
     p.sse = d_sses_recon; p.nonzero = d_nb_nonzero; p.sum_abs = d_sum_abs_levels; p.recon = d_recon; p.rate = d_rate;
     reset_stats(c);
     HIPCHK(c, launch_trquant(p, (hipStream_t)stream));
@@ -515,17 +541,28 @@ int pnn_rd_pass_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pat
                        uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
                        uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream)
 {
+    return pnn_rd_pass_rdoq_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, d_cand_pred, smoothing, qps, nb_qps, lambdas,
+                                   sign_data_hiding, 0, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
+                                   d_workspace, workspace_bytes, stream);
+}
+
+int pnn_rd_pass_rdoq_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                            const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                            int rdoq, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot,
+                            double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes,
+                            void* stream)
+{
     if (!c) return PNN_E_ARG;
     int rc;
     if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing)) ||
         (rc = check_rd_pass(c, width, n, d_cand_pred, qps, nb_qps, lambdas,
                             d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate, d_workspace,
-                            workspace_bytes))) return rc;
+                            workspace_bytes)) || (rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps))) return rc;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
     reset_stats(c);
     return rd_pass_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
-                            lambdas, sign_data_hiding, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
+                            lambdas, sign_data_hiding, rdoq, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
                             d_workspace, (hipStream_t)stream);
 }
 
@@ -536,6 +573,19 @@ int pnn_rd_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_con
                                      uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace,
                                      size_t workspace_bytes, void* stream)
 {
+    return pnn_rd_pass_rdoq_picture_pairs_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols,
+                                                 positions, mask_w, mask_h, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, 0,
+                                                 d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
+                                                 d_workspace, workspace_bytes, stream);
+}
+
+int pnn_rd_pass_rdoq_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                          int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                          int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                          const double* lambdas, int sign_data_hiding, int rdoq, uint8_t* d_cand_modes, double* d_cand_costs,
+                                          uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                                          uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream)
+{
     if (!c) return PNN_E_ARG;
     int rc;
     long n;
@@ -543,7 +593,7 @@ int pnn_rd_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_con
         (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n)) ||
         (rc = check_rd_pass(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas,
                             d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate, d_workspace,
-                            workspace_bytes))) return rc;
+                            workspace_bytes)) || (rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps))) return rc;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
@@ -551,7 +601,7 @@ int pnn_rd_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_con
     if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
     reset_stats(c);
     return rd_pass_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
-                            smoothing, qps, nb_qps, lambdas, sign_data_hiding, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost,
+                            smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost,
                             d_best_sse, d_best_rate, d_workspace, s);
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "pnn_cabac_tables.h"
+#include "pnn_rdoq.h"
 #include "pnn_trquant_tables.h"
 
 namespace pnn {
@@ -333,6 +334,10 @@ struct TrQuantParams {
     uint32_t* sse; uint32_t* nonzero; uint32_t* sum_abs; uint8_t* recon;
     uint64_t* rate; const uint8_t* modes; uint8_t init_states[trquant::kMaxQps][cabac::kNumCtx];
     int sdh;
+    // rdoq nonzero: the kernels with HM's RDOQ in the quantiser's place (with sdh its own hiding): the host-made
+    // constants of each QP, the initial states of the two cbf contexts and the unit's cbf context.  init_states is then read with or
+    // without rate.  (At the end, so that the fields above stay where the kernels without RDOQ read them.)
+    int rdoq; int cbf_ctx; rdoq::Consts rd[trquant::kMaxQps]; uint8_t cbf_states[trquant::kMaxQps][2];
 };
 int trquant_blocks_per_workgroup(int w);
 hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s);

@@ -6,6 +6,7 @@
 // The cost is one IEEE multiply and one IEEE add in double; the pragmas below keep the compiler from contracting them into an FMA,
 // as rd_cost does in rd_decide_kernel (pnn_hevc_intra.hip).
 #include "../../include/pnn_hip.h"
+#include "pnn_rdoq.h"
 
 #include <algorithm>
 #include <cmath>
@@ -36,13 +37,23 @@ int refuse(const char* why)
 extern "C" double pnn_hm_intra_lambda(int qp)
 {
     // TEncSlice::calculateLambda, I slice, GOP size 1, 8-bit, no modifier: dQPFactor 0.57 * 2^((qp - 12) / 3)
-    return 0.57 * std::pow(2.0, (qp - 12) / 3.0);
+    return pnn::rdoq::hm_intra_lambda(qp);
 }
 
 extern "C" int pnn_rd_pass_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
                                 const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas,
                                 int sign_data_hiding, uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode, uint8_t* best_slot,
                                 double* best_cost, uint32_t* best_sse, uint64_t* best_rate)
+{
+    return pnn_rd_pass_rdoq_host(patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, 0,
+                                 cand_modes, cand_costs, best_mode, best_slot, best_cost, best_sse, best_rate);
+}
+
+// rdoq nonzero: the candidates are coded with HM's RDOQ (pnn_trquant_rdoq_host) under the lambda that decides
+extern "C" int pnn_rd_pass_rdoq_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                                     const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas,
+                                     int sign_data_hiding, int rdoq, uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode,
+                                     uint8_t* best_slot, double* best_cost, uint32_t* best_sse, uint64_t* best_rate)
 {
     const int k = pnn_first_pass_list_size(width);
     if (k < 0) return refuse("the width of the target patch is not 4, 8, 16, 32 or 64.");
@@ -53,6 +64,7 @@ extern "C" int pnn_rd_pass_host(const uint8_t* patterns, int pattern_h, int patt
     for (int qi = 0; qi < nb_qps; qi++) {
         if (qps[qi] < 0 || qps[qi] > 51) return refuse("the QPs are not 1 to 8 integers in [0, 51].");
         if (lambdas && !(std::isfinite(lambdas[qi]) && lambdas[qi] >= 0.)) return refuse("a lambda is negative or not finite.");
+        if (rdoq && lambdas && !(lambdas[qi] > 0.)) return refuse("RDOQ with a lambda that is not above 0.");
     }
     const int k1 = k + 1;
     const size_t w2 = (size_t)width * width, pattern = (size_t)pattern_h * pattern_w;
@@ -90,8 +102,8 @@ extern "C" int pnn_rd_pass_host(const uint8_t* patterns, int pattern_h, int patt
                 scan_modes[i * k1 + s] = m > 34 ? 0 : (uint8_t)m;                                        // 35 scans diagonally, as planar does
             }
         }
-        if (pnn_trquant_sdh_host(pred.data(), tgt.data(), width, (int)slots, scan_modes.data(), qps, nb_qps, sse.data(), nullptr, nullptr, nullptr,
-                                 rate.data(), sign_data_hiding) != PNN_OK)
+        if (pnn_trquant_rdoq_host(pred.data(), tgt.data(), width, (int)slots, scan_modes.data(), qps, nb_qps, sse.data(), nullptr, nullptr, nullptr,
+                                  rate.data(), sign_data_hiding, rdoq, rdoq ? lambda : nullptr) != PNN_OK)
             return refuse("the transform coding refused the arguments.");
         for (int qi = 0; qi < nb_qps; qi++)
             for (long i = 0; i < nb; i++) {

@@ -3,8 +3,8 @@
 // scaling lists), inverse transform (xITrMxN), reconstruction -- for 8-bit luma intra blocks, per transform unit: T = w up to 32, the
 // four 32 x 32 quadrants of the one prediction at w = 64 (this project's definition; HM would predict each quadrant again).  The
 // definition is restated at the declarations in include/pnn_hip.h; the constants live in pnn_trquant_tables.h.  HM's butterflies are
-// exact integer factorisations of the matrix products written here, so the integers are the same.  No RDOQ (nor its own sign hiding),
-// no transform skip: they need bit estimates from the running entropy-coder state, which does not exist open-loop.  Sign-data hiding as
+// exact integer factorisations of the matrix products written here, so the integers are the same.  RDOQ with its own sign hiding is an
+// option (pnn_rdoq.h, DESIGN.md section 5m: bit estimates from the state a slice STARTS with); no transform skip.  Sign-data hiding as
 // xQuant does it with RDOQ 0 (signBitHidingHDQ) reads coefficients, levels, remainders and the scan only: it is
 // here, behind a flag.  The CABAC rate of the levels is counted from the state a slice STARTS with:
 // pnn_cabac_tables.h, whose lines the kernel compiles too.
@@ -12,11 +12,20 @@
 // file to a numpy restatement and to recorded outputs of HM's own transforms.
 #include "../../include/pnn_hip.h"
 #include "pnn_cabac_tables.h"
+#include "pnn_rdoq.h"
 #include "pnn_trquant_tables.h"
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <vector>
+
+// RDOQ's costs are doubles rounded once per operation (pnn_rdoq.h): nothing in this file may be contracted
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#elif defined(__GNUC__)
+#pragma GCC optimize("fp-contract=off")
+#endif
 
 namespace {
 
@@ -124,18 +133,69 @@ void sign_hide_unit(int log2_t, int* levels, const int* coeffs, const int* delta
     }
 }
 
+// RDOQ (pnn_rdoq.h): what one QP and lambda turn into at a unit size -- the constants and the bit estimates
+struct Rdoq {
+    pnn::rdoq::Consts k;
+    pnn::rdoq::EstBits e;
+    Rdoq(int log2_t, int qp, double lambda) : k(pnn::rdoq::consts(log2_t, qp, lambda))
+    {
+        using namespace pnn::cabac;
+        uint8_t init[kNumCtx], cbf[2];
+        for (int i = 0; i < kNumCtx; i++) init[i] = (uint8_t)init_state(qp, init_value(i));
+        for (int i = 0; i < 2; i++) cbf[i] = (uint8_t)init_state(qp, pnn::rdoq::kCbfInit[i]);
+        int (*const word)(int, const uint8_t*, const uint8_t*, const int*) =
+            log2_t == 2 ? pnn::rdoq::est_bits_word<2> : log2_t == 3 ? pnn::rdoq::est_bits_word<3> : log2_t == 4 ? pnn::rdoq::est_bits_word<4>
+                                                                                                                  : pnn::rdoq::est_bits_word<5>;
+        int* words = &e.ctx[0][0];
+        for (int i = 0; i < pnn::rdoq::kEstBitsWords; i++) words[i] = word(i, init, cbf, entropy_bits_table());
+    }
+};
+// the cbf context of the unit(s) of a block of width w: one transform unit of a 2N x 2N coding unit at 8, 16, 32; what HM reaches as N x N
+// at 4; the quadrants at 64 (this project's definition)
+int cbf_ctx_of_width(int w) { return w == 8 || w == 16 || w == 32 ? 1 : 0; }
+bool lambda_ok(double lambda) { return std::isfinite(lambda) && lambda > 0.; }
+
+// xRateDistOptQuant of one unit: the levels (and those in front of RDOQ's own hiding), returns uiAbsSum
+template <int L>
+int rdoq_unit(const int* coeffs, int scan, const QpConsts& q, const Rdoq& r, int cbf_ctx, bool sdh, int* levels, int* before_hiding)
+{
+    constexpr int TT = 1 << (2 * L);
+    double cost[TT], cost0[TT], cost_sig[TT], group_sig[TT / 16];
+    int rate_up[TT], rate_down[TT], sig_delta[TT];
+    short delta_u[TT];
+    for (int i = 0; i < TT; i++)
+        cost0[i] = pnn::rdoq::uncoded_cost(pnn::rdoq::level_double(coeffs[pnn::rdoq::block_position<L>(scan, i)], q.scale, q.qbits), r.k.err_scale);
+    const pnn::rdoq::Work w{cost, cost0, cost_sig, group_sig, rate_up, rate_down, sig_delta, delta_u};
+    return pnn::rdoq::unit<L>(coeffs, scan, q.scale, q.qbits, r.k, r.e, cbf_ctx, sdh, levels, w, before_hiding);
+}
+int rdoq_unit(int log2_t, const int* coeffs, int scan, const QpConsts& q, const Rdoq& r, int cbf_ctx, bool sdh, int* levels, int* before_hiding)
+{
+    switch (log2_t) {
+    case 2: return rdoq_unit<2>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding);
+    case 3: return rdoq_unit<3>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding);
+    case 4: return rdoq_unit<4>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding);
+    default: return rdoq_unit<5>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding);
+    }
+}
+
 // quantise -> (hide signs) -> dequantise -> inverse of one unit's coefficients at one QP; the counts ADD into *nb_nonzero / *sum_abs.
 // levels: as quantised; hidden: what is dequantised (the same array may serve for both; equal without sdh)
+// rdoq NULL: HM with RDOQ 0.  Otherwise xRateDistOptQuant with its own hiding: levels = what it leaves in front of the hiding (the
+// same array as hidden may serve), delta_u is not written
 void code_unit(const Matrix& M, const int* coeffs, const QpConsts& q, int scan, bool sdh, int* levels, int* delta_u, int* hidden, int* dequant,
-               int* residual, uint32_t* nb_nonzero, uint32_t* sum_abs)
+               int* residual, uint32_t* nb_nonzero, uint32_t* sum_abs, const Rdoq* rdoq = nullptr, int cbf_ctx = 0)
 {
     const int tt = M.t * M.t;
-    for (int i = 0; i < tt; i++) {
-        int mag;
-        hidden[i] = levels[i] = quant_level(coeffs[i], q, &mag, &delta_u[i]);
-        *sum_abs += (uint32_t)mag;                                             // HM's uiAbsSum: before the clip, before the hiding
+    if (rdoq)
+        *sum_abs += (uint32_t)rdoq_unit(M.log2_t, coeffs, scan, q, *rdoq, cbf_ctx, sdh, hidden, levels == hidden ? nullptr : levels);
+    else {
+        for (int i = 0; i < tt; i++) {
+            int mag;
+            hidden[i] = levels[i] = quant_level(coeffs[i], q, &mag, &delta_u[i]);
+            *sum_abs += (uint32_t)mag;                                         // HM's uiAbsSum: before the clip, before the hiding
+        }
+        if (sdh) sign_hide_unit(M.log2_t, hidden, coeffs, delta_u, scan);
     }
-    if (sdh) sign_hide_unit(M.log2_t, hidden, coeffs, delta_u, scan);
     for (int i = 0; i < tt; i++) {
         dequant[i] = dequant_level(hidden[i], q);
         *nb_nonzero += hidden[i] != 0;
@@ -199,19 +259,32 @@ extern "C" int pnn_trquant_sdh_host(const uint8_t* predictions, const uint8_t* t
                                     int nb_qps, uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon,
                                     uint64_t* rate, int sign_data_hiding)
 {
+    return pnn_trquant_rdoq_host(predictions, targets, width, n, modes, qps, nb_qps, sses_recon, nb_nonzero, sum_abs_levels, recon, rate,
+                                 sign_data_hiding, 0, nullptr);
+}
+
+extern "C" int pnn_trquant_rdoq_host(const uint8_t* predictions, const uint8_t* targets, int width, int n, const uint8_t* modes, const int* qps,
+                                     int nb_qps, uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon,
+                                     uint64_t* rate, int sign_data_hiding, int rdoq, const double* lambdas)
+{
     const bool sdh = sign_data_hiding != 0;
     if (!width_ok(width)) { fprintf(stderr, "The width of the target patch is not 4, 8, 16, 32 or 64.\n"); return PNN_E_ARG; }
     if (n < 0 || (n > 0 && (!predictions || !targets))) { fprintf(stderr, "Bad batch size or NULL inputs.\n"); return PNN_E_ARG; }
     if (!qps_ok(qps, nb_qps)) { fprintf(stderr, "The QPs are not 1 to 8 integers in [0, 51].\n"); return PNN_E_ARG; }
     if (!sses_recon && !nb_nonzero && !sum_abs_levels && !recon && !rate) { fprintf(stderr, "Every output is NULL.\n"); return PNN_E_ARG; }
-    if (modes && !rate && !sdh) { fprintf(stderr, "Intra modes without a rate output or sign-data hiding.\n"); return PNN_E_ARG; }
+    if (modes && !rate && !sdh && !rdoq) { fprintf(stderr, "Intra modes without a rate output, sign-data hiding or RDOQ.\n"); return PNN_E_ARG; }
     for (long b = 0; modes && b < n; b++)
         if (modes[b] > 34) { fprintf(stderr, "An intra mode is above 34.\n"); return PNN_E_ARG; }
+    for (int qi = 0; rdoq && lambdas && qi < nb_qps; qi++)
+        if (!lambda_ok(lambdas[qi])) { fprintf(stderr, "RDOQ with a lambda that is not finite or not above 0.\n"); return PNN_E_ARG; }
     const Matrix M(log2_tu(width));
     const int t = M.t, units = width / t;
     const size_t w2 = (size_t)width * width;
     std::vector<InitStates> init;
     for (int qi = 0; rate && qi < nb_qps; qi++) init.emplace_back(qps[qi]);
+    std::vector<Rdoq> rd;
+    for (int qi = 0; rdoq && qi < nb_qps; qi++) rd.emplace_back(M.log2_t, qps[qi], lambdas ? lambdas[qi] : pnn::rdoq::hm_intra_lambda(qps[qi]));
+    const int cbf_ctx = cbf_ctx_of_width(width);
     int residual[32 * 32], coeffs[32 * 32], levels[32 * 32], delta_u[32 * 32], dequant[32 * 32], decoded[32 * 32];
     for (long b = 0; b < n; b++) {
         const uint8_t* prediction = predictions + b * w2;
@@ -225,7 +298,7 @@ extern "C" int pnn_trquant_sdh_host(const uint8_t* predictions, const uint8_t* t
                 forward(M, residual, coeffs);                                  // once per unit, whatever the number of QPs
                 for (int qi = 0; qi < nb_qps; qi++) {
                     code_unit(M, coeffs, qp_consts(M.log2_t, qps[qi]), scan, sdh, levels, delta_u, levels, dequant, decoded, &nonzero[qi],
-                              &sum_abs[qi]);
+                              &sum_abs[qi], rdoq ? &rd[qi] : nullptr, cbf_ctx);
                     if (rate) bits[qi] += unit_rate(M.log2_t, levels, scan, init[qi], sdh);
                     for (int y = 0; y < t; y++)
                         for (int x = 0; x < t; x++) {
@@ -287,26 +360,66 @@ extern "C" int pnn_trquant_stages_sdh_host(const uint8_t* prediction, const uint
                                            int32_t* coeffs, int32_t* levels, int32_t* delta_u, int32_t* levels_hidden, int32_t* dequant,
                                            int32_t* residual)
 {
+    return pnn_trquant_stages_rdoq_host(prediction, target, width, qp, scan, sign_data_hiding, 0, 0., 0, coeffs, levels, delta_u, levels_hidden,
+                                        dequant, residual);
+}
+
+extern "C" int pnn_trquant_stages_rdoq_host(const uint8_t* prediction, const uint8_t* target, int width, int qp, int scan, int sign_data_hiding,
+                                            int rdoq, double lambda, int cbf_ctx, int32_t* coeffs, int32_t* levels, int32_t* delta_u,
+                                            int32_t* levels_hidden, int32_t* dequant, int32_t* residual)
+{
     if (!width_ok(width)) { fprintf(stderr, "The width of the target patch is not 4, 8, 16, 32 or 64.\n"); return PNN_E_ARG; }
     if (!prediction || !target) { fprintf(stderr, "NULL pointer.\n"); return PNN_E_ARG; }
     if (!qps_ok(&qp, 1)) { fprintf(stderr, "The QP does not belong to [0, 51].\n"); return PNN_E_ARG; }
     if (!scan_ok(scan, width)) { fprintf(stderr, kBadScan); return PNN_E_ARG; }
     if (!coeffs && !levels && !delta_u && !levels_hidden && !dequant && !residual) { fprintf(stderr, "Every output is NULL.\n"); return PNN_E_ARG; }
+    if (rdoq && !lambda_ok(lambda)) { fprintf(stderr, "RDOQ with a lambda that is not finite or not above 0.\n"); return PNN_E_ARG; }
+    if (rdoq && cbf_ctx != 0 && cbf_ctx != 1) { fprintf(stderr, "The cbf context is not 0 or 1.\n"); return PNN_E_ARG; }
     const Matrix M(log2_tu(width));
     const int t = M.t, units = width / t;
     const QpConsts q = qp_consts(M.log2_t, qp);
-    int in[32 * 32], stage[6][32 * 32];
+    const Rdoq rd(M.log2_t, qp, rdoq ? lambda : 1.);
+    int in[32 * 32], stage[6][32 * 32] = {};                                   // (RDOQ leaves delta_u as it is: zero)
     int32_t* const outs[6] = {coeffs, levels, delta_u, levels_hidden, dequant, residual};
     for (int uy = 0; uy < units; uy++)
         for (int ux = 0; ux < units; ux++) {
             uint32_t nonzero = 0, sum_abs = 0;
             unit_residual(prediction, target, width, t, uy, ux, in);
             forward(M, in, stage[0]);
-            code_unit(M, stage[0], q, scan, sign_data_hiding != 0, stage[1], stage[2], stage[3], stage[4], stage[5], &nonzero, &sum_abs);
+            code_unit(M, stage[0], q, scan, sign_data_hiding != 0, stage[1], stage[2], stage[3], stage[4], stage[5], &nonzero, &sum_abs,
+                      rdoq ? &rd : nullptr, cbf_ctx);
             for (int s = 0; s < 6; s++)                                        // each unit's arrays where the unit lies in the block
                 if (outs[s])
                     for (int y = 0; y < t; y++)
                         for (int x = 0; x < t; x++) outs[s][(size_t)(uy * t + y) * width + ux * t + x] = stage[s][y * t + x];
         }
+    return PNN_OK;
+}
+
+extern "C" int pnn_rdoq_unit_host(const int32_t* coeffs, int t, int scan, int qp, double lambda, int cbf_ctx, int sign_data_hiding, int32_t* levels,
+                                  int32_t* abs_sum)
+{
+    if (!unit_size_ok(t)) { fprintf(stderr, "The unit size is not 4, 8, 16 or 32.\n"); return PNN_E_ARG; }
+    if (!coeffs || !levels) { fprintf(stderr, "NULL pointer.\n"); return PNN_E_ARG; }
+    if (!scan_ok(scan, t)) { fprintf(stderr, kBadScan); return PNN_E_ARG; }
+    if (!qps_ok(&qp, 1)) { fprintf(stderr, "The QP does not belong to [0, 51].\n"); return PNN_E_ARG; }
+    if (!lambda_ok(lambda)) { fprintf(stderr, "RDOQ with a lambda that is not finite or not above 0.\n"); return PNN_E_ARG; }
+    if (cbf_ctx != 0 && cbf_ctx != 1) { fprintf(stderr, "The cbf context is not 0 or 1.\n"); return PNN_E_ARG; }
+    for (int i = 0; i < t * t; i++)
+        if (coeffs[i] < -32768 || coeffs[i] > 32767) { fprintf(stderr, "A coefficient is outside [-32768, 32767].\n"); return PNN_E_ARG; }
+    const int log2_t = log2_tu(t);
+    const int sum = rdoq_unit(log2_t, coeffs, scan, qp_consts(log2_t, qp), Rdoq(log2_t, qp, lambda), cbf_ctx, sign_data_hiding != 0, levels, nullptr);
+    if (abs_sum) *abs_sum = sum;
+    return PNN_OK;
+}
+
+extern "C" int pnn_rdoq_est_bits_host(int t, int qp, int32_t* est_bits)
+{
+    if (!unit_size_ok(t)) { fprintf(stderr, "The unit size is not 4, 8, 16 or 32.\n"); return PNN_E_ARG; }
+    if (!est_bits) { fprintf(stderr, "NULL pointer.\n"); return PNN_E_ARG; }
+    if (!qps_ok(&qp, 1)) { fprintf(stderr, "The QP does not belong to [0, 51].\n"); return PNN_E_ARG; }
+    const Rdoq rd(log2_tu(t), qp, 1.);
+    const int* words = &rd.e.ctx[0][0];
+    for (int i = 0; i < pnn::rdoq::kEstBitsWords; i++) est_bits[i] = words[i];
     return PNN_OK;
 }

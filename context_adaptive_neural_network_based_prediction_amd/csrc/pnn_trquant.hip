@@ -37,6 +37,14 @@
 // the winning lane rewrites its one level in LDS.  Behind a barrier every lane reads back the levels of its own samples, counts the
 // nonzero ones and dequantises; from there on the kernel is the one above (the rate walk with the SDH rule of unit_rate).  The
 // instantiations without SDH are the kernels as they were: no statement of theirs mentions the hiding's arrays.
+//
+// RDOQ: the instantiations with RDOQ put HM's xRateDistOptQuant (pnn_rdoq.h, the lines the host twin compiles)
+// in the quantiser's place, and with SDH its own sign hiding in signBitHidingHDQ's.  Per QP: the bit estimates of the QP go to LDS one
+// word per lane, and ONE LANE PER SCAN POSITION (the mapping of the SDH path, hide_at) computes the uncoded cost of its position -- into
+// buf_a / buf_b, which hold nothing between two QPs, read as 2 x 512 doubles (an array of its own at T = 32) --; behind a barrier ONE LANE PER UNIT walks its unit (the
+// chain c1 / c2 / Rice / context set / coded groups / base cost is serial by construction) over LDS arrays: two doubles per position,
+// with SDH three ints and a short, one double per group.  Behind the next barrier every lane reads back the levels of its samples and
+// the kernel is the one above.  The other instantiations are the kernels as they were: no statement of theirs mentions these arrays.
 #include "pnn_cabac_tables.h"
 #include "pnn_kernels.h"
 #include "pnn_trquant_tables.h"
@@ -48,7 +56,7 @@ constexpr int kTqThreads = 256;
 constexpr int kElems = 1024;                      // residual samples a workgroup holds: one 32 x 32 unit, or G smaller blocks
 constexpr int kPerLane = kElems / kTqThreads;
 
-template <int W, bool RATE, bool SDH>
+template <int W, bool RATE, bool SDH, bool RDOQ = false>
 __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams p)
 {
     using namespace trquant;
@@ -58,6 +66,8 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
     constexpr int MS = T + 1;                     // the matrix's row stride in LDS
     constexpr int SEG = TT < 64 ? TT : 64;        // lanes of one wave that share a unit
     __shared__ int mat[T * MS];
+    // (no alignas here: an explicit alignment, even the type's own, takes away the 16 bytes the compiler gives these arrays by itself --
+    // the ds_read_b128 of the stages below -- and changes the code of every instantiation; the RDOQ path's doubles rely on those 16 bytes)
     __shared__ int buf_a[kElems], buf_b[kElems], coef[kElems];
     __shared__ unsigned sums[kMaxQps][3][G];      // [qp][sse, nonzero, sum of magnitudes][block]
 
@@ -72,7 +82,7 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
 
     // the hiding's arrays exist in the SDH instantiations only (the levels are the rate's array where there is one)
     int* du = nullptr; int* lastg = nullptr;
-    if constexpr (SDH) {
+    if constexpr (SDH && !RDOQ) {
         __shared__ int du_s[kElems], lastg_s[G];
         du = du_s; lastg = lastg_s;
         if constexpr (!RATE) {
@@ -81,7 +91,35 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
         }
     }
 
+    // RDOQ's arrays exist in the RDOQ instantiations only (levels and entropy bits are the rate's arrays where there are any)
+    [[maybe_unused]] rdoq::Work rw{};
+    [[maybe_unused]] rdoq::EstBits* est = nullptr;
+    [[maybe_unused]] int* unit_abs = nullptr;
+    if constexpr (RDOQ) {
+        static_assert(2 * sizeof(int) == sizeof(double), "buf_a and buf_b hold the uncoded costs");
+        __shared__ double cost_s[kElems], cost_sig_s[kElems], group_sig_s[kElems / 16];
+        __shared__ rdoq::EstBits est_s;
+        __shared__ int unit_abs_s[G];
+        rw.cost = cost_s; rw.cost_sig = cost_sig_s; rw.group_sig = group_sig_s; est = &est_s; unit_abs = unit_abs_s;
+        if constexpr (T == 32) {                  // one unit of 1024 positions: an array of its own (there is room at this size)
+            __shared__ double cost0_s[kElems];
+            rw.cost0 = cost0_s;
+        }
+        if constexpr (SDH) {
+            __shared__ int rate_up_s[kElems], rate_down_s[kElems], sig_delta_s[kElems];
+            __shared__ short delta_u_s[kElems];
+            rw.rate_up = rate_up_s; rw.rate_down = rate_down_s; rw.sig_delta = sig_delta_s; rw.delta_u = delta_u_s;
+        }
+        if constexpr (!RATE) {
+            __shared__ int lev_rdoq[kElems], ebits_rdoq[128];
+            lev = lev_rdoq; ebits = ebits_rdoq;
+        }
+    }
+
     const int tid = threadIdx.x;
+    if constexpr (RDOQ && !RATE) {
+        if (tid < 128) ebits[tid] = cabac::entropy_bits_table()[tid];
+    }
     if constexpr (RATE) {
         if (tid < 128) ebits[tid] = cabac::entropy_bits_table()[tid];
         if (tid < 64) lps[tid] = cabac::trans_idx_lps_table()[tid];
@@ -105,7 +143,7 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
 
     // SDH: lane tid of round j is scan position (256 j + tid) % TT of unit (256 j + tid) / TT; where that lies in LDS
     [[maybe_unused]] int hide_at[kPerLane];
-    if constexpr (SDH) {
+    if constexpr (SDH || RDOQ) {
 #pragma unroll
         for (int j = 0; j < kPerLane; j++) {
             const int s = j * kTqThreads + tid, u = s / TT, i = s % TT;
@@ -158,7 +196,43 @@ __global__ __launch_bounds__(kTqThreads) void trquant_kernel(const TrQuantParams
         for (int qi = 0; qi < p.nb_qps; qi++) {
             const QpConsts qc = p.qp[qi];
             unsigned nonzero[kPerLane], sum_abs[kPerLane], sse[kPerLane];
-            if constexpr (SDH) {
+            if constexpr (RDOQ) {
+                // below T = 32 the uncoded costs lie in buf_a (scan positions 0 .. 511) and buf_b (512 .. 1023), each read as 512
+                // doubles: no unit straddles the two, and both hold nothing between two QPs
+                // (nothing declares the 8 bytes -- see the arrays' declaration --: a layout that loses them stops here, loudly; two scalar
+                // instructions per QP beside the walk)
+                if (T < 32 && ((reinterpret_cast<uintptr_t>(buf_a) | reinterpret_cast<uintptr_t>(buf_b)) & 7)) __builtin_trap();
+                double* const cost0_lo = T == 32 ? rw.cost0 : reinterpret_cast<double*>(buf_a);
+                double* const cost0_hi = T == 32 ? rw.cost0 + kElems / 2 : reinterpret_cast<double*>(buf_b);
+                __syncthreads();                  // the coefficients are written; buf_b and the last QP's tables and levels are read
+                for (int i = tid; i < rdoq::kEstBitsWords; i += kTqThreads)
+                    (&est->ctx[0][0])[i] = rdoq::est_bits_word<L>(i, p.init_states[qi], p.cbf_states[qi], ebits);
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) {
+                    const double c0 = rdoq::uncoded_cost(rdoq::level_double(coef[hide_at[j]], qc.scale, qc.qbits), p.rd[qi].err_scale);
+                    (j < kPerLane / 2 ? cost0_lo : cost0_hi)[(j % (kPerLane / 2)) * kTqThreads + tid] = c0;
+                }
+                __syncthreads();
+                if (tid < G) {                    // lane g quantises unit g (a unit past N has a zero residual: nothing to decide)
+                    const long b = blk0 + tid;
+                    const int scan = p.modes && b < p.N ? cabac::scan_of_mode(L, p.modes[b]) : cabac::kScanDiag;
+                    rdoq::Work w = rw;
+                    const int s0 = tid * TT;      // the unit's first scan position: in the lower or the upper half of the costs
+                    w.cost0 = (s0 < kElems / 2 ? cost0_lo + s0 : cost0_hi + (s0 - kElems / 2));
+                    w.cost += s0; w.cost_sig += s0; w.group_sig += s0 / 16;
+                    if constexpr (SDH) { w.rate_up += s0; w.rate_down += s0; w.sig_delta += s0; w.delta_u += s0; }
+                    unit_abs[tid] = rdoq::unit<L>(coef + s0, scan, qc.scale, qc.qbits, p.rd[qi], *est, p.cbf_ctx, SDH, lev + s0, w, nullptr);
+                }
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < kPerLane; j++) {
+                    const int level = lev[j * kTqThreads + tid];
+                    nonzero[j] = level != 0;
+                    sum_abs[j] = 0;                                // HM's uiAbsSum is the walk's: added per unit below
+                    buf_a[j * kTqThreads + tid] = dequant_level(level, qc);
+                }
+                if (tid < G) atomicAdd(&sums[qi][2][tid], (unsigned)unit_abs[tid]);
+            } else if constexpr (SDH) {
 #pragma unroll
                 for (int j = 0; j < kPerLane; j++) {
                     int mag, delta_u;
@@ -304,6 +378,19 @@ hipError_t launch_width(const TrQuantParams& p, dim3 grid, dim3 block, hipStream
     return hipGetLastError();
 }
 
+template <bool RATE, bool SDH>
+hipError_t launch_width_rdoq(const TrQuantParams& p, dim3 grid, dim3 block, hipStream_t s)
+{
+    switch (p.w) {
+    case 4: hipLaunchKernelGGL((trquant_kernel<4, RATE, SDH, true>), grid, block, 0, s, p); break;
+    case 8: hipLaunchKernelGGL((trquant_kernel<8, RATE, SDH, true>), grid, block, 0, s, p); break;
+    case 16: hipLaunchKernelGGL((trquant_kernel<16, RATE, SDH, true>), grid, block, 0, s, p); break;
+    case 32: hipLaunchKernelGGL((trquant_kernel<32, RATE, SDH, true>), grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL((trquant_kernel<64, RATE, SDH, true>), grid, block, 0, s, p); break;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
 
 int trquant_blocks_per_workgroup(int w) { return w >= 32 ? 1 : kElems / (w * w); }
@@ -315,6 +402,10 @@ hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s)
     if (trquant::log2_tu(p.w) < 0) return hipErrorInvalidValue;
     const int g = trquant_blocks_per_workgroup(p.w);
     const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kTqThreads);
+    if (p.rdoq) {
+        if (p.rate) return p.sdh ? launch_width_rdoq<true, true>(p, grid, block, s) : launch_width_rdoq<true, false>(p, grid, block, s);
+        return p.sdh ? launch_width_rdoq<false, true>(p, grid, block, s) : launch_width_rdoq<false, false>(p, grid, block, s);
+    }
     if (p.rate) return p.sdh ? launch_width<true, true>(p, grid, block, s) : launch_width<true, false>(p, grid, block, s);
     return p.sdh ? launch_width<false, true>(p, grid, block, s) : launch_width<false, false>(p, grid, block, s);
 }

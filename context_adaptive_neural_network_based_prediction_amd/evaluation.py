@@ -16,11 +16,11 @@ Every function with an HEVC column takes reference_smoothing (0, 1, 2: intrapred
 extracted predictor; 2 makes the HEVC columns and the first-pass ranking those of HM's own predictor, with its reference-sample
 smoothing.  A nonzero value adds the key 'reference_smoothing' to the dictionaries and changes nothing in the PNN's columns.
 Both also take transform_qps, a list of 1 to 8 QPs, for the transform-domain column: what is left of the PNN's prediction and of the best
-HEVC mode's after HM's residual path with RDOQ 0 (intraprediction.transform_code; two more pnn_trquant_sdh_device calls per mask, the
+HEVC mode's after HM's residual path, RDOQ 0 or with transform_rdoq RDOQ 1 (intraprediction.transform_code; two more pnn_trquant_rdoq_device calls per mask, the
 same download).
 rd_pass=True (with first_pass and transform_qps) adds HM's second intra pass: the choice by D + lambda R among the first-pass candidates
-and the PNN (pnn_rd_pass_picture_pairs_device: one more call per mask, the same download).
-Options travel as arguments: every call of the mask loop goes to the widest entry of its operation (*_hm_device, pnn_trquant_sdh_device) with 0
+and the PNN (pnn_rd_pass_rdoq_picture_pairs_device: one more call per mask, the same download).
+Options travel as arguments: every call of the mask loop goes to the widest entry of its operation (*_hm_device, pnn_trquant_rdoq_device) with 0
 or NULL for an option that is off; the narrower entries of include/pnn_hip.h forward to these with those values: the same kernel launch.
 """
 import ctypes
@@ -183,7 +183,7 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                               tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
-                              transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False):
+                              transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False, transform_rdoq=False):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -212,9 +212,9 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     nothing changes: not a key, a call or a byte (the entries without _hm pass that 0 on: the same kernel launch under either name).
 
     transform_qps (1 to 8 integers in [0, 51]; ValueError otherwise, before anything touches the GPU) adds the transform-domain column,
-    open-loop: per mask TWO more calls behind the score call (and the first-pass call), pnn_trquant_sdh_device on the PNN's uint8 predictions
+    open-loop: per mask TWO more calls behind the score call (and the first-pass call), pnn_trquant_rdoq_device on the PNN's uint8 predictions
     and on the best HEVC mode's (the smoothed ones when reference_smoothing says so), both against the targets the first mask left on
-    the device; HM's residual path with RDOQ 0 as include/pnn_hip.h defines it (no RDOQ, sign-data hiding, transform skip or rate; at
+    the device; HM's residual path as include/pnn_hip.h defines it, with RDOQ 0 unless transform_rdoq is set (no transform skip; sign-data hiding, the rate and RDOQ are the options below; at
     w = 64 the four 32 x 32 quadrants of the one prediction).  Their results join the one download.  New keys: 'transform_qps' (tuple),
     'sses_recon_pnn', 'nb_nonzero_levels_pnn', 'sum_abs_levels_pnn' (uint32 [nb_qps, N]), 'psnrs_recon_pnn' (float64 [nb_qps, N]), the same
     four with '_hevc_best_mode' in place of '_pnn', and 'frequency_recon_win_pnn' (one float per QP: the share of blocks whose PNN
@@ -241,21 +241,28 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     rd_pass=True (with first_pass=True and transform_qps; ValueError without either, before anything touches the GPU) adds HM's second
     intra pass (include/pnn_hip.h, "the second intra pass"; TEncSearch.cpp:2476-2605): per block and QP the choice by D + lambda R among
     the first-pass candidates and the PNN, which is appended as 35 where the list lacks it -- ONE more call per mask,
-    pnn_rd_pass_picture_pairs_device, behind the others, with the PNN's uint8 predictions on the device as the candidate, HM's lambda of
+    pnn_rd_pass_rdoq_picture_pairs_device, behind the others, with the PNN's uint8 predictions on the device as the candidate, HM's lambda of
     each QP, reference_smoothing as the candidates' smoothing and transform_sign_hiding as its flag; its results join the one
     download, its scratch is allocated once.  New keys: 'rd_pass_candidates' uint8 [N, K + 1] (the slots' modes, 255 = unused),
     'rd_pass_costs' float64 [nb_qps, N, K + 1] (inf in an unused slot), 'rd_pass_modes' uint8, 'rd_pass_sses' uint32, 'rd_pass_rate_bits'
     float64 (bits), 'psnrs_recon_rd_pass' float64 (each [nb_qps, N], of the winner) and 'frequency_rd_pass_win_pnn' (one float per QP:
     the share of blocks whose winner is 35 -- how often the encoder would pick the PNN).  Equal to intraprediction.rd_pass on the
-    dictionary's own patterns, targets and PNN predictions.  Mode bits, RDOQ and the missing most probable modes are left out, as the
-    header says.  With rd_pass=False nothing changes: not a key, a call or a byte."""
+    dictionary's own patterns, targets and PNN predictions.  Mode bits and the missing most probable modes are left out, as the
+    header says (RDOQ: the next option).  With rd_pass=False nothing changes: not a key, a call or a byte.
+
+    transform_rdoq=True (with transform_qps; ValueError without, before anything touches the GPU) sets the option rdoq of the two
+    transform calls and of the second-pass call (0 without it): HM's RDOQ under HM's lambda of each QP (include/pnn_hip.h,
+    "rate-distortion optimised quantisation").  The transform-domain keys and the rd_pass_* keys are then those of RDOQ 1, and
+    'transform_rdoq': True joins them.  Equal to intraprediction.transform_code(rdoq=True, modes=...) and rd_pass(rdoq=True) on the
+    dictionary's own arrays.  With transform_rdoq=False nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
-                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass)
+                        net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass,
+                        transform_rdoq)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                                    tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
-                                   transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False):
+                                   transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False, transform_rdoq=False):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -270,13 +277,13 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
     original, as in the table above.  reference_smoothing: as for score_masks_from_pictures; the smoothed line is built from the decoded
     plane's samples, as the unsmoothed one is.  transform_qps: as for score_masks_from_pictures; the predictions that get coded are the
     ones made from the decoded plane, the residual's and the SSE's targets come from the original, as in the table above.
-    transform_rate, transform_sign_hiding: as for score_masks_from_pictures."""
+    transform_rate, transform_sign_hiding, transform_rdoq: as for score_masks_from_pictures."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
                         tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps,
-                        transform_rate, transform_sign_hiding, rd_pass)
+                        transform_rate, transform_sign_hiding, rd_pass, transform_rdoq)
 
 def _check_score_masks_arguments(ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                                 reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False):
+                                 reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False, transform_rdoq=False):
     """The argument checks of _score_masks, all before anything touches the GPU; the library is first used by the last, the predictor's mean.
     Returns (masks as int pairs, rows and cols as flat int64 arrays, reference_smoothing as int, transform_qps as a tuple of ints or ())."""
     if ch.dtype != np.uint8:
@@ -308,6 +315,8 @@ def _check_score_masks_arguments(ch, nb_planes, w, row_1sts, col_1sts, predictor
         raise ValueError('`transform_sign_hiding` is set without `transform_qps`.')
     if rd_pass and len(transform_qps) == 0:
         raise ValueError('`rd_pass` is set without `transform_qps`.')
+    if transform_rdoq and len(transform_qps) == 0:
+        raise ValueError('`transform_rdoq` is set without `transform_qps`.')
     masks = [(int(m[0]), int(m[1])) for m in tuples_width_height_masks]
     rows, cols = row_1sts.astype(np.int64).ravel(), col_1sts.astype(np.int64).ravel()
     if nb_images * rows.size == 0:
@@ -366,7 +375,8 @@ def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False):
     return sections, begin, end
 
 
-def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False):
+def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False,
+                            transform_rdoq=False):
     """One mask's dictionary_performance, but for the uint8 blocks, from `view`: the downloaded sections by name."""
     psnrs_pnn = intraprediction.psnrs_from_sses(view['sses_pnn'], w)
     psnrs_hevc = intraprediction.psnrs_from_sses(view['sses_hevc'], w)
@@ -394,6 +404,8 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
                                        for pnn, hevc in zip(d['rate_bits_pnn'], d['rate_bits_hevc_best_mode'])]
     if transform_sign_hiding:
         d['transform_sign_hiding'] = True
+    if transform_rdoq:
+        d['transform_rdoq'] = True
     if rd_pass:
         d.update({key: view[key].copy() for key in ('rd_pass_candidates', 'rd_pass_costs', 'rd_pass_modes', 'rd_pass_sses')})
         d['rd_pass_rate_bits'] = view['rd_pass_rates'].astype(np.float64) / 32768.
@@ -403,14 +415,15 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
 
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
-                 keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False):
+                 keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False,
+                 transform_rdoq=False):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer.  Every option is an argument
     of the one entry its call has (the smoothing; the mode pointer, the rate pointer and the flag), 0 or NULL when off."""
     w = width_target
     masks, rows, cols, reference_smoothing, transform_qps = _check_score_masks_arguments(
         ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns, reference_smoothing,
-        transform_qps, transform_rate, transform_sign_hiding, rd_pass)
+        transform_qps, transform_rate, transform_sign_hiding, rd_pass, transform_rdoq)
     if rd_pass and not first_pass:
         raise ValueError('`rd_pass` is set without `first_pass`.')
     nb_images, height, width = ch.shape[:3]
@@ -450,20 +463,20 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
             for column, predictions in _CODED_COLUMNS if nb_qps else ():
                 # both predictions and the first mask's targets are on the device.  Where the scan is read (by the rate, by the hiding), the
                 # best mode's follows its mode, which the score call left there; the PNN has no mode: the diagonal scan
-                modes = ptr['indices_hevc'] if column == 'hevc_best_mode' and (transform_rate or transform_sign_hiding) else None
-                _lib.check(L.pnn_trquant_sdh_device(
+                modes = ptr['indices_hevc'] if column == 'hevc_best_mode' and (transform_rate or transform_sign_hiding or transform_rdoq) else None
+                _lib.check(L.pnn_trquant_rdoq_device(
                     predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps, ptr['sses_recon_' + column],
                     ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None, ptr['rate_' + column] if transform_rate else None,
-                    int(bool(transform_sign_hiding)), stream), predictor.ctx)
+                    int(bool(transform_sign_hiding)), int(bool(transform_rdoq)), None, stream), predictor.ctx)
             if rd_pass:                                   # the candidate is the PNN's uint8 prediction; NULL lambdas: HM's of each QP
-                _lib.check(L.pnn_rd_pass_picture_pairs_device(
+                _lib.check(L.pnn_rd_pass_rdoq_picture_pairs_device(
                     *blocks, ptr['predictions_pnn'], reference_smoothing, c_qps, nb_qps, None, int(bool(transform_sign_hiding)),
-                    *[ptr[name] for name in _RD_PASS_SECTIONS], d_scratch.data_ptr(), nb_scratch, stream), predictor.ctx)
+                    int(bool(transform_rdoq)), *[ptr[name] for name in _RD_PASS_SECTIONS], d_scratch.data_ptr(), nb_scratch, stream), predictor.ctx)
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
         dictionary_performance = _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate,
-                                                         transform_sign_hiding, rd_pass)
+                                                         transform_sign_hiding, rd_pass, transform_rdoq)
         if keep_predictions:
             if first:
                 targets_uint8 = view['targets'].copy()

@@ -357,12 +357,12 @@ def _blocks_uint8(array_uint8, name):
 
 
 def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reconstructions=False, modes=None, rate=False,
-                   sign_data_hiding=False):
+                   sign_data_hiding=False, rdoq=False, lambdas=None):
     """Open-loop HEVC transform coding of N predictions against their targets (uint8 [N, w, w] or [N, w, w, 1]) at the 1 to 8 QPs of
-    `qps` (integers in [0, 51]): HM's residual path with RDOQ 0 -- forward transform, quantisation, dequantisation, inverse transform,
+    `qps` (integers in [0, 51]): HM's residual path, with RDOQ 0 unless `rdoq` is set -- forward transform, quantisation, dequantisation, inverse transform,
     reconstruction -- as include/pnn_hip.h defines it (T = w up to 32, the four 32 x 32 quadrants of the one prediction at w = 64; no
-    RDOQ, sign-data hiding, transform skip or rate).  device=None runs the host twin (pnn_trquant_sdh_host), an int that GPU
-    (pnn_trquant_sdh_device: one launch for all blocks and QPs); the bits are the same.  The options below are arguments of these two
+    transform skip; RDOQ, sign-data hiding and the rate are the options below).  device=None runs the host twin (pnn_trquant_rdoq_host),
+    an int that GPU (pnn_trquant_rdoq_device: one launch for all blocks and QPs); the bits are the same.  The options below are arguments of these two
     entries -- the rate pointer, the mode pointer, the flag -- NULL or 0 when off, which is what pnn_trquant_host / _device and
     pnn_trquant_rate_host / _device forward to them.
     Returns {'sses_recon', 'nb_nonzero_levels', 'sum_abs_levels': uint32 [nb_qps, N], 'psnrs_recon': float64 [nb_qps, N] (psnrs_from_sses)}
@@ -375,7 +375,12 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     sign_data_hiding=True codes the way HM does with SignHideFlag 1 (its default) and RDOQ 0: signBitHidingHDQ between quantisation and
     dequantisation (include/pnn_hip.h, "sign-data hiding"; the entries' flag).  Same keys; nb_nonzero_levels, the
     reconstruction, sses_recon and rate_bits follow the levels after hiding (the hidden signs cost no bin), sum_abs_levels stays the
-    sum before it.  `modes` is then allowed without `rate`: the scan shapes the levels.  With False nothing changes."""
+    sum before it.  `modes` is then allowed without `rate`: the scan shapes the levels.  With False nothing changes.
+    rdoq=True quantises the way HM does with RDOQ 1 (include/pnn_hip.h, "rate-distortion optimised quantisation"; the option of
+    pnn_trquant_rdoq_host / _device, which every call here goes to, with 0 and NULL when off): xRateDistOptQuant under lambdas -- None
+    (hm_intra_lambda of each QP) or one finite value > 0 per QP -- and, with sign_data_hiding, its own hiding.  Same keys, all of them
+    those of the levels RDOQ leaves; sum_abs_levels is its uiAbsSum.  `modes` is then allowed too.  `lambdas` without rdoq is a
+    ValueError.  With False nothing changes."""
     qps = _check_qps(qps)
     predictions, targets = _blocks_uint8(predictions_uint8, 'predictions_uint8'), _blocks_uint8(targets_uint8, 'targets_uint8')
     if predictions.shape != targets.shape:
@@ -384,8 +389,11 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     nq = len(qps)
     c_qps = (ctypes.c_int * nq)(*qps)
     L = _lib.lib()
-    flag = int(bool(sign_data_hiding))
-    if not (rate or flag):
+    flag, option = int(bool(sign_data_hiding)), int(bool(rdoq))
+    if lambdas is not None and not option:
+        raise ValueError('`lambdas` is given without `rdoq`.')
+    c_lambdas = _check_lambdas(lambdas, nq, positive=True)
+    if not (rate or flag or option):
         if modes is not None:
             raise ValueError('`modes` is given without `rate`.')
     elif modes is not None:
@@ -399,11 +407,11 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
         sses, nonzero, sum_abs = (np.zeros((nq, n), np.uint32) for _ in range(3))
         bits = np.zeros((nq, n), np.uint64) if rate else None
         recon = np.zeros((nq, n, w, w), np.uint8) if keep_reconstructions else None
-        rc = L.pnn_trquant_sdh_host(predictions.ctypes.data, targets.ctypes.data, w, n, _address(modes), c_qps, nq, sses.ctypes.data,
-                                    nonzero.ctypes.data, sum_abs.ctypes.data, _address(recon), _address(bits), flag)
+        rc = L.pnn_trquant_rdoq_host(predictions.ctypes.data, targets.ctypes.data, w, n, _address(modes), c_qps, nq, sses.ctypes.data,
+                                     nonzero.ctypes.data, sum_abs.ctypes.data, _address(recon), _address(bits), flag, option, c_lambdas)
         if rc != 0:                                       # (named as the ABI names the call with these options)
             raise ValueError('pnn_trquant_%shost refused the arguments (width %d, %d blocks).'
-                             % ('sdh_' if flag else 'rate_' if rate else '', w, n))
+                             % ('rdoq_' if option else 'sdh_' if flag else 'rate_' if rate else '', w, n))
     else:
         import torch
         dev = torch.device("cuda", device)
@@ -414,9 +422,10 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
         d_recon = torch.zeros((nq, n, w, w), dtype=torch.uint8, device=dev) if keep_reconstructions else None
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_trquant_sdh_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, _address(d_modes), c_qps, nq,
-                                                d_counts[0].data_ptr(), d_counts[1].data_ptr(), d_counts[2].data_ptr(), _address(d_recon),
-                                                _address(d_bits), flag, ctypes.c_void_p(stream.cuda_stream)), _context(device))
+            _lib.check(L.pnn_trquant_rdoq_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, _address(d_modes), c_qps, nq,
+                                                 d_counts[0].data_ptr(), d_counts[1].data_ptr(), d_counts[2].data_ptr(), _address(d_recon),
+                                                 _address(d_bits), flag, option, c_lambdas, ctypes.c_void_p(stream.cuda_stream)),
+                       _context(device))
         sses, nonzero, sum_abs = d_counts.cpu().numpy().view(np.uint32)      # (waits for the stream)
         bits = None if d_bits is None else d_bits.cpu().numpy().view(np.uint64)
         recon = None if d_recon is None else d_recon.cpu().numpy()
@@ -444,17 +453,20 @@ def rd_pass_shapes(n, nb_qps, width_target):
     return ((n, k1), (nb_qps, n, k1)) + ((nb_qps, n),) * 5
 
 
-def _check_lambdas(lambdas, nb_qps):
-    """None (HM's lambda per QP: a NULL pointer) or nb_qps finite floats >= 0 as a ctypes array."""
+def _check_lambdas(lambdas, nb_qps, positive=False):
+    """None (HM's lambda per QP: a NULL pointer) or nb_qps finite floats >= 0 (> 0 with `positive`: RDOQ divides by them) as a ctypes array."""
     if lambdas is None:
         return None
     values = np.asarray(lambdas, dtype=np.float64).ravel()
     if values.size != nb_qps or not np.all(np.isfinite(values)) or np.any(values < 0.):
         raise ValueError('`lambdas` does not hold one finite value >= 0 per quantisation parameter.')
+    if positive and np.any(values <= 0.):
+        raise ValueError('`lambdas` holds a value that is not above 0, with `rdoq`.')
     return (ctypes.c_double * nb_qps)(*values)
 
 
-def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoothing=0, sign_data_hiding=False, lambdas=None, device=None):
+def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoothing=0, sign_data_hiding=False, lambdas=None, device=None,
+            rdoq=False):
     """HM's second intra pass as include/pnn_hip.h defines it ("the second intra pass"): per block and QP the RD choice among the
     first-pass candidates (mode_hads_*'s list with the candidate prediction competing as 35) and the candidate itself, appended if the
     list lacks it.  numpy uint8 arrays: patterns [n, h, w'], targets and candidate_predictions [n, w, w]; qps: 1 to 8 integers in
@@ -463,7 +475,9 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     Returns {'candidates': uint8 [n, K + 1] (the slots' modes, 255 = unused), 'costs': float64 [nb_qps, n, K + 1] (J = D + lambda R, inf in
     an unused slot), 'modes', 'slots': uint8 [nb_qps, n] (the winner), 'best_costs': float64, 'sses': uint32 (the winner's sse_recon),
     'rates': uint64 (its rate in 2^-15 bit), 'rate_bits': float64 (the same in bits), 'psnrs_recon': float64 (psnrs_from_sses of
-    'sses'), each [nb_qps, n], and 'lambdas': float64 [nb_qps], the values used}."""
+    'sses'), each [nb_qps, n], and 'lambdas': float64 [nb_qps], the values used}.
+    rdoq=True (the option of pnn_rd_pass_rdoq_host / _device, which every call here goes to, with 0 when off): every candidate is coded
+    with HM's RDOQ under the lambda that decides, which must then be > 0.  Same keys.  With False nothing changes."""
     smoothing = _check_smoothing(reference_smoothing)
     qps = _check_qps(qps)
     arrays = (intra_patterns, targets, candidate_predictions)
@@ -474,14 +488,14 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     w, nq = targets.shape[1], len(qps)
     n = _check_mode_hads_arguments(intra_patterns, targets, w, candidate_predictions)
     patterns, targets, candidate = (np.ascontiguousarray(a) for a in arrays)
-    c_qps, c_lambdas = (ctypes.c_int * nq)(*qps), _check_lambdas(lambdas, nq)
-    flag = int(bool(sign_data_hiding))
+    flag, option = int(bool(sign_data_hiding)), int(bool(rdoq))
+    c_qps, c_lambdas = (ctypes.c_int * nq)(*qps), _check_lambdas(lambdas, nq, positive=bool(option))
     shapes = rd_pass_shapes(n, nq, w)
     L = _lib.lib()
     if device is None or n == 0:                          # (no block: nothing to launch, the empty arrays)
         outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
-        rc = L.pnn_rd_pass_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
-                                smoothing, c_qps, nq, c_lambdas, flag, *[o.ctypes.data for o in outs])
+        rc = L.pnn_rd_pass_rdoq_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
+                                     smoothing, c_qps, nq, c_lambdas, flag, option, *[o.ctypes.data for o in outs])
         if rc != 0:
             raise ValueError('pnn_rd_pass_host refused the arguments (patterns %dx%d, width %d).' % (patterns.shape[1], patterns.shape[2], w))
     else:
@@ -494,9 +508,10 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
         d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_rd_pass_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(), n,
-                                            d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, *[o.data_ptr() for o in d_outs],
-                                            d_ws.data_ptr(), nb_bytes, ctypes.c_void_p(stream.cuda_stream)), _context(device))
+            _lib.check(L.pnn_rd_pass_rdoq_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
+                                                 n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option,
+                                                 *[o.data_ptr() for o in d_outs], d_ws.data_ptr(), nb_bytes,
+                                                 ctypes.c_void_p(stream.cuda_stream)), _context(device))
         outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, RD_PASS_OUTPUTS, shapes)]   # (waits)
     result = {name: out for (name, _), out in zip(RD_PASS_OUTPUTS, outs)}
     result['rate_bits'] = result['rates'].astype(np.float64) / 32768.
@@ -550,6 +565,31 @@ def sign_hide_levels(levels, coeffs, delta_u, scan):
     if rc != 0:
         raise ValueError('pnn_sign_hide_unit_host refused the arguments (T %d, scan %s).' % (hidden.shape[0], scan))
     return hidden
+
+
+def rdoq_unit(coeffs, scan, qp, lam=None, cbf_ctx=1, sign_data_hiding=False):
+    """HM's TComTrQuant::xRateDistOptQuant on ONE transform unit (pnn_rdoq_unit_host; include/pnn_hip.h, "rate-distortion optimised
+    quantisation"): (levels int32 [T, T], uiAbsSum int) of the coefficients -- an integer [T, T] array, T in {4, 8, 16, 32}, each in
+    [-32768, 32767] -- under scan 0 / 'diagonal', 1 / 'horizontal' or 2 / 'vertical' (diagonal only at T = 16 and 32) at QP `qp`,
+    lambda `lam` (None: hm_intra_lambda(qp); else finite and > 0) and cbf context `cbf_ctx` (0 or 1); sign_data_hiding=True adds RDOQ's
+    own hiding."""
+    (qp,) = _check_qps((qp,))
+    coeffs = _square_integer_array(coeffs, 'coeffs')
+    if coeffs.min() < -32768 or coeffs.max() > 32767:
+        raise ValueError('`coeffs` has a value outside [-32768, 32767].')
+    scan = _check_scan(scan)
+    lam = hm_intra_lambda(qp) if lam is None else float(lam)
+    if not (np.isfinite(lam) and lam > 0.):
+        raise ValueError('`lam` is not finite and above 0.')
+    if cbf_ctx not in (0, 1):
+        raise ValueError('`cbf_ctx` is not 0 or 1.')
+    coeffs = np.ascontiguousarray(coeffs.astype(np.int32))
+    levels, abs_sum = np.zeros(coeffs.shape, np.int32), ctypes.c_int32(0)
+    rc = _lib.lib().pnn_rdoq_unit_host(coeffs.ctypes.data, coeffs.shape[0], int(scan), qp, lam, int(cbf_ctx), int(bool(sign_data_hiding)),
+                                       levels.ctypes.data, ctypes.byref(abs_sum))
+    if rc != 0:
+        raise ValueError('pnn_rdoq_unit_host refused the arguments (T %d, scan %s, QP %d).' % (coeffs.shape[0], scan, qp))
+    return levels, int(abs_sum.value)
 
 
 def cabac_rate_of_levels(levels, scan, qp, sign_data_hiding=False):

@@ -507,7 +507,7 @@ int pnn_trquant_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, co
  * not.  Unit: 2^-15 bit, uint64.  Luma, intra, 8-bit video, maxLog2TrDynamicRange 15; sign-data hiding (OFF in these entries, a flag
  * of the next group's), transform skip, transquant bypass, extended precision, persistent Rice adaptation and CABAC bypass alignment
  * are all OFF.  NOT COUNTED: cbf_luma (its context
- * depends on a transform tree that does not exist here), mode bits; no RDOQ.  No lambda here either: these entries report bits; the
+ * depends on a transform tree that does not exist here), mode bits; RDOQ is an option of its own group below.  No lambda here either: these entries report bits; the
  * lambda and the cost D + lambda R over them are the second intra pass's, the last group of evaluator entries below.
  *   Units.  The transform units of the entries above: T = width up to 32; at width 64 the four 32 x 32 quadrants, each coded as a unit
  *     of its own (all contexts at their initial states again), bits added.  A unit whose levels are all zero costs 0.
@@ -538,7 +538,7 @@ int pnn_trquant_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, co
  * Pinned to HM: the tables and context-selection functions piece by piece (tests/golden/hm_cabac_rate.npz); the whole of the above --
  * levels, scan of the mode, order of the bins, bits -- to HM's own transformNxN / getCoefScanIdx / codeCoeffNxN / invTransformNxN on
  * whole units (tests/golden/hm_unit_coding.npz), which host twin and kernel are each compared with.  Not pinned: cbf_luma, mode bits,
- * the running contexts of a slice, RDOQ.
+ * the running contexts of a slice.  (RDOQ: its own group below, tests/golden/hm_rdoq.npz.)
  *
  * pnn_trquant_host with the rate: modes NULL or uint8 [n], each in [0, 34] (0 planar, 1 DC, 2 .. 34 angular); rate NULL or uint64
  * [nb_qps][n].  Every other argument and refusal as there; also PNN_E_ARG for a mode above 34, for modes without rate, and `every
@@ -560,7 +560,7 @@ int pnn_trquant_rate_device(pnn_ctx* ctx, int width, const uint8_t* d_prediction
 
 /* With SignHideFlag 1 (HM's default) and RDOQ 0, xQuant hands every unit to TComTrQuant::signBitHidingHDQ, which reads the unit's
  * coefficients, its levels, the rounding remainders deltaU and the scan -- no context model, no lambda, no bit estimate (only the
- * variant inside xRateDistOptQuant needs those: it stays out, with RDOQ).  The entries below are the ones above with a flag
+ * variant inside xRateDistOptQuant needs those: it comes with RDOQ, in its own group below).  The entries below are the ones above with a flag
  * sign_data_hiding; with the flag 0 they ARE the ones above.  Everything of the two groups above holds unless changed here.
  *   Terms.  A group is a 4 x 4 coefficient group; `scan` is the unit's grouped scan as above (from the block's intra mode; diagonal
  *     without a mode array, hence for the PNN: this project's definition); position n = 0 .. 15 of group c is block position
@@ -643,7 +643,7 @@ int pnn_trquant_sdh_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions
  *   Winner.  Slots 0 .. K in order under a strict <, starting from +inf: of equal costs the earlier slot wins, so an appended 35 loses
  *     every tie.  Where no cost is below +inf (a caller's lambda so large that every lambda R overflows) there is no winner: mode and
  *     slot 255, cost +inf, sse and rate 0.
- * STILL LEFT OUT: mode bits, cbf_luma and split flags; RDOQ (campaigns run RDOQ 1 -- this is HM's pass with RDOQ 0); transform skip;
+ * STILL LEFT OUT: mode bits, cbf_luma and split flags; transform skip (RDOQ, which campaigns run, is the option of the next group);
  * the transform quadtree (one unit per block, four quadrants at width 64, as in the transform-coding group); chroma; and the contexts
  * start cold for every candidate, as in the rate group.
  *
@@ -687,6 +687,110 @@ int pnn_rd_pass_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_c
                                      const double* lambdas, int sign_data_hiding, uint8_t* d_cand_modes, double* d_cand_costs,
                                      uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
                                      uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- rate-distortion optimised quantisation: HM's quantiser with RDOQ 1 -------------------------------- */
+
+/* Every group above is HM with RDOQ 0; the reference's configurations and campaigns run RDOQ 1, where TComTrQuant::xRateDistOptQuant
+ * (TComTrQuant.cpp 2119-2661 of HM-16.15) picks every level by distortion + lambda bits.  The entries below are the transform-coding
+ * and second-pass entries with an option rdoq; with rdoq 0 they ARE those entries.  Settings as above: luma, intra, I slice, 8 bit,
+ * maxLog2TrDynamicRange 15, flat quantisation, no transform skip, extended precision, persistent Rice adaptation or adaptive QP
+ * selection, 32-bit Intermediate_Int.  The definition lives in csrc/pnn_rdoq.h, whose lines host and device both compile.
+ *   Bit estimates.  TEncSbac::estBit's tables for luma from the state a slice of the QP STARTS with -- the state the rate group codes
+ *     every unit from; no state moves during RDOQ.  bits(i, b) = entropyBits[initial state of context i ^ b]:
+ *       significantBits[k][b] = bits(sig context k, b), k as in the rate group (0 DC, 1 .. 8 at T = 4, 9 .. / 15 .. at T = 8, 21 .. above);
+ *       m_greaterOneBits[k][b], k = 4 set + c1;  m_levelAbsBits[k][b], k = set;  significantCoeffGroupBits[k][b], k = 0, 1;
+ *       lastXBits[g] = sum_{k < g} bits(lastX context offset + (k >> shift), 1) + (g < top ? bits(.. (g >> shift), 0) : 0), g = 0 .. top
+ *         = 2 L - 1, the group of position T - 1; lastYBits alike; xGetRateLast adds 32768 ((g - 2) >> 1) per coordinate with g > 3;
+ *       blockCbpBits[c][b] = bits(cbf context c, b), initial values 111 (c = 0) and 141 (c = 1).
+ *   cbf context.  getCtxQtCbf: 1 at transform depth 0, else 0.  Width 8, 16, 32 (one unit of a 2N x 2N coding unit): 1.  Width 4 (HM
+ *     reaches 4 x 4 only as N x N): 0.  The four quadrants at width 64: 0, THIS PROJECT'S DEFINITION, as the quadrants themselves are.
+ *     The cbf bits enter RDOQ's decision only; the reported rate stays codeCoeffNxN's on the final levels, without cbf.
+ *   Lambda.  The second pass's: pnn_hm_intra_lambda(QP) or the caller's lambdas [nb_qps]; with rdoq each must be finite and > 0.
+ *   Per-QP constants, made on the HOST in double and handed to the kernel as they are: lambda; errScale = 2^15 * 2^(-2 ts) / scale /
+ *     scale / 1 (setErrScaleCoeff's order; ts = 7 - L); rdFactor = (int64)(inv * inv * (1 << 2 per) / lambda / 16 / 1 + 0.5),
+ *     saturated at 2^52 (lambda below about 5e-9; HM's conversion is undefined once the value leaves 64 bits: this project's definition).
+ *   Arithmetic.  Every cost is an IEEE double, each operation rounded once, in HM's order, never contracted into a fused multiply-add.
+ *   Per position (reverse scan; i = scan position, n = i % 16, group g = i / 16).  lLevelDouble = min(|C| scale, INT32_MAX - (1 <<
+ *     (qbits - 1))); maxAbs = min(32767, (lLevelDouble + (1 << (qbits - 1))) >> qbits); cost0[i] = (double) lLevelDouble squared times
+ *     errScale, added to blockUncoded.  In front of the first position with maxAbs > 0 (the LAST position, whose group is the last
+ *     group) a position adds cost0 to base and its level is 0.  From there on xGetCodedLevel: at the last position the candidates are
+ *     maxAbs and, if maxAbs > 1, maxAbs - 1, without a significance cost; elsewhere, with the sig context of the rate group (pattern from
+ *     the groups RDOQ has left coded), level 0 at cost0 + lambda sig[0] competes when maxAbs < 3, and a level a costs err^2 errScale +
+ *     lambda ICRate(a) + lambda sig[1], err = lLevelDouble - (a << qbits); the least cost under a strict <, maxAbs tried first.
+ *     ICRate is xGetICRate: 32768 for the sign, plus, with base = (c1Idx < 8 ? 2 + (c2Idx < 1) : 1): for a >= base the bypass bins of
+ *     a - base at the Rice parameter (the rate group's formula) and, while c1Idx < 8, greaterOne[ctx][1] and, while c2Idx < 1,
+ *     levelAbs[set][1]; a == 1: greaterOne[ctx][0]; a == 2: greaterOne[ctx][1] + levelAbs[set][0].  Recorded per position: cost, the
+ *     significance part costSig, deltaU = (lLevelDouble - (level << qbits)) >> (qbits - 8), rateIncUp / rateIncDown = ICRate(level +- 1)
+ *     - ICRate(level) (level 0: rateIncUp = greaterOne[ctx][0]), sigRateDelta = sig[1] - sig[0] (0 at the last position).  Then the
+ *     chain: Rice + 1 up to 4 after a level >= base above 3 << Rice; c1Idx + 1 per level; a level > 1 sets c1 = 0, c2Idx + 1; a level 1
+ *     takes c1 up to 3; at n = 0 of a group other than the first, set = (g - 1 > 0 ? 2 : 0) + (c1 == 0) and c1, c1Idx, c2Idx, Rice start
+ *     again.
+ *   Per group, once the last position is passed (group 0 always counts as coded).  Without a level: base += lambda group[ctx][0] - the
+ *     group's costSig sum.  With levels, below the last group: if no level lies above n = 0, costSig of n = 0 leaves base and the sum
+ *     (the flag would be inferred); zero = base + lambda group[ctx][0] + sum cost0 - sum (cost - costSig) - sum costSig over the
+ *     positions with a level (costSig over all), base += lambda group[ctx][1]; if zero < base the group is zeroed: base = zero, its
+ *     levels 0, their cost = cost0, costSig = 0.  ctx = right or lower group coded.
+ *   Best last position.  best = blockUncoded + lambda cbf[c][0]; base += lambda cbf[c][1].  From the last group down: base -= the
+ *     group's flag cost; in a coded group, from n = 15 (from the last position) down: a zero level takes its costSig from base; a level
+ *     gives total = base + lambda RateLast(x, y) - costSig (x and y swapped under the vertical scan), the new best under a strict <;
+ *     a level > 1 ends the search; a level 1 leaves: base = base - cost + cost0.  Levels from the best last position on become 0 (all
+ *     of them when nothing beat "nothing coded"); the others get the coefficient's sign.  sum_abs_levels = HM's uiAbsSum = the sum of
+ *     the magnitudes kept here, BEFORE the hiding.
+ *   Sign-data hiding with rdoq is RDOQ's own (lines 2530-2660), not signBitHidingHDQ.  Groups, first / last, the last group, the
+ *     parity test and the candidates' range as in the hiding group above; costs are int64:
+ *       nonzero level:  up = rdFactor (-deltaU) + rateIncUp;  down = rdFactor deltaU + rateIncDown - (|level| == 1 ? sigRateDelta : 0),
+ *                       less 4 << 15 in the last group at n == last with |level| == 1;  up < down: cost up, change +1;  else change
+ *                       -1 at cost down, not allowed when n == first and |level| == 1
+ *       zero level:     cost rdFactor (-|deltaU|) + (1 << 15) + rateIncUp + sigRateDelta, change +1; not allowed when n < first and
+ *                       the coefficient's sign differs from signbit
+ *     deltaU and the rate increments are those of the level the WALK chose (a zeroed group keeps them).  Strict < while n descends:
+ *     the highest n wins a tie.  HM's guard uiAbsSum >= 2 never decides here either: a group that hides holds two levels.
+ *   Downstream nothing changes: nb_nonzero, dequantisation, inverse transform, reconstruction, sse_recon and the rate use the final
+ *     levels.  Width 64 runs each quadrant as a unit of its own.
+ *   Pinned to HM's own transformNxN with RDOQ on, est-bits tables included (tests/golden/hm_rdoq.npz).
+ *
+ * pnn_trquant_sdh_host with the option: rdoq 0 is that entry (lambdas is not read).  Nonzero: as above; modes are then allowed
+ * without rate or hiding.  PNN_E_ARG also for a lambdas entry that is not finite or not > 0. */
+int pnn_trquant_rdoq_host(const uint8_t* predictions, const uint8_t* targets, int width, int n, const uint8_t* modes, const int* qps,
+                          int nb_qps, uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon, uint64_t* rate,
+                          int sign_data_hiding, int rdoq, const double* lambdas);
+/* pnn_trquant_stages_sdh_host with the option, under lambda and cbf context cbf_ctx (0 or 1, whatever the width): levels = what RDOQ
+ * leaves in front of its hiding, levels_hidden = after it, delta_u stays 0.  With rdoq 0 lambda and cbf_ctx are not read. */
+int pnn_trquant_stages_rdoq_host(const uint8_t* prediction, const uint8_t* target, int width, int qp, int scan, int sign_data_hiding,
+                                 int rdoq, double lambda, int cbf_ctx, int32_t* coeffs, int32_t* levels, int32_t* delta_u,
+                                 int32_t* levels_hidden, int32_t* dequant, int32_t* residual);
+/* xRateDistOptQuant on ONE unit: coeffs int32 [t][t], each in [-32768, 32767], t in {4, 8, 16, 32}, scan 0, 1 or 2 (0 only at t = 16
+ * and 32), qp in [0, 51], lambda finite and > 0, cbf_ctx 0 or 1 -> levels int32 [t][t] and *abs_sum (NULL or HM's uiAbsSum).
+ * PNN_E_ARG + a line on stderr otherwise.  Pure host code. */
+int pnn_rdoq_unit_host(const int32_t* coeffs, int t, int scan, int qp, double lambda, int cbf_ctx, int sign_data_hiding, int32_t* levels,
+                       int32_t* abs_sum);
+/* The bit estimates of unit size t at QP qp, 184 int32: [80][2] per context of the rate group's numbering (last-position contexts:
+ * the single bins), lastXBits [10], lastYBits [10] (entries above 2 log2 t - 1 are 0), blockCbpBits [2][2]. */
+int pnn_rdoq_est_bits_host(int t, int qp, int32_t* est_bits);
+/* pnn_trquant_rdoq_host on the GPU, in ONE launch; bit-identical to the host twin.  With rdoq 0 it launches the kernels
+ * pnn_trquant_sdh_device launched before, unchanged.  lambdas is a HOST array.  PNN_E_ARG before the launch for everything the host twin
+ * refuses but the mode values. */
+int pnn_trquant_rdoq_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
+                            const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
+                            uint8_t* d_recon, uint64_t* d_rate, int sign_data_hiding, int rdoq, const double* lambdas, void* stream);
+/* The second intra pass with the option: the lambda that decides also quantises, the coding of the K + 1 slots is the RDOQ form.  rdoq
+ * 0: the entries above.  Nonzero: PNN_E_ARG also for a lambdas entry that is not > 0.  The workspace is that of
+ * pnn_rd_pass_workspace_bytes. */
+int pnn_rd_pass_rdoq_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                          const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                          int rdoq, uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode, uint8_t* best_slot, double* best_cost,
+                          uint32_t* best_sse, uint64_t* best_rate);
+int pnn_rd_pass_rdoq_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                            const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                            int rdoq, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot,
+                            double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes,
+                            void* stream);
+int pnn_rd_pass_rdoq_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                          int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                          int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                          const double* lambdas, int sign_data_hiding, int rdoq, uint8_t* d_cand_modes, double* d_cand_costs,
+                                          uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                                          uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
