@@ -122,6 +122,16 @@ SIGNATURES = {
                                 [vp] * 8 + [ctypes.c_size_t, vp]),
     "pnn_rd_pass_rdoq_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(ci), ci,
                                                    ctypes.POINTER(ctypes.c_double), ci, ci] + [vp] * 8 + [ctypes.c_size_t, vp]),
+    "pnn_rd_pass_slot_count": (ci, [ci, ci]),
+    "pnn_intra_mode_signal_host": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vp]),
+    "pnn_first_pass_signal_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp, vp]),
+    "pnn_rd_pass_signal_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp] +
+                                [vp] * 9),
+    "pnn_rd_pass_signal_workspace_bytes": (ctypes.c_size_t, [ci, ci, ci, ci]),
+    "pnn_rd_pass_signal_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci,
+                                       vp, vp] + [vp] * 10 + [ctypes.c_size_t, vp]),
+    "pnn_rd_pass_signal_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(ci), ci,
+                                                     ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp] + [vp] * 10 + [ctypes.c_size_t, vp]),
     "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

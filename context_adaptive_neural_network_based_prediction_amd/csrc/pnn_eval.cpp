@@ -7,6 +7,7 @@
 #include "pnn_ctx.h"
 
 #include <algorithm>
+#include <cmath>
 
 using namespace pnn;
 
@@ -230,6 +231,117 @@ int rd_pass_launches(pnn_ctx* c, int width, const uint8_t* patterns, int ph, int
     d.best_rate = d_best_rate;
     HIPCHK(c, launch_rd_decide(d, s));
     c->stat_launches += 4;
+    return PNN_OK;
+}
+
+// The caller's scratch of the second pass with mode signalling, n (K + 3) slots of ONE QP at a time: per-slot rate, SSE and count of
+// nonzero levels, the slots' predictions and replicated targets, every QP's slot modes [nb_qps][n][K + 3], the Hadamard costs of the
+// 35 modes and of the candidate; every section at a multiple of 256 bytes.
+struct RdSignalWorkspace {
+    uint64_t* rate; uint32_t* sse; uint32_t* nonzero; uint8_t* pred; uint8_t* targets; uint8_t* slot_modes; uint32_t* mode_hads; uint32_t* cand_hads;
+    size_t bytes;
+};
+RdSignalWorkspace rd_signal_workspace(void* base, int width, long n, int nb_qps)
+{
+    const size_t slots = (size_t)n * (hevc_first_pass_list_size(width) + msig::kExtraSlots), w2 = (size_t)width * width;
+    const size_t units = slots * (width == 64 ? 4 : 1);       // at width 64 every slot is coded as its four quadrants
+    size_t at = 0;
+    const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
+    RdSignalWorkspace ws;
+    ws.rate = (uint64_t*)take(units * 8);
+    ws.sse = (uint32_t*)take(units * 4);
+    ws.nonzero = (uint32_t*)take(units * 4);
+    ws.pred = take(slots * w2);
+    ws.targets = take(slots * w2);
+    ws.slot_modes = take(slots * nb_qps);
+    ws.mode_hads = (uint32_t*)take((size_t)n * 35 * 4);
+    ws.cand_hads = (uint32_t*)take((size_t)n * 4);
+    ws.bytes = at;
+    return ws;
+}
+
+// what both forms with signalling check behind their blocks: the width (no quadrants), candidate, QPs, lambdas, outputs, scratch and --
+// read back once, the call waits for the stream -- the neighbours' modes
+int check_rd_pass_signal(pnn_ctx* c, int width, int n, const uint8_t* d_cand_pred, const int* qps, int nb_qps, const double* lambdas, int rdoq,
+                         bool any_output, const uint8_t* d_left, const uint8_t* d_above, const void* d_workspace, size_t workspace_bytes, hipStream_t s)
+{
+    if (n > 0 && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_pred is NULL");
+    if ((long)n * (hevc_first_pass_list_size(width) + msig::kExtraSlots) * (width == 64 ? 4 : 1) > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 candidate slots");
+    if (!trquant::qps_ok(qps, nb_qps)) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d integers in [0, %d]", trquant::kMaxQps, trquant::kMaxQp);
+    for (int i = 0; lambdas && i < nb_qps; i++)
+        if (!(lambdas[i] >= 0. && lambdas[i] <= 1.7976931348623157e308)) return fail(c, PNN_E_ARG, "lambda %d is negative or not finite", i);
+    if (const int rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps)) return rc;
+    if (const int rc = check_some_output(c, any_output)) return rc;
+    if (n == 0) return PNN_OK;
+    const size_t need = rd_signal_workspace(nullptr, width, n, nb_qps).bytes;
+    if (!d_workspace || (uintptr_t)d_workspace % 8) return fail(c, PNN_E_ARG, "d_workspace is NULL or not aligned to 8 bytes");
+    if (workspace_bytes < need)
+        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_rd_pass_signal_workspace_bytes asks for %zu", workspace_bytes, need);
+    if (!d_left && !d_above) return PNN_OK;
+    std::vector<uint8_t> modes((size_t)n * 2, (uint8_t)msig::kNoNeighbour);
+    {
+        PNN_UNSAFE_CALLS_GUARD;                               // both arrays, then ONE wait
+        if (d_left) HIPCHK(c, hipMemcpyAsync(modes.data(), d_left, (size_t)n, hipMemcpyDeviceToHost, s));
+        if (d_above) HIPCHK(c, hipMemcpyAsync(modes.data() + n, d_above, (size_t)n, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    for (long i = 0; i < 2L * n; i++)
+        if (!msig::neighbour_ok(modes[i], 1))
+            return fail(c, PNN_E_ARG, "%s neighbour mode %d of block %ld is not 0 .. 35 or 255", i < n ? "left" : "above", modes[i], i % n);
+    return PNN_OK;
+}
+
+// The launches of the second pass with signalling, either form, everything checked: the Hadamard costs (the unchanged first-pass
+// kernel, asked for no list), the lists and slots of every QP, then per QP the slots' predictions, their coding -- the launch of
+// pnn_trquant_rdoq_device with that one QP -- and the decision, all on the same scratch in stream order: 2 + 3 nb_qps launches.
+int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic,
+                            const uint8_t* pic_targets, long n, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                            const double* lambdas, int sign_data_hiding, int rdoq, const uint8_t* d_left, const uint8_t* d_above,
+                            uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
+                            uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
+                            hipStream_t s)
+{
+    const RdSignalWorkspace ws = rd_signal_workspace(d_workspace, width, n, nb_qps);
+    const int slots = hevc_first_pass_list_size(width) + msig::kExtraSlots;
+    const HevcModeHadsParams h = mode_hads_params(patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing, d_cand_pred, ws.mode_hads,
+                                                  ws.cand_hads, nullptr, nullptr);
+    HIPCHK(c, launch_hevc_mode_hads(h, s));
+    SignalListParams l;
+    l.mode_hads = ws.mode_hads; l.cand_hads = ws.cand_hads; l.left = d_left; l.above = d_above; l.N = (int)n; l.w = width; l.nb_qps = nb_qps;
+    double lambda[trquant::kMaxQps];
+    for (int i = 0; i < trquant::kMaxQps; i++) {
+        const int qp = qps[i < nb_qps ? i : 0];
+        lambda[i] = i >= nb_qps ? 0. : lambdas ? lambdas[i] : pnn_hm_intra_lambda(qp);
+        l.bits[i] = msig::flag_bits(qp);
+        l.sqrt_lambda[i] = std::sqrt(lambda[i]);                                  // TComRdCost::setLambda
+    }
+    l.list_costs = d_first_pass_costs; l.slot_modes = d_cand_modes ? d_cand_modes : ws.slot_modes;
+    HIPCHK(c, launch_signal_list(l, s));
+    for (int qi = 0; qi < nb_qps; qi++) {
+        const size_t at = (size_t)qi * n;
+        const uint8_t* slot_modes = l.slot_modes + at * slots;
+        RdCandidatesParams r;
+        set_blocks(r, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
+        r.cand_pred = d_cand_pred; r.list_modes = slot_modes; r.cand_modes = nullptr; r.slot_pred = ws.pred; r.slot_targets = ws.targets;
+        HIPCHK(c, launch_rd_candidates_slots(r, s));
+        // width 64: the slots lie there quadrant by quadrant, 4 n (K + 3) blocks of 32 x 32 under the diagonal scan, each a unit at
+        // transform depth 1 (cbf context 0) -- what the w = 64 instantiation codes, with a count of levels per quadrant
+        const bool quadrants = width == 64;
+        TrQuantParams t = trquant_params(quadrants ? 32 : width, ws.pred, ws.targets, (int)(n * slots * (quadrants ? 4 : 1)),
+                                         quadrants ? nullptr : slot_modes, qps + qi, 1, sign_data_hiding, rdoq, rdoq ? lambda + qi : nullptr);
+        if (quadrants) t.cbf_ctx = 0;
+        t.sse = ws.sse; t.nonzero = ws.nonzero; t.rate = ws.rate;
+        HIPCHK(c, launch_trquant(t, s));
+        RdDecideSignalParams d;
+        d.sse = ws.sse; d.rate = ws.rate; d.nonzero = ws.nonzero; d.slot_modes = slot_modes; d.left = d_left; d.above = d_above;
+        d.N = (int)n; d.w = width; d.cbf_ctx = msig::cbf_context(width); d.lambda = lambda[qi]; d.bits = l.bits[qi];
+        d.cand_costs = d_cand_costs ? d_cand_costs + at * slots : nullptr;
+        d.best_mode = d_best_mode ? d_best_mode + at : nullptr; d.best_slot = d_best_slot ? d_best_slot + at : nullptr;
+        d.best_cost = d_best_cost ? d_best_cost + at : nullptr; d.best_sse = d_best_sse ? d_best_sse + at : nullptr;
+        d.best_rate = d_best_rate ? d_best_rate + at : nullptr; d.best_side_rate = d_best_side_rate ? d_best_side_rate + at : nullptr;
+        HIPCHK(c, launch_rd_decide_signal(d, s));
+    }
+    c->stat_launches += 2 + 3 * nb_qps;
     return PNN_OK;
 }
 
@@ -603,6 +715,78 @@ int pnn_rd_pass_rdoq_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* 
     return rd_pass_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
                             smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost,
                             d_best_sse, d_best_rate, d_workspace, s);
+}
+
+size_t pnn_rd_pass_signal_workspace_bytes(int width, int n, int nb_qps, int signalling)
+{
+    if (!signalling) return pnn_rd_pass_workspace_bytes(width, n, nb_qps);
+    if (width_index(width) < 0 || n < 0 || nb_qps < 1 || nb_qps > trquant::kMaxQps) return 0;
+    return rd_signal_workspace(nullptr, width, n, nb_qps).bytes;
+}
+
+int pnn_rd_pass_signal_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                              const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                              int rdoq, int signalling, const uint8_t* d_left_modes, const uint8_t* d_above_modes, uint8_t* d_cand_modes,
+                              double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                              uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
+                              size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (!signalling) {
+        if (d_first_pass_costs || d_best_side_rate) return fail(c, PNN_E_ARG, "d_first_pass_costs or d_best_side_rate without signalling");
+        return pnn_rd_pass_rdoq_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, d_cand_pred, smoothing, qps, nb_qps, lambdas,
+                                       sign_data_hiding, rdoq, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
+                                       d_workspace, workspace_bytes, stream);
+    }
+    int rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing))) return rc;
+    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = check_rd_pass_signal(c, width, n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
+                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
+                                       d_first_pass_costs || d_best_side_rate,
+                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s))) return rc;
+    if (n == 0) return PNN_OK;
+    reset_stats(c);
+    return rd_pass_signal_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
+                                   lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot,
+                                   d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s);
+}
+
+int pnn_rd_pass_signal_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                            int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                            int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                            const double* lambdas, int sign_data_hiding, int rdoq, int signalling, const uint8_t* d_left_modes,
+                                            const uint8_t* d_above_modes, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode,
+                                            uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate,
+                                            double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace, size_t workspace_bytes,
+                                            void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (!signalling) {
+        if (d_first_pass_costs || d_best_side_rate) return fail(c, PNN_E_ARG, "d_first_pass_costs or d_best_side_rate without signalling");
+        return pnn_rd_pass_rdoq_picture_pairs_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols,
+                                                     positions, mask_w, mask_h, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq,
+                                                     d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
+                                                     d_workspace, workspace_bytes, stream);
+    }
+    int rc;
+    long n;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+        (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n))) return rc;
+    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = check_rd_pass_signal(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
+                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
+                                       d_first_pass_costs || d_best_side_rate,
+                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s))) return rc;
+    if (n == 0) return PNN_OK;
+    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
+    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
+    reset_stats(c);
+    return rd_pass_signal_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
+                                   smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs,
+                                   d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s);
 }
 
 int pnn_score_f32_device(pnn_ctx* c, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,

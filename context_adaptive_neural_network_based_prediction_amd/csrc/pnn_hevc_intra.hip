@@ -413,12 +413,14 @@ __global__ __launch_bounds__(kThreads) void hevc_mode_hads_kernel(const HevcMode
 // consecutive bytes.
 constexpr int kRdThreads = 256;
 
-template <int W, bool PIC, bool SMOOTH>
+// SLOTS: list_modes holds the block's K + 3 slot modes as signal_list_kernel left them, [N][K + 3], and the
+// kernel derives nothing: it predicts them (cand_modes is not written).  Everything else is as it stands.
+template <int W, bool PIC, bool SMOOTH, bool SLOTS = false>
 __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandidatesParams p)
 {
     static_assert(!SMOOTH || W == 8 || W == 16 || W == 32, "no mode smooths at w = 4 and 64");
     constexpr int G = W >= 32 ? 1 : 1024 / (W * W);                // blocks per workgroup: trquant_kernel's
-    constexpr int K = W <= 8 ? 8 : 3, K1 = K + 1;                  // list entries, slots
+    constexpr int K = W <= 8 ? 8 : 3, K1 = SLOTS ? K + msig::kExtraSlots : K + 1;   // list entries, slots
     constexpr int RS = 4 * W + 1, TS = W * W + 4;                  // LDS strides, those of stage_blocks
     __shared__ int ref[G * RS];
     __shared__ int ref_s[SMOOTH ? G * RS : 1];
@@ -433,7 +435,13 @@ __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandi
     __syncthreads();
     stage_dc<W, G>(ref, dcv, tid);
     if (SMOOTH) stage_smoothed<W, G, kRdThreads>(ref, ref_s, strong, p.smoothing == 2, tid);
-    if (tid < G && blk0 + tid < p.N) {
+    if constexpr (SLOTS) {
+        for (int i = tid; i < G * K1; i += kRdThreads)
+            if (blk0 + i / K1 < p.N) {
+                const int m = p.list_modes[blk0 * K1 + i];
+                slot_mode[i] = m > 35 ? kRdUnusedSlot : m;
+            }
+    } else if (tid < G && blk0 + tid < p.N) {
         bool listed = false;
 #pragma unroll
         for (int j = 0; j < K; j++) {
@@ -448,6 +456,27 @@ __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandi
     __syncthreads();
 
     const size_t out0 = (size_t)blk0 * K1 * W * W;
+    if constexpr (SLOTS && W == 64) {
+        // quadrant-major: each slot leaves as four 32 x 32 blocks, which the w = 32 transform launch codes as units of their own
+        // (a loop of its own, so that the one below stays the statements it was)
+        for (int i = tid; i < G * K1 * W * W; i += kRdThreads) {
+            const int g = i / (K1 * W * W), q = (i >> 10) & 3, r = i & 1023;
+            const int e = ((q >> 1) * 32 + (r >> 5)) * 64 + (q & 1) * 32 + (r & 31);
+            if (blk0 + g >= p.N) break;
+            const int m = slot_mode[g * K1 + i / (W * W) % K1];
+            const int t = tgt[g * TS + e];
+            int v = t;
+            if (m == 35) {
+                v = p.cand_pred[(size_t)(blk0 + g) * W * W + e];
+            } else if (m < 35) {
+                const int* rf = ref + g * RS + 2 * W;
+                v = mode_pixel<W>(rf, dcv[g], m, e / W, e % W);
+            }
+            p.slot_pred[out0 + i] = (uint8_t)v;
+            p.slot_targets[out0 + i] = (uint8_t)t;
+        }
+        return;
+    }
     for (int i = tid; i < G * K1 * W * W; i += kRdThreads) {
         const int g = i / (K1 * W * W), e = i % (W * W);
         if (blk0 + g >= p.N) break;
@@ -505,7 +534,135 @@ __global__ __launch_bounds__(kRdThreads) void rd_decide_kernel(const RdDecidePar
     if (p.best_rate) p.best_rate[i] = best_rate;
 }
 
+// The first pass with HM's mode-bit term, behind a launch of hevc_mode_hads_kernel that left the 35 + 1
+// Hadamard costs of every block on the device: one lane per (QP, block) derives the block's most probable modes, ranks the 36 costs
+// SATD + modeBits sqrt(lambda) into HM's list and appends the missing MPMs and 35 -- msig::list_and_slots, the lines the host twin
+// compiles.  The QPs' flag bits and sqrt(lambda) come ready in the argument block; a mode's bits are a few compares on the three MPMs,
+// so there is no table, and the list lives in registers (every index into it is a compile-time one).
+template <int K>
+__global__ __launch_bounds__(kRdThreads) void signal_list_kernel(const SignalListParams p)
+{
+    constexpr int S = K + msig::kExtraSlots;
+    const long i = (long)blockIdx.x * kRdThreads + threadIdx.x;
+    if (i >= (long)p.nb_qps * p.N) return;
+    const int qi = (int)(i / p.N);
+    const long b = i - (long)qi * p.N;
+    const msig::Mpm mpm = msig::derive_mpm(msig::neighbour_dir(p.left ? p.left[b] : msig::kNoNeighbour),
+                                           msig::neighbour_dir(p.above ? p.above[b] : msig::kNoNeighbour));
+    const uint32_t* hads = p.mode_hads + b * 35;
+    const uint32_t cand = p.cand_hads[b];
+    int lm[K], extra[msig::kExtraSlots];
+    double lc[K];
+    msig::list_and_slots<K>([&](int m) { return m < 35 ? hads[m] : cand; }, mpm, p.bits[qi], p.sqrt_lambda[qi], lm, lc, extra);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        if (p.list_costs) p.list_costs[(size_t)i * K + j] = lc[j];
+        p.slot_modes[(size_t)i * S + j] = (uint8_t)lm[j];
+    }
+#pragma unroll
+    for (int t = 0; t < msig::kExtraSlots; t++) p.slot_modes[(size_t)i * S + K + t] = (uint8_t)extra[t];
+}
+
+// rd_decide_kernel with the side bits, for the blocks of ONE QP (the slots are that QP's): J = D + lambda ((mode bits + cbf bin +
+// rate) >> 15), one shift over the sum as HM's counter does over one candidate; the cbf bin follows the slot's count of nonzero levels.
+__device__ inline double rd_cost_bits(uint32_t d, uint64_t whole_bits, double lambda)
+{
+#pragma clang fp contract(off)
+    const double bits = lambda * (double)whole_bits;
+    return (double)d + bits;
+}
+
+// Q: transform units per slot -- 1, or the 4 quadrants of a 64 x 64 block, each coded as a 32 x 32 block of its own: D and the rate
+// add up, and every quadrant pays its own cbf bin.
+template <int S, int Q = 1>
+__global__ __launch_bounds__(kRdThreads) void rd_decide_signal_kernel(const RdDecideSignalParams p)
+{
+    const long b = (long)blockIdx.x * kRdThreads + threadIdx.x;
+    if (b >= p.N) return;
+    const msig::Mpm mpm = msig::derive_mpm(msig::neighbour_dir(p.left ? p.left[b] : msig::kNoNeighbour),
+                                           msig::neighbour_dir(p.above ? p.above[b] : msig::kNoNeighbour));
+    const size_t slot0 = (size_t)b * S;
+    double best = __builtin_inf();
+    int best_slot = kRdUnusedSlot, best_mode = kRdUnusedSlot;
+    uint32_t best_sse = 0;
+    uint64_t best_rate = 0, best_side = 0;
+#pragma unroll
+    for (int s = 0; s < S; s++) {
+        const int m = p.slot_modes[slot0 + s];
+        uint32_t d = 0;
+        uint64_t r = 0, cbf = 0;
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            d += p.sse[(slot0 + s) * Q + q];
+            r += p.rate[(slot0 + s) * Q + q];
+            cbf += msig::side_frac_bits(0, p.bits, p.cbf_ctx, p.nonzero[(slot0 + s) * Q + q]);
+        }
+        uint64_t side = 0;
+        double j = __builtin_inf();
+        if (m != kRdUnusedSlot) {
+            side = msig::mode_frac_bits(m, mpm, p.bits, 1) + cbf;
+            j = rd_cost_bits(d, (side + r) >> 15, p.lambda);
+        }
+        if (p.cand_costs) p.cand_costs[slot0 + s] = j;
+        if (j < best) { best = j; best_slot = s; best_mode = m; best_sse = d; best_rate = r; best_side = side; }
+    }
+    if (p.best_mode) p.best_mode[b] = (uint8_t)best_mode;
+    if (p.best_slot) p.best_slot[b] = (uint8_t)best_slot;
+    if (p.best_cost) p.best_cost[b] = best;
+    if (p.best_sse) p.best_sse[b] = best_sse;
+    if (p.best_rate) p.best_rate[b] = best_rate;
+    if (p.best_side_rate) p.best_side_rate[b] = best_side;
+}
+
 }  // namespace
+
+hipError_t launch_signal_list(const SignalListParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    if (!p.mode_hads || !p.cand_hads || !p.slot_modes || p.nb_qps < 1 || p.nb_qps > trquant::kMaxQps) return hipErrorInvalidValue;
+    const long total = (long)p.nb_qps * p.N;
+    const dim3 grid((unsigned)((total + kRdThreads - 1) / kRdThreads)), block(kRdThreads);
+    if (p.w <= 8) hipLaunchKernelGGL((signal_list_kernel<8>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((signal_list_kernel<3>), grid, block, 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_rd_candidates_slots(const RdCandidatesParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    const int g = rd_candidates_blocks_per_workgroup(p.w);
+    const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kRdThreads);
+    const bool pic = p.patterns == nullptr;
+    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+    if (!p.cand_pred || !p.list_modes || !p.slot_pred || !p.slot_targets) return hipErrorInvalidValue;
+    if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
+#define PNN_RD_LAUNCH(W_, SMOOTH_) \
+    if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, true>), grid, block, 0, s, p); \
+    else hipLaunchKernelGGL((rd_candidates_kernel<W_, false, SMOOTH_, true>), grid, block, 0, s, p);
+#define PNN_RD_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_RD_LAUNCH(W_, true) } else { PNN_RD_LAUNCH(W_, false) }
+    switch (p.w) {                                     // (width 64 writes each slot as its four quadrants, 32 x 32 blocks)
+    case 4: PNN_RD_LAUNCH(4, false) break;
+    case 8: PNN_RD_LAUNCH_SMOOTH(8) break;
+    case 16: PNN_RD_LAUNCH_SMOOTH(16) break;
+    case 32: PNN_RD_LAUNCH_SMOOTH(32) break;
+    case 64: PNN_RD_LAUNCH(64, false) break;
+    default: return hipErrorInvalidValue;
+    }
+#undef PNN_RD_LAUNCH_SMOOTH
+#undef PNN_RD_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_rd_decide_signal(const RdDecideSignalParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    if (!p.sse || !p.rate || !p.nonzero || !p.slot_modes || p.cbf_ctx < 0 || p.cbf_ctx > 1) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((p.N + kRdThreads - 1) / kRdThreads)), block(kRdThreads);
+    if (p.w <= 8) hipLaunchKernelGGL((rd_decide_signal_kernel<8 + msig::kExtraSlots>), grid, block, 0, s, p);
+    else if (p.w == 64) hipLaunchKernelGGL((rd_decide_signal_kernel<3 + msig::kExtraSlots, 4>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((rd_decide_signal_kernel<3 + msig::kExtraSlots>), grid, block, 0, s, p);
+    return hipGetLastError();
+}
 
 int rd_candidates_blocks_per_workgroup(int w) { return w >= 32 ? 1 : 1024 / (w * w); }
 

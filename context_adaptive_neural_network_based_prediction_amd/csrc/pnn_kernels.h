@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "pnn_cabac_tables.h"
+#include "pnn_mode_signal.h"
 #include "pnn_rdoq.h"
 #include "pnn_trquant_tables.h"
 
@@ -321,6 +322,30 @@ struct RdDecideParams {
     double* cand_costs; uint8_t* best_mode; uint8_t* best_slot; double* best_cost; uint32_t* best_sse; uint64_t* best_rate;
 };
 hipError_t launch_rd_decide(const RdDecideParams& p, hipStream_t s);
+
+// The second pass with mode signalling (pnn_hevc_intra.hip; the definition is pnn_mode_signal.h).
+// The first pass with HM's mode-bit term: mode_hads [N][35] and cand_hads [N] as launch_hevc_mode_hads left them, left / above NULL
+// (no neighbour) or uint8 [N] (0 .. 35, 255), per QP the four contexts' bits and sqrt(lambda), made on the host.  Outputs: slot_modes
+// [nb_qps][N][K + 3] (the list, the missing MPMs, 35; 255 behind them), list_costs NULL or double [nb_qps][N][K].
+struct SignalListParams {
+    const uint32_t* mode_hads; const uint32_t* cand_hads; const uint8_t* left; const uint8_t* above; int N; int w; int nb_qps;
+    msig::FlagBits bits[trquant::kMaxQps]; double sqrt_lambda[trquant::kMaxQps];
+    double* list_costs; uint8_t* slot_modes;
+};
+hipError_t launch_signal_list(const SignalListParams& p, hipStream_t s);
+// launch_rd_candidates with list_modes = the slot modes of one QP, [N][K + 3]: they are predicted as they stand; cand_modes is not
+// written.  At width 64 slot_pred and slot_targets leave quadrant-major: [N][K + 3][4 quadrants][32][32].
+hipError_t launch_rd_candidates_slots(const RdCandidatesParams& p, hipStream_t s);
+// The decision of ONE QP over its N (K + 3) slots: sse, rate and nonzero [N (K + 3)] ([N (K + 3)][4] at width 64, per quadrant) of a
+// launch_trquant call with that one QP,
+// J = D + lambda ((mode bits + cbf bin + rate) >> 15).  Outputs, each NULL or: cand_costs [N][K + 3]; best_* and best_side_rate [N].
+struct RdDecideSignalParams {
+    const uint32_t* sse; const uint64_t* rate; const uint32_t* nonzero; const uint8_t* slot_modes; const uint8_t* left; const uint8_t* above;
+    int N; int w; int cbf_ctx; double lambda; msig::FlagBits bits;
+    double* cand_costs; uint8_t* best_mode; uint8_t* best_slot; double* best_cost; uint32_t* best_sse; uint64_t* best_rate;
+    uint64_t* best_side_rate;
+};
+hipError_t launch_rd_decide_signal(const RdDecideSignalParams& p, hipStream_t s);
 
 // Open-loop transform coding (pnn_trquant.hip): N predictions and targets [N][w][w] uint8, nb_qps <= 8 QPs whose constants the host has
 // worked out (trquant::qp_consts at the unit size of w).  Outputs, each NULL or [nb_qps][N] uint32: the SSE of the reconstruction, the

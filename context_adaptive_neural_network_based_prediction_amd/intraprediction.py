@@ -465,8 +465,100 @@ def _check_lambdas(lambdas, nb_qps, positive=False):
     return (ctypes.c_double * nb_qps)(*values)
 
 
+NO_NEIGHBOUR = 255                                        # a neighbour that does not exist or is not intra: HM takes DC
+
+
+def _neighbour_array(modes, n, pnn_flag, name):
+    """None, or [n] neighbour modes (0 .. 34, 35 with the PNN flag, 255) as a contiguous uint8 array; ValueError otherwise."""
+    if modes is None:
+        return None
+    modes = np.asarray(modes)
+    if modes.shape != (n,) or not np.issubdtype(modes.dtype, np.integer):
+        raise ValueError('`%s` is not an integer array of shape [n].' % name)
+    if n and not np.all((modes == NO_NEIGHBOUR) | ((modes >= 0) & (modes <= (35 if pnn_flag else 34)))):
+        raise ValueError('`%s` has a value that is not 0 .. %d or 255.' % (name, 35 if pnn_flag else 34))
+    return np.ascontiguousarray(modes.astype(np.uint8))
+
+
+def rd_pass_slot_count(width_target, signalling=False):
+    """Slots per block of rd_pass (pnn_rd_pass_slot_count): K + 1, with signalling K + 3."""
+    count = _lib.lib().pnn_rd_pass_slot_count(int(width_target), int(bool(signalling)))
+    if count < 0:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    return count
+
+
+def intra_mode_signal(left_modes, above_modes, qp, pnn_flag=True):
+    """The side information of a luma prediction unit as include/pnn_hip.h defines it ("mode signalling"; pnn_intra_mode_signal_host):
+    for n blocks whose left and above neighbours were coded with `left_modes` / `above_modes` (integer [n]: 0 .. 34, 35 with
+    pnn_flag, 255 = no neighbour or not intra; None: 255 everywhere, but not both None) at QP `qp`,
+    {'mpm': uint8 [n, 3] (getIntraDirPredictor of the switch codec), 'num_append': uint8 [n] (how many of them the search appends),
+    'mode_frac_bits': uint32 [n, 36] (the bits of coding each mode, in 2^-15 bit; entry 35 is 0 without pnn_flag),
+    'cbf_frac_bits': uint32 [2, 2] (cbf_luma: [context][value])}."""
+    if left_modes is None and above_modes is None:
+        raise ValueError('both `left_modes` and `above_modes` are None.')
+    n = len(left_modes if left_modes is not None else above_modes)
+    left, above = _neighbour_array(left_modes, n, pnn_flag, 'left_modes'), _neighbour_array(above_modes, n, pnn_flag, 'above_modes')
+    if isinstance(qp, (bool, np.bool_)) or not isinstance(qp, (int, np.integer)) or not 0 <= qp <= 51:
+        raise ValueError('`qp` is not an integer in [0, 51].')
+    mpm, num = np.zeros((n, 3), np.uint8), np.zeros(n, np.uint8)
+    bits, cbf = np.zeros((n, 36), np.uint32), np.zeros((2, 2), np.uint32)
+    rc = _lib.lib().pnn_intra_mode_signal_host(_address(left), _address(above), n, int(qp), int(bool(pnn_flag)), mpm.ctypes.data, num.ctypes.data,
+                                               bits.ctypes.data, cbf.ctypes.data)
+    if rc != 0:
+        raise ValueError('pnn_intra_mode_signal_host refused the arguments.')
+    return {'mpm': mpm, 'num_append': num, 'mode_frac_bits': bits, 'cbf_frac_bits': cbf}
+
+
+RD_PASS_SIGNAL_OUTPUTS = RD_PASS_OUTPUTS + (('first_pass_costs', np.float64), ('side_rates', np.uint64))
+
+
+def rd_pass_signal_shapes(n, nb_qps, width_target):
+    """The shapes of RD_PASS_SIGNAL_OUTPUTS: candidates and costs [nb_qps, n, K + 3], first_pass_costs [nb_qps, n, K], the others [nb_qps, n]."""
+    k, s = first_pass_list_size(width_target), rd_pass_slot_count(width_target, True)
+    return ((nb_qps, n, s), (nb_qps, n, s)) + ((nb_qps, n),) * 5 + ((nb_qps, n, k), (nb_qps, n))
+
+
+def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device):
+    """rd_pass with signalling: the checked arguments -> the dictionary, from pnn_rd_pass_signal_host (device None) or _device."""
+    n, w, nq = targets.shape[0], targets.shape[1], len(qps)
+    left, above = (None, None) if neighbour_modes is None else neighbour_modes
+    left, above = _neighbour_array(left, n, True, 'neighbour_modes[0]'), _neighbour_array(above, n, True, 'neighbour_modes[1]')
+    shapes = rd_pass_signal_shapes(n, nq, w)
+    L = _lib.lib()
+    if device is None or n == 0:
+        outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(RD_PASS_SIGNAL_OUTPUTS, shapes)]
+        rc = L.pnn_rd_pass_signal_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
+                                       smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(left), _address(above),
+                                       *[o.ctypes.data for o in outs])
+        if rc != 0:
+            raise ValueError('pnn_rd_pass_signal_host refused the arguments (patterns %dx%d, width %d).' % (patterns.shape[1], patterns.shape[2], w))
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        d_in = [torch.from_numpy(a).to(dev) for a in (patterns, targets, candidate)]
+        d_left, d_above = (None if a is None else torch.from_numpy(a).to(dev) for a in (left, above))
+        d_outs = [torch.zeros(int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=torch.uint8, device=dev)
+                  for (_, dtype), shape in zip(RD_PASS_SIGNAL_OUTPUTS, shapes)]
+        nb_bytes = L.pnn_rd_pass_signal_workspace_bytes(w, n, nq, 1)
+        d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.pnn_rd_pass_signal_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
+                                                   n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(d_left),
+                                                   _address(d_above), *[o.data_ptr() for o in d_outs], d_ws.data_ptr(), nb_bytes,
+                                                   ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, RD_PASS_SIGNAL_OUTPUTS, shapes)]   # (waits)
+    result = {name: out for (name, _), out in zip(RD_PASS_SIGNAL_OUTPUTS, outs)}
+    result['rate_bits'] = result['rates'].astype(np.float64) / 32768.
+    result['side_rate_bits'] = result['side_rates'].astype(np.float64) / 32768.
+    result['psnrs_recon'] = psnrs_from_sses(result['sses'], w)
+    result['lambdas'] = np.array([hm_intra_lambda(q) for q in qps]) if c_lambdas is None else np.array(list(c_lambdas))
+    return result
+
+
 def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoothing=0, sign_data_hiding=False, lambdas=None, device=None,
-            rdoq=False):
+            rdoq=False, signalling=False, neighbour_modes=None):
     """HM's second intra pass as include/pnn_hip.h defines it ("the second intra pass"): per block and QP the RD choice among the
     first-pass candidates (mode_hads_*'s list with the candidate prediction competing as 35) and the candidate itself, appended if the
     list lacks it.  numpy uint8 arrays: patterns [n, h, w'], targets and candidate_predictions [n, w, w]; qps: 1 to 8 integers in
@@ -477,7 +569,15 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     'rates': uint64 (its rate in 2^-15 bit), 'rate_bits': float64 (the same in bits), 'psnrs_recon': float64 (psnrs_from_sses of
     'sses'), each [nb_qps, n], and 'lambdas': float64 [nb_qps], the values used}.
     rdoq=True (the option of pnn_rd_pass_rdoq_host / _device, which every call here goes to, with 0 when off): every candidate is coded
-    with HM's RDOQ under the lambda that decides, which must then be > 0.  Same keys.  With False nothing changes."""
+    with HM's RDOQ under the lambda that decides, which must then be > 0.  Same keys.  With False nothing changes.
+    signalling=True (the option of pnn_rd_pass_signal_host / _device; include/pnn_hip.h, "mode signalling"): the first pass ranks on
+    SATD + modeBits sqrt(lambda), the most probable modes the list lacks are appended in front of 35, and every candidate is charged
+    its mode bits and cbf_luma.  neighbour_modes: None (no neighbour anywhere) or a pair (left, above) of integer [n] arrays, each
+    None or 0 .. 35 / 255.  The list then depends on the QP: 'candidates' is [nb_qps, n, K + 3], 'costs' [nb_qps, n, K + 3]; 'rates'
+    stays the rate of the winner's levels, and the dictionary gains 'side_rates' uint64 [nb_qps, n] (the winner's mode bits plus cbf bin,
+    2^-15 bit), 'side_rate_bits' (the same in bits) and 'first_pass_costs' float64 [nb_qps, n, K].  At width 64 each of the four
+    quadrants pays its own cbf bin.  With False nothing changes: the same entries are called with signalling 0, which forward to
+    pnn_rd_pass_rdoq_host / _device."""
     smoothing = _check_smoothing(reference_smoothing)
     qps = _check_qps(qps)
     arrays = (intra_patterns, targets, candidate_predictions)
@@ -490,12 +590,16 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     patterns, targets, candidate = (np.ascontiguousarray(a) for a in arrays)
     flag, option = int(bool(sign_data_hiding)), int(bool(rdoq))
     c_qps, c_lambdas = (ctypes.c_int * nq)(*qps), _check_lambdas(lambdas, nq, positive=bool(option))
+    if not signalling and neighbour_modes is not None:
+        raise ValueError('`neighbour_modes` is given without `signalling`.')
+    if signalling:
+        return _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device)
     shapes = rd_pass_shapes(n, nq, w)
     L = _lib.lib()
     if device is None or n == 0:                          # (no block: nothing to launch, the empty arrays)
         outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
-        rc = L.pnn_rd_pass_rdoq_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
-                                     smoothing, c_qps, nq, c_lambdas, flag, option, *[o.ctypes.data for o in outs])
+        rc = L.pnn_rd_pass_signal_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
+                                       smoothing, c_qps, nq, c_lambdas, flag, option, 0, None, None, *[o.ctypes.data for o in outs], None, None)
         if rc != 0:
             raise ValueError('pnn_rd_pass_host refused the arguments (patterns %dx%d, width %d).' % (patterns.shape[1], patterns.shape[2], w))
     else:
@@ -504,14 +608,14 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
         d_in = [torch.from_numpy(a).to(dev) for a in (patterns, targets, candidate)]
         d_outs = [torch.zeros(int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=torch.uint8, device=dev)
                   for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
-        nb_bytes = L.pnn_rd_pass_workspace_bytes(w, n, nq)
+        nb_bytes = L.pnn_rd_pass_signal_workspace_bytes(w, n, nq, 0)
         d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_rd_pass_rdoq_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
-                                                 n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option,
-                                                 *[o.data_ptr() for o in d_outs], d_ws.data_ptr(), nb_bytes,
-                                                 ctypes.c_void_p(stream.cuda_stream)), _context(device))
+            _lib.check(L.pnn_rd_pass_signal_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
+                                                   n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 0, None, None,
+                                                   *[o.data_ptr() for o in d_outs], None, None, d_ws.data_ptr(), nb_bytes,
+                                                   ctypes.c_void_p(stream.cuda_stream)), _context(device))
         outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, RD_PASS_OUTPUTS, shapes)]   # (waits)
     result = {name: out for (name, _), out in zip(RD_PASS_OUTPUTS, outs)}
     result['rate_bits'] = result['rates'].astype(np.float64) / 32768.

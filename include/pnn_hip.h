@@ -643,7 +643,7 @@ int pnn_trquant_sdh_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions
  *   Winner.  Slots 0 .. K in order under a strict <, starting from +inf: of equal costs the earlier slot wins, so an appended 35 loses
  *     every tie.  Where no cost is below +inf (a caller's lambda so large that every lambda R overflows) there is no winner: mode and
  *     slot 255, cost +inf, sse and rate 0.
- * STILL LEFT OUT: mode bits, cbf_luma and split flags; transform skip (RDOQ, which campaigns run, is the option of the next group);
+ * STILL LEFT OUT: split flags (mode bits, cbf_luma and the appended MPMs are the option of the mode-signalling group below); transform skip (RDOQ, which campaigns run, is the option of the next group);
  * the transform quadtree (one unit per block, four quadrants at width 64, as in the transform-coding group); chroma; and the contexts
  * start cold for every candidate, as in the rate group.
  *
@@ -791,6 +791,83 @@ int pnn_rd_pass_rdoq_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t
                                           const double* lambdas, int sign_data_hiding, int rdoq, uint8_t* d_cand_modes, double* d_cand_costs,
                                           uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
                                           uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- mode signalling: the side information HM's intra search charges, and the candidates it adds ---------- */
+
+/* The second pass above compares candidates on D + lambda R(coefficients) alone.  hm_16_15_switch also charges each candidate its
+ * mode bits and cbf_luma, ranks the first pass on SATD + modeBits sqrt(lambda), and appends the most probable modes the list lacks
+ * before it appends 35 (TEncSearch.cpp:2427-2492 of the switch tree).  The entries below are the second-pass entries with an option
+ * `signalling`; with 0 they ARE those entries.  The definition lives in csrc/pnn_mode_signal.h, whose lines host and device compile.
+ *   Neighbours.  left_modes / above_modes: NULL (every block: none) or uint8 [n], a neighbour's coded mode 0 .. 35 or 255 = no
+ *     neighbour or not intra, which HM treats as DC.  HM also treats an above neighbour outside the CTU as DC: a caller who wants that
+ *     rule passes 255 there.  Any other value is PNN_E_ARG; so is 35 with pnn_flag 0.
+ *   MPMs.  TComDataCU::getIntraDirPredictor of the switch tree: left == above: an angular mode a < 35 gives {a, 2 + (a + 29) % 32,
+ *     2 + (a - 1) % 32}, anything else (planar, DC, 35 twice) {0, 1, 26}; num_append 1.  left != above, num_append 2: one of them 35 and
+ *     the other o: {o, 0, 1} for o > 1, {1, 0, 26} for o = 1, {0, 1, 26} for o = 0; else {left, above, t}, t = 0 if neither is planar,
+ *     else 26 if left + above < 2, else 1.  Without a neighbour 35 this is hm_16_15_regular's.
+ *   Mode bits, in 2^-15 bit as a TEncBinCABACCounter adds them for one unit (TEncSbac::codeIntraDirLumaAng): with pnn_flag the flag on
+ *     its own context (initial value 154): mode 35 costs that bin alone; a regular mode the bin for 0, then prev_intra_luma_pred_flag on
+ *     its context (184) and mpm_idx, 1 bypass bin for mpm[0], 2 for mpm[1] and mpm[2], or the 5 bypass bins of the remainder (HM sorts
+ *     the three ascending to form its value; the value costs nothing).  Bypass bins cost 32768.  Both contexts start from the state an
+ *     I slice of the QP begins with (cold contexts, as the rate group).  pnn_flag 0 leaves the first flag out: regular HM.
+ *   cbf_luma.  One bin on context getCtxQtCbf selects: 1 at transform depth 0 (width 8, 16, 32), 0 at depth 1 (width 4), initial
+ *     values 141 and 111, cold.  A unit without a level pays the bin for 0 and no coefficient bits, one with levels the bin for 1
+ *     plus the rate.  Width 64: each of the four 32 x 32 quadrants is a unit at depth 1 and pays its own bin on context 0, four bins
+ *     per candidate (the quadrants are this project's definition, as in the transform-coding group).
+ *   First pass.  cost = (double) SATD + (double) (mode bits >> 15) * sqrt(lambda), sqrt taken once on the host in double
+ *     (TComRdCost::setLambda); one IEEE multiply and one IEEE add, never fused.  The list is xUpdateCandList over modes 0 .. 35 in that
+ *     order under a strict <, K entries.  So the list depends on the QP and on the neighbours.
+ *   Slots.  S = K + 3 = pnn_rd_pass_slot_count(width, 1): the list, then mpm[0 .. num_append - 1] where the list lacks them, in that
+ *     order, then 35 if absent; unused slots carry mode 255 and cost +inf.
+ *   Second pass.  R = (mode bits + cbf bin + rate of the levels) >> 15, ONE shift over the sum; J = D + lambda R and the winner rule
+ *     as above.  A slot is coded at its own QP only.
+ * LEFT OUT: part size, split and subdivision flags (equal for all candidates of a block); the interleaving of the four units' flags in
+ * an N x N coding unit; chroma; running contexts; the substitution codec's signalling; transform skip; the transform quadtree. */
+int pnn_rd_pass_slot_count(int width, int signalling);      /* K + 1 or K + 3; -1 for a bad width */
+/* The unit entry.  Outputs, each NULL (not all) or: mpm uint8 [n][3]; num_append uint8 [n]; mode_frac_bits uint32 [n][36] (entry 35
+ * is 0 with pnn_flag 0); cbf_frac_bits uint32 [2 contexts][2 values] of the QP.  PNN_E_ARG + a line on stderr for n < 0, a QP outside
+ * [0, 51], a bad neighbour mode.  Pure host code. */
+int pnn_intra_mode_signal_host(const uint8_t* left_modes, const uint8_t* above_modes, int n, int qp, int pnn_flag, uint8_t* mpm,
+                               uint8_t* num_append, uint32_t* mode_frac_bits, uint32_t* cbf_frac_bits);
+/* The first pass with the mode-bit term, the candidate competing as 35 (cand_pred is required).  Outputs, each NULL (not all) or:
+ * list_modes uint8 [nb_qps][n][K]; list_costs double [nb_qps][n][K]; slot_modes uint8 [nb_qps][n][K + 3].  Pure host code. */
+int pnn_first_pass_signal_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                               const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas,
+                               const uint8_t* left_modes, const uint8_t* above_modes, uint8_t* list_modes, double* list_costs,
+                               uint8_t* slot_modes);
+/* pnn_rd_pass_rdoq_host with the option.  signalling 0: that entry (the neighbours are not read; first_pass_costs and best_side_rate
+ * must be NULL).  Nonzero: as above; cand_modes is then uint8 [nb_qps][n][K + 3] and cand_costs double [nb_qps][n][K + 3]; the added
+ * outputs are first_pass_costs double [nb_qps][n][K] (the list's costs) and best_side_rate uint64 [nb_qps][n], the winner's mode bits
+ * plus cbf bin in 2^-15 bit (best_rate stays the rate of its levels).  The twin is a composition of the host twins above. */
+int pnn_rd_pass_signal_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                            const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                            int rdoq, int signalling, const uint8_t* left_modes, const uint8_t* above_modes, uint8_t* cand_modes,
+                            double* cand_costs, uint8_t* best_mode, uint8_t* best_slot, double* best_cost, uint32_t* best_sse,
+                            uint64_t* best_rate, double* first_pass_costs, uint64_t* best_side_rate);
+/* The device entries' scratch (signalling 0: pnn_rd_pass_workspace_bytes; 0 for what the entries refuse). */
+size_t pnn_rd_pass_signal_workspace_bytes(int width, int n, int nb_qps, int signalling);
+/* pnn_rd_pass_signal_host on the GPU, bit-identical to it.  signalling 0 forwards to pnn_rd_pass_rdoq_device.  Nonzero: 2 + 3 nb_qps
+ * launches on `stream`: the unchanged first-pass kernel (asked for the Hadamard costs, no list), signal_list_kernel (all QPs), then per
+ * QP the slots form of rd_candidates_kernel, the unchanged launch of pnn_trquant_rdoq_device with that one QP, and
+ * rd_decide_signal_kernel, all on the same scratch.  At width 64 the slots form writes every slot as its four quadrants and the
+ * transform launch is the width-32 one on 4 n (K + 3) blocks under cbf context 0 -- the same units, now with a count of levels each.
+ * d_left_modes / d_above_modes are DEVICE arrays or NULL; when one is given both are read back and checked behind ONE wait for the
+ * stream (as the picture forms wait for their positions), so that every refusal comes before any launch; with both NULL the dense
+ * entry stays asynchronous. */
+int pnn_rd_pass_signal_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                              const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                              int rdoq, int signalling, const uint8_t* d_left_modes, const uint8_t* d_above_modes, uint8_t* d_cand_modes,
+                              double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                              uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
+                              size_t workspace_bytes, void* stream);
+int pnn_rd_pass_signal_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                            int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                            int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                            const double* lambdas, int sign_data_hiding, int rdoq, int signalling, const uint8_t* d_left_modes,
+                                            const uint8_t* d_above_modes, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode,
+                                            uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate,
+                                            double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace, size_t workspace_bytes,
+                                            void* stream);
 
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
