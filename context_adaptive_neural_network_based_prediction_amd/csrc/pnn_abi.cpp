@@ -300,6 +300,7 @@ const OptionRow kOptions[] = {
     {"chain_io",             &pnn_ctx::opt_chain_io,            "PNN_CHAIN_IO",         kStore,       nullptr},
     {"tails",                &pnn_ctx::opt_tails,               "PNN_TAILS",            kStore,       nullptr},
     {"f32_cfg",              &pnn_ctx::opt_f32_cfg,             "PNN_F32_CFG",          kStore,       nullptr},
+    {"f32_pair_occ",         &pnn_ctx::opt_f32_pair_occ,        nullptr,                kRetune,      nullptr},
     {"f32_seg_mode",         &pnn_ctx::opt_f32_seg_mode,        "PNN_F32_SEG_MODE",     kRetune,      nullptr},
     {"f32_persist",          &pnn_ctx::opt_f32_persist,         "PNN_F32_PERSIST",      kRetune,      nullptr},
     {"f32_overlap",          &pnn_ctx::opt_f32_overlap,         "PNN_F32_OVERLAP",      kStore,       nullptr},
@@ -532,6 +533,30 @@ int pnn_last_call_stats(const pnn_ctx* c, int* n_gemm, double* flops, int* n_lau
     if (n_gemm) *n_gemm = c->stat_gemm_launches;
     if (flops) *flops = c->stat_gemm_flops;
     if (n_launches) *n_launches = c->stat_launches;
+    return PNN_OK;
+}
+
+int pnn_f32_pair_stats(const pnn_ctx* c, long* paired, long* fell_back)
+{
+    if (!c) return PNN_E_ARG;
+    if (paired) *paired = c->stat_pair_launches;
+    if (fell_back) *fell_back = c->stat_pair_fallbacks;
+    return PNN_OK;
+}
+
+int pnn_f32_pair_tile(int M, int cout, int wg, int* num_wgs, int* row0, int* col0, int* cols)
+{
+    if (M <= 0 || cout <= 0 || wg < 0) return PNN_E_ARG;
+    int gx = 0, groups = 0, nwg = 0;
+    f32_pair_grid(M, cout, &gx, &groups, &nwg);
+    if (num_wgs) *num_wgs = nwg;
+    if (wg >= nwg) return PNN_E_ARG;
+    const PairTile t = f32_pair_tile(wg, gx);
+    const int c0 = t.group * (kPairWide + kPairNarrow) + (t.narrow ? kPairWide : 0);
+    const bool live = t.group < groups && c0 < cout;
+    if (row0) *row0 = t.bx * 128;
+    if (col0) *col0 = c0;
+    if (cols) *cols = live ? (t.narrow ? kPairNarrow : kPairWide) : 0;
     return PNN_OK;
 }
 

@@ -199,6 +199,10 @@ struct pnn_ctx {
     long opt_f32_small_tiles = 1024;                  // ... "few" = at most this many 16 x 16 tiles
     long opt_f32_overlap = 1;                         // exact-f32 conv passes at batch: the two branches on two streams (see branches_overlap_at_batch)
     long opt_f32_cfg = -1;                            // tuning aid: force this tapgemm_f32 configuration on every layer it is legal for
+    // paired tiles (f32_cfg / the tuner, launch_f32_pair): 0 (default) = ask the runtime whether two workgroups fit a CU, N > 0 = take N
+    // for its answer (1: every paired launch falls back to the one 128 x 160 tile)
+    long opt_f32_pair_occ = 0;
+    long stat_pair_launches = 0, stat_pair_fallbacks = 0;   // launches that ran as pairs / that fell back, since the context was created
     long opt_fuse_first = 1;                          // 1: convimg configurations compute a branch's first (Cin = 1) convolution themselves
     long opt_fuse_last = 1;                           // 1: big FC passes run the output layer inside the last hidden layer's ring kernel
     long opt_f32_seg_mode = 0;                        // K-segmented exact-f32 layers: 0 (default) parallel segments + reduce, 1 in sequence inside the workgroups, -1 by cost model / tuner (same bits)

@@ -62,9 +62,41 @@ int diag_f32_tiles(pnn_ctx* c, const GemmLayer& L, const TapGemmParams& p, int t
     for (int rep = 0; rep < 400; rep++) HIPCHK(c, launch_tapgemm_f32(q, tile, fused, s));   // back to back: the stamps that
                                                                                        // stay are the last launch's, at the steady-state clock
     HIPCHK(c, hipStreamSynchronize(s));
-    const size_t nwg = (size_t)((M + 128L * t.rt - 1) / (128L * t.rt)) * ((p.Cout + 32L * t.nt - 1) / (32L * t.nt)) * p.ncls * par_segs;
+    size_t nwg = (size_t)((M + 128L * t.rt - 1) / (128L * t.rt)) * ((p.Cout + 32L * t.nt - 1) / (32L * t.nt)) * p.ncls * par_segs;
+    if (t.pair && g_last_pair_mode == 1) { int gx, groups, n; f32_pair_grid(p.M, p.Cout, &gx, &groups, &n); nwg = (size_t)n; }
     std::vector<unsigned long long> hbuf(8 * nwg);
     HIPCHK(c, hipMemcpy(hbuf.data(), c->stage_tbs.p, hbuf.size() * 8, hipMemcpyDeviceToHost));
+    if (t.pair && g_last_pair_mode == 1) {
+        // A paired launch: the wide and the narrow tiles apart (slot = workgroup; a slot without stamps had no tile), and where they ran --
+        // per CU (XCC, SE, SH, CU of the hardware id) how many wide and narrow workgroups, and whether a pair's two met on one
+        const int gx = (int)((M + 127) / 128);
+        double sum[2][4] = {}; size_t cnt[2] = {0, 0};
+        unsigned long long r0 = ~0ull, r1 = 0, end[2] = {0, 0};
+        std::map<unsigned long long, std::pair<int, int>> per_cu;
+        std::map<int, unsigned long long> cu_of[2];
+        for (size_t i = 0; i < nwg; i++) {
+            const unsigned long long* d = &hbuf[8 * i];
+            if (!d[3]) continue;
+            const PairTile pt = f32_pair_tile((int)i, gx);
+            const int k = pt.narrow;
+            for (int j = 0; j < 4; j++) sum[k][j] += (double)d[j];
+            cnt[k]++;
+            r0 = std::min(r0, d[4]); r1 = std::max(r1, d[4] + d[3]); end[k] = std::max(end[k], d[4] + d[3]);
+            const unsigned long long cu = ((d[5] >> 32) & 0xf) << 16 | (d[5] & 0xff00);
+            (k ? per_cu[cu].second : per_cu[cu].first)++;
+            cu_of[k][pt.group * gx + pt.bx] = cu;
+        }
+        size_t one_each = 0, together = 0;
+        for (const auto& kv : per_cu) one_each += kv.second.first == 1 && kv.second.second == 1;
+        for (const auto& kv : cu_of[1]) { const auto w = cu_of[0].find(kv.first); together += w != cu_of[0].end() && w->second == kv.second; }
+        for (int k = 0; k < 2; k++)
+            fprintf(stderr, "[pnn-f32diag] M=%ld K=%.0f N=%d pair kc %d %s: %zu WGs; wave 0 mean cycles: prologue %.0f  loop %.0f  epilogue %.0f; lifetime %.1f us; last end %.1f us after the first start\n",
+                    M, L.k_total, p.Cout, t.kc, k ? "narrow 128x64" : "wide 128x96", cnt[k], sum[k][0] / std::max<size_t>(cnt[k], 1), sum[k][1] / std::max<size_t>(cnt[k], 1),
+                    sum[k][2] / std::max<size_t>(cnt[k], 1), sum[k][3] / std::max<size_t>(cnt[k], 1) / 100.0, (double)(end[k] - r0) / 100.0);
+        fprintf(stderr, "[pnn-f32diag]   first start -> last end %.1f us; %zu CUs in use, %zu of them with one wide and one narrow workgroup; %zu of %zu pairs with both tiles on one CU\n",
+                (double)(r1 - r0) / 100.0, per_cu.size(), one_each, together, cu_of[1].size());
+        return PNN_OK;
+    }
     double sum[4] = {0, 0, 0, 0};
     unsigned long long r0 = ~0ull, r1 = 0;
     for (size_t i = 0; i < nwg; i++) {

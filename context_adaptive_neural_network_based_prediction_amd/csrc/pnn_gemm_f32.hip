@@ -74,9 +74,10 @@ __device__ __forceinline__ void wait_vm_le()
 // v_accvgpr_mov per 160 MFMAs, 3 % of an FC layer at batch 4096, FC 8x8 18.1 M -> 17.3 M blocks/s whatever the number of folds,
 // profiles/r06_fcseg_ab.txt; the folds themselves are 0.5 us each per layer.)
 // One tile (bx, by, bz) of the launch's gx x gy x gz tiles -- what a workgroup of the plain launch does once and a workgroup of a
-// PERSISTENT launch (fewer workgroups than tiles, tapgemm_f32_kernel below) does for one tile after the other.
+// PERSISTENT launch (fewer workgroups than tiles, tapgemm_f32_kernel below) does for one tile after the other.  n0: the tile's first
+// column (by * BN; a PAIRED launch, tapgemm_f32_pair_kernel: inside column group by); lin: the tile's number in the launch (diagnostics).
 template <int RT, int NT, int KC, bool FUSE, int SEQ>
-__device__ __forceinline__ void f32_tile(const TapGemmParams& p, f32x4* const lds, const int bx, const int by, const int bz, const int gx, const int gy)
+__device__ __forceinline__ void f32_tile(const TapGemmParams& p, f32x4* const lds, const int bx, const int by, const int bz, const int n0, const int lin)
 {
     static_assert(KC >= 2 && KC % 2 == 0, "fragment sets alternate by chunk parity");
     constexpr int BM = 128 * RT, BN = 32 * NT;
@@ -100,7 +101,6 @@ __device__ __forceinline__ void f32_tile(const TapGemmParams& p, f32x4* const ld
     const int nseg = (!FUSE && !SEQ && p.nseg > 1) ? p.nseg : 1;
     const int cls = nseg > 1 ? bz / nseg : bz;
     const int seg = bz - cls * nseg;
-    const int n0 = by * BN;
     const int m0 = bx * BM + wave * (32 * RT);
 #ifdef PNN_F32_DIAG             // diagnostic library only (make diag): cycle stamps of wave 0 -> p.Xlo[workgroup][8]
     const unsigned long long dq0 = __builtin_amdgcn_s_memtime(), dr0 = __builtin_amdgcn_s_memrealtime();
@@ -438,9 +438,11 @@ __device__ __forceinline__ void f32_tile(const TapGemmParams& p, f32x4* const ld
     dq2 = __builtin_amdgcn_s_memtime();
     auto diag_out = [&]() {
         if (tid == 0 && p.Xlo) {
-            unsigned long long* d = (unsigned long long*)p.Xlo + 8 * ((bz * gy + by) * gx + bx);
+            unsigned long long* d = (unsigned long long*)p.Xlo + 8 * lin;
             d[0] = dq1 - dq0; d[1] = dq2 - dq1; d[2] = __builtin_amdgcn_s_memtime() - dq2; d[3] = __builtin_amdgcn_s_memrealtime() - dr0;
             d[4] = dr0;
+            // where it ran: XCC_ID (hardware register 20) above HW_ID (register 4: CU in bits 8-11, SH bit 12, SE bits 13-15)
+            d[5] = ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11));
         }
     };
 #else
@@ -573,8 +575,23 @@ __global__ __launch_bounds__(256) void tapgemm_f32_kernel(const TapGemmParams p)
     for (int lin = blockIdx.x; lin < ntiles; lin += gridDim.x) {
         if (lin != (int)blockIdx.x) __syncthreads();   // the previous tile's last fragment reads (and its LDS epilogue) before this tile's first LDS-DMA
         const int bx = lin % gx, rest = lin / gx;
-        f32_tile<RT, NT, KC, FUSE, SEQ>(p, lds, bx, rest % gy, rest / gy, gx, gy);
+        f32_tile<RT, NT, KC, FUSE, SEQ>(p, lds, bx, rest % gy, rest / gy, (rest % gy) * (32 * NT), lin);
     }
+}
+
+// The PAIRED launch (PairTile, pnn_kernels.h): workgroup w runs the wide (NT = 3) or the narrow (NT = 2) tile of its pair, the loop
+// body, folds and epilogue of the plain kernel at that width.  Two workgroups per CU: 256 registers per lane.  A narrow tile whose
+// columns all lie past Cout (the last column group of a 1200-wide layer: 80 real columns) has nothing to do.
+template <int KC, int SEQ>
+__global__ __launch_bounds__(256, 2) void tapgemm_f32_pair_kernel(const TapGemmParams p)
+{
+    touch_kernargs<sizeof(TapGemmParams)>();
+    extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
+    const PairTile t = f32_pair_tile((int)blockIdx.x, p.grid_x);
+    if (t.group >= p.grid_y) return;
+    const int n0 = t.group * (kPairWide + kPairNarrow);
+    if (!t.narrow) f32_tile<1, kPairWide / 32, KC, false, SEQ>(p, lds, t.bx, t.group, 0, n0, (int)blockIdx.x);
+    else if (n0 + kPairWide < p.Cout) f32_tile<1, kPairNarrow / 32, KC, false, SEQ>(p, lds, t.bx, t.group, 0, n0 + kPairWide, (int)blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -774,16 +791,19 @@ hipError_t launch_seg_reduce(const float* part, int nseg, size_t n, int Cout, co
     X(1, 5, 4) X(1, 5, 2) X(1, 4, 4) X(1, 4, 2) X(1, 3, 4) X(1, 2, 4) X(1, 2, 2) X(1, 1, 4) X(1, 1, 2) \
     X(2, 4, 2) X(2, 2, 4) X(2, 2, 2) X(2, 1, 4) X(2, 3, 2)
 
+// ... and behind them the PAIRED tiles (PairTile, pnn_kernels.h): a 128 x 160 share as a 128 x 96 and a 128 x 64 workgroup
 static const TileCfg kCfgsF32[] = {
 #define X(rt, nt, kc) {rt, nt, kc, 32},
     PNN_F32_CFGS(X)
 #undef X
+    {1, 5, 4, 32, 4, 2, 1}, {1, 5, 2, 32, 4, 2, 1},
 };
 
 // Registers per lane (arch + acc) of the non-fused instantiations, in the order of PNN_F32_CFGS, as the compiler allocated them
 // (llvm-readelf --notes on the code object, .vgpr_count): what bounds the waves per SIMD -- 512 / this, whole waves -- in
 // choose_cfg_f32's residency estimate.  Re-read after a change of the kernel.
-static const int kRegsF32[] = {360, 360, 296, 296, 224, 176, 152, 116, 92, 492, 288, 252, 208, 360};
+// (the paired tiles: the pair kernel's count in its K-segmented form, at most 256 by its launch bounds -- two workgroups per CU)
+static const int kRegsF32[] = {360, 360, 296, 296, 224, 176, 152, 116, 92, 492, 288, 252, 208, 360, 252, 220};
 static_assert(sizeof(kRegsF32) / sizeof(kRegsF32[0]) == sizeof(kCfgsF32) / sizeof(kCfgsF32[0]), "one register count per tile");
 int tapgemm_f32_regs(int idx) { return kRegsF32[idx]; }
 
@@ -794,7 +814,17 @@ size_t tapgemm_f32_lds_bytes(const TileCfg& t, bool fuse, bool row_out)
     const size_t ring = (size_t)3 * t.kc * 4 * 32 * t.nt, out_tile = (size_t)128 * t.rt * (8 * t.nt + 1);   // pieces: weight stages | the FC epilogue's row tiles
     return (std::max(ring, (row_out && !fuse) ? out_tile : (size_t)0) + (fuse ? (size_t)8 * t.nt * 64 : 0)) * 16;
 }
-bool tapgemm_f32_can_fuse(int idx) { return kCfgsF32[idx].rt == 1 && kCfgsF32[idx].nt == 5; }
+bool tapgemm_f32_can_fuse(int idx) { return kCfgsF32[idx].rt == 1 && kCfgsF32[idx].nt == 5 && !kCfgsF32[idx].pair; }
+
+// the LDS attribute belongs to (function, device): set once per device, and a failure is the launch's error, not an opaque launch failure later
+static hipError_t set_lds_attr(const DeviceInfo& di, const void* fn, int (&done)[16])
+{
+    const int dev = di.dev >= 0 && di.dev < 16 ? di.dev : 0;
+    if (done[dev]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)di.lds);
+    if (e == hipSuccess) done[dev] = 1;
+    return e;
+}
 
 template <int RT, int NT, int KC>
 static hipError_t launch_f32(const TapGemmParams& p0, bool fuse, hipStream_t s)
@@ -852,14 +882,7 @@ static hipError_t launch_f32(const TapGemmParams& p0, bool fuse, hipStream_t s)
         g1.x = (unsigned)di.cus * (unsigned)W;
         lds = std::max(lds, (size_t)(di.lds / (W + 1) + 1024) / 16 * 16);
     }
-    // the LDS attribute belongs to (function, device): set once per device, and a failure is the launch's error, not an opaque launch failure later
-    auto set_attr = [&](const void* fn, int (&done)[16]) -> hipError_t {
-        const int dev = di.dev >= 0 && di.dev < 16 ? di.dev : 0;
-        if (done[dev]) return hipSuccess;
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)di.lds);
-        if (e == hipSuccess) done[dev] = 1;
-        return e;
-    };
+    auto set_attr = [&](const void* fn, int (&done)[16]) { return set_lds_attr(di, fn, done); };
     const bool one_tap = p0.ncls == 1 && p0.tap_begin[1] - p0.tap_begin[0] == 1;
     // whole stages per segment; a one-tap layer: an EVEN number of them, and a last segment that is not empty (SEQ = 2, see f32_tile)
     if (seq && (one_tap ? (p0.seg_chunks == 0 || p0.seg_chunks % (2 * KC) || (long)(p0.nseg - 1) * p0.seg_chunks >= p0.Cin / 16) : ((p0.Cin / 16) % KC) != 0)) return hipErrorInvalidValue;
@@ -909,13 +932,61 @@ static hipError_t launch_f32(const TapGemmParams& p0, bool fuse, hipStream_t s)
     return hipGetLastError();
 }
 
+thread_local int g_last_pair_mode = 0;
+
+// The paired launch of a one-tap (FC) layer: 2 x (row tiles x 160-column groups) workgroups in PairTile's order, at most two per CU
+// (the LDS request says so), every one resident from the start.  Both tiles of a pair must fit a CU together: the occupancy query's
+// answer for the kernel at this LDS size (registers: 256 per lane by its launch bounds; LDS: two of the wide tile's rings or row
+// tiles); where it says one, the layer runs on the one 128 x 160 tile of the same stage depth -- the same bits.
+template <int KC>
+static hipError_t launch_f32_pair(const TapGemmParams& p0, bool fuse, hipStream_t s)
+{
+    const bool seq = p0.nseg > 1 && p0.seg_seq;
+    const bool one_tap = p0.ncls == 1 && p0.tap_begin[1] - p0.tap_begin[0] == 1;
+    if (fuse || !one_tap || (p0.nseg > 1 && !seq)) return hipErrorInvalidValue;
+    if (seq && (p0.seg_chunks == 0 || p0.seg_chunks % (2 * KC) || (long)(p0.nseg - 1) * p0.seg_chunks >= p0.Cin / 16)) return hipErrorInvalidValue;
+    const DeviceInfo& di = device_info();
+    const void* const fn = seq ? (const void*)tapgemm_f32_pair_kernel<KC, 2> : (const void*)tapgemm_f32_pair_kernel<KC, 0>;
+    static int done[2][16] = {}, occ[2][16] = {};
+    hipError_t e = set_lds_attr(di, fn, done[seq]);
+    if (e != hipSuccess) return e;
+    // more than a third of a CU's LDS each: never three on a CU, so that no CU is left with one
+    const size_t lds = std::max(tapgemm_f32_lds_bytes(TileCfg{1, kPairWide / 32, KC, 32}, false, p0.SH * p0.SW == 1), (size_t)(di.lds / 3 + 1024) / 16 * 16);
+    const int dev = di.dev >= 0 && di.dev < 16 ? di.dev : 0;
+    if (!occ[seq][dev]) {
+        int n = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds);
+        if (e != hipSuccess) return e;
+        occ[seq][dev] = std::max(n, 1);
+    }
+    if ((p0.pair_occ > 0 ? p0.pair_occ : occ[seq][dev]) < 2) {
+        TapGemmParams q = p0;
+        q.persist = 0;
+        const hipError_t r = launch_f32<1, 5, KC>(q, false, s);
+        g_last_pair_mode = 2;
+        return r;
+    }
+    TapGemmParams p = p0;
+    int nwg = 0;
+    f32_pair_grid(p0.M, p0.Cout, &p.grid_x, &p.grid_y, &nwg);
+    p.grid_z = 1; p.pm_groups = 0;
+    g_last_issued_frac = 1.0;
+    g_last_pair_mode = 1;
+    if (seq) pnn_launch(tapgemm_f32_pair_kernel<KC, 2>, dim3((unsigned)nwg), dim3(256), lds, s, p);
+    else pnn_launch(tapgemm_f32_pair_kernel<KC, 0>, dim3((unsigned)nwg), dim3(256), lds, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_tapgemm_f32(const TapGemmParams& p, int idx, bool fuse, hipStream_t s)
 {
     if (p.M <= 0) return hipSuccess;
+    g_last_pair_mode = 0;
     int i = 0;
 #define X(rt, nt, kc) if (idx == i++) return launch_f32<rt, nt, kc>(p, fuse, s);
     PNN_F32_CFGS(X)
 #undef X
+    if (idx == i++) return launch_f32_pair<4>(p, fuse, s);
+    if (idx == i++) return launch_f32_pair<2>(p, fuse, s);
     return hipErrorInvalidValue;
 }
 

@@ -123,7 +123,9 @@ struct TapGemmParams {
     int seg_seq;
     // tapgemm_f32_kernel: the launch's tiles (set by launch_f32; the kernel's grid is 1-D over them, or smaller: persistent workgroups)
     int grid_x, grid_y, grid_z;
-    int persist;       // tapgemm_f32 launches: > 0 = persistent workgroups, that many per CU (see launch_f32)
+    // tapgemm_f32 launches: persist > 0 = persistent workgroups, that many per CU (see launch_f32); a PAIRED launch (launch_f32_pair,
+    // never persistent) reads the same bytes as pair_occ: 0 = ask the runtime how many of its workgroups a CU holds, N > 0 = take N for the answer
+    union { int persist; int pair_occ; };
 };
 static_assert(sizeof(TapGemmParams) <= 512, "the argument block of the tap-GEMM kernels: 8 lines of 64 bytes");
 inline int pack_tap(int dy, int dx) { return (int)(((unsigned)dy << 16) | ((unsigned)dx & 0xffffu)); }
@@ -131,7 +133,8 @@ inline int pack_tap(int dy, int dx) { return (int)(((unsigned)dy << 16) | ((unsi
 constexpr int kChunkPad = 4;   // packed weights: every class is zero-padded to a multiple of 4 chunks
 constexpr int kSegDepth = 1600, kSegMinDepth = 2304;   // K segments of the exact-f32 summation order, see finish_gemm_layer (pnn_model.cpp)
 constexpr int kFcSegChunks = 20;                       // ... of a one-tap (FC) layer deeper than this many 16-deep chunks: segments of 320 inputs
-struct TileCfg { int rt, nt, kc, mf, wm = 4, d = 2; };   // a tile configuration of one of the tap-GEMM kernel families (mf: rows of the MFMA shape)
+// a tile configuration of one of the tap-GEMM kernel families (mf: rows of the MFMA shape; pair: tapgemm_f32 only, see PairTile)
+struct TileCfg { int rt, nt, kc, mf, wm = 4, d = 2, pair = 0; };
 int tapgemm_sp_num_cfgs();
 TileCfg tapgemm_sp_cfg(int idx);
 hipError_t launch_tapgemm_sp(const TapGemmParams& p, int idx, hipStream_t s);   // 3 x f16 MFMA, f32-class accuracy
@@ -176,6 +179,30 @@ TileCfg tapgemm_f32_cfg(int idx);
 size_t tapgemm_f32_lds_bytes(const TileCfg& t, bool fuse, bool row_out = false);   // row_out: an FC layer's f32 output leaves through an LDS tile
 bool tapgemm_f32_can_fuse(int idx);
 int tapgemm_f32_regs(int idx);   // registers per lane of tile idx (residency estimate of choose_cfg_f32)
+// PAIRED tiles of tapgemm_f32_kernel (TileCfg::pair; one-tap layers without a fused output layer): the 128 x 160 share of a CU as TWO
+// workgroups, a WIDE one of 128 x 96 (columns [160 g, 160 g + 96) of column group g) and a NARROW one of 128 x 64 (the 64 behind),
+// resident together -- two waves per SIMD of unequal length, so that the narrow tile's epilogue falls under the wide tile's MFMAs.
+// Workgroup w of the 1-D grid (kPairGridStep-aligned, see f32_pair_grid): the hardware deals workgroups to the 8 XCDs in turn, so
+// slot k = w / 8 counts the workgroups of XCD w % 8 in dispatch order.  Slots 2 j and 2 j + 1 are the two tiles of ONE pair (they share
+// the row tile: the second fetch of the activation panel hits the CU's cache), and which of them is the wide one alternates every
+// 32 slots -- whether an XCD's dispatcher fills a CU before it goes to the next or deals its 32 CUs in turn, a CU gets one of each.
+// group >= the launch's column groups: no tile (the grid's padding).
+struct PairTile { int bx, group, narrow; };
+constexpr int kPairGridStep = 16, kPairWide = 96, kPairNarrow = 64;
+__host__ __device__ inline PairTile f32_pair_tile(int w, int gx)
+{
+    const int k = w >> 3, q = (k >> 1) * 8 + (w & 7);
+    return PairTile{q % gx, q / gx, (k ^ (k >> 5)) & 1};
+}
+inline void f32_pair_grid(int M, int Cout, int* gx, int* groups, int* nwg)
+{
+    *gx = (M + 127) / 128;
+    *groups = (Cout + kPairWide + kPairNarrow - 1) / (kPairWide + kPairNarrow);
+    *nwg = (*gx * *groups + 7) / 8 * kPairGridStep;
+}
+// what the last launch_tapgemm_f32 of this thread did with a paired tile: 0 = not a paired tile, 1 = launched the pair, 2 = the pair does
+// not fit a CU together and the one 128 x 160 tile ran instead
+extern thread_local int g_last_pair_mode;
 hipError_t launch_tapgemm_f32(const TapGemmParams& p, int idx, bool fuse, hipStream_t s);
 // Small-M form of the same order on v_mfma_f32_16x16x4_f32 (pnn_gemm_f32_small.hip): one wave per 16 x 16 tile, K segments as grid z;
 // host_input (optional, FC layers): the same rows in HOST memory; when they fit they travel inside the argument block

@@ -213,6 +213,7 @@ int gemm_tiles(pnn_ctx* c, const GemmLayer& L, TapGemmParams& p, const TapGemmPa
         const TileCfg t = tapgemm_f32_cfg(code % ntile);
         if (fcseg && L.fc_seg_chunks % (2 * t.kc)) return false;  // an even number of whole stages per segment (tapgemm_f32_kernel, SEQ = 2)
         if (fcseg && t.rt * t.nt >= 8) return false;              // ... and room for the running total beside the accumulators (the 256 x 128 tile spills)
+        if (t.pair && (!one_tap || next || nseg > 1)) return false;   // paired tiles: FC layers that keep their output (launch_f32_pair)
         return (one_tap || cpt % t.kc == 0) && (!next || tapgemm_f32_can_fuse(code % ntile));
     };
     float* const Yreal = Y;
@@ -220,6 +221,11 @@ int gemm_tiles(pnn_ctx* c, const GemmLayer& L, TapGemmParams& p, const TapGemmPa
     const int act_real = L.proto.act;
     std::function<hipError_t(int)> launch = [&, p, pseq, Yreal, bias_real, act_real, fcseg](int code) {
         if (code >= ntile) return launch_tapgemm_f32(pseq, code - ntile, false, s);
+        if (tapgemm_f32_cfg(code).pair) {             // (one-tap layers: p.persist is 0, and its bytes carry the occupancy answer to take)
+            TapGemmParams q = p;
+            q.pair_occ = (int)std::max(0L, c->opt_f32_pair_occ);
+            return launch_tapgemm_f32(q, code, false, s);
+        }
         const hipError_t e = launch_tapgemm_f32(p, code, next != nullptr, s);
         if (e != hipSuccess || p.nseg <= 1 || fcseg) return e;
         return launch_seg_reduce(p.Y, p.nseg, out_floats, p.Cout, bias_real, act_real, Yreal, s);
@@ -230,7 +236,10 @@ int gemm_tiles(pnn_ctx* c, const GemmLayer& L, TapGemmParams& p, const TapGemmPa
     if (fcseg && !legal(cfg)) {                       // the rule knows nothing of the segments' stage count: the same tile with the legal stage depth, else any legal one
         const TileCfg want = tapgemm_f32_cfg(cfg);
         int alt = -1;
-        for (int i = 0; i < ntile; i++) if (legal(i) && (alt < 0 || (tapgemm_f32_cfg(i).rt == want.rt && tapgemm_f32_cfg(i).nt == want.nt))) alt = i;
+        for (int i = 0; i < ntile; i++) {
+            const TileCfg ti = tapgemm_f32_cfg(i);
+            if (legal(i) && (!ti.pair || want.pair) && (alt < 0 || (ti.rt == want.rt && ti.nt == want.nt && ti.pair == want.pair))) alt = i;
+        }
         if (alt < 0) return fail(c, PNN_E_ARG, "no tapgemm_f32 tile fits K segments of %d chunks", L.fc_seg_chunks);
         cfg = alt;
     }
@@ -261,13 +270,15 @@ int gemm_tiles(pnn_ctx* c, const GemmLayer& L, TapGemmParams& p, const TapGemmPa
     const TileCfg t = tapgemm_f32_cfg(cfg % ntile);
     if (tiles_out) *tiles_out = (int)((p.Cout + 32L * t.nt - 1) / (32L * t.nt));
     if (debug) fprintf(stderr, "[pnn] gemm M=%ld K=%.0f N=%d ncls=%d -> f32 cfg %d {rt %d, nt %d, kc %d}%s%s\n", M, L.k_total, p.Cout, p.ncls,
-                       cfg, t.rt, t.nt, t.kc, next ? " + fused output layer" : "",
+                       cfg, t.rt, t.nt, t.kc, t.pair ? " as paired 128 x 96 + 128 x 64 tiles" : next ? " + fused output layer" : "",
                        nseg > 1 ? (seq ? ", K segments in sequence" : ", K segments in parallel + reduce") : "");
     const int trc = timed_launch(c, 0, flops, env_profile(), [&] { return launch(cfg); },
                                  "[pnn-prof] M=%ld K=%.0f N=%d ncls=%d f32 cfg=%d rt=%d nt=%d kc=%d mf=%d us=%.1f tflops=%.1f\n", M, L.k_total,
                                  p.Cout, p.ncls, cfg, t.rt, t.nt, t.kc, t.mf);
     if (trc) return trc;
     if (nseg > 1 && !seq) c->stat_launches++;          // the reduction of the parallel form (launched by `launch`)
+    if (g_last_pair_mode == 1) c->stat_pair_launches++;
+    if (g_last_pair_mode == 2) c->stat_pair_fallbacks++;
     c->stat_gemm_flops_skipped += flops * (1.0 - g_last_issued_frac);
     return env_f32_diag() ? diag_f32_tiles(c, L, seq ? pseq : p, cfg % ntile, next != nullptr, seq ? 1 : nseg, s) : PNN_OK;   // (diagnostic library only)
 }

@@ -27,7 +27,7 @@ int choose_cfg_f32(const pnn_ctx* c, long M, int cout, int ncls, int cin, double
     const bool one_tap = (k_total == (double)cin);
     if (c->opt_f32_cfg >= 0 && c->opt_f32_cfg < tapgemm_f32_num_cfgs()) {
         const TileCfg t = tapgemm_f32_cfg((int)c->opt_f32_cfg);
-        if ((one_tap || cpt % t.kc == 0) && (!fused || tapgemm_f32_can_fuse((int)c->opt_f32_cfg))) { if (cost_out) *cost_out = 0.0; return (int)c->opt_f32_cfg; }
+        if ((one_tap || cpt % t.kc == 0) && (!fused || tapgemm_f32_can_fuse((int)c->opt_f32_cfg)) && (!t.pair || (one_tap && !fused))) { if (cost_out) *cost_out = 0.0; return (int)c->opt_f32_cfg; }
     }
     int best = -1;
     double best_cost = 1e300;
@@ -37,6 +37,7 @@ int choose_cfg_f32(const pnn_ctx* c, long M, int cout, int ncls, int cin, double
         const TileCfg t = tapgemm_f32_cfg(i);
         if (fused && !tapgemm_f32_can_fuse(i)) continue;
         if (!one_tap && cpt % t.kc) continue;
+        if (t.pair) continue;                         // the paired tiles: not by this model, see below
         const long bm = 128L * t.rt, bn = 32L * t.nt;
         const double wgs = (double)((M + bm - 1) / bm) * (double)((cout + bn - 1) / bn) * ncls;
         const double regs = tapgemm_f32_regs(i);
@@ -57,6 +58,17 @@ int choose_cfg_f32(const pnn_ctx* c, long M, int cout, int ncls, int cin, double
         if (cost < best_cost) { best_cost = cost; best = i; }
     }
     if (cost_out) *cost_out = best_cost;              // cycles, for the caller's choice between the two forms of a K-segmented layer
+    // The paired tiles (PairTile, pnn_kernels.h) where they were measured: an FC layer that keeps its output and whose 128 x 160 tiles
+    // are exactly one per CU -- all of them go through prologue and epilogue in the same microsecond.  As a 128 x 96 and a 128 x 64
+    // workgroup per CU (two waves per SIMD, the narrow one done first) the FC 8x8 layers at batch 4096 take 28.8 / 91.8 us where the one
+    // tile takes 30.7 / 95.7, the pass 0.2268 ms for 0.2333 (profiles/r07_fc_pair_ab.txt).  Elsewhere the tuner may take them.
+    if (best >= 0 && one_tap && !fused) {
+        const TileCfg t = tapgemm_f32_cfg(best);
+        const double wgs = (double)((M + 127) / 128) * (double)((cout + 159) / 160) * ncls;
+        if (t.rt == 1 && t.nt == 5 && wgs == ncu)
+            for (int i = 0; i < tapgemm_f32_num_cfgs(); i++)
+                if (tapgemm_f32_cfg(i).pair && tapgemm_f32_cfg(i).kc == t.kc) return i;
+    }
     return best;
 }
 

@@ -86,6 +86,10 @@ float pnn_mean(const pnn_ctx* ctx);
  *                              last of its five tiles to arrive) and the last transposed convolution inside the launch of the GEMM in front of it (per
  *                              block) -- two launches less per single-block call, the same bits; 0: every layer its own launch
  *   "f32_cfg"             -1   >= 0: force tile code [0, pnn_num_f32_configs()) of tapgemm_f32_kernel on every layer it is legal for
+ *                              (the last two codes: PAIRED tiles for FC layers that keep their output -- a CU's 128 x 160 share as a 128 x 96
+ *                              and a 128 x 64 workgroup resident together; off by rule, the tuner may take them)
+ *   "f32_pair_occ"         0   paired tiles: 0 ask the runtime whether two such workgroups fit a CU (one: the launch runs the one 128 x 160 tile
+ *                              instead, the same bits); N > 0: take N for its answer (tuning aid)
  *   "f32_seg_mode"         0   K segments of the deep convolution layers (> 2304 per output: summed in segments of <= 1600, whole taps,
  *                              added in order): 0 separate workgroups + a reduction launch, 1 in sequence inside the workgroups, -1 by model
  *   "f32_persist"         -1   convolution launches of 2-6 tiles per CU on two persistent workgroups per CU; 0 never; N > 0: N per CU
@@ -161,6 +165,12 @@ int pnn_arithmetic_tag(const pnn_ctx* ctx, char* out, size_t bytes);
 int pnn_num_split_configs(void);
 /* Number of configuration codes "f32_cfg" accepts (tiles of tapgemm_f32_kernel; all of them give the same bits). */
 int pnn_num_f32_configs(void);
+/* Paired tiles of tapgemm_f32_kernel: launches of this context that ran as pairs / that fell back to the one 128 x 160 tile. */
+int pnn_f32_pair_stats(const pnn_ctx* ctx, long* paired, long* fell_back);
+/* ... and the grid arithmetic of such a launch of an M x cout layer (host only, no device needed): *num_wgs = workgroups of its 1-D
+ * grid; workgroup wg < *num_wgs owns rows [*row0, *row0 + 128) and columns [*col0, *col0 + *cols), clipped to the layer; *cols = 0:
+ * it has no tile. */
+int pnn_f32_pair_tile(int M, int cout, int wg, int* num_wgs, int* row0, int* col0, int* cols);
 /* Hits / misses of the "cache_mb" prediction cache since the option was last set. */
 int pnn_cache_stats(pnn_ctx* ctx, long* hits, long* misses);
 
