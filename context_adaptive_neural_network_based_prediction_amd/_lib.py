@@ -134,7 +134,19 @@ SIGNATURES = {
                                        vp, vp] + [vp] * 10 + [ctypes.c_size_t, vp]),
     "pnn_rd_pass_signal_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(ci), ci,
                                                      ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp] + [vp] * 10 + [ctypes.c_size_t, vp]),
-    "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
+    "pnn_rd_pass_codec_slot_count": (ci, [ci, ci, ci]),
+    "pnn_rd_pass_codec_workspace_bytes": (ctypes.c_size_t, [ci, ci, ci, ci, ci]),
+    "pnn_first_pass_codec_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), vp, vp, ci, vp, vp,
+                                       vp]),
+    "pnn_rd_pass_codec_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, ci] +
+                               [vp] * 9),
+    "pnn_rd_pass_codec_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci,
+                                      vp, vp, ci] + [vp] * 10 + [ctypes.c_size_t, vp]),
+    "pnn_rd_pass_codec_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(ci), ci,
+                                                    ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, ci] + [vp] * 10 + [ctypes.c_size_t, vp]),
+    "pnn_rd_pass_mode_stats_host": (ci, [vp, ci, ci, vp, ci, ci, vp]),
+    "pnn_rd_pass_mode_stats_device": (ci, [vp, vp, ci, ci, vp, ci, ci, vp, vp]),
+    "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci),ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
 

@@ -158,6 +158,13 @@ TrQuantParams trquant_params(int width, const uint8_t* d_predictions, const uint
     return p;
 }
 
+// the codec of the second pass: 0 the switch codec, 1 the substitution codec, which HM never searches without the mode bits
+int check_codec(pnn_ctx* c, int codec, int signalling)
+{
+    if (codec != 0 && codec != 1) return fail(c, PNN_E_ARG, "codec %d is not 0 (switch) or 1 (substitution)", codec);
+    return codec && !signalling ? fail(c, PNN_E_ARG, "the substitution codec without signalling") : PNN_OK;
+}
+
 // the option rdoq of the transform coding and of the second pass: with it a caller's lambda is finite and above 0 (rdFactor divides by it)
 int check_rdoq_lambdas(pnn_ctx* c, int rdoq, const double* lambdas, int nb_qps)
 {
@@ -241,9 +248,11 @@ struct RdSignalWorkspace {
     uint64_t* rate; uint32_t* sse; uint32_t* nonzero; uint8_t* pred; uint8_t* targets; uint8_t* slot_modes; uint32_t* mode_hads; uint32_t* cand_hads;
     size_t bytes;
 };
-RdSignalWorkspace rd_signal_workspace(void* base, int width, long n, int nb_qps)
+// (codec 1, the substitution codec of DESIGN.md section 5o: K + 2 slots wherever the switch codec has K + 3)
+int signal_slots(int width, int codec) { return hevc_first_pass_list_size(width) + (codec ? msig::kExtraSlotsSubstitution : msig::kExtraSlots); }
+RdSignalWorkspace rd_signal_workspace(void* base, int width, long n, int nb_qps, int codec = 0)
 {
-    const size_t slots = (size_t)n * (hevc_first_pass_list_size(width) + msig::kExtraSlots), w2 = (size_t)width * width;
+    const size_t slots = (size_t)n * signal_slots(width, codec), w2 = (size_t)width * width;
     const size_t units = slots * (width == 64 ? 4 : 1);       // at width 64 every slot is coded as its four quadrants
     size_t at = 0;
     const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
@@ -263,20 +272,22 @@ RdSignalWorkspace rd_signal_workspace(void* base, int width, long n, int nb_qps)
 // what both forms with signalling check behind their blocks: the width (no quadrants), candidate, QPs, lambdas, outputs, scratch and --
 // read back once, the call waits for the stream -- the neighbours' modes
 int check_rd_pass_signal(pnn_ctx* c, int width, int n, const uint8_t* d_cand_pred, const int* qps, int nb_qps, const double* lambdas, int rdoq,
-                         bool any_output, const uint8_t* d_left, const uint8_t* d_above, const void* d_workspace, size_t workspace_bytes, hipStream_t s)
+                         bool any_output, const uint8_t* d_left, const uint8_t* d_above, const void* d_workspace, size_t workspace_bytes, hipStream_t s,
+                         int codec = 0)
 {
     if (n > 0 && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_pred is NULL");
-    if ((long)n * (hevc_first_pass_list_size(width) + msig::kExtraSlots) * (width == 64 ? 4 : 1) > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 candidate slots");
+    if ((long)n * signal_slots(width, codec) * (width == 64 ? 4 : 1) > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 candidate slots");
     if (!trquant::qps_ok(qps, nb_qps)) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d integers in [0, %d]", trquant::kMaxQps, trquant::kMaxQp);
     for (int i = 0; lambdas && i < nb_qps; i++)
         if (!(lambdas[i] >= 0. && lambdas[i] <= 1.7976931348623157e308)) return fail(c, PNN_E_ARG, "lambda %d is negative or not finite", i);
     if (const int rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps)) return rc;
     if (const int rc = check_some_output(c, any_output)) return rc;
     if (n == 0) return PNN_OK;
-    const size_t need = rd_signal_workspace(nullptr, width, n, nb_qps).bytes;
+    const size_t need = rd_signal_workspace(nullptr, width, n, nb_qps, codec).bytes;
     if (!d_workspace || (uintptr_t)d_workspace % 8) return fail(c, PNN_E_ARG, "d_workspace is NULL or not aligned to 8 bytes");
     if (workspace_bytes < need)
-        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_rd_pass_signal_workspace_bytes asks for %zu", workspace_bytes, need);
+        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, %s asks for %zu", workspace_bytes,
+                    codec ? "pnn_rd_pass_codec_workspace_bytes" : "pnn_rd_pass_signal_workspace_bytes", need);
     if (!d_left && !d_above) return PNN_OK;
     std::vector<uint8_t> modes((size_t)n * 2, (uint8_t)msig::kNoNeighbour);
     {
@@ -286,8 +297,9 @@ int check_rd_pass_signal(pnn_ctx* c, int width, int n, const uint8_t* d_cand_pre
         HIPCHK(c, hipStreamSynchronize(s));
     }
     for (long i = 0; i < 2L * n; i++)
-        if (!msig::neighbour_ok(modes[i], 1))
-            return fail(c, PNN_E_ARG, "%s neighbour mode %d of block %ld is not 0 .. 35 or 255", i < n ? "left" : "above", modes[i], i % n);
+        if (!msig::neighbour_ok(modes[i], !codec))
+            return fail(c, PNN_E_ARG, "%s neighbour mode %d of block %ld is not 0 .. %d or 255", i < n ? "left" : "above", modes[i], i % n,
+                        codec ? 34 : 35);
     return PNN_OK;
 }
 
@@ -299,10 +311,10 @@ int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int 
                             const double* lambdas, int sign_data_hiding, int rdoq, const uint8_t* d_left, const uint8_t* d_above,
                             uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
                             uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
-                            hipStream_t s)
+                            hipStream_t s, int codec = 0)
 {
-    const RdSignalWorkspace ws = rd_signal_workspace(d_workspace, width, n, nb_qps);
-    const int slots = hevc_first_pass_list_size(width) + msig::kExtraSlots;
+    const RdSignalWorkspace ws = rd_signal_workspace(d_workspace, width, n, nb_qps, codec);
+    const int slots = signal_slots(width, codec);
     const HevcModeHadsParams h = mode_hads_params(patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing, d_cand_pred, ws.mode_hads,
                                                   ws.cand_hads, nullptr, nullptr);
     HIPCHK(c, launch_hevc_mode_hads(h, s));
@@ -316,14 +328,14 @@ int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int 
         l.sqrt_lambda[i] = std::sqrt(lambda[i]);                                  // TComRdCost::setLambda
     }
     l.list_costs = d_first_pass_costs; l.slot_modes = d_cand_modes ? d_cand_modes : ws.slot_modes;
-    HIPCHK(c, launch_signal_list(l, s));
+    HIPCHK(c, codec ? launch_substitution_list(l, s) : launch_signal_list(l, s));
     for (int qi = 0; qi < nb_qps; qi++) {
         const size_t at = (size_t)qi * n;
         const uint8_t* slot_modes = l.slot_modes + at * slots;
         RdCandidatesParams r;
         set_blocks(r, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
         r.cand_pred = d_cand_pred; r.list_modes = slot_modes; r.cand_modes = nullptr; r.slot_pred = ws.pred; r.slot_targets = ws.targets;
-        HIPCHK(c, launch_rd_candidates_slots(r, s));
+        HIPCHK(c, codec ? launch_rd_candidates_substitution(r, s) : launch_rd_candidates_slots(r, s));
         // width 64: the slots lie there quadrant by quadrant, 4 n (K + 3) blocks of 32 x 32 under the diagonal scan, each a unit at
         // transform depth 1 (cbf context 0) -- what the w = 64 instantiation codes, with a count of levels per quadrant
         const bool quadrants = width == 64;
@@ -339,7 +351,7 @@ int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int 
         d.best_mode = d_best_mode ? d_best_mode + at : nullptr; d.best_slot = d_best_slot ? d_best_slot + at : nullptr;
         d.best_cost = d_best_cost ? d_best_cost + at : nullptr; d.best_sse = d_best_sse ? d_best_sse + at : nullptr;
         d.best_rate = d_best_rate ? d_best_rate + at : nullptr; d.best_side_rate = d_best_side_rate ? d_best_side_rate + at : nullptr;
-        HIPCHK(c, launch_rd_decide_signal(d, s));
+        HIPCHK(c, codec ? launch_rd_decide_substitution(d, s) : launch_rd_decide_signal(d, s));
     }
     c->stat_launches += 2 + 3 * nb_qps;
     return PNN_OK;
@@ -787,6 +799,104 @@ int pnn_rd_pass_signal_picture_pairs_device(pnn_ctx* c, int width, const uint8_t
     return rd_pass_signal_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
                                    smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs,
                                    d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s);
+}
+
+// ---- the codec as an argument (include/pnn_hip.h, "the substitution codec") ----
+size_t pnn_rd_pass_codec_workspace_bytes(int width, int n, int nb_qps, int signalling, int codec)
+{
+    if (codec == 0) return pnn_rd_pass_signal_workspace_bytes(width, n, nb_qps, signalling);
+    if (codec != 1 || !signalling || width_index(width) < 0 || n < 0 || nb_qps < 1 || nb_qps > trquant::kMaxQps) return 0;
+    return rd_signal_workspace(nullptr, width, n, nb_qps, 1).bytes;
+}
+
+int pnn_rd_pass_codec_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                             const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                             int rdoq, int signalling, const uint8_t* d_left_modes, const uint8_t* d_above_modes, int codec, uint8_t* d_cand_modes,
+                             double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                             uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
+                             size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (codec == 0)
+        return pnn_rd_pass_signal_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, d_cand_pred, smoothing, qps, nb_qps, lambdas,
+                                         sign_data_hiding, rdoq, signalling, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode,
+                                         d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace,
+                                         workspace_bytes, stream);
+    int rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_codec(c, codec, signalling)) || (rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) ||
+        (rc = check_smoothing(c, smoothing))) return rc;
+    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = check_rd_pass_signal(c, width, n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
+                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
+                                       d_first_pass_costs || d_best_side_rate,
+                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s, 1))) return rc;
+    if (n == 0) return PNN_OK;
+    reset_stats(c);
+    return rd_pass_signal_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
+                                   lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot,
+                                   d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s, 1);
+}
+
+int pnn_rd_pass_codec_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                           int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                           const double* lambdas, int sign_data_hiding, int rdoq, int signalling, const uint8_t* d_left_modes,
+                                           const uint8_t* d_above_modes, int codec, uint8_t* d_cand_modes, double* d_cand_costs,
+                                           uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                                           uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
+                                           size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (codec == 0)
+        return pnn_rd_pass_signal_picture_pairs_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols,
+                                                       positions, mask_w, mask_h, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding,
+                                                       rdoq, signalling, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode,
+                                                       d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate,
+                                                       d_workspace, workspace_bytes, stream);
+    int rc;
+    long n;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_codec(c, codec, signalling)) ||
+        (rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+        (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n))) return rc;
+    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = check_rd_pass_signal(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
+                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
+                                       d_first_pass_costs || d_best_side_rate,
+                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s, 1))) return rc;
+    if (n == 0) return PNN_OK;
+    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
+    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
+    reset_stats(c);
+    return rd_pass_signal_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
+                                   smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs,
+                                   d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s,
+                                   1);
+}
+
+// The mode statistics of a second pass whose slot modes and winners are on the device: the output is zeroed on the stream, then one
+// launch adds every workgroup's counts to it.
+int pnn_rd_pass_mode_stats_device(pnn_ctx* c, const uint8_t* d_slot_modes, int per_qp, int slots, const uint8_t* d_best_mode, int n, int nb_qps,
+                                  uint32_t* d_stats, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (n < 0) return fail(c, PNN_E_ARG, "negative batch size");
+    if (slots < 1 || slots > 16) return fail(c, PNN_E_ARG, "%d slots per block: not 1 to 16", slots);
+    if (nb_qps < 1 || nb_qps > trquant::kMaxQps) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d", trquant::kMaxQps);
+    if (!d_stats) return fail(c, PNN_E_ARG, "the output is NULL");
+    if ((uintptr_t)d_stats % 4) return fail(c, PNN_E_ARG, "the output is not aligned to 4 bytes");
+    if (n > 0 && (!d_slot_modes || !d_best_mode)) return fail(c, PNN_E_ARG, "the slot modes or the best modes are NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    reset_stats(c);
+    HIPCHK(c, hipMemsetAsync(d_stats, 0, (size_t)nb_qps * 3 * 36 * 4, s));
+    if (n == 0) return PNN_OK;
+    ModeStatsParams p;
+    p.slot_modes = d_slot_modes; p.best_mode = d_best_mode; p.per_qp = per_qp != 0; p.S = slots; p.N = n; p.nb_qps = nb_qps; p.stats = d_stats;
+    HIPCHK(c, launch_mode_stats(p, s));
+    c->stat_launches++;
+    return PNN_OK;
 }
 
 int pnn_score_f32_device(pnn_ctx* c, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,

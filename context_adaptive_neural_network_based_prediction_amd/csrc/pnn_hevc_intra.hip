@@ -415,12 +415,16 @@ constexpr int kRdThreads = 256;
 
 // SLOTS: list_modes holds the block's K + 3 slot modes as signal_list_kernel left them, [N][K + 3], and the
 // kernel derives nothing: it predicts them (cand_modes is not written).  Everything else is as it stands.
-template <int W, bool PIC, bool SMOOTH, bool SLOTS = false>
+// SUBST (with SLOTS): the substitution codec's K + 2 slots, in which mode 18 is the candidate's prediction and 35
+// does not occur.  Without it the statements are the ones they were.
+template <int W, bool PIC, bool SMOOTH, bool SLOTS = false, bool SUBST = false>
 __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandidatesParams p)
 {
     static_assert(!SMOOTH || W == 8 || W == 16 || W == 32, "no mode smooths at w = 4 and 64");
     constexpr int G = W >= 32 ? 1 : 1024 / (W * W);                // blocks per workgroup: trquant_kernel's
-    constexpr int K = W <= 8 ? 8 : 3, K1 = SLOTS ? K + msig::kExtraSlots : K + 1;   // list entries, slots
+    static_assert(!SUBST || SLOTS, "the substitution codec has the slots form only");
+    constexpr int K = W <= 8 ? 8 : 3, K1 = SLOTS ? K + (SUBST ? msig::kExtraSlotsSubstitution : msig::kExtraSlots) : K + 1;   // list entries, slots
+    constexpr int kCand = SUBST ? msig::kSubstitutedMode : 35;     // the mode whose prediction is the caller's candidate
     constexpr int RS = 4 * W + 1, TS = W * W + 4;                  // LDS strides, those of stage_blocks
     __shared__ int ref[G * RS];
     __shared__ int ref_s[SMOOTH ? G * RS : 1];
@@ -439,7 +443,7 @@ __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandi
         for (int i = tid; i < G * K1; i += kRdThreads)
             if (blk0 + i / K1 < p.N) {
                 const int m = p.list_modes[blk0 * K1 + i];
-                slot_mode[i] = m > 35 ? kRdUnusedSlot : m;
+                slot_mode[i] = m > (SUBST ? 34 : 35) ? kRdUnusedSlot : m;
             }
     } else if (tid < G && blk0 + tid < p.N) {
         bool listed = false;
@@ -466,7 +470,7 @@ __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandi
             const int m = slot_mode[g * K1 + i / (W * W) % K1];
             const int t = tgt[g * TS + e];
             int v = t;
-            if (m == 35) {
+            if (m == kCand) {
                 v = p.cand_pred[(size_t)(blk0 + g) * W * W + e];
             } else if (m < 35) {
                 const int* rf = ref + g * RS + 2 * W;
@@ -483,7 +487,7 @@ __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandi
         const int m = slot_mode[g * K1 + i / (W * W) % K1];
         const int t = tgt[g * TS + e];
         int v = t;
-        if (m == 35) {
+        if (m == kCand) {
             v = p.cand_pred[(size_t)(blk0 + g) * W * W + e];
         } else if (m < 35) {
             const int* rf = (SMOOTH && mode_smooths<W>(m) ? ref_s : ref) + g * RS + 2 * W;
@@ -563,6 +567,33 @@ __global__ __launch_bounds__(kRdThreads) void signal_list_kernel(const SignalLis
     for (int t = 0; t < msig::kExtraSlots; t++) p.slot_modes[(size_t)i * S + K + t] = (uint8_t)extra[t];
 }
 
+// The substitution codec's first pass: signal_list_kernel over HM's 35 modes, mode 18's Hadamard cost being the
+// candidate's, without a flag bin and with K + 2 slots -- msig::list_and_slots_substitution, the lines the host twin compiles.
+template <int K>
+__global__ __launch_bounds__(kRdThreads) void substitution_list_kernel(const SignalListParams p)
+{
+    constexpr int S = K + msig::kExtraSlotsSubstitution;
+    const long i = (long)blockIdx.x * kRdThreads + threadIdx.x;
+    if (i >= (long)p.nb_qps * p.N) return;
+    const int qi = (int)(i / p.N);
+    const long b = i - (long)qi * p.N;
+    const msig::Mpm mpm = msig::derive_mpm(msig::neighbour_dir(p.left ? p.left[b] : msig::kNoNeighbour),
+                                           msig::neighbour_dir(p.above ? p.above[b] : msig::kNoNeighbour));
+    const uint32_t* hads = p.mode_hads + b * 35;
+    const uint32_t cand = p.cand_hads[b];
+    int lm[K], extra[msig::kExtraSlotsSubstitution];
+    double lc[K];
+    msig::list_and_slots_substitution<K>([&](int m) { return m == msig::kSubstitutedMode ? cand : hads[m]; }, mpm, p.bits[qi], p.sqrt_lambda[qi],
+                                         lm, lc, extra);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        if (p.list_costs) p.list_costs[(size_t)i * K + j] = lc[j];
+        p.slot_modes[(size_t)i * S + j] = (uint8_t)lm[j];
+    }
+#pragma unroll
+    for (int t = 0; t < msig::kExtraSlotsSubstitution; t++) p.slot_modes[(size_t)i * S + K + t] = (uint8_t)extra[t];
+}
+
 // rd_decide_kernel with the side bits, for the blocks of ONE QP (the slots are that QP's): J = D + lambda ((mode bits + cbf bin +
 // rate) >> 15), one shift over the sum as HM's counter does over one candidate; the cbf bin follows the slot's count of nonzero levels.
 __device__ inline double rd_cost_bits(uint32_t d, uint64_t whole_bits, double lambda)
@@ -573,8 +604,9 @@ __device__ inline double rd_cost_bits(uint32_t d, uint64_t whole_bits, double la
 }
 
 // Q: transform units per slot -- 1, or the 4 quadrants of a 64 x 64 block, each coded as a 32 x 32 block of its own: D and the rate
-// add up, and every quadrant pays its own cbf bin.
-template <int S, int Q = 1>
+// add up, and every quadrant pays its own cbf bin.  FLAG: 1 with the switch codec's PNN flag in the mode bits, 0 without (the
+// substitution codec, whose S is K + 2).
+template <int S, int Q = 1, int FLAG = 1>
 __global__ __launch_bounds__(kRdThreads) void rd_decide_signal_kernel(const RdDecideSignalParams p)
 {
     const long b = (long)blockIdx.x * kRdThreads + threadIdx.x;
@@ -600,7 +632,7 @@ __global__ __launch_bounds__(kRdThreads) void rd_decide_signal_kernel(const RdDe
         uint64_t side = 0;
         double j = __builtin_inf();
         if (m != kRdUnusedSlot) {
-            side = msig::mode_frac_bits(m, mpm, p.bits, 1) + cbf;
+            side = msig::mode_frac_bits(m, mpm, p.bits, FLAG) + cbf;
             j = rd_cost_bits(d, (side + r) >> 15, p.lambda);
         }
         if (p.cand_costs) p.cand_costs[slot0 + s] = j;
@@ -614,7 +646,93 @@ __global__ __launch_bounds__(kRdThreads) void rd_decide_signal_kernel(const RdDe
     if (p.best_side_rate) p.best_side_rate[b] = best_side;
 }
 
+// The mode statistics of a second pass: per QP three histograms over the modes 0 .. 35 -- the mode occupies a used
+// slot, the mode is in slot 0, the mode wins -- as stats [nb_qps][3][36].  One lane per (QP, block), the QP in blockIdx.y; the slot
+// modes are [N][S] for all QPs or, per_qp, [nb_qps][N][S]; a value above 35 (255: unused slot, no winner) counts nowhere.  Every
+// workgroup counts into LDS and adds its nonzero bins to the output, which the launcher's caller zeroed on the stream: integer sums,
+// so the order of the atomics does not show.
+constexpr int kStatsBins = 3 * 36;
+__global__ __launch_bounds__(kRdThreads) void mode_stats_kernel(const ModeStatsParams p)
+{
+    __shared__ uint32_t hist[kStatsBins];
+    const int tid = threadIdx.x, qi = blockIdx.y;
+    for (int i = tid; i < kStatsBins; i += kRdThreads) hist[i] = 0;
+    __syncthreads();
+    const long b = (long)blockIdx.x * kRdThreads + tid;
+    if (b < p.N) {
+        const uint8_t* slots = p.slot_modes + ((p.per_qp ? (size_t)qi * p.N : 0) + b) * p.S;
+        for (int s = 0; s < p.S; s++) {
+            const int m = slots[s];
+            if (m > 35) continue;
+            atomicAdd(&hist[m], 1u);
+            if (s == 0) atomicAdd(&hist[36 + m], 1u);
+        }
+        const int winner = p.best_mode[(size_t)qi * p.N + b];
+        if (winner <= 35) atomicAdd(&hist[72 + winner], 1u);
+    }
+    __syncthreads();
+    for (int i = tid; i < kStatsBins; i += kRdThreads)
+        if (hist[i]) atomicAdd(&p.stats[(size_t)qi * kStatsBins + i], hist[i]);
+}
+
 }  // namespace
+
+hipError_t launch_mode_stats(const ModeStatsParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    if (!p.slot_modes || !p.best_mode || !p.stats || p.S < 1 || p.nb_qps < 1 || p.nb_qps > trquant::kMaxQps) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((p.N + kRdThreads - 1) / kRdThreads), (unsigned)p.nb_qps), block(kRdThreads);
+    hipLaunchKernelGGL(mode_stats_kernel, grid, block, 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_substitution_list(const SignalListParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    if (!p.mode_hads || !p.cand_hads || !p.slot_modes || p.nb_qps < 1 || p.nb_qps > trquant::kMaxQps) return hipErrorInvalidValue;
+    const long total = (long)p.nb_qps * p.N;
+    const dim3 grid((unsigned)((total + kRdThreads - 1) / kRdThreads)), block(kRdThreads);
+    if (p.w <= 8) hipLaunchKernelGGL((substitution_list_kernel<8>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((substitution_list_kernel<3>), grid, block, 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_rd_candidates_substitution(const RdCandidatesParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    const int g = rd_candidates_blocks_per_workgroup(p.w);
+    const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kRdThreads);
+    const bool pic = p.patterns == nullptr;
+    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+    if (!p.cand_pred || !p.list_modes || !p.slot_pred || !p.slot_targets) return hipErrorInvalidValue;
+    if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
+#define PNN_RD_LAUNCH(W_, SMOOTH_) \
+    if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, true, true>), grid, block, 0, s, p); \
+    else hipLaunchKernelGGL((rd_candidates_kernel<W_, false, SMOOTH_, true, true>), grid, block, 0, s, p);
+#define PNN_RD_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_RD_LAUNCH(W_, true) } else { PNN_RD_LAUNCH(W_, false) }
+    switch (p.w) {                                     // (width 64 writes each slot as its four quadrants, 32 x 32 blocks)
+    case 4: PNN_RD_LAUNCH(4, false) break;
+    case 8: PNN_RD_LAUNCH_SMOOTH(8) break;
+    case 16: PNN_RD_LAUNCH_SMOOTH(16) break;
+    case 32: PNN_RD_LAUNCH_SMOOTH(32) break;
+    case 64: PNN_RD_LAUNCH(64, false) break;
+    default: return hipErrorInvalidValue;
+    }
+#undef PNN_RD_LAUNCH_SMOOTH
+#undef PNN_RD_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_rd_decide_substitution(const RdDecideSignalParams& p, hipStream_t s)
+{
+    if (p.N <= 0) return hipSuccess;
+    if (!p.sse || !p.rate || !p.nonzero || !p.slot_modes || p.cbf_ctx < 0 || p.cbf_ctx > 1) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((p.N + kRdThreads - 1) / kRdThreads)), block(kRdThreads);
+    if (p.w <= 8) hipLaunchKernelGGL((rd_decide_signal_kernel<8 + msig::kExtraSlotsSubstitution, 1, 0>), grid, block, 0, s, p);
+    else if (p.w == 64) hipLaunchKernelGGL((rd_decide_signal_kernel<3 + msig::kExtraSlotsSubstitution, 4, 0>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((rd_decide_signal_kernel<3 + msig::kExtraSlotsSubstitution, 1, 0>), grid, block, 0, s, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_signal_list(const SignalListParams& p, hipStream_t s)
 {

@@ -373,6 +373,16 @@ struct RdDecideSignalParams {
     uint64_t* best_side_rate;
 };
 hipError_t launch_rd_decide_signal(const RdDecideSignalParams& p, hipStream_t s);
+// The substitution codec's forms of the three (msig::list_and_slots_substitution): K + 2 slots wherever the ones
+// above have K + 3, HM's 35 modes with mode 18's Hadamard cost and prediction the candidate's, no flag bin in the mode bits.
+hipError_t launch_substitution_list(const SignalListParams& p, hipStream_t s);
+hipError_t launch_rd_candidates_substitution(const RdCandidatesParams& p, hipStream_t s);
+hipError_t launch_rd_decide_substitution(const RdDecideSignalParams& p, hipStream_t s);
+// The mode statistics of a second pass: slot_modes [N][S] (per_qp 0: shared by the QPs) or [nb_qps][N][S], best_mode [nb_qps][N];
+// stats uint32 [nb_qps][3][36] (used slot, slot 0, winner; a mode above 35 counts nowhere), ZEROED by the caller on the stream: the
+// kernel adds to it.
+struct ModeStatsParams { const uint8_t* slot_modes; const uint8_t* best_mode; int per_qp; int S; int N; int nb_qps; uint32_t* stats; };
+hipError_t launch_mode_stats(const ModeStatsParams& p, hipStream_t s);
 
 // Open-loop transform coding (pnn_trquant.hip): N predictions and targets [N][w][w] uint8, nb_qps <= 8 QPs whose constants the host has
 // worked out (trquant::qp_consts at the unit size of w).  Outputs, each NULL or [nb_qps][N] uint32: the SSE of the reconstruction, the

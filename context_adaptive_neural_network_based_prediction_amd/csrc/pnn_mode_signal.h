@@ -9,7 +9,9 @@
 // Cold contexts, as the rate of the levels (section 5j): the PNN flag's context and prev_intra_luma_pred_flag's start every unit from
 // the state an I slice of the QP begins with, and so do the two cbf contexts.  LEFT OUT: part size, split and subdivision flags (equal
 // for all candidates of a block), the interleaving of the four units' flags in an N x N coding unit (the counter adds the same bins in
-// any order), chroma, running contexts, the substitution codec's signalling.
+// any order), chroma, running contexts.
+// The substitution codec (hm_16_15_substitution) keeps HM's 35 modes and signalling -- derive_mpm without a
+// neighbour 35, mode_frac_bits with pnn_flag 0 -- and predicts mode 18 with the PNN: list_and_slots_substitution below.
 #pragma once
 
 #include "pnn_cabac_tables.h"
@@ -132,6 +134,50 @@ PNN_TQ_HD inline void list_and_slots(Satd satd, const Mpm& mpm, const FlagBits& 
         if (missing) {
 #pragma unroll
             for (int t = 0; t < kExtraSlots; t++)
+                if (count == t) extra[t] = cand;
+            count++;
+        }
+    }
+}
+
+// The substitution codec's first pass of one block at one QP (hm_16_15_substitution, TEncSearch.cpp:2325-2430): HM's own loop.  satd(i):
+// the Hadamard cost of mode i, 0 .. 34 (18: the candidate's, whose prediction stands in that mode's place).  xUpdateCandList over modes
+// 0 .. 34 in that order on SATD + (bits without a flag bin >> 15) sqrt(lambda), then the slots: the K list entries, mpm[0 ..
+// num_append - 1] where the list lacks them, 255 behind them.  Nothing is appended for the PNN: 18 is coded if listed or a missing MPM.
+constexpr int kSubstitutedMode = 18, kNbRegularModes = 35;
+constexpr int kExtraSlotsSubstitution = 2;        // two most probable modes behind the K list entries
+template <int K, typename Satd>
+PNN_TQ_HD inline void list_and_slots_substitution(Satd satd, const Mpm& mpm, const FlagBits& f, double sqrt_lambda, int (&list_mode)[K],
+                                                  double (&list_cost)[K], int (&extra)[kExtraSlotsSubstitution])
+{
+#pragma unroll
+    for (int j = 0; j < K; j++) { list_cost[j] = __builtin_inf(); list_mode[j] = kUnusedSlot; }
+#pragma unroll 1
+    for (int i = 0; i < kNbRegularModes; i++) {
+        double ci = first_pass_cost(satd(i), mode_frac_bits(i, mpm, f, 0), sqrt_lambda);
+        int mi = i;
+        bool in = false;
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            in = in || ci < list_cost[j];
+            const double tc = list_cost[j];
+            const int tm = list_mode[j];
+            list_cost[j] = in ? ci : tc; list_mode[j] = in ? mi : tm;
+            ci = in ? tc : ci; mi = in ? tm : mi;
+        }
+    }
+    int count = 0;
+#pragma unroll
+    for (int t = 0; t < kExtraSlotsSubstitution; t++) extra[t] = kUnusedSlot;
+#pragma unroll
+    for (int a = 0; a < kExtraSlotsSubstitution; a++) {
+        const int cand = a == 0 ? mpm.m0 : mpm.m1;
+        bool missing = a == 0 || mpm.num_append == 2;
+#pragma unroll
+        for (int j = 0; j < K; j++) missing = missing && list_mode[j] != cand;
+        if (missing) {
+#pragma unroll
+            for (int t = 0; t < kExtraSlotsSubstitution; t++)
                 if (count == t) extra[t] = cand;
             count++;
         }

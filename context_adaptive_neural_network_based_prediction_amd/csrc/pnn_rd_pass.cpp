@@ -182,6 +182,39 @@ void first_pass_signal(const uint32_t* hads, const uint32_t* cand, int n, const 
     }
 }
 
+// ... and the substitution codec's: 35 modes, mode 18's cost the candidate's, slots [n][K + 2]
+template <int K>
+void first_pass_substitution(const uint32_t* hads, const uint32_t* cand, int n, const uint8_t* left, const uint8_t* above, const msig::FlagBits& f,
+                             double sqrt_lambda, uint8_t* list_modes, double* list_costs, uint8_t* slot_modes)
+{
+    constexpr int S = K + msig::kExtraSlotsSubstitution;
+    for (long b = 0; b < n; b++) {
+        int lm[K], extra[msig::kExtraSlotsSubstitution];
+        double lc[K];
+        msig::list_and_slots_substitution<K>([&](int i) { return i == msig::kSubstitutedMode ? cand[b] : hads[b * 35 + i]; },
+                                             block_mpm(left, above, b), f, sqrt_lambda, lm, lc, extra);
+        for (int j = 0; j < K; j++) {
+            if (list_modes) list_modes[b * K + j] = (uint8_t)lm[j];
+            if (list_costs) list_costs[b * K + j] = lc[j];
+            if (slot_modes) slot_modes[b * S + j] = (uint8_t)lm[j];
+        }
+        for (int t = 0; slot_modes && t < msig::kExtraSlotsSubstitution; t++) slot_modes[b * S + K + t] = (uint8_t)extra[t];
+    }
+}
+
+int extra_slots(int codec) { return codec ? msig::kExtraSlotsSubstitution : msig::kExtraSlots; }
+
+// the bodies of pnn_first_pass_signal_host / pnn_rd_pass_signal_host (codec 0, under their names) and of the substitution codec's
+// forms of the two (codec 1, under the *_codec_* names)
+int first_pass_body(const char* entry, int codec, const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                    const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, const uint8_t* left_modes,
+                    const uint8_t* above_modes, uint8_t* list_modes, double* list_costs, uint8_t* slot_modes);
+int rd_pass_body(const char* entry, int codec, const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                 const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding, int rdoq,
+                 const uint8_t* left_modes, const uint8_t* above_modes, uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode,
+                 uint8_t* best_slot, double* best_cost, uint32_t* best_sse, uint64_t* best_rate, double* first_pass_costs,
+                 uint64_t* best_side_rate);
+
 }  // namespace
 
 extern "C" int pnn_rd_pass_slot_count(int width, int signalling)
@@ -215,7 +248,16 @@ extern "C" int pnn_first_pass_signal_host(const uint8_t* patterns, int pattern_h
                                           const uint8_t* left_modes, const uint8_t* above_modes, uint8_t* list_modes, double* list_costs,
                                           uint8_t* slot_modes)
 {
-    const char* entry = "pnn_first_pass_signal_host";
+    return first_pass_body("pnn_first_pass_signal_host", 0, patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps,
+                           lambdas, left_modes, above_modes, list_modes, list_costs, slot_modes);
+}
+
+namespace {
+
+int first_pass_body(const char* entry, int codec, const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                    const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, const uint8_t* left_modes,
+                    const uint8_t* above_modes, uint8_t* list_modes, double* list_costs, uint8_t* slot_modes)
+{
     const int k = pnn_first_pass_list_size(width);
     if (k < 0) return refuse_signal(entry, "the width of the target patch is not 4, 8, 16, 32 or 64.");
     if (n < 0) return refuse_signal(entry, "negative batch size.");
@@ -226,24 +268,28 @@ extern "C" int pnn_first_pass_signal_host(const uint8_t* patterns, int pattern_h
         if (qps[qi] < 0 || qps[qi] > 51) return refuse_signal(entry, "the QPs are not 1 to 8 integers in [0, 51].");
         if (lambdas && !(std::isfinite(lambdas[qi]) && lambdas[qi] >= 0.)) return refuse_signal(entry, "a lambda is negative or not finite.");
     }
-    if (!neighbours_ok(left_modes, n, 1) || !neighbours_ok(above_modes, n, 1))
-        return refuse_signal(entry, "a neighbour mode is not 0 .. 35 or 255.");
+    if (!neighbours_ok(left_modes, n, !codec) || !neighbours_ok(above_modes, n, !codec))
+        return refuse_signal(entry, codec ? "a neighbour mode is not 0 .. 34 or 255." : "a neighbour mode is not 0 .. 35 or 255.");
     std::vector<uint32_t> hads((size_t)std::max(n, 1) * 35), cand((size_t)std::max(n, 1));
     if (pnn_hevc_mode_hads_hm_host(patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, hads.data(),
                                    cand_pred ? cand.data() : nullptr, nullptr, nullptr) != PNN_OK)                  // (no candidate: no block)
         return refuse_signal(entry, "the first pass refused the arguments (pattern sides, NULL inputs or smoothing).");
-    const int s = k + msig::kExtraSlots;
+    const int s = k + extra_slots(codec);
     for (int qi = 0; qi < nb_qps; qi++) {
         const msig::FlagBits f = msig::flag_bits(qps[qi]);
         const double sqrt_lambda = std::sqrt(lambdas ? lambdas[qi] : pnn_hm_intra_lambda(qps[qi]));   // TComRdCost::setLambda
         uint8_t* lm = list_modes ? list_modes + (size_t)qi * n * k : nullptr;
         double* lc = list_costs ? list_costs + (size_t)qi * n * k : nullptr;
         uint8_t* sm = slot_modes ? slot_modes + (size_t)qi * n * s : nullptr;
-        if (k == 8) first_pass_signal<8>(hads.data(), cand.data(), n, left_modes, above_modes, f, sqrt_lambda, lm, lc, sm);
+        if (codec && k == 8) first_pass_substitution<8>(hads.data(), cand.data(), n, left_modes, above_modes, f, sqrt_lambda, lm, lc, sm);
+        else if (codec) first_pass_substitution<3>(hads.data(), cand.data(), n, left_modes, above_modes, f, sqrt_lambda, lm, lc, sm);
+        else if (k == 8) first_pass_signal<8>(hads.data(), cand.data(), n, left_modes, above_modes, f, sqrt_lambda, lm, lc, sm);
         else first_pass_signal<3>(hads.data(), cand.data(), n, left_modes, above_modes, f, sqrt_lambda, lm, lc, sm);
     }
     return PNN_OK;
 }
+
+}  // namespace
 
 extern "C" int pnn_rd_pass_signal_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
                                        const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas,
@@ -257,6 +303,20 @@ extern "C" int pnn_rd_pass_signal_host(const uint8_t* patterns, int pattern_h, i
         return pnn_rd_pass_rdoq_host(patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding,
                                      rdoq, cand_modes, cand_costs, best_mode, best_slot, best_cost, best_sse, best_rate);
     }
+    return rd_pass_body(entry, 0, patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq,
+                        left_modes, above_modes, cand_modes, cand_costs, best_mode, best_slot, best_cost, best_sse, best_rate, first_pass_costs,
+                        best_side_rate);
+}
+
+namespace {
+
+int rd_pass_body(const char* entry, int codec, const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                 const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding, int rdoq,
+                 const uint8_t* left_modes, const uint8_t* above_modes, uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode,
+                 uint8_t* best_slot, double* best_cost, uint32_t* best_sse, uint64_t* best_rate, double* first_pass_costs,
+                 uint64_t* best_side_rate)
+{
+    const int candidate = codec ? msig::kSubstitutedMode : kCandidate;            // the mode the caller's prediction stands for
     const int k = pnn_first_pass_list_size(width);
     if (k < 0) return refuse_signal(entry, "the width of the target patch is not 4, 8, 16, 32 or 64.");
     if (!cand_modes && !cand_costs && !best_mode && !best_slot && !best_cost && !best_sse && !best_rate && !first_pass_costs && !best_side_rate)
@@ -264,10 +324,11 @@ extern "C" int pnn_rd_pass_signal_host(const uint8_t* patterns, int pattern_h, i
     for (int qi = 0; rdoq && lambdas && qps && qi < nb_qps && qi < 8; qi++)
         if (!(lambdas[qi] > 0.)) return refuse_signal(entry, "RDOQ with a lambda that is not above 0.");
     // the lists and slots of every QP, which also checks everything else but the outputs
-    const int s = k + msig::kExtraSlots;
+    const int s = k + extra_slots(codec);
     std::vector<uint8_t> slots_all((size_t)std::max(nb_qps, 1) * std::max(n, 1) * s);
-    if (const int rc = pnn_first_pass_signal_host(patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas,
-                                                  left_modes, above_modes, nullptr, first_pass_costs, slots_all.data()))
+    if (const int rc = first_pass_body(codec ? "pnn_first_pass_codec_host" : "pnn_first_pass_signal_host", codec, patterns, pattern_h, pattern_w, targets,
+                                       width, n, cand_pred, smoothing, qps, nb_qps, lambdas, left_modes, above_modes, nullptr, first_pass_costs,
+                                       slots_all.data()))
         return rc;
     if (n == 0) return PNN_OK;
     const size_t w2 = (size_t)width * width, pattern = (size_t)pattern_h * pattern_w;
@@ -290,7 +351,7 @@ extern "C" int pnn_rd_pass_signal_host(const uint8_t* patterns, int pattern_h, i
                     const int m = slot_modes[b * s + j];
                     uint8_t* out = pred.data() + (i * s + j) * w2;
                     std::copy(targets + b * w2, targets + (b + 1) * w2, tgt.data() + (i * s + j) * w2);
-                    if (m == kCandidate) std::copy(cand_pred + b * w2, cand_pred + (b + 1) * w2, out);
+                    if (m == candidate) std::copy(cand_pred + b * w2, cand_pred + (b + 1) * w2, out);
                     else if (m == kUnused) std::copy(targets + b * w2, targets + (b + 1) * w2, out);
                     else if (pnn_hevc_intra_predict_hm(patterns + b * pattern, pattern_h, pattern_w, width, m, smoothing, out) != 0)
                         return refuse_signal(entry, "the predictor refused a listed mode.");
@@ -329,7 +390,7 @@ extern "C" int pnn_rd_pass_signal_host(const uint8_t* patterns, int pattern_h, i
                     uint64_t side = 0;
                     double cost = std::numeric_limits<double>::infinity();
                     if (m != kUnused) {
-                        side = msig::mode_frac_bits(m, mpm, f, 1);
+                        side = msig::mode_frac_bits(m, mpm, f, codec ? 0 : 1);
                         if (width == 64)
                             for (int q = 0; q < 4; q++) side += msig::side_frac_bits(0, f, ctx, quadrant_coded[(i * s + j) * 4 + q]);
                         else side += msig::side_frac_bits(0, f, ctx, nonzero[i * s + j]);
@@ -348,6 +409,74 @@ extern "C" int pnn_rd_pass_signal_host(const uint8_t* patterns, int pattern_h, i
             }
         }
         if (cand_modes) std::copy(slot_modes, slot_modes + (size_t)n * s, cand_modes + (size_t)qi * n * s);
+    }
+    return PNN_OK;
+}
+
+}  // namespace
+
+// ---- The codec as an argument (include/pnn_hip.h, "the substitution codec") ----
+extern "C" int pnn_rd_pass_codec_slot_count(int width, int signalling, int codec)
+{
+    if (codec == 0) return pnn_rd_pass_slot_count(width, signalling);
+    const int k = pnn_first_pass_list_size(width);
+    return codec != 1 || !signalling || k < 0 ? -1 : k + msig::kExtraSlotsSubstitution;
+}
+
+extern "C" int pnn_first_pass_codec_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                                         const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas,
+                                         const uint8_t* left_modes, const uint8_t* above_modes, int codec, uint8_t* list_modes, double* list_costs,
+                                         uint8_t* slot_modes)
+{
+    if (codec == 0)
+        return pnn_first_pass_signal_host(patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas, left_modes,
+                                          above_modes, list_modes, list_costs, slot_modes);
+    if (codec != 1) return refuse_signal("pnn_first_pass_codec_host", "the codec is not 0 (switch) or 1 (substitution).");
+    return first_pass_body("pnn_first_pass_codec_host", 1, patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas,
+                           left_modes, above_modes, list_modes, list_costs, slot_modes);
+}
+
+extern "C" int pnn_rd_pass_codec_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                                      const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas,
+                                      int sign_data_hiding, int rdoq, int signalling, const uint8_t* left_modes, const uint8_t* above_modes, int codec,
+                                      uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode, uint8_t* best_slot, double* best_cost,
+                                      uint32_t* best_sse, uint64_t* best_rate, double* first_pass_costs, uint64_t* best_side_rate)
+{
+    const char* entry = "pnn_rd_pass_codec_host";
+    if (codec == 0)
+        return pnn_rd_pass_signal_host(patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding,
+                                       rdoq, signalling, left_modes, above_modes, cand_modes, cand_costs, best_mode, best_slot, best_cost, best_sse,
+                                       best_rate, first_pass_costs, best_side_rate);
+    if (codec != 1) return refuse_signal(entry, "the codec is not 0 (switch) or 1 (substitution).");
+    if (!signalling) return refuse_signal(entry, "the substitution codec without signalling: HM never searches without the mode bits.");
+    return rd_pass_body(entry, 1, patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq,
+                        left_modes, above_modes, cand_modes, cand_costs, best_mode, best_slot, best_cost, best_sse, best_rate, first_pass_costs,
+                        best_side_rate);
+}
+
+// The mode statistics (include/pnn_hip.h, "mode statistics"): the yardstick of mode_stats_kernel, three plain counts.
+extern "C" int pnn_rd_pass_mode_stats_host(const uint8_t* slot_modes, int per_qp, int slots, const uint8_t* best_mode, int n, int nb_qps,
+                                           uint32_t* stats)
+{
+    const char* entry = "pnn_rd_pass_mode_stats_host";
+    if (n < 0) return refuse_signal(entry, "negative batch size.");
+    if (slots < 1 || slots > 16) return refuse_signal(entry, "the slots per block are not 1 to 16.");
+    if (nb_qps < 1 || nb_qps > 8) return refuse_signal(entry, "the QPs are not 1 to 8.");
+    if (!stats) return refuse_signal(entry, "the output is NULL.");
+    if (n > 0 && (!slot_modes || !best_mode)) return refuse_signal(entry, "the slot modes or the best modes are NULL.");
+    std::fill(stats, stats + (size_t)nb_qps * 3 * 36, 0u);
+    for (int qi = 0; qi < nb_qps; qi++) {
+        uint32_t* out = stats + (size_t)qi * 3 * 36;
+        for (long b = 0; b < n; b++) {
+            const uint8_t* row = slot_modes + ((per_qp ? (size_t)qi * n : 0) + b) * slots;
+            for (int j = 0; j < slots; j++) {
+                if (row[j] > 35) continue;
+                out[row[j]]++;
+                if (j == 0) out[36 + row[j]]++;
+            }
+            const int winner = best_mode[(size_t)qi * n + b];
+            if (winner <= 35) out[72 + winner]++;
+        }
     }
     return PNN_OK;
 }

@@ -184,7 +184,7 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                               tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
                               transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False, transform_rdoq=False,
-                              rd_pass_signalling=False, rd_pass_neighbour_modes=None):
+                              rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -258,6 +258,18 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     'rd_pass_candidates' and 'rd_pass_costs' per QP with K + 3 slots ([nb_qps, N, K + 3]), plus 'rd_pass_side_rate_bits' float64
     [nb_qps, N] (the winner's mode bits and cbf bins); 'frequency_rd_pass_win_pnn' is computed from the new winners.  With the default
     nothing changes: not a key, a launch or a byte.
+    rd_pass_codec='substitution' (needs rd_pass_signalling=True; ValueError otherwise, and for any other name than 'switch', before
+    anything touches the GPU) runs the second pass of the reference's other codec (include/pnn_hip.h, "the substitution codec";
+    intraprediction.rd_pass(codec='substitution')): HM's own search over modes 0 .. 34 with the PNN's prediction in the place of mode
+    18's -- no flag bin, no mode 35, neighbours 0 .. 34 / 255.  The same rd_pass_* keys are written with K + 2 slots, and
+    'frequency_rd_pass_win_pnn' is the share of winners equal to 18.  The call is pnn_rd_pass_codec_picture_pairs_device, which every
+    second pass here goes through (codec 0 forwards to the entry it was).  With 'switch' nothing changes: not a key, a launch or a byte.
+    rd_pass_mode_stats=True (needs rd_pass=True; ValueError otherwise), either codec: ONE more launch per mask,
+    pnn_rd_pass_mode_stats_device, counts the tables the reference's codecs print per width from the slots and winners the second pass
+    left on the device; they join the one download.  New keys: 'rd_pass_mode_fast_selections', 'rd_pass_mode_fast_wins',
+    'rd_pass_mode_rd_wins' (uint32 [nb_qps, 36]: the mode occupies a used slot, is in slot 0, wins), 'rd_pass_modes_for_rd' (int64
+    [nb_qps], the used slots: m_cumNbModesForRD) and 'rd_pass_runs' (N: m_nbFastRDRuns).  Equal to
+    intraprediction.rd_pass_mode_stats on the dictionary's own 'rd_pass_candidates' and 'rd_pass_modes'.  With False nothing changes.
 
     transform_rdoq=True (with transform_qps; ValueError without, before anything touches the GPU) sets the option rdoq of the two
     transform calls and of the second-pass call (0 without it): HM's RDOQ under HM's lambda of each QP (include/pnn_hip.h,
@@ -266,13 +278,13 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     dictionary's own arrays.  With transform_rdoq=False nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
                         net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass,
-                        transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes)
+                        transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec, rd_pass_mode_stats)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                                    tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
                                    transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False, transform_rdoq=False,
-                                   rd_pass_signalling=False, rd_pass_neighbour_modes=None):
+                                   rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -287,10 +299,12 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
     original, as in the table above.  reference_smoothing: as for score_masks_from_pictures; the smoothed line is built from the decoded
     plane's samples, as the unsmoothed one is.  transform_qps: as for score_masks_from_pictures; the predictions that get coded are the
     ones made from the decoded plane, the residual's and the SSE's targets come from the original, as in the table above.
-    transform_rate, transform_sign_hiding, transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes: as for score_masks_from_pictures."""
+    transform_rate, transform_sign_hiding, transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec, rd_pass_mode_stats:
+    as for score_masks_from_pictures."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
                         tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps,
-                        transform_rate, transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes)
+                        transform_rate, transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec,
+                        rd_pass_mode_stats)
 
 def _check_score_masks_arguments(ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
                                  reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False, transform_rdoq=False):
@@ -360,7 +374,7 @@ _RD_PASS_SECTIONS = ('rd_pass_candidates', 'rd_pass_costs', 'rd_pass_modes', 'rd
                      'rd_pass_rates')                                                      # intraprediction.RD_PASS_OUTPUTS, in the entry's order
 
 
-def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False, rd_pass_signalling=False):
+def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False, rd_pass_signalling=False, rd_pass_codec='switch', rd_pass_mode_stats=False):
     """Every output of a mask's calls in ONE buffer, described once as (name, dtype, shape): the small results first, then the uint8
     blocks of the PNN, of HEVC and the targets; a download is a prefix of it.  Each section starts at a multiple of its item size.
     Returns (sections, begin, end), the last two the byte offsets by name; end['targets'] is the size of the buffer."""
@@ -373,13 +387,15 @@ def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False, rd_p
         sections += [('%s_%s' % (name, column), np.uint32, (nb_qps, n)) for name in _COUNTS]
         if transform_rate:
             sections.append(('rate_' + column, np.uint64, (nb_qps, n)))
-    if rd_pass and rd_pass_signalling:                    # per QP, K + 3 slots; the list's costs are not asked for
-        shapes = intraprediction.rd_pass_signal_shapes(n, nb_qps, w)
+    if rd_pass and rd_pass_signalling:                    # per QP, K + 3 slots (K + 2: the substitution codec); the list's costs are not asked for
+        shapes = intraprediction.rd_pass_signal_shapes(n, nb_qps, w, rd_pass_codec)
         sections += [(name, dtype, shape) for name, (_, dtype), shape in zip(_RD_PASS_SECTIONS, intraprediction.RD_PASS_OUTPUTS, shapes)]
         sections.append(('rd_pass_side_rates', np.uint64, shapes[-1]))
     elif rd_pass:
         sections += [(name, dtype, shape) for name, (_, dtype), shape in zip(_RD_PASS_SECTIONS, intraprediction.RD_PASS_OUTPUTS,
                                                                              intraprediction.rd_pass_shapes(n, nb_qps, w))]
+    if rd_pass_mode_stats:
+        sections.append(('rd_pass_mode_stats', np.uint32, (nb_qps, 3, intraprediction.NB_STATS_BINS)))
     sections += [(name, np.uint8, (n, w, w, 1)) for name in ('predictions_pnn', 'predictions_hevc', 'targets')]
     begin, end, offset = {}, {}, 0
     for name, dtype, shape in sections:
@@ -390,7 +406,7 @@ def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False, rd_p
 
 
 def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False,
-                            transform_rdoq=False, rd_pass_signalling=False):
+                            transform_rdoq=False, rd_pass_signalling=False, rd_pass_codec='switch', rd_pass_mode_stats=False):
     """One mask's dictionary_performance, but for the uint8 blocks, from `view`: the downloaded sections by name."""
     psnrs_pnn = intraprediction.psnrs_from_sses(view['sses_pnn'], w)
     psnrs_hevc = intraprediction.psnrs_from_sses(view['sses_hevc'], w)
@@ -424,15 +440,20 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
         d.update({key: view[key].copy() for key in ('rd_pass_candidates', 'rd_pass_costs', 'rd_pass_modes', 'rd_pass_sses')})
         d['rd_pass_rate_bits'] = view['rd_pass_rates'].astype(np.float64) / 32768.
         d['psnrs_recon_rd_pass'] = intraprediction.psnrs_from_sses(view['rd_pass_sses'], w)
-        d['frequency_rd_pass_win_pnn'] = [float(np.count_nonzero(modes == intraprediction.NB_MODES)) / n for modes in d['rd_pass_modes']]
+        pnn_mode = intraprediction.SUBSTITUTED_MODE if intraprediction.CODECS[rd_pass_codec] else intraprediction.NB_MODES
+        d['frequency_rd_pass_win_pnn'] = [float(np.count_nonzero(modes == pnn_mode)) / n for modes in d['rd_pass_modes']]
         if rd_pass_signalling:
             d['rd_pass_side_rate_bits'] = view['rd_pass_side_rates'].astype(np.float64) / 32768.
+        if rd_pass_mode_stats:
+            stats = intraprediction.mode_stats_dictionary(view['rd_pass_mode_stats'], n)
+            d.update({'rd_pass_mode_fast_selections': stats['fast_selections'], 'rd_pass_mode_fast_wins': stats['fast_wins'],
+                      'rd_pass_mode_rd_wins': stats['rd_wins'], 'rd_pass_modes_for_rd': stats['modes_for_rd'], 'rd_pass_runs': stats['runs']})
     return d
 
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
                  keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False,
-                 transform_rdoq=False, rd_pass_signalling=False, rd_pass_neighbour_modes=None):
+                 transform_rdoq=False, rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer.  Every option is an argument
     of the one entry its call has (the smoothing; the mode pointer, the rate pointer and the flag), 0 or NULL when off."""
@@ -441,6 +462,13 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         raise ValueError('`rd_pass_signalling` is set without `rd_pass`.')
     if rd_pass_neighbour_modes is not None and not rd_pass_signalling:
         raise ValueError('`rd_pass_neighbour_modes` is given without `rd_pass_signalling`.')
+    if rd_pass_codec not in intraprediction.CODECS:
+        raise ValueError("`rd_pass_codec` is not 'switch' or 'substitution'.")
+    codec = intraprediction.CODECS[rd_pass_codec]
+    if codec and not rd_pass_signalling:
+        raise ValueError("`rd_pass_codec` 'substitution' is set without `rd_pass_signalling`.")
+    if rd_pass_mode_stats and not rd_pass:
+        raise ValueError('`rd_pass_mode_stats` is set without `rd_pass`.')
     masks, rows, cols, reference_smoothing, transform_qps = _check_score_masks_arguments(
         ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns, reference_smoothing,
         transform_qps, transform_rate, transform_sign_hiding, rd_pass, transform_rdoq)
@@ -452,21 +480,21 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     L = _lib.lib()
     signalling = int(bool(rd_pass_signalling))
     left, above = (None, None) if rd_pass_neighbour_modes is None else rd_pass_neighbour_modes
-    left = intraprediction._neighbour_array(left, n, True, 'rd_pass_neighbour_modes[0]')
-    above = intraprediction._neighbour_array(above, n, True, 'rd_pass_neighbour_modes[1]')
+    left = intraprediction._neighbour_array(left, n, not codec, 'rd_pass_neighbour_modes[0]')
+    above = intraprediction._neighbour_array(above, n, not codec, 'rd_pass_neighbour_modes[1]')
 
     import torch
     dev = torch.device('cuda', predictor.device)
     d_planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(ch, 3, 0))).to(dev)      # [planes, images, H, W]: one copy, one upload
     d_target_channels, d_context_channels = d_planes[0], d_planes[nb_planes - 1]
     d_rows, d_cols = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (rows, cols))
-    sections, begin, end = _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass, rd_pass_signalling)
+    sections, begin, end = _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass, rd_pass_signalling, rd_pass_codec, rd_pass_mode_stats)
     d_out = torch.empty(end['targets'], dtype=torch.uint8, device=dev)       # the last section
     ptr = {name: d_out.data_ptr() + begin[name] for name in begin}
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     c_qps = (ctypes.c_int * max(nb_qps, 1))(*transform_qps)
     if rd_pass:                                           # the entry's scratch, the caller's: once for all masks
-        nb_scratch = L.pnn_rd_pass_signal_workspace_bytes(w, n, nb_qps, signalling)
+        nb_scratch = L.pnn_rd_pass_codec_workspace_bytes(w, n, nb_qps, signalling, codec)
         d_scratch = torch.empty(nb_scratch, dtype=torch.uint8, device=dev)
         d_left, d_above = (None if a is None else torch.from_numpy(a).to(dev) for a in (left, above))
     results, targets_uint8 = {}, None
@@ -494,17 +522,23 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                     ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None, ptr['rate_' + column] if transform_rate else None,
                     int(bool(transform_sign_hiding)), int(bool(transform_rdoq)), None, stream), predictor.ctx)
             if rd_pass:                                   # the candidate is the PNN's uint8 prediction; NULL lambdas: HM's of each QP
-                # (the one entry of the second pass; signalling 0 forwards to pnn_rd_pass_rdoq_picture_pairs_device: the same launches)
-                _lib.check(L.pnn_rd_pass_signal_picture_pairs_device(
+                # (the one entry of the second pass; codec 0 forwards to pnn_rd_pass_signal_picture_pairs_device, whose signalling 0 forwards
+                # to pnn_rd_pass_rdoq_picture_pairs_device: the same launches)
+                _lib.check(L.pnn_rd_pass_codec_picture_pairs_device(
                     *blocks, ptr['predictions_pnn'], reference_smoothing, c_qps, nb_qps, None, int(bool(transform_sign_hiding)),
                     int(bool(transform_rdoq)), signalling, None if d_left is None else d_left.data_ptr(),
-                    None if d_above is None else d_above.data_ptr(), *[ptr[name] for name in _RD_PASS_SECTIONS], None,
+                    None if d_above is None else d_above.data_ptr(), codec, *[ptr[name] for name in _RD_PASS_SECTIONS], None,
                     ptr['rd_pass_side_rates'] if signalling else None, d_scratch.data_ptr(), nb_scratch, stream), predictor.ctx)
+                if rd_pass_mode_stats:                    # from the slots and winners the call above left in the output buffer
+                    _lib.check(L.pnn_rd_pass_mode_stats_device(
+                        predictor.ctx, ptr['rd_pass_candidates'], signalling, intraprediction.rd_pass_slot_count(w, signalling, rd_pass_codec),
+                        ptr['rd_pass_modes'], n, nb_qps, ptr['rd_pass_mode_stats'], stream), predictor.ctx)
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
         dictionary_performance = _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate,
-                                                         transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling)
+                                                         transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling, rd_pass_codec,
+                                                         rd_pass_mode_stats)
         if keep_predictions:
             if first:
                 targets_uint8 = view['targets'].copy()

@@ -480,12 +480,68 @@ def _neighbour_array(modes, n, pnn_flag, name):
     return np.ascontiguousarray(modes.astype(np.uint8))
 
 
-def rd_pass_slot_count(width_target, signalling=False):
-    """Slots per block of rd_pass (pnn_rd_pass_slot_count): K + 1, with signalling K + 3."""
-    count = _lib.lib().pnn_rd_pass_slot_count(int(width_target), int(bool(signalling)))
+CODECS = {'switch': 0, 'substitution': 1}                 # the reference's two modified HM codecs, as the ABI's `codec`
+SUBSTITUTED_MODE = 18                                     # the mode whose place the candidate takes under 'substitution'
+NB_STATS_BINS = 36                                        # modes 0 .. 35 of the mode statistics
+
+
+def _check_codec(codec, signalling):
+    """The codec's name as the ABI's number; 'substitution' needs the signalling."""
+    if codec not in CODECS:
+        raise ValueError("`codec` is not 'switch' or 'substitution'.")
+    if CODECS[codec] and not signalling:
+        raise ValueError("the codec 'substitution' needs `signalling`: HM never searches without the mode bits.")
+    return CODECS[codec]
+
+
+def rd_pass_slot_count(width_target, signalling=False, codec='switch'):
+    """Slots per block of rd_pass (pnn_rd_pass_codec_slot_count): K + 1, with signalling K + 3; codec 'substitution': K + 2."""
+    count = _lib.lib().pnn_rd_pass_codec_slot_count(int(width_target), int(bool(signalling)), _check_codec(codec, signalling))
     if count < 0:
         raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
     return count
+
+
+def rd_pass_mode_stats(candidates, modes, device=None):
+    """The mode statistics of a second pass (pnn_rd_pass_mode_stats_host / _device; include/pnn_hip.h, "mode statistics"), the tables
+    the reference's codecs accumulate per width.  candidates: rd_pass's 'candidates', uint8 [n, S] (shared by the QPs) or
+    [nb_qps, n, S]; modes: its 'modes', uint8 [nb_qps, n].  Returns {'fast_selections', 'fast_wins', 'rd_wins': uint32 [nb_qps, 36]
+    (a mode occupies a used slot; is in slot 0; wins), 'modes_for_rd': int64 [nb_qps] (the sum of 'fast_selections':
+    m_cumNbModesForRD), 'runs': n (m_nbFastRDRuns)}.  255 -- an unused slot, a block without a winner -- counts nowhere."""
+    arrays = (candidates, modes)
+    if any(not isinstance(a, np.ndarray) or a.dtype != np.uint8 for a in arrays):
+        raise TypeError('the arrays must be `numpy.ndarray`s of dtype `numpy.uint8`.')
+    if modes.ndim != 2 or not 1 <= modes.shape[0] <= 8:
+        raise ValueError('`modes` is not [nb_qps, n] with 1 to 8 QPs.')
+    nq, n = modes.shape
+    per_qp = candidates.ndim == 3
+    if candidates.ndim not in (2, 3) or candidates.shape[-2] != n or not 1 <= candidates.shape[-1] <= 16 or (per_qp and candidates.shape[0] != nq):
+        raise ValueError('`candidates` is not [n, S] or [nb_qps, n, S] with 1 to 16 slots.')
+    candidates, modes = np.ascontiguousarray(candidates), np.ascontiguousarray(modes)
+    slots = candidates.shape[-1]
+    L = _lib.lib()
+    if device is None:
+        stats = np.zeros((nq, 3, NB_STATS_BINS), np.uint32)
+        if L.pnn_rd_pass_mode_stats_host(candidates.ctypes.data, int(per_qp), slots, modes.ctypes.data, n, nq, stats.ctypes.data) != 0:
+            raise ValueError('pnn_rd_pass_mode_stats_host refused the arguments.')
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        d_in = [torch.from_numpy(a).to(dev) for a in (candidates, modes)]
+        d_stats = torch.empty((nq, 3, NB_STATS_BINS), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.pnn_rd_pass_mode_stats_device(_context(device), _address(d_in[0]) if n else None, int(per_qp), slots,
+                                                       _address(d_in[1]) if n else None, n, nq, d_stats.data_ptr(),
+                                                       ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        stats = d_stats.cpu().numpy().view(np.uint32)     # (waits for the stream)
+    return mode_stats_dictionary(stats, n)
+
+
+def mode_stats_dictionary(stats, n):
+    """uint32 [nb_qps, 3, 36] as the entries return it -> rd_pass_mode_stats's dictionary."""
+    return {'fast_selections': stats[:, 0].copy(), 'fast_wins': stats[:, 1].copy(), 'rd_wins': stats[:, 2].copy(),
+            'modes_for_rd': stats[:, 0].astype(np.int64).sum(axis=1), 'runs': int(n)}
 
 
 def intra_mode_signal(left_modes, above_modes, qp, pnn_flag=True):
@@ -513,24 +569,26 @@ def intra_mode_signal(left_modes, above_modes, qp, pnn_flag=True):
 RD_PASS_SIGNAL_OUTPUTS = RD_PASS_OUTPUTS + (('first_pass_costs', np.float64), ('side_rates', np.uint64))
 
 
-def rd_pass_signal_shapes(n, nb_qps, width_target):
-    """The shapes of RD_PASS_SIGNAL_OUTPUTS: candidates and costs [nb_qps, n, K + 3], first_pass_costs [nb_qps, n, K], the others [nb_qps, n]."""
-    k, s = first_pass_list_size(width_target), rd_pass_slot_count(width_target, True)
+def rd_pass_signal_shapes(n, nb_qps, width_target, codec='switch'):
+    """The shapes of RD_PASS_SIGNAL_OUTPUTS: candidates and costs [nb_qps, n, K + 3] (codec 'substitution': K + 2), first_pass_costs
+    [nb_qps, n, K], the others [nb_qps, n]."""
+    k, s = first_pass_list_size(width_target), rd_pass_slot_count(width_target, True, codec)
     return ((nb_qps, n, s), (nb_qps, n, s)) + ((nb_qps, n),) * 5 + ((nb_qps, n, k), (nb_qps, n))
 
 
-def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device):
-    """rd_pass with signalling: the checked arguments -> the dictionary, from pnn_rd_pass_signal_host (device None) or _device."""
+def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device, codec='switch'):
+    """rd_pass with signalling: the checked arguments -> the dictionary, from pnn_rd_pass_codec_host (device None) or _device."""
     n, w, nq = targets.shape[0], targets.shape[1], len(qps)
     left, above = (None, None) if neighbour_modes is None else neighbour_modes
-    left, above = _neighbour_array(left, n, True, 'neighbour_modes[0]'), _neighbour_array(above, n, True, 'neighbour_modes[1]')
-    shapes = rd_pass_signal_shapes(n, nq, w)
+    with_35 = not CODECS[codec]                           # a neighbour coded with 35 exists in the switch codec only
+    left, above = _neighbour_array(left, n, with_35, 'neighbour_modes[0]'), _neighbour_array(above, n, with_35, 'neighbour_modes[1]')
+    shapes = rd_pass_signal_shapes(n, nq, w, codec)
     L = _lib.lib()
     if device is None or n == 0:
         outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(RD_PASS_SIGNAL_OUTPUTS, shapes)]
-        rc = L.pnn_rd_pass_signal_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
-                                       smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(left), _address(above),
-                                       *[o.ctypes.data for o in outs])
+        rc = L.pnn_rd_pass_codec_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
+                                      smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(left), _address(above), CODECS[codec],
+                                      *[o.ctypes.data for o in outs])
         if rc != 0:
             raise ValueError('pnn_rd_pass_signal_host refused the arguments (patterns %dx%d, width %d).' % (patterns.shape[1], patterns.shape[2], w))
     else:
@@ -540,14 +598,14 @@ def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, 
         d_left, d_above = (None if a is None else torch.from_numpy(a).to(dev) for a in (left, above))
         d_outs = [torch.zeros(int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=torch.uint8, device=dev)
                   for (_, dtype), shape in zip(RD_PASS_SIGNAL_OUTPUTS, shapes)]
-        nb_bytes = L.pnn_rd_pass_signal_workspace_bytes(w, n, nq, 1)
+        nb_bytes = L.pnn_rd_pass_codec_workspace_bytes(w, n, nq, 1, CODECS[codec])
         d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_rd_pass_signal_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
-                                                   n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(d_left),
-                                                   _address(d_above), *[o.data_ptr() for o in d_outs], d_ws.data_ptr(), nb_bytes,
-                                                   ctypes.c_void_p(stream.cuda_stream)), _context(device))
+            _lib.check(L.pnn_rd_pass_codec_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
+                                                  n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(d_left),
+                                                  _address(d_above), CODECS[codec], *[o.data_ptr() for o in d_outs], d_ws.data_ptr(), nb_bytes,
+                                                  ctypes.c_void_p(stream.cuda_stream)), _context(device))
         outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, RD_PASS_SIGNAL_OUTPUTS, shapes)]   # (waits)
     result = {name: out for (name, _), out in zip(RD_PASS_SIGNAL_OUTPUTS, outs)}
     result['rate_bits'] = result['rates'].astype(np.float64) / 32768.
@@ -558,7 +616,7 @@ def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, 
 
 
 def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoothing=0, sign_data_hiding=False, lambdas=None, device=None,
-            rdoq=False, signalling=False, neighbour_modes=None):
+            rdoq=False, signalling=False, neighbour_modes=None, codec='switch'):
     """HM's second intra pass as include/pnn_hip.h defines it ("the second intra pass"): per block and QP the RD choice among the
     first-pass candidates (mode_hads_*'s list with the candidate prediction competing as 35) and the candidate itself, appended if the
     list lacks it.  numpy uint8 arrays: patterns [n, h, w'], targets and candidate_predictions [n, w, w]; qps: 1 to 8 integers in
@@ -577,7 +635,12 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     stays the rate of the winner's levels, and the dictionary gains 'side_rates' uint64 [nb_qps, n] (the winner's mode bits plus cbf bin,
     2^-15 bit), 'side_rate_bits' (the same in bits) and 'first_pass_costs' float64 [nb_qps, n, K].  At width 64 each of the four
     quadrants pays its own cbf bin.  With False nothing changes: the same entries are called with signalling 0, which forward to
-    pnn_rd_pass_rdoq_host / _device."""
+    pnn_rd_pass_rdoq_host / _device.
+    codec='substitution' (the argument of pnn_rd_pass_codec_host / _device, which every call here goes to, with 0 for 'switch';
+    include/pnn_hip.h, "the substitution codec"; needs signalling=True): HM's own search over modes 0 .. 34 with the candidate as mode
+    18's prediction -- no flag bin, no mode 35, neighbours 0 .. 34 / 255, 'candidates' and 'costs' [nb_qps, n, K + 2]; the winner is the
+    candidate where 'modes' is 18.  Same keys.  With 'switch' nothing changes."""
+    number = _check_codec(codec, signalling)
     smoothing = _check_smoothing(reference_smoothing)
     qps = _check_qps(qps)
     arrays = (intra_patterns, targets, candidate_predictions)
@@ -593,13 +656,13 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     if not signalling and neighbour_modes is not None:
         raise ValueError('`neighbour_modes` is given without `signalling`.')
     if signalling:
-        return _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device)
+        return _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device, codec)
     shapes = rd_pass_shapes(n, nq, w)
     L = _lib.lib()
     if device is None or n == 0:                          # (no block: nothing to launch, the empty arrays)
         outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
-        rc = L.pnn_rd_pass_signal_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
-                                       smoothing, c_qps, nq, c_lambdas, flag, option, 0, None, None, *[o.ctypes.data for o in outs], None, None)
+        rc = L.pnn_rd_pass_codec_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
+                                      smoothing, c_qps, nq, c_lambdas, flag, option, 0, None, None, number, *[o.ctypes.data for o in outs], None, None)
         if rc != 0:
             raise ValueError('pnn_rd_pass_host refused the arguments (patterns %dx%d, width %d).' % (patterns.shape[1], patterns.shape[2], w))
     else:
@@ -608,14 +671,14 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
         d_in = [torch.from_numpy(a).to(dev) for a in (patterns, targets, candidate)]
         d_outs = [torch.zeros(int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=torch.uint8, device=dev)
                   for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
-        nb_bytes = L.pnn_rd_pass_signal_workspace_bytes(w, n, nq, 0)
+        nb_bytes = L.pnn_rd_pass_codec_workspace_bytes(w, n, nq, 0, number)
         d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_rd_pass_signal_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
-                                                   n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 0, None, None,
-                                                   *[o.data_ptr() for o in d_outs], None, None, d_ws.data_ptr(), nb_bytes,
-                                                   ctypes.c_void_p(stream.cuda_stream)), _context(device))
+            _lib.check(L.pnn_rd_pass_codec_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
+                                                  n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 0, None, None, number,
+                                                  *[o.data_ptr() for o in d_outs], None, None, d_ws.data_ptr(), nb_bytes,
+                                                  ctypes.c_void_p(stream.cuda_stream)), _context(device))
         outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, RD_PASS_OUTPUTS, shapes)]   # (waits)
     result = {name: out for (name, _), out in zip(RD_PASS_OUTPUTS, outs)}
     result['rate_bits'] = result['rates'].astype(np.float64) / 32768.

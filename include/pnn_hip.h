@@ -832,7 +832,7 @@ int pnn_rd_pass_rdoq_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t
  *   Second pass.  R = (mode bits + cbf bin + rate of the levels) >> 15, ONE shift over the sum; J = D + lambda R and the winner rule
  *     as above.  A slot is coded at its own QP only.
  * LEFT OUT: part size, split and subdivision flags (equal for all candidates of a block); the interleaving of the four units' flags in
- * an N x N coding unit; chroma; running contexts; the substitution codec's signalling; transform skip; the transform quadtree. */
+ * an N x N coding unit; chroma; running contexts; transform skip; the transform quadtree.  (The substitution codec: the next group.) */
 int pnn_rd_pass_slot_count(int width, int signalling);      /* K + 1 or K + 3; -1 for a bad width */
 /* The unit entry.  Outputs, each NULL (not all) or: mpm uint8 [n][3]; num_append uint8 [n]; mode_frac_bits uint32 [n][36] (entry 35
  * is 0 with pnn_flag 0); cbf_frac_bits uint32 [2 contexts][2 values] of the QP.  PNN_E_ARG + a line on stderr for n < 0, a QP outside
@@ -878,6 +878,73 @@ int pnn_rd_pass_signal_picture_pairs_device(pnn_ctx* ctx, int width, const uint8
                                             uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate,
                                             double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace, size_t workspace_bytes,
                                             void* stream);
+
+/* ---- the substitution codec: HM's own intra search with the PNN in the place of mode 18; mode statistics ---------- */
+
+/* hm_16_15_substitution keeps HM's 35 luma modes and lets the PNN's block stand for mode 18 (predIntraAng, TComPrediction.cpp:506-556
+ * of that tree); its search loop (TEncSearch.cpp:2325-2584) is otherwise HM's.  The entries below are the second-pass entries of the
+ * group above with one more argument, `codec`: 0 is the switch codec -- they then ARE those entries, byte for byte -- and 1 the
+ * substitution codec, defined by csrc/pnn_mode_signal.h (list_and_slots_substitution) as follows.  Any other codec is PNN_E_ARG.
+ *   Modes.  0 .. 34 only.  Mode 18's prediction is the caller's candidate (cand_pred, required), every other mode's is
+ *     pnn_hevc_intra_predict_hm's with the given `smoothing`.  Mode 35 does not exist and appears in no output.
+ *   Neighbours.  0 .. 34 or 255; 35 is PNN_E_ARG.  A neighbour 18 is an ordinary angular mode (equal neighbours 18: MPMs 18, 17, 19).
+ *   MPMs and bits.  getIntraDirPredictor and codeIntraDirLumaAng of that tree are hm_16_15_regular's: the MPMs above without a
+ *     neighbour 35, the mode bits above with pnn_flag 0 (prev_intra_luma_pred_flag, mpm_idx or the remainder's 5 bypass bins, no flag
+ *     bin) -- what pnn_intra_mode_signal_host returns with pnn_flag 0.  cbf_luma as above.  Cold contexts.
+ *   First pass.  cost = (double) SATD + (double) (mode bits >> 15) * sqrt(lambda) over modes 0 .. 34 in that order, mode 18's SATD being
+ *     the candidate's Hadamard cost; xUpdateCandList's rule and the unfused arithmetic as above.
+ *   Slots.  S = K + 2: the K list entries, then mpm[0 .. num_append - 1] where the list lacks them, then 255.  Nothing is appended for
+ *     the PNN: if 18 is neither listed nor an appended MPM it is not coded.
+ *   Coding.  The transform coding above with the slot's mode as its scan mode (18 scans diagonally, HM's getCoefScanIdx); sign-data
+ *     hiding and RDOQ as given.
+ *   Second pass.  R = (mode bits + cbf bin + rate) >> 15, J = D + lambda R, strict < in slot order; width 64 by quadrants as above.
+ *   Signalling.  codec 1 requires signalling nonzero (HM never searches without the mode bits); otherwise PNN_E_ARG.
+ *   No context.  Where the codec finds no usable context (contextFlag false) its PNN predicts zeros.  That stays the caller's business:
+ *     a caller models it by passing a zero candidate for such a block.
+ * Argument order: the *_signal_* signatures with `codec` behind above_modes, in front of the outputs. */
+int pnn_rd_pass_codec_slot_count(int width, int signalling, int codec);   /* K + 1, K + 3; codec 1: K + 2; -1 for what is refused */
+size_t pnn_rd_pass_codec_workspace_bytes(int width, int n, int nb_qps, int signalling, int codec);   /* 0 for what the entries refuse */
+/* The first pass.  codec 0: pnn_first_pass_signal_host.  codec 1: slot_modes is uint8 [nb_qps][n][K + 2].  Pure host code. */
+int pnn_first_pass_codec_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                              const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas,
+                              const uint8_t* left_modes, const uint8_t* above_modes, int codec, uint8_t* list_modes, double* list_costs,
+                              uint8_t* slot_modes);
+/* The second pass.  codec 1: cand_modes uint8 and cand_costs double [nb_qps][n][K + 2]; every other output as with signalling.  The
+ * host twin composes the host twins above and the header, never fusing the cost's multiply and add. */
+int pnn_rd_pass_codec_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                           const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                           int rdoq, int signalling, const uint8_t* left_modes, const uint8_t* above_modes, int codec, uint8_t* cand_modes,
+                           double* cand_costs, uint8_t* best_mode, uint8_t* best_slot, double* best_cost, uint32_t* best_sse,
+                           uint64_t* best_rate, double* first_pass_costs, uint64_t* best_side_rate);
+/* pnn_rd_pass_codec_host on the GPU, bit-identical to it.  codec 1: the 2 + 3 nb_qps launches of pnn_rd_pass_signal_device with
+ * substitution_list_kernel, the K + 2 slots form of rd_candidates_kernel (mode 18 reads d_cand_pred) and the decision without the flag
+ * bin; the first-pass and transform launches are the unchanged ones.  Every refusal -- a bad codec, a neighbour 35, signalling 0, a
+ * NULL candidate, a workspace below pnn_rd_pass_codec_workspace_bytes and those of the group above -- comes before any launch. */
+int pnn_rd_pass_codec_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                             const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                             int rdoq, int signalling, const uint8_t* d_left_modes, const uint8_t* d_above_modes, int codec, uint8_t* d_cand_modes,
+                             double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                             uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
+                             size_t workspace_bytes, void* stream);
+int pnn_rd_pass_codec_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                           int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                           const double* lambdas, int sign_data_hiding, int rdoq, int signalling, const uint8_t* d_left_modes,
+                                           const uint8_t* d_above_modes, int codec, uint8_t* d_cand_modes, double* d_cand_costs,
+                                           uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                                           uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
+                                           size_t workspace_bytes, void* stream);
+/* Mode statistics of a second pass, either codec: the tables the reference's codecs accumulate per mode (m_nbFastSelections,
+ * m_nbFastWins, m_nbRDWins) for the blocks of ONE width.  slot_modes: the cand_modes of a second-pass entry, uint8 [n][slots] shared
+ * by the QPs (per_qp 0: the entries without signalling) or [nb_qps][n][slots] (per_qp nonzero); best_mode uint8 [nb_qps][n]; slots 1
+ * to 16.  stats uint32 [nb_qps][3][36]: [0] fast selections, the mode occupies a used slot (appended MPMs and 35 included: HM counts
+ * after the appends); [1] fast wins, the mode is in slot 0; [2] RD wins, the mode is best_mode.  A value above 35 (255: an unused
+ * slot, a block without a winner) counts nowhere.  m_cumNbModesForRD is the sum of [0] and m_nbFastRDRuns is n: no entry computes them.
+ * The device entry zeroes d_stats on `stream`, then one launch (mode_stats_kernel) adds each workgroup's counts: integer sums, the same
+ * whatever the order.  PNN_E_ARG for n < 0, slots outside [1, 16], nb_qps outside [1, 8], a NULL output or (n > 0) NULL inputs. */
+int pnn_rd_pass_mode_stats_host(const uint8_t* slot_modes, int per_qp, int slots, const uint8_t* best_mode, int n, int nb_qps, uint32_t* stats);
+int pnn_rd_pass_mode_stats_device(pnn_ctx* ctx, const uint8_t* d_slot_modes, int per_qp, int slots, const uint8_t* d_best_mode, int n,
+                                  int nb_qps, uint32_t* d_stats, void* stream);
 
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
