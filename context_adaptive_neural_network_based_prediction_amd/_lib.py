@@ -119,6 +119,20 @@ SIGNATURES = {
     "pnn_rdoq_est_bits_host": (ci, [ci, ci, vp]),
     "pnn_trquant_rdoq_device": (ci, [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, ci, ci, ctypes.POINTER(ctypes.c_double),
                                      vp]),
+    "pnn_tskip_unit_host": (ci, [vp, ci, ci, ci, ci, ctypes.c_double, ci, vp, vp, ctypes.POINTER(ctypes.c_int32), vp, vp, vp]),
+    "pnn_trquant_tskip_host": (ci, [vp, vp, ci, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, ci, ci, ctypes.POINTER(ctypes.c_double),
+                                    ci, vp, ci, vp]),
+    "pnn_trquant_tskip_workspace_bytes": (ctypes.c_size_t, [ci, ci, ci]),
+    "pnn_trquant_tskip_device": (ci, [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci), ci, vp, vp, vp, vp, vp, ci, ci, ctypes.POINTER(ctypes.c_double),
+                                      ci, vp, ci, vp, vp, ctypes.c_size_t, vp]),
+    "pnn_rd_pass_tskip_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, ci,
+                                    ci] + [vp] * 10),
+    "pnn_rd_pass_tskip_workspace_bytes": (ctypes.c_size_t, [ci, ci, ci, ci, ci, ci]),
+    "pnn_rd_pass_tskip_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp,
+                                      vp, ci, ci] + [vp] * 11 + [ctypes.c_size_t, vp]),
+    "pnn_rd_pass_tskip_picture_pairs_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, ci, ctypes.POINTER(ci), ci,
+                                                    ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, ci, ci] + [vp] * 11 +
+                                               [ctypes.c_size_t, vp]),
     "pnn_rd_pass_rdoq_host": (ci, [vp, ci, ci, vp, ci, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci] + [vp] * 7),
     "pnn_rd_pass_rdoq_device": (ci, [vp, ci, vp, ci, ci, vp, ci, vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci] +
                                 [vp] * 8 + [ctypes.c_size_t, vp]),

@@ -173,6 +173,34 @@ int check_rdoq_lambdas(pnn_ctx* c, int rdoq, const double* lambdas, int nb_qps)
     return PNN_OK;
 }
 
+// the option transform_skip: 0 .. top, and nonzero at width 4 only
+int check_tskip_option(pnn_ctx* c, int width, int transform_skip, int top)
+{
+    if (transform_skip < 0 || transform_skip > top) return fail(c, PNN_E_ARG, "transform_skip %d is not in 0 .. %d", transform_skip, top);
+    return transform_skip && width != tskip::kWidth ? fail(c, PNN_E_ARG, "transform skip at width %d (4 only)", width) : PNN_OK;
+}
+
+// The caller's scratch of the transform coding with transform skip: both forms' outputs, [0] transformed and [1] skipped, each
+// [nb_qps][n] (recon [nb_qps][n][4][4]); every section at a multiple of 256 bytes.
+struct TskipOut { uint32_t* sse; uint32_t* nonzero; uint32_t* sum_abs; uint64_t* rate; uint8_t* recon; };
+struct TskipWorkspace { TskipOut form[2]; size_t bytes; };
+TskipWorkspace tskip_workspace(void* base, long n, int nb_qps)
+{
+    const size_t qn = (size_t)n * nb_qps;
+    size_t at = 0;
+    const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
+    TskipWorkspace ws;
+    for (TskipOut& o : ws.form) {
+        o.rate = (uint64_t*)take(qn * 8);
+        o.sse = (uint32_t*)take(qn * 4);
+        o.nonzero = (uint32_t*)take(qn * 4);
+        o.sum_abs = (uint32_t*)take(qn * 4);
+        o.recon = take(qn * 16);
+    }
+    ws.bytes = at;
+    return ws;
+}
+
 // The caller's scratch of the second intra pass, n (K + 1) slots: per-slot rate and SSE [nb_qps][slots], the slots' predictions and
 // replicated targets [slots][w][w], their modes [slots], the first-pass list [n][K]; every section at a multiple of 256 bytes.
 struct RdWorkspace { uint64_t* rate; uint32_t* sse; uint8_t* pred; uint8_t* targets; uint8_t* modes; uint8_t* list; size_t bytes; };
@@ -269,6 +297,42 @@ RdSignalWorkspace rd_signal_workspace(void* base, int width, long n, int nb_qps,
     return ws;
 }
 
+// The scratch the second pass with transform skip adds behind rd_signal_workspace's: the skipped form's rate, SSE and count of the
+// slots of ONE QP, the slots' mode bits and flags, the winners' slots; every section at a multiple of 256 bytes.
+struct RdTskipWorkspace { uint64_t* rate; uint32_t* sse; uint32_t* nonzero; uint32_t* mode_bits; uint8_t* ts_flag; uint8_t* best_slot; size_t bytes; };
+RdTskipWorkspace rd_tskip_workspace(void* base, size_t slots, long n)
+{
+    size_t at = 0;
+    const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
+    RdTskipWorkspace ws;
+    ws.rate = (uint64_t*)take(slots * 8);
+    ws.sse = (uint32_t*)take(slots * 4);
+    ws.nonzero = (uint32_t*)take(slots * 4);
+    ws.mode_bits = (uint32_t*)take(slots * 4);
+    ws.ts_flag = take(slots);
+    ws.best_slot = take((size_t)n);
+    ws.bytes = at;
+    return ws;
+}
+
+// what the second-pass entries with the option transform_skip check in front of everything else: the option, the width, signalling, a
+// lambda the decision can use, the whole scratch
+int check_rd_pass_tskip(pnn_ctx* c, int width, int n, const int* qps, int nb_qps, const double* lambdas, int signalling, int codec, int transform_skip,
+                        const void* d_workspace, size_t workspace_bytes)
+{
+    if (const int rc = check_tskip_option(c, width, transform_skip, 1)) return rc;
+    if (const int rc = check_codec(c, codec, signalling)) return rc;
+    if (!signalling) return fail(c, PNN_E_ARG, "the second pass with transform skip without signalling");
+    if (!transform_skip) return PNN_OK;
+    if (const int rc = check_rdoq_lambdas(c, 1, lambdas, trquant::qps_ok(qps, nb_qps) ? nb_qps : 0)) return rc;
+    if (n <= 0 || !trquant::qps_ok(qps, nb_qps)) return PNN_OK;             // (refused or empty further down)
+    const size_t base = rd_signal_workspace(nullptr, width, n, nb_qps, codec).bytes;
+    const size_t need = base + rd_tskip_workspace(nullptr, (size_t)n * signal_slots(width, codec), n).bytes;
+    if (d_workspace && workspace_bytes < need)
+        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_rd_pass_tskip_workspace_bytes asks for %zu", workspace_bytes, need);
+    return PNN_OK;
+}
+
 // what both forms with signalling check behind their blocks: the width (no quadrants), candidate, QPs, lambdas, outputs, scratch and --
 // read back once, the call waits for the stream -- the neighbours' modes
 int check_rd_pass_signal(pnn_ctx* c, int width, int n, const uint8_t* d_cand_pred, const int* qps, int nb_qps, const double* lambdas, int rdoq,
@@ -311,10 +375,12 @@ int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int 
                             const double* lambdas, int sign_data_hiding, int rdoq, const uint8_t* d_left, const uint8_t* d_above,
                             uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
                             uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
-                            hipStream_t s, int codec = 0)
+                            hipStream_t s, int codec = 0, int transform_skip = 0, uint8_t* d_best_ts_flag = nullptr)
 {
     const RdSignalWorkspace ws = rd_signal_workspace(d_workspace, width, n, nb_qps, codec);
     const int slots = signal_slots(width, codec);
+    // transform skip (width 4): the skipped form's arrays lie behind the pass's own scratch
+    const RdTskipWorkspace ts = rd_tskip_workspace((uint8_t*)d_workspace + ws.bytes, n * slots, n);
     const HevcModeHadsParams h = mode_hads_params(patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing, d_cand_pred, ws.mode_hads,
                                                   ws.cand_hads, nullptr, nullptr);
     HIPCHK(c, launch_hevc_mode_hads(h, s));
@@ -344,6 +410,26 @@ int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int 
         if (quadrants) t.cbf_ctx = 0;
         t.sse = ws.sse; t.nonzero = ws.nonzero; t.rate = ws.rate;
         HIPCHK(c, launch_trquant(t, s));
+        if (transform_skip) {
+            // both forms of every slot, decided per slot as the tree does inside each candidate's coding: the skipped form beside the
+            // transformed one, the mode bits the decision charges, the merge IN PLACE (sse, count and rate become the kept form's, the
+            // rate with the flag bin); the unchanged decision below then compares the slots' merged D and R
+            TrQuantParams k = t;
+            k.sse = ts.sse; k.nonzero = ts.nonzero; k.rate = ts.rate;
+            HIPCHK(c, launch_tskip4(k, s));
+            TskipSlotBitsParams sb;
+            sb.slot_modes = slot_modes; sb.left = d_left; sb.above = d_above; sb.N = (int)n; sb.S = slots; sb.pnn_flag = codec ? 0 : 1;
+            sb.bits = l.bits[qi]; sb.mode_bits = ts.mode_bits;
+            HIPCHK(c, launch_tskip_slot_bits(sb, s));
+            TskipDecideParams m;
+            m.N = (int)(n * slots); m.nb_qps = 1; m.decide = 1; m.charge_cbf = 1; m.mode_bits = ts.mode_bits;
+            m.transformed = TskipForm{ws.sse, ws.nonzero, nullptr, ws.rate, nullptr};
+            m.skipped = TskipForm{ts.sse, ts.nonzero, nullptr, ts.rate, nullptr};
+            for (int i = 0; i < trquant::kMaxQps; i++) { m.lambda[i] = lambda[qi]; m.bits[i] = tskip::qp_bits(qps[qi]); }
+            m.sse = ws.sse; m.nonzero = ws.nonzero; m.sum_abs = nullptr; m.recon = nullptr; m.rate = ws.rate; m.ts_flag = ts.ts_flag;
+            HIPCHK(c, launch_tskip_decide(m, s));
+            c->stat_launches += 3;
+        }
         RdDecideSignalParams d;
         d.sse = ws.sse; d.rate = ws.rate; d.nonzero = ws.nonzero; d.slot_modes = slot_modes; d.left = d_left; d.above = d_above;
         d.N = (int)n; d.w = width; d.cbf_ctx = msig::cbf_context(width); d.lambda = lambda[qi]; d.bits = l.bits[qi];
@@ -351,7 +437,13 @@ int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int 
         d.best_mode = d_best_mode ? d_best_mode + at : nullptr; d.best_slot = d_best_slot ? d_best_slot + at : nullptr;
         d.best_cost = d_best_cost ? d_best_cost + at : nullptr; d.best_sse = d_best_sse ? d_best_sse + at : nullptr;
         d.best_rate = d_best_rate ? d_best_rate + at : nullptr; d.best_side_rate = d_best_side_rate ? d_best_side_rate + at : nullptr;
+        if (transform_skip && !d.best_slot) d.best_slot = ts.best_slot;
         HIPCHK(c, codec ? launch_rd_decide_substitution(d, s) : launch_rd_decide_signal(d, s));
+        if (transform_skip && d_best_ts_flag) {
+            const TskipBestFlagParams g{ts.ts_flag, d.best_slot, (int)n, slots, d_best_ts_flag + at};
+            HIPCHK(c, launch_tskip_best_flag(g, s));
+            c->stat_launches++;
+        }
     }
     c->stat_launches += 2 + 3 * nb_qps;
     return PNN_OK;
@@ -654,6 +746,61 @@ int pnn_trquant_rdoq_device(pnn_ctx* c, int width, const uint8_t* d_predictions,
     return PNN_OK;
 }
 
+size_t pnn_trquant_tskip_workspace_bytes(int width, int n, int nb_qps)
+{
+    if (width != tskip::kWidth || n < 0 || nb_qps < 1 || nb_qps > trquant::kMaxQps) return 0;
+    return tskip_workspace(nullptr, n, nb_qps).bytes;
+}
+
+int pnn_trquant_tskip_device(pnn_ctx* c, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
+                             const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
+                             uint8_t* d_recon, uint64_t* d_rate, int sign_data_hiding, int rdoq, const double* lambdas, int transform_skip,
+                             const uint32_t* d_mode_bits, int charge_cbf, uint8_t* d_ts_flag, void* d_workspace, size_t workspace_bytes,
+                             void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    if (const int rc = check_tskip_option(c, width, transform_skip, 2)) return rc;
+    if (charge_cbf != 0 && charge_cbf != 1) return fail(c, PNN_E_ARG, "charge_cbf %d is not 0 or 1", charge_cbf);
+    if (!transform_skip) {                                // (needs one of the five outputs of the entry it forwards to)
+        const int rc = pnn_trquant_rdoq_device(c, width, d_predictions, d_targets, n, d_modes, qps, nb_qps, d_sses_recon, d_nb_nonzero,
+                                               d_sum_abs_levels, d_recon, d_rate, sign_data_hiding, rdoq, lambdas, stream);
+        if (rc == PNN_OK && d_ts_flag && n > 0) HIPCHK(c, hipMemsetAsync(d_ts_flag, 0, (size_t)nb_qps * n, (hipStream_t)stream));
+        return rc;
+    }
+    if (const int rc = check_trquant(c, width, d_predictions, d_targets, n, qps, nb_qps,
+                                     d_sses_recon || d_nb_nonzero || d_sum_abs_levels || d_recon || d_rate || d_ts_flag)) return rc;
+    const bool decide = transform_skip == 2;
+    if (const int rc = check_rdoq_lambdas(c, rdoq || decide, lambdas, nb_qps)) return rc;
+    if (n == 0) return PNN_OK;
+    const TskipWorkspace ws = tskip_workspace(d_workspace, n, nb_qps);
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return fail(c, PNN_E_ARG, "d_workspace is NULL or not aligned to 16 bytes");
+    if (workspace_bytes < ws.bytes)
+        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_trquant_tskip_workspace_bytes asks for %zu", workspace_bytes, ws.bytes);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    TrQuantParams p = trquant_params(width, d_predictions, d_targets, n, d_modes, qps, nb_qps, sign_data_hiding, rdoq, lambdas);
+    reset_stats(c);
+    for (int form = decide ? 0 : 1; form < 2; form++) {   // the transformed form first (decide only), then the skipped one
+        const TskipOut& o = ws.form[form];
+        p.sse = o.sse; p.nonzero = o.nonzero; p.sum_abs = o.sum_abs; p.recon = o.recon; p.rate = o.rate;
+        HIPCHK(c, form ? launch_tskip4(p, s) : launch_trquant(p, s));
+        c->stat_launches++;
+    }
+    TskipDecideParams d;
+    d.N = n; d.nb_qps = nb_qps; d.decide = decide; d.charge_cbf = charge_cbf; d.mode_bits = d_mode_bits;
+    d.transformed = TskipForm{ws.form[0].sse, ws.form[0].nonzero, ws.form[0].sum_abs, ws.form[0].rate, ws.form[0].recon};
+    d.skipped = TskipForm{ws.form[1].sse, ws.form[1].nonzero, ws.form[1].sum_abs, ws.form[1].rate, ws.form[1].recon};
+    for (int i = 0; i < trquant::kMaxQps; i++) {
+        const int qp = qps[i < nb_qps ? i : 0];
+        d.lambda[i] = lambdas ? lambdas[i < nb_qps ? i : 0] : pnn_hm_intra_lambda(qp);
+        d.bits[i] = tskip::qp_bits(qp);
+    }
+    d.sse = d_sses_recon; d.nonzero = d_nb_nonzero; d.sum_abs = d_sum_abs_levels; d.recon = d_recon; d.rate = d_rate; d.ts_flag = d_ts_flag;
+    HIPCHK(c, launch_tskip_decide(d, s));
+    c->stat_launches++;
+    return PNN_OK;
+}
+
 size_t pnn_rd_pass_workspace_bytes(int width, int n, int nb_qps)
 {
     if (width_index(width) < 0 || n < 0 || nb_qps < 1 || nb_qps > trquant::kMaxQps) return 0;
@@ -873,6 +1020,74 @@ int pnn_rd_pass_codec_picture_pairs_device(pnn_ctx* c, int width, const uint8_t*
                                    smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs,
                                    d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s,
                                    1);
+}
+
+// ---- the second pass with transform skip (include/pnn_hip.h, "transform skip") ----
+size_t pnn_rd_pass_tskip_workspace_bytes(int width, int n, int nb_qps, int signalling, int codec, int transform_skip)
+{
+    const size_t base = pnn_rd_pass_codec_workspace_bytes(width, n, nb_qps, signalling, codec);
+    if (!transform_skip || !base) return base;
+    if (transform_skip != 1 || width != tskip::kWidth) return 0;
+    return base + rd_tskip_workspace(nullptr, (size_t)n * signal_slots(width, codec), n).bytes;
+}
+
+int pnn_rd_pass_tskip_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                             const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                             int rdoq, int signalling, const uint8_t* d_left_modes, const uint8_t* d_above_modes, int codec, int transform_skip,
+                             uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
+                             uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate,
+                             uint8_t* d_best_ts_flag, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_rd_pass_tskip(c, width, n, qps, nb_qps, lambdas, signalling, codec, transform_skip, d_workspace, workspace_bytes)) ||
+        (rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing))) return rc;
+    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = check_rd_pass_signal(c, width, n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
+                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
+                                       d_first_pass_costs || d_best_side_rate || d_best_ts_flag,
+                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s, codec))) return rc;
+    if (n == 0) return PNN_OK;
+    reset_stats(c);
+    if (!transform_skip && d_best_ts_flag) HIPCHK(c, hipMemsetAsync(d_best_ts_flag, 0, (size_t)nb_qps * n, s));
+    return rd_pass_signal_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
+                                   lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot,
+                                   d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s, codec, transform_skip,
+                                   d_best_ts_flag);
+}
+
+int pnn_rd_pass_tskip_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                           int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                           const double* lambdas, int sign_data_hiding, int rdoq, int signalling, const uint8_t* d_left_modes,
+                                           const uint8_t* d_above_modes, int codec, int transform_skip, uint8_t* d_cand_modes, double* d_cand_costs,
+                                           uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
+                                           uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, uint8_t* d_best_ts_flag,
+                                           void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    long n = 0;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_tskip_option(c, width, transform_skip, 1)) || (rc = check_codec(c, codec, signalling)) ||
+        (rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+        (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n)) ||
+        (rc = check_rd_pass_tskip(c, width, (int)n, qps, nb_qps, lambdas, signalling, codec, transform_skip, d_workspace, workspace_bytes))) return rc;
+    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = check_rd_pass_signal(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
+                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
+                                       d_first_pass_costs || d_best_side_rate || d_best_ts_flag,
+                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s, codec))) return rc;
+    if (n == 0) return PNN_OK;
+    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
+    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
+    reset_stats(c);
+    if (!transform_skip && d_best_ts_flag) HIPCHK(c, hipMemsetAsync(d_best_ts_flag, 0, (size_t)nb_qps * n, s));
+    return rd_pass_signal_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
+                                   smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs,
+                                   d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s,
+                                   codec, transform_skip, d_best_ts_flag);
 }
 
 // The mode statistics of a second pass whose slot modes and winners are on the device: the output is zeroed on the stream, then one

@@ -9,6 +9,7 @@
 #include "pnn_mode_signal.h"
 #include "pnn_rdoq.h"
 #include "pnn_trquant_tables.h"
+#include "pnn_tskip.h"
 
 namespace pnn {
 
@@ -403,6 +404,30 @@ struct TrQuantParams {
 };
 int trquant_blocks_per_workgroup(int w);
 hipError_t launch_trquant(const TrQuantParams& p, hipStream_t s);
+
+// Transform skip of 4 x 4 units (pnn_tskip.hip).  launch_tskip4: the skipped form of the units of a TrQuantParams
+// with w = 4 -- the same inputs, outputs and layouts as launch_trquant; the rate is walked where rate is given.  launch_tskip_decide:
+// per (QP, unit) the merge of the two forms a launch_trquant and a launch_tskip4 call left in the caller's workspace (each array
+// [nb_qps][N], recon [nb_qps][N][4][4] at a multiple of 16 bytes): decide 0 takes the skipped form of every unit (the transformed one
+// is not read), decide 1 applies tskip::skipped_wins with mode_bits NULL (0) or uint32 [nb_qps][N].  Outputs, each NULL or as
+// launch_trquant's, the rate with the flag bin of the kept form; ts_flag NULL or uint8 [nb_qps][N].
+struct TskipForm { const uint32_t* sse; const uint32_t* nonzero; const uint32_t* sum_abs; const uint64_t* rate; const uint8_t* recon; };
+struct TskipDecideParams {
+    int N; int nb_qps; int decide; int charge_cbf; TskipForm transformed; TskipForm skipped; const uint32_t* mode_bits;
+    double lambda[trquant::kMaxQps]; tskip::QpBits bits[trquant::kMaxQps];
+    uint32_t* sse; uint32_t* nonzero; uint32_t* sum_abs; uint8_t* recon; uint64_t* rate; uint8_t* ts_flag;
+};
+hipError_t launch_tskip4(const TrQuantParams& p, hipStream_t s);
+hipError_t launch_tskip_decide(const TskipDecideParams& p, hipStream_t s);
+// The second pass with transform skip (width 4, the slots of ONE QP): launch_tskip_slot_bits writes the mode bits the tree charges
+// each of the N S slots (msig::mode_frac_bits under the block's MPMs; 0 for an unused slot) for launch_tskip_decide's mode_bits;
+// launch_tskip_best_flag gathers the winner's flag: best_flag[b] = ts_flag[b S + best_slot[b]], 0 for a block without a winner.
+struct TskipSlotBitsParams {
+    const uint8_t* slot_modes; const uint8_t* left; const uint8_t* above; int N; int S; int pnn_flag; msig::FlagBits bits; uint32_t* mode_bits;
+};
+hipError_t launch_tskip_slot_bits(const TskipSlotBitsParams& p, hipStream_t s);
+struct TskipBestFlagParams { const uint8_t* ts_flag; const uint8_t* best_slot; int N; int S; uint8_t* best_flag; };
+hipError_t launch_tskip_best_flag(const TskipBestFlagParams& p, hipStream_t s);
 
 // IPFCN-S, the evaluator's second competitor (pnn_ipfcns.hip).  Blocks b0 .. b0 + nb - 1 of images x positions (image-major): the
 // two groups of 8 reference lines at line origin (rows[pos], cols[pos]) of uint8 picture `img` [H][W] -- rows [r, r + 8) x columns

@@ -6,6 +6,7 @@
 // The cost is one IEEE multiply and one IEEE add in double; the pragmas below keep the compiler from contracting them into an FMA,
 // as rd_cost does in rd_decide_kernel (pnn_hevc_intra.hip).
 #include "../../include/pnn_hip.h"
+#include "pnn_rd_pass_host.h"
 #include "pnn_rdoq.h"
 
 #include <algorithm>
@@ -213,7 +214,7 @@ int rd_pass_body(const char* entry, int codec, const uint8_t* patterns, int patt
                  const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding, int rdoq,
                  const uint8_t* left_modes, const uint8_t* above_modes, uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode,
                  uint8_t* best_slot, double* best_cost, uint32_t* best_sse, uint64_t* best_rate, double* first_pass_costs,
-                 uint64_t* best_side_rate);
+                 uint64_t* best_side_rate, pnn::RdSlotCoder coder = nullptr, uint8_t* best_ts_flag = nullptr);
 
 }  // namespace
 
@@ -314,12 +315,13 @@ int rd_pass_body(const char* entry, int codec, const uint8_t* patterns, int patt
                  const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding, int rdoq,
                  const uint8_t* left_modes, const uint8_t* above_modes, uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode,
                  uint8_t* best_slot, double* best_cost, uint32_t* best_sse, uint64_t* best_rate, double* first_pass_costs,
-                 uint64_t* best_side_rate)
+                 uint64_t* best_side_rate, pnn::RdSlotCoder coder, uint8_t* best_ts_flag)
 {
     const int candidate = codec ? msig::kSubstitutedMode : kCandidate;            // the mode the caller's prediction stands for
     const int k = pnn_first_pass_list_size(width);
     if (k < 0) return refuse_signal(entry, "the width of the target patch is not 4, 8, 16, 32 or 64.");
-    if (!cand_modes && !cand_costs && !best_mode && !best_slot && !best_cost && !best_sse && !best_rate && !first_pass_costs && !best_side_rate)
+    if (!cand_modes && !cand_costs && !best_mode && !best_slot && !best_cost && !best_sse && !best_rate && !first_pass_costs && !best_side_rate &&
+        !best_ts_flag)
         return refuse_signal(entry, "every output is NULL.");
     for (int qi = 0; rdoq && lambdas && qps && qi < nb_qps && qi < 8; qi++)
         if (!(lambdas[qi] > 0.)) return refuse_signal(entry, "RDOQ with a lambda that is not above 0.");
@@ -337,6 +339,8 @@ int rd_pass_body(const char* entry, int codec, const uint8_t* patterns, int patt
     std::vector<uint8_t> scan_modes(chunk * s), pred(chunk * s * w2), tgt(chunk * s * w2);
     std::vector<uint32_t> sse(chunk * s), nonzero(chunk * s);
     std::vector<uint64_t> rate(chunk * s);
+    std::vector<uint32_t> mode_bits(coder ? chunk * s : 0);                // transform skip: what each slot's
+    std::vector<uint8_t> ts_flag(coder ? chunk * s : 0);                   // decision charges, and which form it keeps
     std::vector<int32_t> levels(width == 64 ? w2 : 0);
     std::vector<uint8_t> quadrant_coded(width == 64 ? chunk * s * 4 : 0);
     for (int qi = 0; qi < nb_qps; qi++) {
@@ -358,7 +362,20 @@ int rd_pass_body(const char* entry, int codec, const uint8_t* patterns, int patt
                     scan_modes[i * s + j] = m > 34 ? 0 : (uint8_t)m;
                 }
             }
-            if (pnn_trquant_rdoq_host(pred.data(), tgt.data(), width, (int)(nb * s), scan_modes.data(), qps + qi, 1, sse.data(), nonzero.data(), nullptr,
+            if (coder) {
+                // both forms of every slot, decided per slot inside the candidate's coding (pnn_tskip.cpp's coder, so that this file
+                // links without it): sse, count and rate are the kept form's
+                for (long i = 0; i < nb; i++) {
+                    const msig::Mpm mpm = block_mpm(left_modes, above_modes, b0 + i);
+                    for (int j = 0; j < s; j++) {
+                        const int m = slot_modes[(b0 + i) * s + j];
+                        mode_bits[i * s + j] = m == kUnused ? 0u : msig::mode_frac_bits(m, mpm, f, codec ? 0 : 1);
+                    }
+                }
+                if (coder(pred.data(), tgt.data(), (int)(nb * s), scan_modes.data(), qps[qi], sse.data(), nonzero.data(), rate.data(), sign_data_hiding,
+                          rdoq, lambda, mode_bits.data(), ts_flag.data()) != PNN_OK)
+                    return refuse_signal(entry, "the transform coding with transform skip refused the arguments.");
+            } else if (pnn_trquant_rdoq_host(pred.data(), tgt.data(), width, (int)(nb * s), scan_modes.data(), qps + qi, 1, sse.data(), nonzero.data(), nullptr,
                                       nullptr, rate.data(), sign_data_hiding, rdoq, rdoq ? &lambda : nullptr) != PNN_OK)
                 return refuse_signal(entry, "the transform coding refused the arguments.");
             // width 64: one cbf bin per quadrant (transform depth 1, context 0), so the levels themselves are asked for -- the stages entry
@@ -406,6 +423,7 @@ int rd_pass_body(const char* entry, int codec, const uint8_t* patterns, int patt
                 if (best_sse) best_sse[at] = d_best;
                 if (best_rate) best_rate[at] = r_best;
                 if (best_side_rate) best_side_rate[at] = side_best;
+                if (best_ts_flag) best_ts_flag[at] = coder && slot != kUnused ? ts_flag[i * s + slot] : (uint8_t)0;
             }
         }
         if (cand_modes) std::copy(slot_modes, slot_modes + (size_t)n * s, cand_modes + (size_t)qi * n * s);
@@ -452,6 +470,19 @@ extern "C" int pnn_rd_pass_codec_host(const uint8_t* patterns, int pattern_h, in
     return rd_pass_body(entry, 1, patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq,
                         left_modes, above_modes, cand_modes, cand_costs, best_mode, best_slot, best_cost, best_sse, best_rate, first_pass_costs,
                         best_side_rate);
+}
+
+// The body with signalling for pnn_tskip.cpp, which brings the coder of the slots' two forms: this file does not
+// name that file's entries, so it links without it.
+int pnn::rd_pass_host_with_coder(const char* entry, int codec, const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width,
+                                 int n, const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                                 int rdoq, const uint8_t* left_modes, const uint8_t* above_modes, uint8_t* cand_modes, double* cand_costs,
+                                 uint8_t* best_mode, uint8_t* best_slot, double* best_cost, uint32_t* best_sse, uint64_t* best_rate,
+                                 double* first_pass_costs, uint64_t* best_side_rate, pnn::RdSlotCoder coder, uint8_t* best_ts_flag)
+{
+    return rd_pass_body(entry, codec, patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq,
+                        left_modes, above_modes, cand_modes, cand_costs, best_mode, best_slot, best_cost, best_sse, best_rate, first_pass_costs,
+                        best_side_rate, coder, best_ts_flag);
 }
 
 // The mode statistics (include/pnn_hip.h, "mode statistics"): the yardstick of mode_stats_kernel, three plain counts.

@@ -184,7 +184,8 @@ def context_descriptor_fields(width_target, height, width, index_image, row_1st,
 def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                               tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
                               transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False, transform_rdoq=False,
-                              rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False):
+                              rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False,
+                              transform_skip='off', rd_pass_transform_skip=False):
     """comparing_pnn_ipfcns_hevc_best_mode.py:324-452 (`predict_masks`) on the GPU: the dictionary_performance of
     predict_mask_vs_hevc_best_mode for every mask of `tuples_width_height_masks`, as {(mask_w, mask_h): dictionary}, same keys,
     dtypes and bits.  With `net_ipfcns` the mask (0, 0) also gets the IPFCN-S keys of predict_without_mask_via_ipfcns.
@@ -275,16 +276,31 @@ def score_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, 
     transform calls and of the second-pass call (0 without it): HM's RDOQ under HM's lambda of each QP (include/pnn_hip.h,
     "rate-distortion optimised quantisation").  The transform-domain keys and the rd_pass_* keys are then those of RDOQ 1, and
     'transform_rdoq': True joins them.  Equal to intraprediction.transform_code(rdoq=True, modes=...) and rd_pass(rdoq=True) on the
-    dictionary's own arrays.  With transform_rdoq=False nothing changes: not a key, a call or a byte."""
+    dictionary's own arrays.  With transform_rdoq=False nothing changes: not a key, a call or a byte.
+    transform_skip='forced' or 'decide' (width 4 and transform_qps; ValueError otherwise, and for any other name than 'off', before
+    anything touches the GPU; include/pnn_hip.h, "transform skip"; at width 4 'decide' is what the reference's configuration does): the two
+    transform-coding calls go to pnn_trquant_tskip_device -- every 4 x 4 unit in its skipped form, or in the form HM's rule keeps under
+    HM's lambda of each QP, no mode bits, the cbf bin charged; the scan of the best mode's column follows its mode.  The transform-domain
+    keys are then the kept form's (the rate with the flag's bin), and new keys join them: 'transform_skip': the name,
+    'transform_skip_flags_pnn' and 'transform_skip_flags_hevc_best_mode' (uint8 [nb_qps, N]: one per coded column, as every other
+    transform-domain key) and 'frequency_transform_skip_pnn' / '_hevc_best_mode' (one float per QP: the share of units kept skipped).
+    Equal to intraprediction.transform_code(transform_skip=..., modes=...) on the dictionary's own arrays.
+    rd_pass_transform_skip=True (width 4 and rd_pass_signalling=True; ValueError otherwise, before anything touches the GPU): the second
+    pass is pnn_rd_pass_tskip_picture_pairs_device's, either codec -- every slot keeps its cheaper form before the slots are compared, so
+    'frequency_rd_pass_win_pnn' is computed against the competitor HM runs.  New keys: 'rd_pass_best_transform_skip' (uint8 [nb_qps, N],
+    the winner's flag) and 'frequency_rd_pass_transform_skip' (one float per QP: the share of winners kept skipped).  Equal to
+    intraprediction.rd_pass(transform_skip=True).  With the defaults nothing changes: not a key, a call or a byte."""
     return _score_masks(channels_uint8, 1, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks,
                         net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass,
-                        transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec, rd_pass_mode_stats)
+                        transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec, rd_pass_mode_stats, transform_skip,
+                        rd_pass_transform_skip)
 
 
 def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training,
                                    tuples_width_height_masks, net_ipfcns=None, keep_predictions=True, first_pass=False, reference_smoothing=0,
                                    transform_qps=(), transform_rate=False, transform_sign_hiding=False, rd_pass=False, transform_rdoq=False,
-                                   rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False):
+                                   rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False,
+                                   transform_skip='off', rd_pass_transform_skip=False):
     """score_masks_from_pictures for the "pair" models (trained on contexts of HEVC-decoded pictures with targets of the originals):
     channels_pair_uint8 [images, H, W, 2] as the reference carries such data, channel 0 the original, channel 1 the decoded picture.
     Same arguments otherwise, same dictionaries per mask, same `keep_predictions`, same errors before anything touches the GPU.
@@ -299,12 +315,12 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
     original, as in the table above.  reference_smoothing: as for score_masks_from_pictures; the smoothed line is built from the decoded
     plane's samples, as the unsmoothed one is.  transform_qps: as for score_masks_from_pictures; the predictions that get coded are the
     ones made from the decoded plane, the residual's and the SSE's targets come from the original, as in the table above.
-    transform_rate, transform_sign_hiding, transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec, rd_pass_mode_stats:
-    as for score_masks_from_pictures."""
+    transform_rate, transform_sign_hiding, transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec, rd_pass_mode_stats,
+    transform_skip, rd_pass_transform_skip: as for score_masks_from_pictures."""
     return _score_masks(channels_pair_uint8, 2, width_target, row_1sts, col_1sts, predictor, mean_training,
                         tuples_width_height_masks, net_ipfcns, keep_predictions, first_pass, reference_smoothing, transform_qps,
                         transform_rate, transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec,
-                        rd_pass_mode_stats)
+                        rd_pass_mode_stats, transform_skip, rd_pass_transform_skip)
 
 def _check_score_masks_arguments(ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
                                  reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False, transform_rdoq=False):
@@ -374,7 +390,8 @@ _RD_PASS_SECTIONS = ('rd_pass_candidates', 'rd_pass_costs', 'rd_pass_modes', 'rd
                      'rd_pass_rates')                                                      # intraprediction.RD_PASS_OUTPUTS, in the entry's order
 
 
-def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False, rd_pass_signalling=False, rd_pass_codec='switch', rd_pass_mode_stats=False):
+def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False, rd_pass_signalling=False, rd_pass_codec='switch', rd_pass_mode_stats=False,
+                   transform_skip=0, rd_pass_transform_skip=False):
     """Every output of a mask's calls in ONE buffer, described once as (name, dtype, shape): the small results first, then the uint8
     blocks of the PNN, of HEVC and the targets; a download is a prefix of it.  Each section starts at a multiple of its item size.
     Returns (sections, begin, end), the last two the byte offsets by name; end['targets'] is the size of the buffer."""
@@ -387,10 +404,14 @@ def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False, rd_p
         sections += [('%s_%s' % (name, column), np.uint32, (nb_qps, n)) for name in _COUNTS]
         if transform_rate:
             sections.append(('rate_' + column, np.uint64, (nb_qps, n)))
+        if transform_skip:
+            sections.append(('transform_skip_flags_' + column, np.uint8, (nb_qps, n)))
     if rd_pass and rd_pass_signalling:                    # per QP, K + 3 slots (K + 2: the substitution codec); the list's costs are not asked for
         shapes = intraprediction.rd_pass_signal_shapes(n, nb_qps, w, rd_pass_codec)
         sections += [(name, dtype, shape) for name, (_, dtype), shape in zip(_RD_PASS_SECTIONS, intraprediction.RD_PASS_OUTPUTS, shapes)]
         sections.append(('rd_pass_side_rates', np.uint64, shapes[-1]))
+        if rd_pass_transform_skip:
+            sections.append(('rd_pass_best_transform_skip', np.uint8, (nb_qps, n)))
     elif rd_pass:
         sections += [(name, dtype, shape) for name, (_, dtype), shape in zip(_RD_PASS_SECTIONS, intraprediction.RD_PASS_OUTPUTS,
                                                                              intraprediction.rd_pass_shapes(n, nb_qps, w))]
@@ -406,7 +427,8 @@ def _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass=False, rd_p
 
 
 def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False,
-                            transform_rdoq=False, rd_pass_signalling=False, rd_pass_codec='switch', rd_pass_mode_stats=False):
+                            transform_rdoq=False, rd_pass_signalling=False, rd_pass_codec='switch', rd_pass_mode_stats=False,
+                            transform_skip='off', rd_pass_transform_skip=False):
     """One mask's dictionary_performance, but for the uint8 blocks, from `view`: the downloaded sections by name."""
     psnrs_pnn = intraprediction.psnrs_from_sses(view['sses_pnn'], w)
     psnrs_hevc = intraprediction.psnrs_from_sses(view['sses_hevc'], w)
@@ -436,6 +458,11 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
         d['transform_sign_hiding'] = True
     if transform_rdoq:
         d['transform_rdoq'] = True
+    if transform_skip != 'off':
+        d['transform_skip'] = transform_skip
+        for column, _ in _CODED_COLUMNS:
+            d['transform_skip_flags_' + column] = view['transform_skip_flags_' + column].copy()
+            d['frequency_transform_skip_' + column] = [float(np.count_nonzero(flags)) / n for flags in d['transform_skip_flags_' + column]]
     if rd_pass:
         d.update({key: view[key].copy() for key in ('rd_pass_candidates', 'rd_pass_costs', 'rd_pass_modes', 'rd_pass_sses')})
         d['rd_pass_rate_bits'] = view['rd_pass_rates'].astype(np.float64) / 32768.
@@ -444,6 +471,9 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
         d['frequency_rd_pass_win_pnn'] = [float(np.count_nonzero(modes == pnn_mode)) / n for modes in d['rd_pass_modes']]
         if rd_pass_signalling:
             d['rd_pass_side_rate_bits'] = view['rd_pass_side_rates'].astype(np.float64) / 32768.
+        if rd_pass_transform_skip:
+            d['rd_pass_best_transform_skip'] = view['rd_pass_best_transform_skip'].copy()
+            d['frequency_rd_pass_transform_skip'] = [float(np.count_nonzero(flags)) / n for flags in d['rd_pass_best_transform_skip']]
         if rd_pass_mode_stats:
             stats = intraprediction.mode_stats_dictionary(view['rd_pass_mode_stats'], n)
             d.update({'rd_pass_mode_fast_selections': stats['fast_selections'], 'rd_pass_mode_fast_wins': stats['fast_wins'],
@@ -453,7 +483,8 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
 
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
                  keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False,
-                 transform_rdoq=False, rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False):
+                 transform_rdoq=False, rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False,
+                 transform_skip='off', rd_pass_transform_skip=False):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer.  Every option is an argument
     of the one entry its call has (the smoothing; the mode pointer, the rate pointer and the flag), 0 or NULL when off."""
@@ -469,6 +500,16 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         raise ValueError("`rd_pass_codec` 'substitution' is set without `rd_pass_signalling`.")
     if rd_pass_mode_stats and not rd_pass:
         raise ValueError('`rd_pass_mode_stats` is set without `rd_pass`.')
+    if transform_skip not in intraprediction._TRANSFORM_SKIP:
+        raise ValueError("`transform_skip` is not 'off', 'forced' or 'decide'.")
+    skip = intraprediction._TRANSFORM_SKIP[transform_skip]
+    if skip and len(transform_qps) == 0:
+        raise ValueError('`transform_skip` is on without `transform_qps`.')
+    if rd_pass_transform_skip and not rd_pass_signalling:
+        raise ValueError('`rd_pass_transform_skip` is set without `rd_pass_signalling`.')
+    if (skip or rd_pass_transform_skip) and w != 4:
+        raise ValueError('`transform_skip` / `rd_pass_transform_skip` is on at a width other than 4.')
+    rd_skip = int(bool(rd_pass_transform_skip))
     masks, rows, cols, reference_smoothing, transform_qps = _check_score_masks_arguments(
         ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns, reference_smoothing,
         transform_qps, transform_rate, transform_sign_hiding, rd_pass, transform_rdoq)
@@ -488,15 +529,20 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     d_planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(ch, 3, 0))).to(dev)      # [planes, images, H, W]: one copy, one upload
     d_target_channels, d_context_channels = d_planes[0], d_planes[nb_planes - 1]
     d_rows, d_cols = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (rows, cols))
-    sections, begin, end = _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass, rd_pass_signalling, rd_pass_codec, rd_pass_mode_stats)
+    sections, begin, end = _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass, rd_pass_signalling, rd_pass_codec, rd_pass_mode_stats,
+                                          skip, rd_skip)
     d_out = torch.empty(end['targets'], dtype=torch.uint8, device=dev)       # the last section
     ptr = {name: d_out.data_ptr() + begin[name] for name in begin}
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     c_qps = (ctypes.c_int * max(nb_qps, 1))(*transform_qps)
     if rd_pass:                                           # the entry's scratch, the caller's: once for all masks
-        nb_scratch = L.pnn_rd_pass_codec_workspace_bytes(w, n, nb_qps, signalling, codec)
+        nb_scratch = (L.pnn_rd_pass_tskip_workspace_bytes(w, n, nb_qps, signalling, codec, 1) if rd_skip else
+                      L.pnn_rd_pass_codec_workspace_bytes(w, n, nb_qps, signalling, codec))
         d_scratch = torch.empty(nb_scratch, dtype=torch.uint8, device=dev)
         d_left, d_above = (None if a is None else torch.from_numpy(a).to(dev) for a in (left, above))
+    if skip:                                              # the scratch of the two forms, the caller's: once for all masks and both columns
+        nb_skip_scratch = L.pnn_trquant_tskip_workspace_bytes(w, n, nb_qps)
+        d_skip_scratch = torch.empty(nb_skip_scratch, dtype=torch.uint8, device=dev)
     results, targets_uint8 = {}, None
     for i, mask in enumerate(masks):
         if mask in results:
@@ -516,12 +562,26 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
             for column, predictions in _CODED_COLUMNS if nb_qps else ():
                 # both predictions and the first mask's targets are on the device.  Where the scan is read (by the rate, by the hiding), the
                 # best mode's follows its mode, which the score call left there; the PNN has no mode: the diagonal scan
-                modes = ptr['indices_hevc'] if column == 'hevc_best_mode' and (transform_rate or transform_sign_hiding or transform_rdoq) else None
+                modes = ptr['indices_hevc'] if column == 'hevc_best_mode' and (transform_rate or transform_sign_hiding or transform_rdoq or
+                                                                               skip) else None
+                if skip:                                  # (with the option off the call below is the one of before, argument for argument)
+                    _lib.check(L.pnn_trquant_tskip_device(
+                        predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps, ptr['sses_recon_' + column],
+                        ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None, ptr['rate_' + column] if transform_rate else None,
+                        int(bool(transform_sign_hiding)), int(bool(transform_rdoq)), None, skip, None, 1, ptr['transform_skip_flags_' + column],
+                        d_skip_scratch.data_ptr(), nb_skip_scratch, stream), predictor.ctx)
+                    continue
                 _lib.check(L.pnn_trquant_rdoq_device(
                     predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps, ptr['sses_recon_' + column],
                     ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None, ptr['rate_' + column] if transform_rate else None,
                     int(bool(transform_sign_hiding)), int(bool(transform_rdoq)), None, stream), predictor.ctx)
-            if rd_pass:                                   # the candidate is the PNN's uint8 prediction; NULL lambdas: HM's of each QP
+            if rd_pass and rd_skip:                       # the second pass with transform skip: the codec entry's arguments and two more
+                _lib.check(L.pnn_rd_pass_tskip_picture_pairs_device(
+                    *blocks, ptr['predictions_pnn'], reference_smoothing, c_qps, nb_qps, None, int(bool(transform_sign_hiding)),
+                    int(bool(transform_rdoq)), signalling, None if d_left is None else d_left.data_ptr(),
+                    None if d_above is None else d_above.data_ptr(), codec, 1, *[ptr[name] for name in _RD_PASS_SECTIONS], None,
+                    ptr['rd_pass_side_rates'], ptr['rd_pass_best_transform_skip'], d_scratch.data_ptr(), nb_scratch, stream), predictor.ctx)
+            elif rd_pass:                                 # the candidate is the PNN's uint8 prediction; NULL lambdas: HM's of each QP
                 # (the one entry of the second pass; codec 0 forwards to pnn_rd_pass_signal_picture_pairs_device, whose signalling 0 forwards
                 # to pnn_rd_pass_rdoq_picture_pairs_device: the same launches)
                 _lib.check(L.pnn_rd_pass_codec_picture_pairs_device(
@@ -529,16 +589,16 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                     int(bool(transform_rdoq)), signalling, None if d_left is None else d_left.data_ptr(),
                     None if d_above is None else d_above.data_ptr(), codec, *[ptr[name] for name in _RD_PASS_SECTIONS], None,
                     ptr['rd_pass_side_rates'] if signalling else None, d_scratch.data_ptr(), nb_scratch, stream), predictor.ctx)
-                if rd_pass_mode_stats:                    # from the slots and winners the call above left in the output buffer
-                    _lib.check(L.pnn_rd_pass_mode_stats_device(
-                        predictor.ctx, ptr['rd_pass_candidates'], signalling, intraprediction.rd_pass_slot_count(w, signalling, rd_pass_codec),
-                        ptr['rd_pass_modes'], n, nb_qps, ptr['rd_pass_mode_stats'], stream), predictor.ctx)
+            if rd_pass and rd_pass_mode_stats:            # from the slots and winners the call above left in the output buffer
+                _lib.check(L.pnn_rd_pass_mode_stats_device(
+                    predictor.ctx, ptr['rd_pass_candidates'], signalling, intraprediction.rd_pass_slot_count(w, signalling, rd_pass_codec),
+                    ptr['rd_pass_modes'], n, nb_qps, ptr['rd_pass_mode_stats'], stream), predictor.ctx)
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
         dictionary_performance = _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transform_qps, transform_rate,
                                                          transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling, rd_pass_codec,
-                                                         rd_pass_mode_stats)
+                                                         rd_pass_mode_stats, transform_skip, rd_skip)
         if keep_predictions:
             if first:
                 targets_uint8 = view['targets'].copy()

@@ -356,8 +356,11 @@ def _blocks_uint8(array_uint8, name):
     return np.ascontiguousarray(array_uint8)
 
 
+_TRANSFORM_SKIP = {'off': 0, 'forced': 1, 'decide': 2}
+
+
 def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reconstructions=False, modes=None, rate=False,
-                   sign_data_hiding=False, rdoq=False, lambdas=None):
+                   sign_data_hiding=False, rdoq=False, lambdas=None, transform_skip='off', mode_bits=None, charge_cbf=True):
     """Open-loop HEVC transform coding of N predictions against their targets (uint8 [N, w, w] or [N, w, w, 1]) at the 1 to 8 QPs of
     `qps` (integers in [0, 51]): HM's residual path, with RDOQ 0 unless `rdoq` is set -- forward transform, quantisation, dequantisation, inverse transform,
     reconstruction -- as include/pnn_hip.h defines it (T = w up to 32, the four 32 x 32 quadrants of the one prediction at w = 64; no
@@ -380,20 +383,39 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
     pnn_trquant_rdoq_host / _device, which every call here goes to, with 0 and NULL when off): xRateDistOptQuant under lambdas -- None
     (hm_intra_lambda of each QP) or one finite value > 0 per QP -- and, with sign_data_hiding, its own hiding.  Same keys, all of them
     those of the levels RDOQ leaves; sum_abs_levels is its uiAbsSum.  `modes` is then allowed too.  `lambdas` without rdoq is a
-    ValueError.  With False nothing changes."""
+    ValueError.  With False nothing changes.
+    transform_skip (include/pnn_hip.h, "transform skip"; width 4 only, what the reference's configuration does there): 'off', 'forced'
+    (every unit in its skipped form) or 'decide' (both forms, HM's choice per unit and QP by D + lambda (R >> 15) under `lambdas` --
+    then allowed without rdoq --, R with `mode_bits`, None or integers [nb_qps, N] in 2^-15 bit, and with the cbf_luma bin unless
+    charge_cbf is False).  Adds the key 'transform_skip_flags' (uint8 [nb_qps, N]); the other keys are the kept form's, rate_bits with
+    the flag's bin.  The calls go to pnn_trquant_tskip_host / _device, which with 'off' forward to the entries above: the same bytes
+    and launches.  A width other than 4 with the option on is a ValueError before anything touches the GPU."""
     qps = _check_qps(qps)
     predictions, targets = _blocks_uint8(predictions_uint8, 'predictions_uint8'), _blocks_uint8(targets_uint8, 'targets_uint8')
     if predictions.shape != targets.shape:
         raise ValueError('`predictions_uint8.shape` is not equal to `targets_uint8.shape`.')
     n, w = targets.shape[0], targets.shape[1]
+    if transform_skip not in _TRANSFORM_SKIP:
+        raise ValueError("`transform_skip` is not 'off', 'forced' or 'decide'.")
+    skip = _TRANSFORM_SKIP[transform_skip]
+    if skip and w != 4:
+        raise ValueError('`transform_skip` is on at a width other than 4.')
+    if mode_bits is not None and skip != 2:
+        raise ValueError("`mode_bits` is given without `transform_skip` 'decide'.")
+    if mode_bits is not None:
+        mode_bits = np.asarray(mode_bits)
+        if mode_bits.shape != (len(qps), n) or not np.issubdtype(mode_bits.dtype, np.integer) or (n and (mode_bits.min() < 0 or mode_bits.max() >= 2 ** 32)):
+            raise ValueError('`mode_bits` is not an array of shape [nb_qps, N] of integers in [0, 2^32).')
+        mode_bits = np.ascontiguousarray(mode_bits.astype(np.uint32))
+    cbf = int(bool(charge_cbf))
     nq = len(qps)
     c_qps = (ctypes.c_int * nq)(*qps)
     L = _lib.lib()
     flag, option = int(bool(sign_data_hiding)), int(bool(rdoq))
-    if lambdas is not None and not option:
+    if lambdas is not None and not option and skip != 2:
         raise ValueError('`lambdas` is given without `rdoq`.')
     c_lambdas = _check_lambdas(lambdas, nq, positive=True)
-    if not (rate or flag or option):
+    if not (rate or flag or option or skip):
         if modes is not None:
             raise ValueError('`modes` is given without `rate`.')
     elif modes is not None:
@@ -407,11 +429,13 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
         sses, nonzero, sum_abs = (np.zeros((nq, n), np.uint32) for _ in range(3))
         bits = np.zeros((nq, n), np.uint64) if rate else None
         recon = np.zeros((nq, n, w, w), np.uint8) if keep_reconstructions else None
-        rc = L.pnn_trquant_rdoq_host(predictions.ctypes.data, targets.ctypes.data, w, n, _address(modes), c_qps, nq, sses.ctypes.data,
-                                     nonzero.ctypes.data, sum_abs.ctypes.data, _address(recon), _address(bits), flag, option, c_lambdas)
+        ts_flags = np.zeros((nq, n), np.uint8) if skip else None
+        rc = L.pnn_trquant_tskip_host(predictions.ctypes.data, targets.ctypes.data, w, n, _address(modes), c_qps, nq, sses.ctypes.data,
+                                      nonzero.ctypes.data, sum_abs.ctypes.data, _address(recon), _address(bits), flag, option, c_lambdas,
+                                      skip, _address(mode_bits), cbf, _address(ts_flags))
         if rc != 0:                                       # (named as the ABI names the call with these options)
             raise ValueError('pnn_trquant_%shost refused the arguments (width %d, %d blocks).'
-                             % ('rdoq_' if option else 'sdh_' if flag else 'rate_' if rate else '', w, n))
+                             % ('tskip_' if skip else 'rdoq_' if option else 'sdh_' if flag else 'rate_' if rate else '', w, n))
     else:
         import torch
         dev = torch.device("cuda", device)
@@ -420,12 +444,18 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
         d_counts = torch.zeros((3, nq, n), dtype=torch.int32, device=dev)
         d_bits = torch.zeros((nq, n), dtype=torch.int64, device=dev) if rate else None
         d_recon = torch.zeros((nq, n, w, w), dtype=torch.uint8, device=dev) if keep_reconstructions else None
+        d_flags = torch.zeros((nq, n), dtype=torch.uint8, device=dev) if skip else None
+        d_mode_bits = None if mode_bits is None else torch.from_numpy(mode_bits.view(np.int32)).to(dev)
+        ws_bytes = L.pnn_trquant_tskip_workspace_bytes(w, n, nq) if skip else 0
+        d_ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_trquant_rdoq_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, _address(d_modes), c_qps, nq,
-                                                 d_counts[0].data_ptr(), d_counts[1].data_ptr(), d_counts[2].data_ptr(), _address(d_recon),
-                                                 _address(d_bits), flag, option, c_lambdas, ctypes.c_void_p(stream.cuda_stream)),
+            _lib.check(L.pnn_trquant_tskip_device(_context(device), w, d_pred.data_ptr(), d_tg.data_ptr(), n, _address(d_modes), c_qps, nq,
+                                                  d_counts[0].data_ptr(), d_counts[1].data_ptr(), d_counts[2].data_ptr(), _address(d_recon),
+                                                  _address(d_bits), flag, option, c_lambdas, skip, _address(d_mode_bits), cbf,
+                                                  _address(d_flags), _address(d_ws), ws_bytes, ctypes.c_void_p(stream.cuda_stream)),
                        _context(device))
+        ts_flags = None if d_flags is None else d_flags.cpu().numpy()
         sses, nonzero, sum_abs = d_counts.cpu().numpy().view(np.uint32)      # (waits for the stream)
         bits = None if d_bits is None else d_bits.cpu().numpy().view(np.uint64)
         recon = None if d_recon is None else d_recon.cpu().numpy()
@@ -434,6 +464,8 @@ def transform_code(predictions_uint8, targets_uint8, qps, device=None, keep_reco
         result['rate_bits'] = bits.astype(np.float64) / 32768.
     if keep_reconstructions:
         result['reconstructions_uint8'] = recon
+    if skip:
+        result['transform_skip_flags'] = ts_flags
     return result
 
 
@@ -576,38 +608,48 @@ def rd_pass_signal_shapes(n, nb_qps, width_target, codec='switch'):
     return ((nb_qps, n, s), (nb_qps, n, s)) + ((nb_qps, n),) * 5 + ((nb_qps, n, k), (nb_qps, n))
 
 
-def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device, codec='switch'):
-    """rd_pass with signalling: the checked arguments -> the dictionary, from pnn_rd_pass_codec_host (device None) or _device."""
+def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device, codec='switch',
+                    transform_skip=False):
+    """rd_pass with signalling: the checked arguments -> the dictionary, from pnn_rd_pass_codec_host (device None) or _device; with
+    transform_skip from pnn_rd_pass_tskip_host / _device, which take the option behind the codec and one more output behind the others
+    ('best_transform_skip' uint8 [nb_qps, n]) and have a scratch function of their own."""
     n, w, nq = targets.shape[0], targets.shape[1], len(qps)
     left, above = (None, None) if neighbour_modes is None else neighbour_modes
     with_35 = not CODECS[codec]                           # a neighbour coded with 35 exists in the switch codec only
     left, above = _neighbour_array(left, n, with_35, 'neighbour_modes[0]'), _neighbour_array(above, n, with_35, 'neighbour_modes[1]')
-    shapes = rd_pass_signal_shapes(n, nq, w, codec)
+    outputs, shapes = tuple(RD_PASS_SIGNAL_OUTPUTS), tuple(rd_pass_signal_shapes(n, nq, w, codec))
     L = _lib.lib()
+    if transform_skip:
+        name, option_arguments = 'pnn_rd_pass_tskip_', (CODECS[codec], 1)
+        outputs, shapes = outputs + (('best_transform_skip', np.uint8),), shapes + ((nq, n),)
+        nb_bytes = L.pnn_rd_pass_tskip_workspace_bytes(w, n, nq, 1, CODECS[codec], 1)
+    else:
+        name, option_arguments = 'pnn_rd_pass_codec_', (CODECS[codec],)
+        nb_bytes = L.pnn_rd_pass_codec_workspace_bytes(w, n, nq, 1, CODECS[codec])
     if device is None or n == 0:
-        outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(RD_PASS_SIGNAL_OUTPUTS, shapes)]
-        rc = L.pnn_rd_pass_codec_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
-                                      smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(left), _address(above), CODECS[codec],
-                                      *[o.ctypes.data for o in outs])
+        outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(outputs, shapes)]
+        rc = getattr(L, name + 'host')(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
+                                       smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(left), _address(above), *option_arguments,
+                                       *[o.ctypes.data for o in outs])
         if rc != 0:
-            raise ValueError('pnn_rd_pass_signal_host refused the arguments (patterns %dx%d, width %d).' % (patterns.shape[1], patterns.shape[2], w))
+            raise ValueError('%s refused the arguments (patterns %dx%d, width %d).'
+                             % ('pnn_rd_pass_tskip_host' if transform_skip else 'pnn_rd_pass_signal_host', patterns.shape[1], patterns.shape[2], w))
     else:
         import torch
         dev = torch.device("cuda", device)
         d_in = [torch.from_numpy(a).to(dev) for a in (patterns, targets, candidate)]
         d_left, d_above = (None if a is None else torch.from_numpy(a).to(dev) for a in (left, above))
         d_outs = [torch.zeros(int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=torch.uint8, device=dev)
-                  for (_, dtype), shape in zip(RD_PASS_SIGNAL_OUTPUTS, shapes)]
-        nb_bytes = L.pnn_rd_pass_codec_workspace_bytes(w, n, nq, 1, CODECS[codec])
+                  for (_, dtype), shape in zip(outputs, shapes)]
         d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_rd_pass_codec_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
-                                                  n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(d_left),
-                                                  _address(d_above), CODECS[codec], *[o.data_ptr() for o in d_outs], d_ws.data_ptr(), nb_bytes,
-                                                  ctypes.c_void_p(stream.cuda_stream)), _context(device))
-        outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, RD_PASS_SIGNAL_OUTPUTS, shapes)]   # (waits)
-    result = {name: out for (name, _), out in zip(RD_PASS_SIGNAL_OUTPUTS, outs)}
+            _lib.check(getattr(L, name + 'device')(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
+                                                   n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(d_left),
+                                                   _address(d_above), *option_arguments, *[o.data_ptr() for o in d_outs], d_ws.data_ptr(), nb_bytes,
+                                                   ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, outputs, shapes)]   # (waits)
+    result = {name: out for (name, _), out in zip(outputs, outs)}
     result['rate_bits'] = result['rates'].astype(np.float64) / 32768.
     result['side_rate_bits'] = result['side_rates'].astype(np.float64) / 32768.
     result['psnrs_recon'] = psnrs_from_sses(result['sses'], w)
@@ -616,7 +658,7 @@ def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, 
 
 
 def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoothing=0, sign_data_hiding=False, lambdas=None, device=None,
-            rdoq=False, signalling=False, neighbour_modes=None, codec='switch'):
+            rdoq=False, signalling=False, neighbour_modes=None, codec='switch', transform_skip=False):
     """HM's second intra pass as include/pnn_hip.h defines it ("the second intra pass"): per block and QP the RD choice among the
     first-pass candidates (mode_hads_*'s list with the candidate prediction competing as 35) and the candidate itself, appended if the
     list lacks it.  numpy uint8 arrays: patterns [n, h, w'], targets and candidate_predictions [n, w, w]; qps: 1 to 8 integers in
@@ -639,7 +681,16 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     codec='substitution' (the argument of pnn_rd_pass_codec_host / _device, which every call here goes to, with 0 for 'switch';
     include/pnn_hip.h, "the substitution codec"; needs signalling=True): HM's own search over modes 0 .. 34 with the candidate as mode
     18's prediction -- no flag bin, no mode 35, neighbours 0 .. 34 / 255, 'candidates' and 'costs' [nb_qps, n, K + 2]; the winner is the
-    candidate where 'modes' is 18.  Same keys.  With 'switch' nothing changes."""
+    candidate where 'modes' is 18.  Same keys.  With 'switch' nothing changes.
+    transform_skip=True (pnn_rd_pass_tskip_host / _device; include/pnn_hip.h, "transform skip"; width 4 and signalling=True only, either
+    codec; ValueError otherwise, before anything touches the GPU): every slot is coded transformed and transform-skipped and keeps the
+    cheaper form by HM's rule before the slots are compared; 'rates' then holds the flag's bin, and the dictionary gains
+    'best_transform_skip' uint8 [nb_qps, n], the winning slot's flag.  Every lambda must be > 0.  With False nothing changes: the same
+    entries as before are called with the same arguments."""
+    if transform_skip and not signalling:
+        raise ValueError('`transform_skip` is given without `signalling`.')
+    if transform_skip and not (isinstance(targets, np.ndarray) and len(targets.shape) == 3 and targets.shape[1] == 4):
+        raise ValueError('`transform_skip` is on at a width other than 4.')
     number = _check_codec(codec, signalling)
     smoothing = _check_smoothing(reference_smoothing)
     qps = _check_qps(qps)
@@ -652,11 +703,12 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     n = _check_mode_hads_arguments(intra_patterns, targets, w, candidate_predictions)
     patterns, targets, candidate = (np.ascontiguousarray(a) for a in arrays)
     flag, option = int(bool(sign_data_hiding)), int(bool(rdoq))
-    c_qps, c_lambdas = (ctypes.c_int * nq)(*qps), _check_lambdas(lambdas, nq, positive=bool(option))
+    c_qps, c_lambdas = (ctypes.c_int * nq)(*qps), _check_lambdas(lambdas, nq, positive=bool(option) or bool(transform_skip))
     if not signalling and neighbour_modes is not None:
         raise ValueError('`neighbour_modes` is given without `signalling`.')
     if signalling:
-        return _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device, codec)
+        return _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device, codec,
+                               bool(transform_skip))
     shapes = rd_pass_shapes(n, nq, w)
     L = _lib.lib()
     if device is None or n == 0:                          # (no block: nothing to launch, the empty arrays)

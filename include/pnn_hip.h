@@ -946,6 +946,81 @@ int pnn_rd_pass_mode_stats_host(const uint8_t* slot_modes, int per_qp, int slots
 int pnn_rd_pass_mode_stats_device(pnn_ctx* ctx, const uint8_t* d_slot_modes, int per_qp, int slots, const uint8_t* d_best_mode, int n,
                                   int nb_qps, uint32_t* d_stats, void* stream);
 
+/* ---- transform skip: HM-16.15's second form of a 4 x 4 luma unit, as intra_main_rext.cfg switches it on
+ * (TransformSkip 1, TransformSkipFast 1, RDOQTS 1), for the transform coding above.  Width 4 only: Log2MaxTransformSkipBlockSize is 2.
+ * 8-bit luma, maxLog2TrDynamicRange 15; rotation, RDPCM, extended precision, transform_skip_context, scaling lists and transquant
+ * bypass off.
+ *   Forward (xTransformSkip): coefficient = residual << 5.  Quantisation, hiding, RDOQ (RDOQTS = RDOQ) and dequantisation: the
+ *     transform coding's, on those coefficients, under the unit's scan; nothing in them reads the flag.
+ *   Inverse (xITransformSkip): residual' = (coefficient' + 16) >> 5; reconstruction and SSE as in the transform coding.
+ *   Rate: codeCoeffNxN with the PPS flag on codes transform_skip_flag in front of the levels of every 4 x 4 unit WITH a level -- one
+ *     bin of a context of its own (I-slice initial value 139) from the state the QP starts with, value 0 for the transformed form --;
+ *     a unit without a level codes neither.
+ *   Decision (xRecurIntraCodingLumaQT, checkTransformSkip), per unit and QP: J = D + lambda (R >> 15), one multiply and one add,
+ *     R = mode_bits + (charge_cbf: the cbf_luma bin of the form's cbf, context 0) + (cbf 1: flag bin + level bits); the transformed
+ *     form first, the skipped one second, forbidden when its cbf is 0; strict <, so a tie stays transformed.  cbf = a nonzero level.
+ *   Pinned to HM's own transformNxN / invTransformNxN / codeCoeffNxN / codeTransformSkipFlags (tests/golden/hm_transform_skip.npz).
+ *
+ * pnn_tskip_unit_host, ONE unit: residual int32 [4][4] in [-255, 255], scan 0 .. 2, qp in [0, 51], transform_skip 0 (the transformed
+ * form: the transform coding's stages) or 1 -> each NULL or: coeffs, levels (the final ones), residual_back int32 [4][4], *abs_sum HM's
+ * uiAbsSum, *bits what codeCoeffNxN adds with the PPS flag on (0 without a level), flag_bins [2] the flag's bin alone for 0 and 1.
+ * lambda is read with rdoq only (finite, > 0).  Pure host code. */
+int pnn_tskip_unit_host(const int32_t* residual, int scan, int qp, int sign_data_hiding, int rdoq, double lambda, int transform_skip,
+                        int32_t* coeffs, int32_t* levels, int32_t* abs_sum, int32_t* residual_back, uint64_t* bits, uint64_t* flag_bins);
+/* pnn_trquant_rdoq_host with the option.  transform_skip 0: that entry, byte for byte (ts_flag, where given, is zeroed).  1, forced:
+ * every unit in its skipped form.  2, decide: both forms, the rule above per unit and QP under lambdas (NULL: pnn_hm_intra_lambda of
+ * each QP; the same lambda quantises with rdoq), mode_bits NULL (0) or uint32 [nb_qps][n] in 2^-15 bit, charge_cbf 0 or 1.  Outputs as
+ * pnn_trquant_rdoq_host's, of the kept form: rate = the levels' bits + the flag bin, 0 without a level; ts_flag NULL or uint8
+ * [nb_qps][n] (forced: 1 everywhere; with option 0 one of the other five outputs is needed, as that entry asks).  Modes are allowed
+ * whatever the outputs.  PNN_E_ARG also for: a nonzero option at a width other
+ * than 4, an option outside 0 .. 2, charge_cbf outside 0 .. 1, with decide or rdoq a lambdas entry that is not finite or not > 0. */
+int pnn_trquant_tskip_host(const uint8_t* predictions, const uint8_t* targets, int width, int n, const uint8_t* modes, const int* qps,
+                           int nb_qps, uint32_t* sses_recon, uint32_t* nb_nonzero, uint32_t* sum_abs_levels, uint8_t* recon, uint64_t* rate,
+                           int sign_data_hiding, int rdoq, const double* lambdas, int transform_skip, const uint32_t* mode_bits, int charge_cbf,
+                           uint8_t* ts_flag);
+/* The same on the GPU, bit-identical to the host twin.  transform_skip 0: pnn_trquant_rdoq_device's launch, unchanged; the workspace is
+ * not read and ts_flag, where given, is zeroed on the stream.  1: tskip4_kernel into the workspace, tskip_decide_kernel out of it (2
+ * launches); 2: the unchanged transform-coding launch and tskip4_kernel into the workspace, then tskip_decide_kernel (3 launches).
+ * d_workspace: at least pnn_trquant_tskip_workspace_bytes(width, n, nb_qps) bytes of device memory at a multiple of 16 (0 for a width
+ * other than 4 or bad sizes), needed with a nonzero option only.  d_mode_bits is a DEVICE array, qps and lambdas are HOST arrays.  Every
+ * refusal (the host twin's but the mode values, a NULL, misaligned or short workspace) comes before any launch. */
+size_t pnn_trquant_tskip_workspace_bytes(int width, int n, int nb_qps);
+int pnn_trquant_tskip_device(pnn_ctx* ctx, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes,
+                             const int* qps, int nb_qps, uint32_t* d_sses_recon, uint32_t* d_nb_nonzero, uint32_t* d_sum_abs_levels,
+                             uint8_t* d_recon, uint64_t* d_rate, int sign_data_hiding, int rdoq, const double* lambdas, int transform_skip,
+                             const uint32_t* d_mode_bits, int charge_cbf, uint8_t* d_ts_flag, void* d_workspace, size_t workspace_bytes,
+                             void* stream);
+
+/* The second intra pass with the option, for both codecs: pnn_rd_pass_codec_*'s arguments with transform_skip (0 or 1) behind `codec`
+ * and the output best_ts_flag (NULL or uint8 [nb_qps][n]) behind best_side_rate.  signalling is required (PNN_E_ARG without), whatever
+ * the option.  transform_skip 0: the pass of pnn_rd_pass_codec_* with signalling; best_ts_flag, where given, is zeroed.  1, width 4
+ * only: per QP every slot is coded in both forms and decided per slot by the rule above (mode_bits = the slot's mode bits under the
+ * block's MPMs, charge_cbf 1, the QP's lambda, which must be finite and > 0); the slots' merged D, count and R (with the flag bin)
+ * then go to the unchanged decision.  cand_costs, best_* are those of the merged slots; best_ts_flag is the winning slot's flag (0
+ * for a block without a winner).  Device: per QP 4 more launches (tskip4_kernel, the slots' mode bits, tskip_decide_kernel in place,
+ * the winners' flags); the workspace is pnn_rd_pass_tskip_workspace_bytes (pnn_rd_pass_codec_workspace_bytes with the option 0; 0
+ * for what the entries refuse).  Every refusal comes before any launch. */
+int pnn_rd_pass_tskip_host(const uint8_t* patterns, int pattern_h, int pattern_w, const uint8_t* targets, int width, int n,
+                           const uint8_t* cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                           int rdoq, int signalling, const uint8_t* left_modes, const uint8_t* above_modes, int codec, int transform_skip,
+                           uint8_t* cand_modes, double* cand_costs, uint8_t* best_mode, uint8_t* best_slot, double* best_cost,
+                           uint32_t* best_sse, uint64_t* best_rate, double* first_pass_costs, uint64_t* best_side_rate, uint8_t* best_ts_flag);
+size_t pnn_rd_pass_tskip_workspace_bytes(int width, int n, int nb_qps, int signalling, int codec, int transform_skip);
+int pnn_rd_pass_tskip_device(pnn_ctx* ctx, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
+                             const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding,
+                             int rdoq, int signalling, const uint8_t* d_left_modes, const uint8_t* d_above_modes, int codec, int transform_skip,
+                             uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
+                             uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate,
+                             uint8_t* d_best_ts_flag, void* d_workspace, size_t workspace_bytes, void* stream);
+int pnn_rd_pass_tskip_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                           int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                                           const double* lambdas, int sign_data_hiding, int rdoq, int signalling, const uint8_t* d_left_modes,
+                                           const uint8_t* d_above_modes, int codec, int transform_skip, uint8_t* d_cand_modes,
+                                           double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
+                                           uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate,
+                                           uint8_t* d_best_ts_flag, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
 int pnn_last_call_stats(const pnn_ctx* ctx, int* n_gemm_launches, double* gemm_flops, int* n_launches);
