@@ -160,7 +160,10 @@ SIGNATURES = {
                                                     ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, ci] + [vp] * 10 + [ctypes.c_size_t, vp]),
     "pnn_rd_pass_mode_stats_host": (ci, [vp, ci, ci, vp, ci, ci, vp]),
     "pnn_rd_pass_mode_stats_device": (ci, [vp, vp, ci, ci, vp, ci, ci, vp, vp]),
-    "pnn_last_call_stats": (ci, [vp, ctypes.POINTER(ci),ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
+    "pnn_cu_tree_host": (ci, [ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, vp, vp, vp, vp, vp, ci] + [vp] * 8),
+    "pnn_cu_tree_device": (ci, [vp, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, vp, vp, vp, vp, vp, ci] + [vp] * 9),
+    "pnn_cu_tree_bins_host": (ci, [ci, vp]),
+    "pnn_last_call_stats": (ci,[vp, ctypes.POINTER(ci),ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
 

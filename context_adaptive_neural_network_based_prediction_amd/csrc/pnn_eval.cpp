@@ -1114,6 +1114,55 @@ int pnn_rd_pass_mode_stats_device(pnn_ctx* c, const uint8_t* d_slot_modes, int p
     return PNN_OK;
 }
 
+// The coding-tree pass on leaves that lie on the device: the refusals are cutree::refusal's, the host twin's own;
+// the edge depths are read back once (the call waits for the stream) and checked before the launch, as the positions of a picture are.
+// selected / selected_pnn are zeroed on the stream, then ONE launch (cu_tree_kernel) does everything.
+int pnn_cu_tree_device(pnn_ctx* c, const int* qps, int nb_qps, const double* lambdas, int n_ctu, const uint32_t* const* d_dists,
+                       const uint64_t* const* d_rates, const uint8_t* const* d_modes, const uint8_t* d_left_depths, const uint8_t* d_above_depths,
+                       int pnn_mode, uint8_t* d_cu_depths, uint8_t* d_part_nxn, double* d_node_costs, double* d_ctu_costs, uint64_t* d_ctu_dists,
+                       uint64_t* d_ctu_rates, uint32_t* d_selected, uint32_t* d_selected_pnn, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    const bool any = d_cu_depths || d_part_nxn || d_node_costs || d_ctu_costs || d_ctu_dists || d_ctu_rates || d_selected || d_selected_pnn;
+    if (const char* refusal = cutree::refusal(qps, nb_qps, lambdas, n_ctu, d_dists, d_rates, d_modes, pnn_mode, any, d_selected_pnn != nullptr))
+        return fail(c, PNN_E_ARG, "%s", refusal);
+    for (int k = 0; k < cutree::kWidths; k++)
+        if ((uintptr_t)d_dists[k] % 4 || (uintptr_t)d_rates[k] % 8) return fail(c, PNN_E_ARG, "a leaf array is not aligned to its element");
+    if ((uintptr_t)d_node_costs % 8 || (uintptr_t)d_ctu_costs % 8 || (uintptr_t)d_ctu_dists % 8 || (uintptr_t)d_ctu_rates % 8 ||
+        (uintptr_t)d_selected % 4 || (uintptr_t)d_selected_pnn % 4) return fail(c, PNN_E_ARG, "an output is not aligned to its element");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (d_left_depths || d_above_depths) {
+        const size_t cells = (size_t)nb_qps * n_ctu * 8;
+        std::vector<uint8_t> left(d_left_depths ? cells : 0), above(d_above_depths ? cells : 0);
+        {
+            PNN_UNSAFE_CALLS_GUARD;
+            if (d_left_depths) HIPCHK(c, hipMemcpyAsync(left.data(), d_left_depths, cells, hipMemcpyDeviceToHost, s));
+            if (d_above_depths) HIPCHK(c, hipMemcpyAsync(above.data(), d_above_depths, cells, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+        }
+        const char* refusal = cutree::edge_refusal(left.data(), left.size());
+        if (!refusal) refusal = cutree::edge_refusal(above.data(), above.size());
+        if (refusal) return fail(c, PNN_E_ARG, "%s", refusal);
+    }
+    reset_stats(c);
+    CuTreeParams p;
+    for (int k = 0; k < cutree::kWidths; k++) { p.dist[k] = d_dists[k]; p.rate[k] = d_rates[k]; p.mode[k] = d_modes ? d_modes[k] : nullptr; }
+    p.left = d_left_depths; p.above = d_above_depths; p.n_ctu = n_ctu; p.nb_qps = nb_qps; p.pnn_mode = pnn_mode;
+    for (int i = 0; i < cutree::kMaxQps; i++) {
+        const int qp = qps[i < nb_qps ? i : 0];
+        p.lambda[i] = lambdas ? lambdas[i < nb_qps ? i : 0] : pnn_hm_intra_lambda(qp);
+        p.bits[i] = cutree::qp_bits(qp);
+    }
+    p.cu_depths = d_cu_depths; p.part_nxn = d_part_nxn; p.node_costs = d_node_costs; p.ctu_costs = d_ctu_costs; p.ctu_dists = d_ctu_dists;
+    p.ctu_rates = d_ctu_rates; p.selected = d_selected; p.selected_pnn = d_selected_pnn;
+    if (d_selected) HIPCHK(c, hipMemsetAsync(d_selected, 0, (size_t)nb_qps * cutree::kWidths * 4, s));
+    if (d_selected_pnn) HIPCHK(c, hipMemsetAsync(d_selected_pnn, 0, (size_t)nb_qps * cutree::kWidths * 4, s));
+    HIPCHK(c, launch_cu_tree(p, s));
+    c->stat_launches++;
+    return PNN_OK;
+}
+
 int pnn_score_f32_device(pnn_ctx* c, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,
                          int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, uint8_t* d_pred_u8,
                          uint32_t* d_sse, void* stream)

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "pnn_cabac_tables.h"
+#include "pnn_cu_tree.h"
 #include "pnn_mode_signal.h"
 #include "pnn_rdoq.h"
 #include "pnn_trquant_tables.h"
@@ -428,6 +429,20 @@ struct TskipSlotBitsParams {
 hipError_t launch_tskip_slot_bits(const TskipSlotBitsParams& p, hipStream_t s);
 struct TskipBestFlagParams { const uint8_t* ts_flag; const uint8_t* best_slot; int N; int S; uint8_t* best_flag; };
 hipError_t launch_tskip_best_flag(const TskipBestFlagParams& p, hipStream_t s);
+
+// The coding-tree pass (pnn_cu_tree.hip; the definition is pnn_cu_tree.h): per (QP, CTU) the partition of
+// xCompressCU's recursion from the leaves dist / rate [5 widths: 4 .. 64] of [nb_qps][n_ctu][(64 / w)^2] (z-order), mode NULL or
+// likewise, left / above NULL or uint8 [nb_qps][n_ctu][8], per QP lambda and the bins' bits, made on the host.  Outputs, each NULL or:
+// cu_depths, part_nxn [nb_qps][n_ctu][64]; node_costs [nb_qps][n_ctu][85][2]; ctu_costs, ctu_dists, ctu_rates [nb_qps][n_ctu];
+// selected, selected_pnn uint32 [nb_qps][5], ZEROED by the caller on the stream: the kernel adds to them.
+struct CuTreeParams {
+    const uint32_t* dist[cutree::kWidths]; const uint64_t* rate[cutree::kWidths]; const uint8_t* mode[cutree::kWidths];
+    const uint8_t* left; const uint8_t* above; int n_ctu; int nb_qps; int pnn_mode;
+    double lambda[cutree::kMaxQps]; cutree::QpBits bits[cutree::kMaxQps];
+    uint8_t* cu_depths; uint8_t* part_nxn; double* node_costs; double* ctu_costs; uint64_t* ctu_dists; uint64_t* ctu_rates;
+    uint32_t* selected; uint32_t* selected_pnn;
+};
+hipError_t launch_cu_tree(const CuTreeParams& p, hipStream_t s);
 
 // IPFCN-S, the evaluator's second competitor (pnn_ipfcns.hip).  Blocks b0 .. b0 + nb - 1 of images x positions (image-major): the
 // two groups of 8 reference lines at line origin (rows[pos], cols[pos]) of uint8 picture `img` [H][W] -- rows [r, r + 8) x columns

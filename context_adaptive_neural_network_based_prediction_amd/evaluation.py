@@ -614,3 +614,47 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                                                                       pred_u8=keep_predictions)
         _fill_ipfcns_keys(results[(0, 0)], sses, w, pred_u8)
     return results
+
+
+def coding_tree_from_scores(scores_by_width, left_depths=None, above_depths=None, device=0):
+    """The coding-tree pass (include/pnn_hip.h, "the coding tree"; intraprediction.cu_tree) over the second passes of the five widths:
+    which of the blocks that `frequency_rd_pass_win_pnn` counts HM's recursion would actually code, per 64 x 64 CTU and QP.
+    scores_by_width: {4: .., 8: .., 16: .., 32: .., 64: ..}, each the dictionary of mask (0, 0) -- or the {(0, 0): dictionary} a call
+    returns -- of score_masks_from_pictures / _picture_pairs with rd_pass=True and rd_pass_signalling=True (either codec, the same for
+    all five) on the positions intraprediction.ctu_block_positions gives that width for ONE list of CTUs, so that every width's blocks
+    arrive in (image, CTU, z-order) order.  The five must share their QPs, their codec (told by the slots per block) and their number
+    of CTUs; a mismatch is a ValueError before anything touches the GPU.  left_depths / above_depths: as for cu_tree, per (QP, CTU) with
+    the CTUs counted image-major.  The leaves are rebuilt on the host from the dictionaries' own arrays -- 'rd_pass_sses' and the two
+    rates, 12 bytes per block and QP -- uploaded, and decided by pnn_cu_tree_device on `device`; lambda is HM's of each QP, as in the
+    second passes.  Returns cu_tree's dictionary; the mode that stands for the PNN is 35 under the switch codec, 18 under substitution."""
+    if not isinstance(scores_by_width, dict) or sorted(scores_by_width) != list(intraprediction.WIDTHS):
+        raise ValueError('`scores_by_width` is not a dictionary with the keys 4, 8, 16, 32 and 64.')
+    needed = ('transform_qps', 'rd_pass_sses', 'rd_pass_rate_bits', 'rd_pass_side_rate_bits', 'rd_pass_modes', 'rd_pass_candidates')
+    leaves, qps, codec, n_ctu = {}, None, None, None
+    for w in intraprediction.WIDTHS:
+        d = scores_by_width[w]
+        if isinstance(d, dict) and (0, 0) in d:
+            d = d[(0, 0)]
+        if not isinstance(d, dict) or any(key not in d for key in needed):
+            raise ValueError('the dictionary of width %d lacks the second pass with signalling (rd_pass=True, rd_pass_signalling=True).' % w)
+        slots = d['rd_pass_candidates'].shape[-1]
+        names = [name for name in intraprediction.CODECS if intraprediction.rd_pass_slot_count(w, True, name) == slots]
+        if len(names) != 1:
+            raise ValueError('the dictionary of width %d has %d slots per block: no codec with signalling has.' % (w, slots))
+        count = (intraprediction.CTU_WIDTH // w) ** 2
+        n = d['rd_pass_sses'].shape[1]
+        if n == 0 or n % count:
+            raise ValueError('the dictionary of width %d holds %d blocks: not whole CTUs of %d.' % (w, n, count))
+        if qps is None:
+            qps, codec, n_ctu = tuple(d['transform_qps']), names[0], n // count
+        if tuple(d['transform_qps']) != qps:
+            raise ValueError('the dictionaries differ in their QPs (width %d).' % w)
+        if names[0] != codec:
+            raise ValueError('the dictionaries differ in their codec (width %d).' % w)
+        if n // count != n_ctu:
+            raise ValueError('the dictionaries differ in their CTU list (width %d: %d CTUs, width 4: %d).' % (w, n // count, n_ctu))
+        # the rates are whole numbers of 2^-15 bit below 2^53: the division that made the bits and this multiplication are exact
+        leaves[w] = (d['rd_pass_sses'], (d['rd_pass_rate_bits'] * 32768.).astype(np.uint64), (d['rd_pass_side_rate_bits'] * 32768.).astype(np.uint64),
+                     d['rd_pass_modes'])
+    pnn_mode = intraprediction.SUBSTITUTED_MODE if intraprediction.CODECS[codec] else intraprediction.NB_MODES
+    return intraprediction.cu_tree(leaves, qps, None, left_depths, above_depths, pnn_mode, device)

@@ -865,3 +865,150 @@ def transform_stages(prediction_uint8, target_uint8, qp, sign_data_hiding=False,
     return stages
 
 
+
+
+CTU_WIDTH = 64                                            # the coding tree (include/pnn_hip.h, "the coding tree"): CTU 64, minimum CU 8
+CU_TREE_OUTPUTS = (('cu_depths', np.uint8), ('part_nxn', np.uint8), ('node_costs', np.float64), ('ctu_costs', np.float64),
+                   ('ctu_dists', np.uint64), ('ctu_rates', np.uint64), ('selected', np.uint32), ('selected_pnn', np.uint32))
+
+
+def cu_tree_shapes(nb_qps, n_ctu):
+    """The shapes of CU_TREE_OUTPUTS, in the entries' order."""
+    return ((nb_qps, n_ctu, 64), (nb_qps, n_ctu, 64), (nb_qps, n_ctu, 85, 2)) + ((nb_qps, n_ctu),) * 3 + ((nb_qps, len(WIDTHS)),) * 2
+
+
+def z_order_offsets(side):
+    """(x, y) of the side^2 cells of a square in HM's z-order (side a power of two): bit 2 j of the index is bit j of x, bit 2 j + 1
+    bit j of y."""
+    index = np.arange(side * side)
+    x, y = np.zeros_like(index), np.zeros_like(index)
+    for j in range(max(side.bit_length() - 1, 0)):
+        x |= ((index >> (2 * j)) & 1) << j
+        y |= ((index >> (2 * j + 1)) & 1) << j
+    return x, y
+
+
+def ctu_block_positions(width_target, ctu_row_1sts, ctu_col_1sts):
+    """The positions of every aligned block of width `width_target` inside the listed 64 x 64 CTUs, in (CTU, z-order) order, as the
+    `row_1sts` / `col_1sts` the evaluator expects -- the corner of the block's context, block position - width_target --, so that the
+    outputs of a second pass over them arrive in the layout of cu_tree's leaves.  ctu_row_1sts / ctu_col_1sts: the CTUs' own top-left
+    samples (integers, equally many, >= width_target so that the context exists).  Returns (row_1sts, col_1sts), int64
+    [n_ctu * (64 / width_target)^2]."""
+    if width_target not in WIDTHS:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    rows, cols = np.asarray(ctu_row_1sts), np.asarray(ctu_col_1sts)
+    if rows.ndim != 1 or rows.shape != cols.shape or not (np.issubdtype(rows.dtype, np.integer) and np.issubdtype(cols.dtype, np.integer)):
+        raise ValueError('`ctu_row_1sts` and `ctu_col_1sts` are not two integer arrays of one length.')
+    if rows.size and (rows.min() < width_target or cols.min() < width_target):
+        raise ValueError("a CTU lies closer than `width_target` to the picture's top or left: its first block has no context.")
+    x, y = z_order_offsets(CTU_WIDTH // width_target)
+    w = width_target
+    return ((rows.astype(np.int64)[:, None] + y[None, :] * w - w).ravel(), (cols.astype(np.int64)[:, None] + x[None, :] * w - w).ravel())
+
+
+def _cu_tree_leaf(leaf, width, nb_qps):
+    """One width's leaves as (dist uint32, rate uint64, modes uint8 or None), each [nb_qps, n]; rate = 'rates' + 'side_rates'."""
+    if isinstance(leaf, dict):
+        missing = [k for k in ('sses', 'rates', 'side_rates', 'modes') if k not in leaf]
+        if missing:
+            raise ValueError('the leaves of width %d lack %s (rd_pass with signalling=True returns them).' % (width, missing))
+        leaf = (leaf['sses'], leaf['rates'], leaf['side_rates'], leaf['modes'])
+    if not isinstance(leaf, (tuple, list)) or len(leaf) != 4:
+        raise ValueError('the leaves of width %d are not an rd_pass dictionary or (sses, rates, side_rates, modes).' % width)
+    sses, rates, side_rates, modes = leaf
+    for array, dtype, name in ((sses, np.uint32, 'sses'), (rates, np.uint64, 'rates'), (side_rates, np.uint64, 'side_rates'), (modes, np.uint8, 'modes')):
+        if array is None and name == 'modes':
+            continue
+        if not isinstance(array, np.ndarray) or array.dtype != dtype or array.ndim != 2 or array.shape[0] != nb_qps:
+            raise ValueError("`%s` of width %d is not a %s array [nb_qps, n]." % (name, width, np.dtype(dtype).name))
+        if array.shape != sses.shape:
+            raise ValueError('the leaves of width %d differ in shape.' % width)
+    return np.ascontiguousarray(sses), np.ascontiguousarray(rates + side_rates), None if modes is None else np.ascontiguousarray(modes)
+
+
+def _edge_depths(depths, nb_qps, n_ctu, name):
+    if depths is None:
+        return None
+    depths = np.asarray(depths)
+    if depths.shape != (nb_qps, n_ctu, 8) or not np.issubdtype(depths.dtype, np.integer):
+        raise ValueError('`%s` is not an integer array [nb_qps, n_ctu, 8].' % name)
+    if np.any((depths != NO_NEIGHBOUR) & ((depths < 0) | (depths > 3))):
+        raise ValueError('`%s` holds a depth outside 0 .. 3 / 255.' % name)
+    return np.ascontiguousarray(depths.astype(np.uint8))
+
+
+def cu_tree(leaves, qps, lambdas=None, left_depths=None, above_depths=None, pnn_mode=35, device=None):
+    """The coding-tree pass as include/pnn_hip.h defines it ("the coding tree"; pnn_cu_tree_host / _device): per QP and 64 x 64 CTU the
+    partition HM's recursion (TEncCu::xCompressCU) chooses among the second pass's winners -- split or not at 64, 32 and 16, 2N x 2N
+    or N x N at 8 -- its cost, and how many blocks of each width it selects.
+    leaves: {4: .., 8: .., 16: .., 32: .., 64: ..}, each an rd_pass(signalling=True) dictionary or (sses, rates, side_rates, modes)
+    with modes None allowed; each array [nb_qps, n_ctu * (64 / w)^2], the blocks in (CTU, z-order) order (ctu_block_positions).
+    qps: 1 to 8 integers in [0, 51]; lambdas None (hm_intra_lambda of each QP) or one finite value >= 0 per QP; left_depths /
+    above_depths None (no neighbouring CTU) or integer [nb_qps, n_ctu, 8], the CU depth 0 .. 3 beside each 8 samples of the CTU's
+    left / upper edge, 255 = not available; pnn_mode: the mode that stands for the PNN, 35 (switch codec) or 18 (substitution).
+    device=None runs the host twin, an int that GPU; the bits are the same.
+    Returns {'cu_depths', 'part_nxn': uint8 [nb_qps, n_ctu, 64] (z-order over the 8 x 8 cells), 'node_costs': float64
+    [nb_qps, n_ctu, 85, 2] (unsplit / split, at depth 3 2N x 2N / N x N), 'ctu_costs': float64, 'ctu_dists', 'ctu_rates': uint64
+    [nb_qps, n_ctu] (rates in 2^-15 bit), 'selected': uint32 [nb_qps, 5] (blocks of width 4 .. 64 in the chosen partitions),
+    'selected_pnn' (those whose mode is pnn_mode; only with modes at every width), 'frequency_selected_pnn': float64 [nb_qps, 5]
+    (their share, NaN where a width is never selected; only with modes), 'area_share': float64 [nb_qps, 5] (the share of samples
+    coded at each width), 'lambdas': float64 [nb_qps], the values used}."""
+    qps = _check_qps(qps)
+    nq = len(qps)
+    if not isinstance(leaves, dict) or sorted(leaves) != list(WIDTHS):
+        raise ValueError('`leaves` is not a dictionary with the keys 4, 8, 16, 32 and 64.')
+    if isinstance(pnn_mode, (bool, np.bool_)) or not isinstance(pnn_mode, (int, np.integer)) or not 0 <= pnn_mode <= 255:
+        raise ValueError('`pnn_mode` is not an integer in [0, 255].')
+    arrays = [_cu_tree_leaf(leaves[w], w, nq) for w in WIDTHS]
+    n_ctu = arrays[-1][0].shape[1]
+    if n_ctu < 1 or any(a[0].shape[1] != n_ctu * (CTU_WIDTH // w) ** 2 for a, w in zip(arrays, WIDTHS)):
+        raise ValueError('the leaves do not hold the blocks of one list of at least one CTU: n_ctu * (64 / w)^2 per width.')
+    with_modes = all(a[2] is not None for a in arrays)
+    c_qps, c_lambdas = (ctypes.c_int * nq)(*qps), _check_lambdas(lambdas, nq)
+    left, above = _edge_depths(left_depths, nq, n_ctu, 'left_depths'), _edge_depths(above_depths, nq, n_ctu, 'above_depths')
+    shapes = cu_tree_shapes(nq, n_ctu)
+    wanted = [with_modes or name != 'selected_pnn' for name, _ in CU_TREE_OUTPUTS]
+    pointers = ctypes.c_void_p * len(WIDTHS)
+    L = _lib.lib()
+    if device is None:
+        outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(CU_TREE_OUTPUTS, shapes)]
+        rc = L.pnn_cu_tree_host(c_qps, nq, c_lambdas, n_ctu, pointers(*[a[0].ctypes.data for a in arrays]),
+                                pointers(*[a[1].ctypes.data for a in arrays]), pointers(*[a[2].ctypes.data for a in arrays]) if with_modes else None,
+                                _address(left), _address(above), int(pnn_mode), *[o.ctypes.data if want else None for o, want in zip(outs, wanted)])
+        if rc != 0:
+            raise ValueError('pnn_cu_tree_host refused the arguments.')
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        d_in = [[None if a is None else torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32
+                                                         else a).to(dev) for a in triple] for triple in arrays]
+        d_edges = [None if a is None else torch.from_numpy(a).to(dev) for a in (left, above)]
+        d_outs = [torch.zeros(max(int(np.prod(shape)) * np.dtype(dtype).itemsize, 8), dtype=torch.uint8, device=dev)
+                  for (_, dtype), shape in zip(CU_TREE_OUTPUTS, shapes)]
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.pnn_cu_tree_device(_context(device), c_qps, nq, c_lambdas, n_ctu, pointers(*[t[0].data_ptr() for t in d_in]),
+                                            pointers(*[t[1].data_ptr() for t in d_in]),
+                                            pointers(*[t[2].data_ptr() for t in d_in]) if with_modes else None,
+                                            *[None if e is None else e.data_ptr() for e in d_edges], int(pnn_mode),
+                                            *[o.data_ptr() if want else None for o, want in zip(d_outs, wanted)],
+                                            ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        outs = [o.cpu().numpy()[:int(np.prod(shape)) * np.dtype(dtype).itemsize].view(dtype).reshape(shape)      # (waits for the stream)
+                for o, (_, dtype), shape in zip(d_outs, CU_TREE_OUTPUTS, shapes)]
+    result = {name: out for (name, _), out, want in zip(CU_TREE_OUTPUTS, outs, wanted) if want}
+    selected = result['selected'].astype(np.float64)
+    if with_modes:
+        with np.errstate(invalid='ignore', divide='ignore'):
+            result['frequency_selected_pnn'] = np.where(selected > 0, result['selected_pnn'] / selected, np.nan)
+    result['area_share'] = selected * np.array([w * w for w in WIDTHS], np.float64) / float(n_ctu * CTU_WIDTH * CTU_WIDTH)
+    result['lambdas'] = np.array([hm_intra_lambda(q) for q in qps]) if c_lambdas is None else np.array(list(c_lambdas))
+    return result
+
+
+def cu_tree_bins(qp):
+    """The bins of the coding tree at QP `qp` in 2^-15 bit (pnn_cu_tree_bins_host): {'split': uint32 [3, 2] ([context][value] of
+    split_cu_flag), 'part': uint32 [2] (part_mode: [0] N x N, [1] 2N x 2N)}, each from the state an I slice of the QP starts with."""
+    out = np.zeros(8, np.uint32)
+    if isinstance(qp, (bool, np.bool_)) or not isinstance(qp, (int, np.integer)) or _lib.lib().pnn_cu_tree_bins_host(int(qp), out.ctypes.data) != 0:
+        raise ValueError('`qp` is not an integer in [0, 51].')
+    return {'split': out[:6].reshape(3, 2).copy(), 'part': out[6:].copy()}

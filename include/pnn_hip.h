@@ -1021,6 +1021,56 @@ int pnn_rd_pass_tskip_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_
                                            uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate,
                                            uint8_t* d_best_ts_flag, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the coding tree: the decision of TEncCu::xCompressCU between a coding unit and its four sub-units, and at
+ * 8 x 8 between SIZE_2Nx2N and SIZE_NxN, from the winners the second pass left at every aligned block of the five widths.  HM-16.15
+ * regular tree, I slice, luma only (the reference codes its luminance sets as 4:0:0); CTU 64, minimum CU 8 (MaxPartitionDepth 4); PCM,
+ * transquant bypass, cu_qp_delta and AMP off; whole CTUs only.  The quadtree of TRANSFORM units is not part of it.
+ *   Nodes.  85 CU nodes per CTU, depth d = 0 .. 3 of size 64 >> d; below each depth-3 node four 4 x 4 prediction units.  Every per-CTU
+ *     array is in HM's z-order, depth by depth: 1 + 4 + 16 + 64 nodes (node i of depth d has the children 4 i .. 4 i + 3 one depth
+ *     down); 256 units, the four of a CU adjacent.  Cell z of a 64-entry map is the 8 x 8 cell whose x has bit j at bit 2 j of z and
+ *     whose y has bit j at bit 2 j + 1.
+ *   Leaves.  Per width w = 4, 8, 16, 32, 64 (the order of every per-width argument), each [nb_qps][n_ctu][(64 / w)^2]: dist uint32, the
+ *     winner's SSE; rate uint64 in 2^-15 bit, the winner's rate + side rate (mode bits and cbf inside); optionally mode uint8.
+ *   Depth 3, no neighbour involved.  2N x 2N: D = dist_8, F = rate_8 + the part_mode bin of value 1.  N x N: D = the four dist_4, F =
+ *     the four rate_4 + the bin of value 0.  The bin is one bin of the part-size model, context 0, from the state an I slice of the QP
+ *     starts with.  J = (double) D + lambda * (double) (F >> 15): one IEEE multiply and one IEEE add, never fused.  2N x 2N first,
+ *     N x N second, strict <: a tie stays 2N x 2N.
+ *   Depths 2, 1, 0, in z-order post-order.  Unsplit: D and F of the node's own leaf + the split_cu_flag bin of value 0.  Split: the
+ *     four children's chosen D and F (at depth 3 the winner above, which codes no split flag) + the bin of value 1.  Unsplit first,
+ *     strict <: a tie stays unsplit.  The children's F are summed exactly; the shift by 15 happens once per comparison.
+ *   Context of split_cu_flag (TComDataCU::getCtxSplitFlag): [left available and its CU depth > d] + [above available and its CU depth
+ *     > d], "left" the CU that covers the sample left of the node's top-left sample, "above" the one over it.  Inside the CTU the depth
+ *     comes from an 8 x 8 map of minimum-CU cells into which a subtree writes its final depth when its root is decided; outside from
+ *     left_depths / above_depths, uint8 [nb_qps][n_ctu][8], one cell per 8 samples along the edge (top to bottom, left to right),
+ *     0 .. 3 or 255 = not available; NULL: nothing available.  No CTU's result is chained into the next CTU's edge.
+ *   The three contexts start from the state an I slice of the QP begins with (initial values 139, 141, 157; part size 184).
+ *   Where this differs from the tree (whole bits per CU, the counter's carried fraction, running contexts): DESIGN.md section 5q.
+ * Outputs, each NULL or: cu_depths uint8 [nb_qps][n_ctu][64], the final map; part_nxn uint8 [nb_qps][n_ctu][64], 1 where the cell is
+ * an 8 x 8 CU coded N x N; node_costs double [nb_qps][n_ctu][85][2], [0] unsplit (depth 3: 2N x 2N) and [1] split (depth 3: N x N) --
+ * both alternatives exist at every node of this setting, +inf is reserved for one that does not; ctu_costs double, ctu_dists and
+ * ctu_rates uint64 [nb_qps][n_ctu], the root's chosen J, D and F; selected uint32 [nb_qps][5], the blocks of each width in the chosen
+ * partitions (an N x N CU counts four of width 4); selected_pnn uint32 [nb_qps][5], those of them whose mode equals pnn_mode (35 for
+ * the switch codec, 18 for substitution; 0 .. 255).  lambdas NULL: pnn_hm_intra_lambda of each QP.
+ * PNN_E_ARG, before any launch: nb_qps outside 1 .. 8 or a QP outside [0, 51]; n_ctu < 1; a missing leaf array (dists, rates or one of
+ * their five entries NULL; modes given with a NULL entry); a lambda not finite or < 0; an edge depth outside 0 .. 3 / 255; selected_pnn
+ * without modes; no output; pnn_mode outside [0, 255].
+ * pnn_cu_tree_device: the same on leaves in device memory, bit-identical; dists, rates and modes are HOST arrays of five device
+ * pointers, qps and lambdas HOST arrays.  Asynchronous on `stream` and without allocation on the device (with edges it first reads
+ * them back and waits, to check them): the two count outputs are zeroed on the stream, then ONE launch.  Also PNN_E_ARG for an array
+ * that is not aligned to its element.
+ * pnn_cu_tree_bins_host: the bins' bits at one QP in 2^-15 bit, out [8]: split_cu_flag [2 ctx + value] for contexts 0 .. 2, then
+ * part_mode of value 0 (N x N) and 1 (2N x 2N).  Pinned to HM's own counter (tests/golden/hm_cu_tree.npz). */
+int pnn_cu_tree_host(const int* qps, int nb_qps, const double* lambdas, int n_ctu, const uint32_t* const* dists, const uint64_t* const* rates,
+                     const uint8_t* const* modes, const uint8_t* left_depths, const uint8_t* above_depths, int pnn_mode, uint8_t* cu_depths,
+                     uint8_t* part_nxn, double* node_costs, double* ctu_costs, uint64_t* ctu_dists, uint64_t* ctu_rates, uint32_t* selected,
+                     uint32_t* selected_pnn);
+int pnn_cu_tree_device(pnn_ctx* ctx, const int* qps, int nb_qps, const double* lambdas, int n_ctu, const uint32_t* const* d_dists,
+                       const uint64_t* const* d_rates, const uint8_t* const* d_modes, const uint8_t* d_left_depths,
+                       const uint8_t* d_above_depths, int pnn_mode, uint8_t* d_cu_depths, uint8_t* d_part_nxn, double* d_node_costs,
+                       double* d_ctu_costs, uint64_t* d_ctu_dists, uint64_t* d_ctu_rates, uint32_t* d_selected, uint32_t* d_selected_pnn,
+                       void* stream);
+int pnn_cu_tree_bins_host(int qp, uint32_t* out);
+
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
 int pnn_last_call_stats(const pnn_ctx* ctx, int* n_gemm_launches, double* gemm_flops, int* n_launches);
