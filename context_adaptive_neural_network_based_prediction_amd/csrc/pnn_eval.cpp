@@ -3,7 +3,10 @@
 // suffix is the sibling called with 0), IPFCN-S, the scores from pictures and pairs of pictures, the open-loop transform
 // coding of predictions, HM's second intra pass over the first-pass candidates.  Contexts, models, staging and the
 // predictor's entries: pnn_abi.cpp.  Each argument check is written once and composed per entry; an entry's ORDER of checks is part of
-// its behaviour (which of two bad arguments pnn_last_error names), so it is spelled out in the entry.
+// its behaviour (which of two bad arguments pnn_last_error names), so it is spelled out in the entry -- for the ten entries of the
+// second pass in rd_pass, the one body behind them: the narrower entries forward upwards with the option they lack at 0, the _codec_
+// and _tskip_ entries fill an RdPassCall, and rd_pass branches, with a comment, wherever rungs or forms of blocks differ in their order.
+// tests/test_gpu_eval_errors.py pins every refusal and these orders.
 #include "pnn_ctx.h"
 
 #include <algorithm>
@@ -52,42 +55,6 @@ int check_dense_blocks(pnn_ctx* c, int width, const uint8_t* d_patterns, int pat
         return fail(c, PNN_E_ARG, "intra pattern %dx%d: both sides must lie in [%d, %d]", pattern_h, pattern_w, width + 1, 2 * width + 1);
     return n < 0 || (n > 0 && (!d_patterns || !d_targets)) ? fail(c, PNN_E_ARG, "bad batch size or input buffers") : PNN_OK;
 }
-// picture-pair form, everything in front of the outputs: both planes or none, width, masks, sizes
-int check_pair_geometry(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images, int height,
-                        int width_ch, int positions, int mask_w, int mask_h)
-{
-    int rc;
-    if (!d_context_channels != !d_target_channels)
-        return fail(c, PNN_E_ARG, "one plane of the pair is NULL (%s)", d_context_channels ? "d_target_channels" : "d_context_channels");
-    if ((rc = check_width(c, width)) || (rc = check_masks(c, width, mask_w, mask_h))) return rc;
-    return check_sizes(c, images, positions, height, width_ch);
-}
-
-// The positions are read back once (the call waits for the stream) and checked before any launch: the span x span pixels at each of
-// them lie inside the picture.  `what` and `leaves` word the refusal: "position" / "context leaves" for the 3w contexts, "line origin" /
-// "lines leave" for the 2w + 8 reference lines of IPFCN-S.
-int check_positions(pnn_ctx* c, const int32_t* d_rows, const int32_t* d_cols, int positions, int span, int height, int width_ch,
-                    const char* what, const char* leaves, hipStream_t s)
-{
-    std::vector<int32_t> rows(positions), cols(positions);
-    {
-        PNN_UNSAFE_CALLS_GUARD;
-        HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(cols.data(), d_cols, (size_t)positions * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    for (int i = 0; i < positions; i++)
-        if (rows[i] < 0 || cols[i] < 0 || (long)rows[i] + span > height || (long)cols[i] + span > width_ch)
-            return fail(c, PNN_E_ARG, "%s %d (%d, %d): the %dx%d %s the %dx%d picture", what, i, rows[i], cols[i], span, span, leaves, height, width_ch);
-    return PNN_OK;
-}
-
-// inputs common to the scoring entries: the buffers, then every 3w x 3w context inside the picture
-int check_picture_blocks(pnn_ctx* c, int width, const PictureBlocks& pic, hipStream_t s)
-{
-    if (!pic.channels || !pic.rows || !pic.cols) return fail(c, PNN_E_ARG, "NULL input buffers");
-    return check_positions(c, pic.rows, pic.cols, pic.positions, 3 * width, pic.H, pic.W, "position", "context leaves", s);
-}
 
 PictureBlocks picture_blocks(const uint8_t* d_channels, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions)
 {
@@ -96,31 +63,88 @@ PictureBlocks picture_blocks(const uint8_t* d_channels, int height, int width_ch
     return b;
 }
 
-// Where a 35-mode kernel reads its blocks, the fields both parameter structs have (pnn_kernels.h).  Dense form: patterns and targets, no
-// picture.  Picture form: patterns == NULL, the planes in *pic and pic_targets, ph / pw = 2w + 1 - mask_h / mask_w (what the masks leave
-// of the pattern's first column and row).  smoothing: the checked option.
-template <typename P>
-void set_blocks(P& p, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets, long n, int width,
-                int smoothing)
+// Where a 35-mode kernel reads its n blocks.  Dense form: patterns [n][ph][pw] and targets [n][w][w].  Picture form (`pictures`):
+// contexts and intra patterns from the plane and the positions of `pic`, targets from the plane target_channels, the masks (what they
+// leave of a pattern's first column and row: 2w + 1 - mask_h / mask_w); n = images * positions, set by count_blocks.
+struct BlockSource {
+    bool pictures = false;
+    const uint8_t* patterns = nullptr; int ph = 0, pw = 0; const uint8_t* targets = nullptr;
+    PictureBlocks pic{}; const uint8_t* target_channels = nullptr; int images = 0, mask_w = 0, mask_h = 0;
+    long n = 0;
+};
+BlockSource dense_blocks(const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n)
 {
-    p.patterns = patterns; p.ph = ph; p.pw = pw; p.targets = targets; p.N = (int)n; p.w = width;
-    p.pic = pic ? *pic : PictureBlocks{}; p.pic_targets = pic_targets; p.smoothing = smoothing;
+    BlockSource b;
+    b.patterns = d_patterns; b.ph = pattern_h; b.pw = pattern_w; b.targets = d_targets; b.n = n;
+    return b;
 }
-HevcBestModeParams best_mode_params(const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets,
-                                    long n, int width, int smoothing, uint8_t* best_mode, uint32_t* best_sse, uint8_t* best_pred, uint32_t* mode_sse)
+BlockSource picture_pair_blocks(const PictureBlocks& context, const uint8_t* d_target_channels, int images, int mask_w, int mask_h)
+{
+    BlockSource b;
+    b.pictures = true; b.pic = context; b.target_channels = d_target_channels; b.images = images; b.mask_w = mask_w; b.mask_h = mask_h;
+    return b;
+}
+
+// picture-pair form, everything in front of the outputs: both planes or none, width, masks, sizes
+int check_pair_geometry(pnn_ctx* c, int width, const BlockSource& b)
+{
+    int rc;
+    if (!b.pic.channels != !b.target_channels)
+        return fail(c, PNN_E_ARG, "one plane of the pair is NULL (%s)", b.pic.channels ? "d_target_channels" : "d_context_channels");
+    if ((rc = check_width(c, width)) || (rc = check_masks(c, width, b.mask_w, b.mask_h))) return rc;
+    return check_sizes(c, b.images, b.pic.positions, b.pic.H, b.pic.W);
+}
+// either form, everything in front of the smoothing
+int check_blocks(pnn_ctx* c, int width, const BlockSource& b)
+{
+    return b.pictures ? check_pair_geometry(c, width, b) : check_dense_blocks(c, width, b.patterns, b.ph, b.pw, b.targets, (int)b.n);
+}
+
+// The positions are read back once (the call waits for the stream) and checked before any launch: the span x span pixels at each of
+// them lie inside the picture.  `what` and `leaves` word the refusal: "position" / "context leaves" for the 3w contexts, "line origin" /
+// "lines leave" for the 2w + 8 reference lines of IPFCN-S.
+int check_positions(pnn_ctx* c, const PictureBlocks& pic, int span, const char* what, const char* leaves, hipStream_t s)
+{
+    std::vector<int32_t> rows(pic.positions), cols(pic.positions);
+    {
+        PNN_UNSAFE_CALLS_GUARD;
+        HIPCHK(c, hipMemcpyAsync(rows.data(), pic.rows, (size_t)pic.positions * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(cols.data(), pic.cols, (size_t)pic.positions * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    for (int i = 0; i < pic.positions; i++)
+        if (rows[i] < 0 || cols[i] < 0 || (long)rows[i] + span > pic.H || (long)cols[i] + span > pic.W)
+            return fail(c, PNN_E_ARG, "%s %d (%d, %d): the %dx%d %s the %dx%d picture", what, i, rows[i], cols[i], span, span, leaves, pic.H, pic.W);
+    return PNN_OK;
+}
+
+// inputs common to the scoring entries: the buffers, then every 3w x 3w context inside the picture
+int check_picture_blocks(pnn_ctx* c, int width, const PictureBlocks& pic, hipStream_t s)
+{
+    if (!pic.channels || !pic.rows || !pic.cols) return fail(c, PNN_E_ARG, "NULL input buffers");
+    return check_positions(c, pic, 3 * width, "position", "context leaves", s);
+}
+
+// The blocks of a 35-mode kernel, the fields its parameter structs share (pnn_kernels.h): the dense form has no picture, the picture
+// form patterns == NULL.  smoothing: the checked option.  The outputs of the two structs made below are the caller's to set.
+template <typename P>
+void set_blocks(P& p, const BlockSource& b, int width, int smoothing)
+{
+    p.patterns = b.patterns; p.targets = b.targets; p.N = (int)b.n; p.w = width; p.pic = b.pic; p.pic_targets = b.target_channels;
+    p.ph = b.pictures ? 2 * width + 1 - b.mask_h : b.ph; p.pw = b.pictures ? 2 * width + 1 - b.mask_w : b.pw; p.smoothing = smoothing;
+}
+HevcBestModeParams best_mode_params(const BlockSource& b, int width, int smoothing)
 {
     HevcBestModeParams p;
-    set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
-    p.best_mode = best_mode; p.best_sse = best_sse; p.best_pred = best_pred; p.mode_sse = mode_sse;
+    set_blocks(p, b, width, smoothing);
+    p.best_mode = nullptr; p.best_sse = nullptr; p.best_pred = nullptr; p.mode_sse = nullptr;
     return p;
 }
-HevcModeHadsParams mode_hads_params(const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic, const uint8_t* pic_targets,
-                                    long n, int width, int smoothing, const uint8_t* cand_pred, uint32_t* mode_hads, uint32_t* cand_hads,
-                                    uint8_t* list_modes, uint32_t* list_costs)
+HevcModeHadsParams mode_hads_params(const BlockSource& b, int width, int smoothing, const uint8_t* cand_pred)
 {
     HevcModeHadsParams p;
-    set_blocks(p, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
-    p.cand_pred = cand_pred; p.mode_hads = mode_hads; p.cand_hads = cand_hads; p.list_modes = list_modes; p.list_costs = list_costs;
+    set_blocks(p, b, width, smoothing);
+    p.cand_pred = cand_pred; p.mode_hads = nullptr; p.cand_hads = nullptr; p.list_modes = nullptr; p.list_costs = nullptr;
     return p;
 }
 
@@ -134,9 +158,12 @@ int check_trquant(pnn_ctx* c, int width, const uint8_t* d_predictions, const uin
 }
 
 // the launch's inputs: the QPs' constants and initial context states, worked out here; the outputs are the caller's to set
+struct TrQuantOptions { int sign_data_hiding; int rdoq; const double* lambdas; };
 TrQuantParams trquant_params(int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const uint8_t* d_modes, const int* qps,
-                             int nb_qps, int sign_data_hiding, int rdoq, const double* lambdas)
+                             int nb_qps, const TrQuantOptions& o)
 {
+    const int sign_data_hiding = o.sign_data_hiding, rdoq = o.rdoq;
+    const double* lambdas = o.lambdas;
     TrQuantParams p;
     p.pred = d_predictions; p.targets = d_targets; p.N = n; p.w = width; p.nb_qps = nb_qps;
     for (int i = 0; i < trquant::kMaxQps; i++) {
@@ -180,237 +207,265 @@ int check_tskip_option(pnn_ctx* c, int width, int transform_skip, int top)
     return transform_skip && width != tskip::kWidth ? fail(c, PNN_E_ARG, "transform skip at width %d (4 only)", width) : PNN_OK;
 }
 
+// Carves a caller's scratch into sections, each at a multiple of 256 bytes.  With base NULL only `at`, the bytes taken, is of use.
+struct Carver {
+    void* base; size_t at = 0;
+    template <typename T>
+    T* take(size_t count)
+    {
+        T* p = (T*)((uintptr_t)base + at);
+        at += (count * sizeof(T) + 255) / 256 * 256;
+        return p;
+    }
+};
+
 // The caller's scratch of the transform coding with transform skip: both forms' outputs, [0] transformed and [1] skipped, each
-// [nb_qps][n] (recon [nb_qps][n][4][4]); every section at a multiple of 256 bytes.
+// [nb_qps][n] (recon [nb_qps][n][4][4]).
 struct TskipOut { uint32_t* sse; uint32_t* nonzero; uint32_t* sum_abs; uint64_t* rate; uint8_t* recon; };
 struct TskipWorkspace { TskipOut form[2]; size_t bytes; };
 TskipWorkspace tskip_workspace(void* base, long n, int nb_qps)
 {
     const size_t qn = (size_t)n * nb_qps;
-    size_t at = 0;
-    const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
+    Carver cv{base};
     TskipWorkspace ws;
     for (TskipOut& o : ws.form) {
-        o.rate = (uint64_t*)take(qn * 8);
-        o.sse = (uint32_t*)take(qn * 4);
-        o.nonzero = (uint32_t*)take(qn * 4);
-        o.sum_abs = (uint32_t*)take(qn * 4);
-        o.recon = take(qn * 16);
+        o.rate = cv.take<uint64_t>(qn);
+        o.sse = cv.take<uint32_t>(qn);
+        o.nonzero = cv.take<uint32_t>(qn);
+        o.sum_abs = cv.take<uint32_t>(qn);
+        o.recon = cv.take<uint8_t>(qn * 16);
     }
-    ws.bytes = at;
+    ws.bytes = cv.at;
     return ws;
 }
 
 // The caller's scratch of the second intra pass, n (K + 1) slots: per-slot rate and SSE [nb_qps][slots], the slots' predictions and
-// replicated targets [slots][w][w], their modes [slots], the first-pass list [n][K]; every section at a multiple of 256 bytes.
+// replicated targets [slots][w][w], their modes [slots], the first-pass list [n][K].
 struct RdWorkspace { uint64_t* rate; uint32_t* sse; uint8_t* pred; uint8_t* targets; uint8_t* modes; uint8_t* list; size_t bytes; };
 RdWorkspace rd_workspace(void* base, int width, long n, int nb_qps)
 {
     const int k = hevc_first_pass_list_size(width);
     const size_t slots = (size_t)n * (k + 1), w2 = (size_t)width * width;
-    size_t at = 0;
-    const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
+    Carver cv{base};
     RdWorkspace ws;
-    ws.rate = (uint64_t*)take(slots * nb_qps * 8);
-    ws.sse = (uint32_t*)take(slots * nb_qps * 4);
-    ws.pred = take(slots * w2);
-    ws.targets = take(slots * w2);
-    ws.modes = take(slots);
-    ws.list = take((size_t)n * k);
-    ws.bytes = at;
+    ws.rate = cv.take<uint64_t>(slots * nb_qps);
+    ws.sse = cv.take<uint32_t>(slots * nb_qps);
+    ws.pred = cv.take<uint8_t>(slots * w2);
+    ws.targets = cv.take<uint8_t>(slots * w2);
+    ws.modes = cv.take<uint8_t>(slots);
+    ws.list = cv.take<uint8_t>((size_t)n * k);
+    ws.bytes = cv.at;
     return ws;
-}
-
-// what both forms of the second intra pass check behind their blocks (the width is checked): candidate, QPs, lambdas, outputs, scratch
-int check_rd_pass(pnn_ctx* c, int width, int n, const uint8_t* d_cand_pred, const int* qps, int nb_qps, const double* lambdas, bool any_output,
-                  const void* d_workspace, size_t workspace_bytes)
-{
-    if (n > 0 && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_pred is NULL");
-    if ((long)n * (hevc_first_pass_list_size(width) + 1) > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 candidate slots");
-    if (!trquant::qps_ok(qps, nb_qps)) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d integers in [0, %d]", trquant::kMaxQps, trquant::kMaxQp);
-    for (int i = 0; lambdas && i < nb_qps; i++)
-        if (!(lambdas[i] >= 0. && lambdas[i] <= 1.7976931348623157e308)) return fail(c, PNN_E_ARG, "lambda %d is negative or not finite", i);
-    if (const int rc = check_some_output(c, any_output)) return rc;
-    if (n == 0) return PNN_OK;
-    const size_t need = rd_workspace(nullptr, width, n, nb_qps).bytes;
-    if (!d_workspace || (uintptr_t)d_workspace % 8) return fail(c, PNN_E_ARG, "d_workspace is NULL or not aligned to 8 bytes");
-    if (workspace_bytes < need) return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_rd_pass_workspace_bytes asks for %zu", workspace_bytes, need);
-    return PNN_OK;
-}
-
-// The four launches of the second intra pass, either form (dense: patterns and targets; pictures: *pic and pic_targets), everything
-// checked: the first-pass list into the scratch, the candidates' predictions, the transform coding of the n (K + 1) slots -- the
-// launch of pnn_trquant_sdh_device with the slots' modes as its mode array --, the decision.
-int rd_pass_launches(pnn_ctx* c, int width, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic,
-                     const uint8_t* pic_targets, long n, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
-                     const double* lambdas, int sign_data_hiding, int rdoq, uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode,
-                     uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, hipStream_t s)
-{
-    const RdWorkspace ws = rd_workspace(d_workspace, width, n, nb_qps);
-    const int k1 = hevc_first_pass_list_size(width) + 1;
-    const HevcModeHadsParams h = mode_hads_params(patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing, d_cand_pred, nullptr, nullptr,
-                                                  ws.list, nullptr);
-    HIPCHK(c, launch_hevc_mode_hads(h, s));
-    RdCandidatesParams r;
-    set_blocks(r, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
-    r.cand_pred = d_cand_pred; r.list_modes = ws.list; r.cand_modes = d_cand_modes ? d_cand_modes : ws.modes;
-    r.slot_pred = ws.pred; r.slot_targets = ws.targets;
-    HIPCHK(c, launch_rd_candidates(r, s));
-    TrQuantParams t = trquant_params(width, ws.pred, ws.targets, (int)(n * k1), r.cand_modes, qps, nb_qps, sign_data_hiding, rdoq, lambdas);
-    t.sse = ws.sse; t.rate = ws.rate;
-    HIPCHK(c, launch_trquant(t, s));
-    RdDecideParams d;
-    d.sse = ws.sse; d.rate = ws.rate; d.cand_modes = r.cand_modes; d.N = (int)n; d.w = width; d.nb_qps = nb_qps;
-    for (int i = 0; i < trquant::kMaxQps; i++) d.lambda[i] = i >= nb_qps ? 0. : lambdas ? lambdas[i] : pnn_hm_intra_lambda(qps[i]);
-    d.cand_costs = d_cand_costs; d.best_mode = d_best_mode; d.best_slot = d_best_slot; d.best_cost = d_best_cost; d.best_sse = d_best_sse;
-    d.best_rate = d_best_rate;
-    HIPCHK(c, launch_rd_decide(d, s));
-    c->stat_launches += 4;
-    return PNN_OK;
 }
 
 // The caller's scratch of the second pass with mode signalling, n (K + 3) slots of ONE QP at a time: per-slot rate, SSE and count of
 // nonzero levels, the slots' predictions and replicated targets, every QP's slot modes [nb_qps][n][K + 3], the Hadamard costs of the
-// 35 modes and of the candidate; every section at a multiple of 256 bytes.
+// 35 modes and of the candidate.
 struct RdSignalWorkspace {
     uint64_t* rate; uint32_t* sse; uint32_t* nonzero; uint8_t* pred; uint8_t* targets; uint8_t* slot_modes; uint32_t* mode_hads; uint32_t* cand_hads;
     size_t bytes;
 };
 // (codec 1, the substitution codec of DESIGN.md section 5o: K + 2 slots wherever the switch codec has K + 3)
 int signal_slots(int width, int codec) { return hevc_first_pass_list_size(width) + (codec ? msig::kExtraSlotsSubstitution : msig::kExtraSlots); }
-RdSignalWorkspace rd_signal_workspace(void* base, int width, long n, int nb_qps, int codec = 0)
+RdSignalWorkspace rd_signal_workspace(void* base, int width, long n, int nb_qps, int codec)
 {
     const size_t slots = (size_t)n * signal_slots(width, codec), w2 = (size_t)width * width;
     const size_t units = slots * (width == 64 ? 4 : 1);       // at width 64 every slot is coded as its four quadrants
-    size_t at = 0;
-    const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
+    Carver cv{base};
     RdSignalWorkspace ws;
-    ws.rate = (uint64_t*)take(units * 8);
-    ws.sse = (uint32_t*)take(units * 4);
-    ws.nonzero = (uint32_t*)take(units * 4);
-    ws.pred = take(slots * w2);
-    ws.targets = take(slots * w2);
-    ws.slot_modes = take(slots * nb_qps);
-    ws.mode_hads = (uint32_t*)take((size_t)n * 35 * 4);
-    ws.cand_hads = (uint32_t*)take((size_t)n * 4);
-    ws.bytes = at;
+    ws.rate = cv.take<uint64_t>(units);
+    ws.sse = cv.take<uint32_t>(units);
+    ws.nonzero = cv.take<uint32_t>(units);
+    ws.pred = cv.take<uint8_t>(slots * w2);
+    ws.targets = cv.take<uint8_t>(slots * w2);
+    ws.slot_modes = cv.take<uint8_t>(slots * nb_qps);
+    ws.mode_hads = cv.take<uint32_t>((size_t)n * 35);
+    ws.cand_hads = cv.take<uint32_t>((size_t)n);
+    ws.bytes = cv.at;
     return ws;
 }
 
 // The scratch the second pass with transform skip adds behind rd_signal_workspace's: the skipped form's rate, SSE and count of the
-// slots of ONE QP, the slots' mode bits and flags, the winners' slots; every section at a multiple of 256 bytes.
+// slots of ONE QP, the slots' mode bits and flags, the winners' slots.
 struct RdTskipWorkspace { uint64_t* rate; uint32_t* sse; uint32_t* nonzero; uint32_t* mode_bits; uint8_t* ts_flag; uint8_t* best_slot; size_t bytes; };
 RdTskipWorkspace rd_tskip_workspace(void* base, size_t slots, long n)
 {
-    size_t at = 0;
-    const auto take = [&](size_t bytes) { uint8_t* p = (uint8_t*)((uintptr_t)base + at); at += (bytes + 255) / 256 * 256; return p; };
+    Carver cv{base};
     RdTskipWorkspace ws;
-    ws.rate = (uint64_t*)take(slots * 8);
-    ws.sse = (uint32_t*)take(slots * 4);
-    ws.nonzero = (uint32_t*)take(slots * 4);
-    ws.mode_bits = (uint32_t*)take(slots * 4);
-    ws.ts_flag = take(slots);
-    ws.best_slot = take((size_t)n);
-    ws.bytes = at;
+    ws.rate = cv.take<uint64_t>(slots);
+    ws.sse = cv.take<uint32_t>(slots);
+    ws.nonzero = cv.take<uint32_t>(slots);
+    ws.mode_bits = cv.take<uint32_t>(slots);
+    ws.ts_flag = cv.take<uint8_t>(slots);
+    ws.best_slot = cv.take<uint8_t>((size_t)n);
+    ws.bytes = cv.at;
     return ws;
 }
 
-// what the second-pass entries with the option transform_skip check in front of everything else: the option, the width, signalling, a
-// lambda the decision can use, the whole scratch
-int check_rd_pass_tskip(pnn_ctx* c, int width, int n, const int* qps, int nb_qps, const double* lambdas, int signalling, int codec, int transform_skip,
-                        const void* d_workspace, size_t workspace_bytes)
+// One call of the second intra pass, whichever of the ten entries it came through (the narrower ones forward up to the _codec_
+// entries with the options they lack at 0; the _tskip_ entries have checks of their own): the blocks, the candidate, the coding's
+// arguments, the options, the outputs (NULL where the entry has none), the scratch.
+struct RdPassOutputs {
+    uint8_t* cand_modes; double* cand_costs; uint8_t* best_mode; uint8_t* best_slot; double* best_cost; uint32_t* best_sse; uint64_t* best_rate;
+    double* first_pass_costs; uint64_t* best_side_rate; uint8_t* best_ts_flag;
+    bool any() const
+    {
+        return cand_modes || cand_costs || best_mode || best_slot || best_cost || best_sse || best_rate || first_pass_costs || best_side_rate ||
+               best_ts_flag;
+    }
+};
+struct RdPassCall {
+    int width; BlockSource blocks; const uint8_t* cand_pred; int smoothing;
+    const int* qps; int nb_qps; const double* lambdas; int sign_data_hiding;
+    int rdoq = 0, signalling = 0, codec = 0, transform_skip = 0;
+    bool tskip_entry = false;                                 // came through a _tskip_ entry, whose checks no other rung has
+    const uint8_t* left = nullptr; const uint8_t* above = nullptr;
+    RdPassOutputs out{};
+    void* workspace = nullptr; size_t workspace_bytes = 0; hipStream_t stream = nullptr;
+    double lambda(int i) const { return lambdas ? lambdas[i] : pnn_hm_intra_lambda(qps[i]); }
+};
+RdPassCall rd_pass_call(int width, const BlockSource& blocks, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
+                        const double* lambdas, int sign_data_hiding)
 {
-    if (const int rc = check_tskip_option(c, width, transform_skip, 1)) return rc;
-    if (const int rc = check_codec(c, codec, signalling)) return rc;
-    if (!signalling) return fail(c, PNN_E_ARG, "the second pass with transform skip without signalling");
-    if (!transform_skip) return PNN_OK;
-    if (const int rc = check_rdoq_lambdas(c, 1, lambdas, trquant::qps_ok(qps, nb_qps) ? nb_qps : 0)) return rc;
-    if (n <= 0 || !trquant::qps_ok(qps, nb_qps)) return PNN_OK;             // (refused or empty further down)
-    const size_t base = rd_signal_workspace(nullptr, width, n, nb_qps, codec).bytes;
-    const size_t need = base + rd_tskip_workspace(nullptr, (size_t)n * signal_slots(width, codec), n).bytes;
-    if (d_workspace && workspace_bytes < need)
-        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_rd_pass_tskip_workspace_bytes asks for %zu", workspace_bytes, need);
+    RdPassCall q;
+    q.width = width; q.blocks = blocks; q.cand_pred = d_cand_pred; q.smoothing = smoothing; q.qps = qps; q.nb_qps = nb_qps; q.lambdas = lambdas;
+    q.sign_data_hiding = sign_data_hiding;
+    return q;
+}
+
+// what the _tskip_ entries check behind the option and the codec: signalling, a lambda the decision can use, the whole scratch
+int check_rd_pass_tskip(pnn_ctx* c, const RdPassCall& q)
+{
+    const long n = q.blocks.n;
+    if (!q.signalling) return fail(c, PNN_E_ARG, "the second pass with transform skip without signalling");
+    if (!q.transform_skip) return PNN_OK;
+    if (const int rc = check_rdoq_lambdas(c, 1, q.lambdas, trquant::qps_ok(q.qps, q.nb_qps) ? q.nb_qps : 0)) return rc;
+    if (n <= 0 || !trquant::qps_ok(q.qps, q.nb_qps)) return PNN_OK;         // (refused or empty further down)
+    const size_t need = rd_signal_workspace(nullptr, q.width, n, q.nb_qps, q.codec).bytes +
+                        rd_tskip_workspace(nullptr, (size_t)n * signal_slots(q.width, q.codec), n).bytes;
+    if (q.workspace && q.workspace_bytes < need)                            // (a NULL or misaligned scratch: check_rd_pass_arguments names it)
+        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_rd_pass_tskip_workspace_bytes asks for %zu", q.workspace_bytes, need);
     return PNN_OK;
 }
 
-// what both forms with signalling check behind their blocks: the width (no quadrants), candidate, QPs, lambdas, outputs, scratch and --
-// read back once, the call waits for the stream -- the neighbours' modes
-int check_rd_pass_signal(pnn_ctx* c, int width, int n, const uint8_t* d_cand_pred, const int* qps, int nb_qps, const double* lambdas, int rdoq,
-                         bool any_output, const uint8_t* d_left, const uint8_t* d_above, const void* d_workspace, size_t workspace_bytes, hipStream_t s,
-                         int codec = 0)
+// what every rung checks behind its blocks (the width is checked), up to the scratch: candidate, slot count, QPs, lambdas, outputs
+int check_rd_pass_arguments(pnn_ctx* c, const RdPassCall& q)
 {
-    if (n > 0 && !d_cand_pred) return fail(c, PNN_E_ARG, "d_cand_pred is NULL");
-    if ((long)n * signal_slots(width, codec) * (width == 64 ? 4 : 1) > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 candidate slots");
-    if (!trquant::qps_ok(qps, nb_qps)) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d integers in [0, %d]", trquant::kMaxQps, trquant::kMaxQp);
-    for (int i = 0; lambdas && i < nb_qps; i++)
-        if (!(lambdas[i] >= 0. && lambdas[i] <= 1.7976931348623157e308)) return fail(c, PNN_E_ARG, "lambda %d is negative or not finite", i);
-    if (const int rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps)) return rc;
-    if (const int rc = check_some_output(c, any_output)) return rc;
+    const long n = q.blocks.n;
+    const long slots = q.signalling ? n * signal_slots(q.width, q.codec) * (q.width == 64 ? 4 : 1) : n * (hevc_first_pass_list_size(q.width) + 1);
+    if (n > 0 && !q.cand_pred) return fail(c, PNN_E_ARG, "d_cand_pred is NULL");
+    if (slots > 0x7fffffffL) return fail(c, PNN_E_ARG, "more than 2^31 - 1 candidate slots");
+    if (!trquant::qps_ok(q.qps, q.nb_qps)) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d integers in [0, %d]", trquant::kMaxQps, trquant::kMaxQp);
+    for (int i = 0; q.lambdas && i < q.nb_qps; i++)
+        if (!(q.lambdas[i] >= 0. && q.lambdas[i] <= 1.7976931348623157e308)) return fail(c, PNN_E_ARG, "lambda %d is negative or not finite", i);
+    // with signalling RDOQ's lambda is checked here, in front of the outputs; without it behind the scratch (rd_pass)
+    if (q.signalling)
+        if (const int rc = check_rdoq_lambdas(c, q.rdoq, q.lambdas, q.nb_qps)) return rc;
+    if (const int rc = check_some_output(c, q.out.any())) return rc;
     if (n == 0) return PNN_OK;
-    const size_t need = rd_signal_workspace(nullptr, width, n, nb_qps, codec).bytes;
-    if (!d_workspace || (uintptr_t)d_workspace % 8) return fail(c, PNN_E_ARG, "d_workspace is NULL or not aligned to 8 bytes");
-    if (workspace_bytes < need)
-        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, %s asks for %zu", workspace_bytes,
-                    codec ? "pnn_rd_pass_codec_workspace_bytes" : "pnn_rd_pass_signal_workspace_bytes", need);
-    if (!d_left && !d_above) return PNN_OK;
+    const size_t need = q.signalling ? rd_signal_workspace(nullptr, q.width, n, q.nb_qps, q.codec).bytes : rd_workspace(nullptr, q.width, n, q.nb_qps).bytes;
+    if (!q.workspace || (uintptr_t)q.workspace % 8) return fail(c, PNN_E_ARG, "d_workspace is NULL or not aligned to 8 bytes");
+    if (q.workspace_bytes < need)                             // (the text names the rung's size function, not the entry's)
+        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, %s asks for %zu", q.workspace_bytes,
+                    !q.signalling ? "pnn_rd_pass_workspace_bytes" : q.codec ? "pnn_rd_pass_codec_workspace_bytes" : "pnn_rd_pass_signal_workspace_bytes",
+                    need);
+    return PNN_OK;
+}
+
+// the neighbours' modes of a call with signalling, read back once: the call waits for the stream
+int check_neighbours(pnn_ctx* c, const RdPassCall& q)
+{
+    const long n = q.blocks.n;
+    if (!q.left && !q.above) return PNN_OK;
     std::vector<uint8_t> modes((size_t)n * 2, (uint8_t)msig::kNoNeighbour);
     {
         PNN_UNSAFE_CALLS_GUARD;                               // both arrays, then ONE wait
-        if (d_left) HIPCHK(c, hipMemcpyAsync(modes.data(), d_left, (size_t)n, hipMemcpyDeviceToHost, s));
-        if (d_above) HIPCHK(c, hipMemcpyAsync(modes.data() + n, d_above, (size_t)n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
+        if (q.left) HIPCHK(c, hipMemcpyAsync(modes.data(), q.left, (size_t)n, hipMemcpyDeviceToHost, q.stream));
+        if (q.above) HIPCHK(c, hipMemcpyAsync(modes.data() + n, q.above, (size_t)n, hipMemcpyDeviceToHost, q.stream));
+        HIPCHK(c, hipStreamSynchronize(q.stream));
     }
     for (long i = 0; i < 2L * n; i++)
-        if (!msig::neighbour_ok(modes[i], !codec))
+        if (!msig::neighbour_ok(modes[i], !q.codec))
             return fail(c, PNN_E_ARG, "%s neighbour mode %d of block %ld is not 0 .. %d or 255", i < n ? "left" : "above", modes[i], i % n,
-                        codec ? 34 : 35);
+                        q.codec ? 34 : 35);
     return PNN_OK;
 }
 
-// The launches of the second pass with signalling, either form, everything checked: the Hadamard costs (the unchanged first-pass
-// kernel, asked for no list), the lists and slots of every QP, then per QP the slots' predictions, their coding -- the launch of
-// pnn_trquant_rdoq_device with that one QP -- and the decision, all on the same scratch in stream order: 2 + 3 nb_qps launches.
-int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int ph, int pw, const uint8_t* targets, const PictureBlocks* pic,
-                            const uint8_t* pic_targets, long n, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
-                            const double* lambdas, int sign_data_hiding, int rdoq, const uint8_t* d_left, const uint8_t* d_above,
-                            uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost,
-                            uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
-                            hipStream_t s, int codec = 0, int transform_skip = 0, uint8_t* d_best_ts_flag = nullptr)
+// The four launches of the second intra pass without signalling, everything checked: the first-pass list into the scratch, the
+// candidates' predictions, the transform coding of the n (K + 1) slots -- the launch of pnn_trquant_rdoq_device with the slots' modes
+// as its mode array and every QP at once --, the decision.
+int rd_pass_launches(pnn_ctx* c, const RdPassCall& q)
 {
-    const RdSignalWorkspace ws = rd_signal_workspace(d_workspace, width, n, nb_qps, codec);
+    const long n = q.blocks.n;
+    hipStream_t s = q.stream;
+    const RdWorkspace ws = rd_workspace(q.workspace, q.width, n, q.nb_qps);
+    const int k1 = hevc_first_pass_list_size(q.width) + 1;
+    HevcModeHadsParams h = mode_hads_params(q.blocks, q.width, q.smoothing, q.cand_pred);
+    h.list_modes = ws.list;
+    HIPCHK(c, launch_hevc_mode_hads(h, s));
+    RdCandidatesParams r;
+    set_blocks(r, q.blocks, q.width, q.smoothing);
+    r.cand_pred = q.cand_pred; r.list_modes = ws.list; r.cand_modes = q.out.cand_modes ? q.out.cand_modes : ws.modes;
+    r.slot_pred = ws.pred; r.slot_targets = ws.targets;
+    HIPCHK(c, launch_rd_candidates(r, s));
+    TrQuantParams t = trquant_params(q.width, ws.pred, ws.targets, (int)(n * k1), r.cand_modes, q.qps, q.nb_qps,
+                                     {q.sign_data_hiding, q.rdoq, q.lambdas});
+    t.sse = ws.sse; t.rate = ws.rate;
+    HIPCHK(c, launch_trquant(t, s));
+    RdDecideParams d;
+    d.sse = ws.sse; d.rate = ws.rate; d.cand_modes = r.cand_modes; d.N = (int)n; d.w = q.width; d.nb_qps = q.nb_qps;
+    for (int i = 0; i < trquant::kMaxQps; i++) d.lambda[i] = i >= q.nb_qps ? 0. : q.lambda(i);
+    d.cand_costs = q.out.cand_costs; d.best_mode = q.out.best_mode; d.best_slot = q.out.best_slot; d.best_cost = q.out.best_cost;
+    d.best_sse = q.out.best_sse; d.best_rate = q.out.best_rate;
+    HIPCHK(c, launch_rd_decide(d, s));
+    c->stat_launches += 4;
+    return PNN_OK;
+}
+
+// The launches of the second pass with signalling, everything checked: the Hadamard costs (the unchanged first-pass kernel, asked for
+// no list), the lists and slots of every QP, then per QP the slots' predictions, their coding -- the launch of pnn_trquant_rdoq_device
+// with that one QP -- and the decision, all on the same scratch in stream order: 2 + 3 nb_qps launches; with transform skip four
+// more per QP, the last of them only for the flag output.
+int rd_pass_signal_launches(pnn_ctx* c, const RdPassCall& q)
+{
+    const long n = q.blocks.n;
+    const int width = q.width, nb_qps = q.nb_qps, codec = q.codec;
+    const RdPassOutputs& out = q.out;
+    hipStream_t s = q.stream;
+    const RdSignalWorkspace ws = rd_signal_workspace(q.workspace, width, n, nb_qps, codec);
     const int slots = signal_slots(width, codec);
     // transform skip (width 4): the skipped form's arrays lie behind the pass's own scratch
-    const RdTskipWorkspace ts = rd_tskip_workspace((uint8_t*)d_workspace + ws.bytes, n * slots, n);
-    const HevcModeHadsParams h = mode_hads_params(patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing, d_cand_pred, ws.mode_hads,
-                                                  ws.cand_hads, nullptr, nullptr);
+    const RdTskipWorkspace ts = rd_tskip_workspace((uint8_t*)q.workspace + ws.bytes, n * slots, n);
+    HevcModeHadsParams h = mode_hads_params(q.blocks, width, q.smoothing, q.cand_pred);
+    h.mode_hads = ws.mode_hads; h.cand_hads = ws.cand_hads;
     HIPCHK(c, launch_hevc_mode_hads(h, s));
     SignalListParams l;
-    l.mode_hads = ws.mode_hads; l.cand_hads = ws.cand_hads; l.left = d_left; l.above = d_above; l.N = (int)n; l.w = width; l.nb_qps = nb_qps;
+    l.mode_hads = ws.mode_hads; l.cand_hads = ws.cand_hads; l.left = q.left; l.above = q.above; l.N = (int)n; l.w = width; l.nb_qps = nb_qps;
     double lambda[trquant::kMaxQps];
     for (int i = 0; i < trquant::kMaxQps; i++) {
-        const int qp = qps[i < nb_qps ? i : 0];
-        lambda[i] = i >= nb_qps ? 0. : lambdas ? lambdas[i] : pnn_hm_intra_lambda(qp);
-        l.bits[i] = msig::flag_bits(qp);
+        lambda[i] = i >= nb_qps ? 0. : q.lambda(i);
+        l.bits[i] = msig::flag_bits(q.qps[i < nb_qps ? i : 0]);
         l.sqrt_lambda[i] = std::sqrt(lambda[i]);                                  // TComRdCost::setLambda
     }
-    l.list_costs = d_first_pass_costs; l.slot_modes = d_cand_modes ? d_cand_modes : ws.slot_modes;
+    l.list_costs = out.first_pass_costs; l.slot_modes = out.cand_modes ? out.cand_modes : ws.slot_modes;
     HIPCHK(c, codec ? launch_substitution_list(l, s) : launch_signal_list(l, s));
     for (int qi = 0; qi < nb_qps; qi++) {
         const size_t at = (size_t)qi * n;
         const uint8_t* slot_modes = l.slot_modes + at * slots;
         RdCandidatesParams r;
-        set_blocks(r, patterns, ph, pw, targets, pic, pic_targets, n, width, smoothing);
-        r.cand_pred = d_cand_pred; r.list_modes = slot_modes; r.cand_modes = nullptr; r.slot_pred = ws.pred; r.slot_targets = ws.targets;
+        set_blocks(r, q.blocks, width, q.smoothing);
+        r.cand_pred = q.cand_pred; r.list_modes = slot_modes; r.cand_modes = nullptr; r.slot_pred = ws.pred; r.slot_targets = ws.targets;
         HIPCHK(c, codec ? launch_rd_candidates_substitution(r, s) : launch_rd_candidates_slots(r, s));
         // width 64: the slots lie there quadrant by quadrant, 4 n (K + 3) blocks of 32 x 32 under the diagonal scan, each a unit at
         // transform depth 1 (cbf context 0) -- what the w = 64 instantiation codes, with a count of levels per quadrant
         const bool quadrants = width == 64;
         TrQuantParams t = trquant_params(quadrants ? 32 : width, ws.pred, ws.targets, (int)(n * slots * (quadrants ? 4 : 1)),
-                                         quadrants ? nullptr : slot_modes, qps + qi, 1, sign_data_hiding, rdoq, rdoq ? lambda + qi : nullptr);
+                                         quadrants ? nullptr : slot_modes, q.qps + qi, 1,
+                                         {q.sign_data_hiding, q.rdoq, q.rdoq ? lambda + qi : nullptr});
         if (quadrants) t.cbf_ctx = 0;
         t.sse = ws.sse; t.nonzero = ws.nonzero; t.rate = ws.rate;
         HIPCHK(c, launch_trquant(t, s));
-        if (transform_skip) {
+        if (q.transform_skip) {
             // both forms of every slot, decided per slot as the tree does inside each candidate's coding: the skipped form beside the
             // transformed one, the mode bits the decision charges, the merge IN PLACE (sse, count and rate become the kept form's, the
             // rate with the flag bin); the unchanged decision below then compares the slots' merged D and R
@@ -418,35 +473,67 @@ int rd_pass_signal_launches(pnn_ctx* c, int width, const uint8_t* patterns, int 
             k.sse = ts.sse; k.nonzero = ts.nonzero; k.rate = ts.rate;
             HIPCHK(c, launch_tskip4(k, s));
             TskipSlotBitsParams sb;
-            sb.slot_modes = slot_modes; sb.left = d_left; sb.above = d_above; sb.N = (int)n; sb.S = slots; sb.pnn_flag = codec ? 0 : 1;
+            sb.slot_modes = slot_modes; sb.left = q.left; sb.above = q.above; sb.N = (int)n; sb.S = slots; sb.pnn_flag = codec ? 0 : 1;
             sb.bits = l.bits[qi]; sb.mode_bits = ts.mode_bits;
             HIPCHK(c, launch_tskip_slot_bits(sb, s));
             TskipDecideParams m;
             m.N = (int)(n * slots); m.nb_qps = 1; m.decide = 1; m.charge_cbf = 1; m.mode_bits = ts.mode_bits;
             m.transformed = TskipForm{ws.sse, ws.nonzero, nullptr, ws.rate, nullptr};
             m.skipped = TskipForm{ts.sse, ts.nonzero, nullptr, ts.rate, nullptr};
-            for (int i = 0; i < trquant::kMaxQps; i++) { m.lambda[i] = lambda[qi]; m.bits[i] = tskip::qp_bits(qps[qi]); }
+            for (int i = 0; i < trquant::kMaxQps; i++) { m.lambda[i] = lambda[qi]; m.bits[i] = tskip::qp_bits(q.qps[qi]); }
             m.sse = ws.sse; m.nonzero = ws.nonzero; m.sum_abs = nullptr; m.recon = nullptr; m.rate = ws.rate; m.ts_flag = ts.ts_flag;
             HIPCHK(c, launch_tskip_decide(m, s));
             c->stat_launches += 3;
         }
         RdDecideSignalParams d;
-        d.sse = ws.sse; d.rate = ws.rate; d.nonzero = ws.nonzero; d.slot_modes = slot_modes; d.left = d_left; d.above = d_above;
+        d.sse = ws.sse; d.rate = ws.rate; d.nonzero = ws.nonzero; d.slot_modes = slot_modes; d.left = q.left; d.above = q.above;
         d.N = (int)n; d.w = width; d.cbf_ctx = msig::cbf_context(width); d.lambda = lambda[qi]; d.bits = l.bits[qi];
-        d.cand_costs = d_cand_costs ? d_cand_costs + at * slots : nullptr;
-        d.best_mode = d_best_mode ? d_best_mode + at : nullptr; d.best_slot = d_best_slot ? d_best_slot + at : nullptr;
-        d.best_cost = d_best_cost ? d_best_cost + at : nullptr; d.best_sse = d_best_sse ? d_best_sse + at : nullptr;
-        d.best_rate = d_best_rate ? d_best_rate + at : nullptr; d.best_side_rate = d_best_side_rate ? d_best_side_rate + at : nullptr;
-        if (transform_skip && !d.best_slot) d.best_slot = ts.best_slot;
+        d.cand_costs = out.cand_costs ? out.cand_costs + at * slots : nullptr;
+        d.best_mode = out.best_mode ? out.best_mode + at : nullptr; d.best_slot = out.best_slot ? out.best_slot + at : nullptr;
+        d.best_cost = out.best_cost ? out.best_cost + at : nullptr; d.best_sse = out.best_sse ? out.best_sse + at : nullptr;
+        d.best_rate = out.best_rate ? out.best_rate + at : nullptr; d.best_side_rate = out.best_side_rate ? out.best_side_rate + at : nullptr;
+        if (q.transform_skip && !d.best_slot) d.best_slot = ts.best_slot;
         HIPCHK(c, codec ? launch_rd_decide_substitution(d, s) : launch_rd_decide_signal(d, s));
-        if (transform_skip && d_best_ts_flag) {
-            const TskipBestFlagParams g{ts.ts_flag, d.best_slot, (int)n, slots, d_best_ts_flag + at};
+        if (q.transform_skip && out.best_ts_flag) {
+            const TskipBestFlagParams g{ts.ts_flag, d.best_slot, (int)n, slots, out.best_ts_flag + at};
             HIPCHK(c, launch_tskip_best_flag(g, s));
             c->stat_launches++;
         }
     }
     c->stat_launches += 2 + 3 * nb_qps;
     return PNN_OK;
+}
+
+// One call of the second intra pass from its checks to its launches.  The ORDER below is the entries' behaviour: where the rungs or
+// the two forms of blocks differ, the branch says so.
+int rd_pass(pnn_ctx* c, RdPassCall& q)
+{
+    int rc;
+    BlockSource& b = q.blocks;
+    // the options of the wider rungs, in front of everything (codec 0 and signalling 0 pass check_codec)
+    if (q.tskip_entry && (rc = check_tskip_option(c, q.width, q.transform_skip, 1))) return rc;
+    if ((rc = check_codec(c, q.codec, q.signalling))) return rc;
+    if (!q.tskip_entry && !q.signalling && (q.out.first_pass_costs || q.out.best_side_rate))
+        return fail(c, PNN_E_ARG, "d_first_pass_costs or d_best_side_rate without signalling");
+    // a _tskip_ entry checks signalling, lambda and scratch size on dense blocks BEFORE the blocks ...
+    if (q.tskip_entry && !b.pictures && (rc = check_rd_pass_tskip(c, q))) return rc;
+    if ((rc = check_blocks(c, q.width, b)) || (rc = check_smoothing(c, q.smoothing))) return rc;
+    if (b.pictures && (rc = count_blocks(c, b.images, b.pic.positions, &b.n))) return rc;
+    // ... and on picture pairs BEHIND geometry, smoothing and block count
+    if (q.tskip_entry && b.pictures && (rc = check_rd_pass_tskip(c, q))) return rc;
+    // with signalling the device is set in front of the checks that end in the neighbours' read-back, without it behind every check
+    if (q.signalling && b.n > 0) HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = check_rd_pass_arguments(c, q))) return rc;
+    // without signalling RDOQ's lambda is checked behind the scratch, also of a call without blocks
+    if (!q.signalling && (rc = check_rdoq_lambdas(c, q.rdoq, q.lambdas, q.nb_qps))) return rc;
+    if (b.n == 0) return PNN_OK;
+    if (!q.signalling) HIPCHK(c, hipSetDevice(c->device));
+    if (q.signalling && (rc = check_neighbours(c, q))) return rc;
+    if (b.pictures && (rc = check_picture_blocks(c, q.width, b.pic, q.stream))) return rc;
+    reset_stats(c);
+    if (!q.signalling) return rd_pass_launches(c, q);
+    if (!q.transform_skip && q.out.best_ts_flag) HIPCHK(c, hipMemsetAsync(q.out.best_ts_flag, 0, (size_t)q.nb_qps * b.n, q.stream));
+    return rd_pass_signal_launches(c, q);
 }
 
 Model* ipfcns_for(pnn_ctx* c, int width, int* rc)
@@ -480,8 +567,8 @@ int pnn_hevc_best_mode_hm_device(pnn_ctx* c, int width, const uint8_t* d_pattern
         (rc = check_some_output(c, d_best_mode || d_best_sse || d_best_pred || d_mode_sse))) return rc;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const HevcBestModeParams p = best_mode_params(d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, width, smoothing, d_best_mode,
-                                                  d_best_sse, d_best_pred, d_mode_sse);
+    HevcBestModeParams p = best_mode_params(dense_blocks(d_patterns, pattern_h, pattern_w, d_targets, n), width, smoothing);
+    p.best_mode = d_best_mode; p.best_sse = d_best_sse; p.best_pred = d_best_pred; p.mode_sse = d_mode_sse;
     HIPCHK(c, launch_hevc_best_mode(p, (hipStream_t)stream));
     return PNN_OK;
 }
@@ -504,8 +591,8 @@ int pnn_hevc_mode_hads_hm_device(pnn_ctx* c, int width, const uint8_t* d_pattern
         (rc = check_hads_outputs(c, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs))) return rc;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const HevcModeHadsParams p = mode_hads_params(d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, width, smoothing, d_cand_pred,
-                                                  d_mode_hads, d_cand_hads, d_list_modes, d_list_costs);
+    HevcModeHadsParams p = mode_hads_params(dense_blocks(d_patterns, pattern_h, pattern_w, d_targets, n), width, smoothing, d_cand_pred);
+    p.mode_hads = d_mode_hads; p.cand_hads = d_cand_hads; p.list_modes = d_list_modes; p.list_costs = d_list_costs;
     HIPCHK(c, launch_hevc_mode_hads(p, (hipStream_t)stream));
     return PNN_OK;
 }
@@ -557,7 +644,8 @@ int pnn_ipfcns_predict_device(pnn_ctx* c, int width, const uint8_t* d_channels, 
     if (!d_channels || !d_rows || !d_cols) return fail(c, PNN_E_ARG, "NULL input buffers");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_positions(c, d_rows, d_cols, positions, 2 * width + 8, height, width_ch, "line origin", "lines leave", s))) return rc;
+    const PictureBlocks lines = picture_blocks(d_channels, height, width_ch, d_rows, d_cols, positions);
+    if ((rc = check_positions(c, lines, 2 * width + 8, "line origin", "lines leave", s))) return rc;
     reset_stats(c);
     int K, H;
     ipfcns_dims(width, &K, &H);
@@ -612,20 +700,21 @@ int pnn_score_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_co
 {
     if (!c) return PNN_E_ARG;
     int rc;
-    long n;
     const bool want_pnn = d_pnn_u8 || d_pnn_f32 || d_pnn_sse, want_hevc = d_hevc_mode || d_hevc_sse || d_hevc_pred;
-    if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
+    // contexts and intra patterns from the context plane, targets (hence both SSEs) from the target plane
+    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
+    const PictureBlocks pic_tg = picture_blocks(d_target_channels, height, width_ch, d_rows, d_cols, positions);
+    BlockSource blocks = picture_pair_blocks(pic, d_target_channels, images, mask_w, mask_h);
+    if ((rc = check_pair_geometry(c, width, blocks)) ||
         (rc = check_smoothing(c, smoothing)) ||
         (rc = check_some_output(c, d_targets || want_pnn || want_hevc))) return rc;
     Model* m = want_pnn ? c->models[width_index(width)] : nullptr;
     if (want_pnn && !m) return fail(c, PNN_E_ARG, "a PNN output is asked for, but no model is loaded for width %d", width);
-    if ((rc = count_blocks(c, images, positions, &n))) return rc;
+    if ((rc = count_blocks(c, images, positions, &blocks.n))) return rc;
+    const long n = blocks.n;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    // contexts and intra patterns from the context plane, targets (hence both SSEs) from the target plane
-    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
-    const PictureBlocks pic_tg = picture_blocks(d_target_channels, height, width_ch, d_rows, d_cols, positions);
     if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
     if (want_pnn && (rc = pending_range_error(c))) return rc;
     reset_stats(c);
@@ -661,8 +750,8 @@ int pnn_score_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_co
         }
     }
     if (want_hevc) {
-        const HevcBestModeParams p = best_mode_params(nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n,
-                                                      width, smoothing, d_hevc_mode, d_hevc_sse, d_hevc_pred, nullptr);
+        HevcBestModeParams p = best_mode_params(blocks, width, smoothing);
+        p.best_mode = d_hevc_mode; p.best_sse = d_hevc_sse; p.best_pred = d_hevc_pred;
         HIPCHK(c, launch_hevc_best_mode(p, s));
         c->stat_launches++;
     }
@@ -686,19 +775,18 @@ int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t*
 {
     if (!c) return PNN_E_ARG;
     int rc;
-    long n;
-    if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
-        (rc = check_smoothing(c, smoothing)) ||
+    BlockSource blocks = picture_pair_blocks(picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions), d_target_channels,
+                                             images, mask_w, mask_h);
+    if ((rc = check_pair_geometry(c, width, blocks)) || (rc = check_smoothing(c, smoothing)) ||
         (rc = check_hads_outputs(c, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs)) ||
-        (rc = count_blocks(c, images, positions, &n))) return rc;
-    if (n == 0) return PNN_OK;
+        (rc = count_blocks(c, images, positions, &blocks.n))) return rc;
+    if (blocks.n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
-    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
+    if ((rc = check_picture_blocks(c, width, blocks.pic, s))) return rc;
     reset_stats(c);
-    const HevcModeHadsParams p = mode_hads_params(nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n,
-                                                  width, smoothing, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs);
+    HevcModeHadsParams p = mode_hads_params(blocks, width, smoothing, d_cand_pred);
+    p.mode_hads = d_mode_hads; p.cand_hads = d_cand_hads; p.list_modes = d_list_modes; p.list_costs = d_list_costs;
     HIPCHK(c, launch_hevc_mode_hads(p, s));
     c->stat_launches++;
     return PNN_OK;
@@ -738,7 +826,7 @@ int pnn_trquant_rdoq_device(pnn_ctx* c, int width, const uint8_t* d_predictions,
     if (const int rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps)) return rc;
     if (n == 0) return PNN_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    TrQuantParams p = trquant_params(width, d_predictions, d_targets, n, d_modes, qps, nb_qps, sign_data_hiding, rdoq, lambdas);
+    TrQuantParams p = trquant_params(width, d_predictions, d_targets, n, d_modes, qps, nb_qps, {sign_data_hiding, rdoq, lambdas});
     p.sse = d_sses_recon; p.nonzero = d_nb_nonzero; p.sum_abs = d_sum_abs_levels; p.recon = d_recon; p.rate = d_rate;
     reset_stats(c);
     HIPCHK(c, launch_trquant(p, (hipStream_t)stream));
@@ -778,7 +866,7 @@ int pnn_trquant_tskip_device(pnn_ctx* c, int width, const uint8_t* d_predictions
         return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_trquant_tskip_workspace_bytes asks for %zu", workspace_bytes, ws.bytes);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    TrQuantParams p = trquant_params(width, d_predictions, d_targets, n, d_modes, qps, nb_qps, sign_data_hiding, rdoq, lambdas);
+    TrQuantParams p = trquant_params(width, d_predictions, d_targets, n, d_modes, qps, nb_qps, {sign_data_hiding, rdoq, lambdas});
     reset_stats(c);
     for (int form = decide ? 0 : 1; form < 2; form++) {   // the transformed form first (decide only), then the skipped one
         const TskipOut& o = ws.form[form];
@@ -823,18 +911,9 @@ int pnn_rd_pass_rdoq_device(pnn_ctx* c, int width, const uint8_t* d_patterns, in
                             double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes,
                             void* stream)
 {
-    if (!c) return PNN_E_ARG;
-    int rc;
-    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing)) ||
-        (rc = check_rd_pass(c, width, n, d_cand_pred, qps, nb_qps, lambdas,
-                            d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate, d_workspace,
-                            workspace_bytes)) || (rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps))) return rc;
-    if (n == 0) return PNN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    reset_stats(c);
-    return rd_pass_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
-                            lambdas, sign_data_hiding, rdoq, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
-                            d_workspace, (hipStream_t)stream);
+    return pnn_rd_pass_signal_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, d_cand_pred, smoothing, qps, nb_qps, lambdas,
+                                     sign_data_hiding, rdoq, 0, nullptr, nullptr, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost,
+                                     d_best_sse, d_best_rate, nullptr, nullptr, d_workspace, workspace_bytes, stream);
 }
 
 int pnn_rd_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
@@ -857,30 +936,17 @@ int pnn_rd_pass_rdoq_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* 
                                           uint8_t* d_best_mode, uint8_t* d_best_slot, double* d_best_cost, uint32_t* d_best_sse,
                                           uint64_t* d_best_rate, void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    if (!c) return PNN_E_ARG;
-    int rc;
-    long n;
-    if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
-        (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n)) ||
-        (rc = check_rd_pass(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas,
-                            d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate, d_workspace,
-                            workspace_bytes)) || (rc = check_rdoq_lambdas(c, rdoq, lambdas, nb_qps))) return rc;
-    if (n == 0) return PNN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
-    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
-    reset_stats(c);
-    return rd_pass_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
-                            smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost,
-                            d_best_sse, d_best_rate, d_workspace, s);
+    return pnn_rd_pass_signal_picture_pairs_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols,
+                                                   positions, mask_w, mask_h, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, 0,
+                                                   nullptr, nullptr, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse,
+                                                   d_best_rate, nullptr, nullptr, d_workspace, workspace_bytes, stream);
 }
 
 size_t pnn_rd_pass_signal_workspace_bytes(int width, int n, int nb_qps, int signalling)
 {
     if (!signalling) return pnn_rd_pass_workspace_bytes(width, n, nb_qps);
     if (width_index(width) < 0 || n < 0 || nb_qps < 1 || nb_qps > trquant::kMaxQps) return 0;
-    return rd_signal_workspace(nullptr, width, n, nb_qps).bytes;
+    return rd_signal_workspace(nullptr, width, n, nb_qps, 0).bytes;
 }
 
 int pnn_rd_pass_signal_device(pnn_ctx* c, int width, const uint8_t* d_patterns, int pattern_h, int pattern_w, const uint8_t* d_targets, int n,
@@ -890,26 +956,10 @@ int pnn_rd_pass_signal_device(pnn_ctx* c, int width, const uint8_t* d_patterns, 
                               uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace,
                               size_t workspace_bytes, void* stream)
 {
-    if (!c) return PNN_E_ARG;
-    if (!signalling) {
-        if (d_first_pass_costs || d_best_side_rate) return fail(c, PNN_E_ARG, "d_first_pass_costs or d_best_side_rate without signalling");
-        return pnn_rd_pass_rdoq_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, d_cand_pred, smoothing, qps, nb_qps, lambdas,
-                                       sign_data_hiding, rdoq, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
-                                       d_workspace, workspace_bytes, stream);
-    }
-    int rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing))) return rc;
-    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = check_rd_pass_signal(c, width, n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
-                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
-                                       d_first_pass_costs || d_best_side_rate,
-                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s))) return rc;
-    if (n == 0) return PNN_OK;
-    reset_stats(c);
-    return rd_pass_signal_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
-                                   lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot,
-                                   d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s);
+    return pnn_rd_pass_codec_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, d_cand_pred, smoothing, qps, nb_qps, lambdas,
+                                    sign_data_hiding, rdoq, signalling, d_left_modes, d_above_modes, 0, d_cand_modes, d_cand_costs, d_best_mode,
+                                    d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace,
+                                    workspace_bytes, stream);
 }
 
 int pnn_rd_pass_signal_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
@@ -921,31 +971,11 @@ int pnn_rd_pass_signal_picture_pairs_device(pnn_ctx* c, int width, const uint8_t
                                             double* d_first_pass_costs, uint64_t* d_best_side_rate, void* d_workspace, size_t workspace_bytes,
                                             void* stream)
 {
-    if (!c) return PNN_E_ARG;
-    if (!signalling) {
-        if (d_first_pass_costs || d_best_side_rate) return fail(c, PNN_E_ARG, "d_first_pass_costs or d_best_side_rate without signalling");
-        return pnn_rd_pass_rdoq_picture_pairs_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols,
-                                                     positions, mask_w, mask_h, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq,
-                                                     d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate,
-                                                     d_workspace, workspace_bytes, stream);
-    }
-    int rc;
-    long n;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
-        (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n))) return rc;
-    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = check_rd_pass_signal(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
-                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
-                                       d_first_pass_costs || d_best_side_rate,
-                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s))) return rc;
-    if (n == 0) return PNN_OK;
-    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
-    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
-    reset_stats(c);
-    return rd_pass_signal_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
-                                   smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs,
-                                   d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s);
+    return pnn_rd_pass_codec_picture_pairs_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols,
+                                                  positions, mask_w, mask_h, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq,
+                                                  signalling, d_left_modes, d_above_modes, 0, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot,
+                                                  d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace,
+                                                  workspace_bytes, stream);
 }
 
 // ---- the codec as an argument (include/pnn_hip.h, "the substitution codec") ----
@@ -964,25 +994,13 @@ int pnn_rd_pass_codec_device(pnn_ctx* c, int width, const uint8_t* d_patterns, i
                              size_t workspace_bytes, void* stream)
 {
     if (!c) return PNN_E_ARG;
-    if (codec == 0)
-        return pnn_rd_pass_signal_device(c, width, d_patterns, pattern_h, pattern_w, d_targets, n, d_cand_pred, smoothing, qps, nb_qps, lambdas,
-                                         sign_data_hiding, rdoq, signalling, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode,
-                                         d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace,
-                                         workspace_bytes, stream);
-    int rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_codec(c, codec, signalling)) || (rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) ||
-        (rc = check_smoothing(c, smoothing))) return rc;
-    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = check_rd_pass_signal(c, width, n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
-                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
-                                       d_first_pass_costs || d_best_side_rate,
-                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s, 1))) return rc;
-    if (n == 0) return PNN_OK;
-    reset_stats(c);
-    return rd_pass_signal_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
-                                   lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot,
-                                   d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s, 1);
+    RdPassCall q = rd_pass_call(width, dense_blocks(d_patterns, pattern_h, pattern_w, d_targets, n), d_cand_pred, smoothing, qps, nb_qps, lambdas,
+                                sign_data_hiding);
+    q.rdoq = rdoq; q.signalling = signalling; q.left = d_left_modes; q.above = d_above_modes; q.codec = codec;
+    q.out = {d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate,
+             nullptr};
+    q.workspace = d_workspace; q.workspace_bytes = workspace_bytes; q.stream = (hipStream_t)stream;
+    return rd_pass(c, q);
 }
 
 int pnn_rd_pass_codec_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
@@ -995,31 +1013,14 @@ int pnn_rd_pass_codec_picture_pairs_device(pnn_ctx* c, int width, const uint8_t*
                                            size_t workspace_bytes, void* stream)
 {
     if (!c) return PNN_E_ARG;
-    if (codec == 0)
-        return pnn_rd_pass_signal_picture_pairs_device(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols,
-                                                       positions, mask_w, mask_h, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding,
-                                                       rdoq, signalling, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode,
-                                                       d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate,
-                                                       d_workspace, workspace_bytes, stream);
-    int rc;
-    long n;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_codec(c, codec, signalling)) ||
-        (rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
-        (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n))) return rc;
-    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = check_rd_pass_signal(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
-                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
-                                       d_first_pass_costs || d_best_side_rate,
-                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s, 1))) return rc;
-    if (n == 0) return PNN_OK;
-    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
-    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
-    reset_stats(c);
-    return rd_pass_signal_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
-                                   smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs,
-                                   d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s,
-                                   1);
+    const BlockSource blocks = picture_pair_blocks(picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions),
+                                                   d_target_channels, images, mask_w, mask_h);
+    RdPassCall q = rd_pass_call(width, blocks, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding);
+    q.rdoq = rdoq; q.signalling = signalling; q.left = d_left_modes; q.above = d_above_modes; q.codec = codec;
+    q.out = {d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate,
+             nullptr};
+    q.workspace = d_workspace; q.workspace_bytes = workspace_bytes; q.stream = (hipStream_t)stream;
+    return rd_pass(c, q);
 }
 
 // ---- the second pass with transform skip (include/pnn_hip.h, "transform skip") ----
@@ -1039,22 +1040,14 @@ int pnn_rd_pass_tskip_device(pnn_ctx* c, int width, const uint8_t* d_patterns, i
                              uint8_t* d_best_ts_flag, void* d_workspace, size_t workspace_bytes, void* stream)
 {
     if (!c) return PNN_E_ARG;
-    int rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_rd_pass_tskip(c, width, n, qps, nb_qps, lambdas, signalling, codec, transform_skip, d_workspace, workspace_bytes)) ||
-        (rc = check_dense_blocks(c, width, d_patterns, pattern_h, pattern_w, d_targets, n)) || (rc = check_smoothing(c, smoothing))) return rc;
-    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = check_rd_pass_signal(c, width, n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
-                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
-                                       d_first_pass_costs || d_best_side_rate || d_best_ts_flag,
-                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s, codec))) return rc;
-    if (n == 0) return PNN_OK;
-    reset_stats(c);
-    if (!transform_skip && d_best_ts_flag) HIPCHK(c, hipMemsetAsync(d_best_ts_flag, 0, (size_t)nb_qps * n, s));
-    return rd_pass_signal_launches(c, width, d_patterns, pattern_h, pattern_w, d_targets, nullptr, nullptr, n, d_cand_pred, smoothing, qps, nb_qps,
-                                   lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs, d_best_mode, d_best_slot,
-                                   d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s, codec, transform_skip,
-                                   d_best_ts_flag);
+    RdPassCall q = rd_pass_call(width, dense_blocks(d_patterns, pattern_h, pattern_w, d_targets, n), d_cand_pred, smoothing, qps, nb_qps, lambdas,
+                                sign_data_hiding);
+    q.rdoq = rdoq; q.signalling = signalling; q.left = d_left_modes; q.above = d_above_modes; q.codec = codec;
+    q.transform_skip = transform_skip; q.tskip_entry = true;
+    q.out = {d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate,
+             d_best_ts_flag};
+    q.workspace = d_workspace; q.workspace_bytes = workspace_bytes; q.stream = (hipStream_t)stream;
+    return rd_pass(c, q);
 }
 
 int pnn_rd_pass_tskip_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
@@ -1067,27 +1060,15 @@ int pnn_rd_pass_tskip_picture_pairs_device(pnn_ctx* c, int width, const uint8_t*
                                            void* d_workspace, size_t workspace_bytes, void* stream)
 {
     if (!c) return PNN_E_ARG;
-    int rc;
-    long n = 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = check_tskip_option(c, width, transform_skip, 1)) || (rc = check_codec(c, codec, signalling)) ||
-        (rc = check_pair_geometry(c, width, d_context_channels, d_target_channels, images, height, width_ch, positions, mask_w, mask_h)) ||
-        (rc = check_smoothing(c, smoothing)) || (rc = count_blocks(c, images, positions, &n)) ||
-        (rc = check_rd_pass_tskip(c, width, (int)n, qps, nb_qps, lambdas, signalling, codec, transform_skip, d_workspace, workspace_bytes))) return rc;
-    if (n > 0) HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = check_rd_pass_signal(c, width, (int)n, d_cand_pred, qps, nb_qps, lambdas, rdoq,
-                                   d_cand_modes || d_cand_costs || d_best_mode || d_best_slot || d_best_cost || d_best_sse || d_best_rate ||
-                                       d_first_pass_costs || d_best_side_rate || d_best_ts_flag,
-                                   d_left_modes, d_above_modes, d_workspace, workspace_bytes, s, codec))) return rc;
-    if (n == 0) return PNN_OK;
-    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
-    if ((rc = check_picture_blocks(c, width, pic, s))) return rc;
-    reset_stats(c);
-    if (!transform_skip && d_best_ts_flag) HIPCHK(c, hipMemsetAsync(d_best_ts_flag, 0, (size_t)nb_qps * n, s));
-    return rd_pass_signal_launches(c, width, nullptr, 2 * width + 1 - mask_h, 2 * width + 1 - mask_w, nullptr, &pic, d_target_channels, n, d_cand_pred,
-                                   smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, d_left_modes, d_above_modes, d_cand_modes, d_cand_costs,
-                                   d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate, d_workspace, s,
-                                   codec, transform_skip, d_best_ts_flag);
+    const BlockSource blocks = picture_pair_blocks(picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions),
+                                                   d_target_channels, images, mask_w, mask_h);
+    RdPassCall q = rd_pass_call(width, blocks, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding);
+    q.rdoq = rdoq; q.signalling = signalling; q.left = d_left_modes; q.above = d_above_modes; q.codec = codec;
+    q.transform_skip = transform_skip; q.tskip_entry = true;
+    q.out = {d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate,
+             d_best_ts_flag};
+    q.workspace = d_workspace; q.workspace_bytes = workspace_bytes; q.stream = (hipStream_t)stream;
+    return rd_pass(c, q);
 }
 
 // The mode statistics of a second pass whose slot modes and winners are on the device: the output is zeroed on the stream, then one

@@ -608,53 +608,40 @@ def rd_pass_signal_shapes(n, nb_qps, width_target, codec='switch'):
     return ((nb_qps, n, s), (nb_qps, n, s)) + ((nb_qps, n),) * 5 + ((nb_qps, n, k), (nb_qps, n))
 
 
-def _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device, codec='switch',
-                    transform_skip=False):
-    """rd_pass with signalling: the checked arguments -> the dictionary, from pnn_rd_pass_codec_host (device None) or _device; with
-    transform_skip from pnn_rd_pass_tskip_host / _device, which take the option behind the codec and one more output behind the others
-    ('best_transform_skip' uint8 [nb_qps, n]) and have a scratch function of their own."""
-    n, w, nq = targets.shape[0], targets.shape[1], len(qps)
-    left, above = (None, None) if neighbour_modes is None else neighbour_modes
-    with_35 = not CODECS[codec]                           # a neighbour coded with 35 exists in the switch codec only
-    left, above = _neighbour_array(left, n, with_35, 'neighbour_modes[0]'), _neighbour_array(above, n, with_35, 'neighbour_modes[1]')
-    outputs, shapes = tuple(RD_PASS_SIGNAL_OUTPUTS), tuple(rd_pass_signal_shapes(n, nq, w, codec))
+def _rd_pass_call(arrays, coding, neighbours, options, outputs, shapes, nb_padding, size_function, refused, device):
+    """One call of the second pass: pnn_rd_pass_codec_host / _device or, with two `options` (the codec and transform skip),
+    pnn_rd_pass_tskip_host / _device -- the host twin with device None or without a block (nothing to launch), else that GPU.
+    arrays: contiguous patterns, targets, candidate; coding: the arguments from the smoothing to the signalling; neighbours: (left,
+    above), each None or a uint8 array; outputs / shapes: (name, dtype) and shape of each output the call fills, behind which go
+    nb_padding NULL outputs; size_function: the scratch's, called with (w, n, nb_qps, signalling, *options); refused: the name in the
+    ValueError of a refusal by the host twin.  -> {name: array}."""
+    patterns, targets, candidate = arrays
+    n, w, (ph, pw) = targets.shape[0], targets.shape[1], patterns.shape[1:3]
     L = _lib.lib()
-    if transform_skip:
-        name, option_arguments = 'pnn_rd_pass_tskip_', (CODECS[codec], 1)
-        outputs, shapes = outputs + (('best_transform_skip', np.uint8),), shapes + ((nq, n),)
-        nb_bytes = L.pnn_rd_pass_tskip_workspace_bytes(w, n, nq, 1, CODECS[codec], 1)
-    else:
-        name, option_arguments = 'pnn_rd_pass_codec_', (CODECS[codec],)
-        nb_bytes = L.pnn_rd_pass_codec_workspace_bytes(w, n, nq, 1, CODECS[codec])
+    entry = 'pnn_rd_pass_tskip_' if len(options) == 2 else 'pnn_rd_pass_codec_'
+    padding = (None,) * nb_padding
     if device is None or n == 0:
         outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(outputs, shapes)]
-        rc = getattr(L, name + 'host')(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
-                                       smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(left), _address(above), *option_arguments,
-                                       *[o.ctypes.data for o in outs])
+        rc = getattr(L, entry + 'host')(patterns.ctypes.data, ph, pw, targets.ctypes.data, w, n, candidate.ctypes.data, *coding,
+                                        *[_address(a) for a in neighbours], *options, *[o.ctypes.data for o in outs], *padding)
         if rc != 0:
-            raise ValueError('%s refused the arguments (patterns %dx%d, width %d).'
-                             % ('pnn_rd_pass_tskip_host' if transform_skip else 'pnn_rd_pass_signal_host', patterns.shape[1], patterns.shape[2], w))
+            raise ValueError('%s refused the arguments (patterns %dx%d, width %d).' % (refused, ph, pw, w))
     else:
         import torch
         dev = torch.device("cuda", device)
-        d_in = [torch.from_numpy(a).to(dev) for a in (patterns, targets, candidate)]
-        d_left, d_above = (None if a is None else torch.from_numpy(a).to(dev) for a in (left, above))
+        d_in = [torch.from_numpy(a).to(dev) for a in arrays]
+        d_neighbours = [None if a is None else torch.from_numpy(a).to(dev) for a in neighbours]
         d_outs = [torch.zeros(int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=torch.uint8, device=dev)
                   for (_, dtype), shape in zip(outputs, shapes)]
+        nb_bytes = size_function(w, n, coding[2], coding[-1], *options)
         d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(getattr(L, name + 'device')(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
-                                                   n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 1, _address(d_left),
-                                                   _address(d_above), *option_arguments, *[o.data_ptr() for o in d_outs], d_ws.data_ptr(), nb_bytes,
-                                                   ctypes.c_void_p(stream.cuda_stream)), _context(device))
+            _lib.check(getattr(L, entry + 'device')(_context(device), w, d_in[0].data_ptr(), ph, pw, d_in[1].data_ptr(), n, d_in[2].data_ptr(),
+                                                    *coding, *[_address(a) for a in d_neighbours], *options, *[o.data_ptr() for o in d_outs],
+                                                    *padding, d_ws.data_ptr(), nb_bytes, ctypes.c_void_p(stream.cuda_stream)), _context(device))
         outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, outputs, shapes)]   # (waits)
-    result = {name: out for (name, _), out in zip(outputs, outs)}
-    result['rate_bits'] = result['rates'].astype(np.float64) / 32768.
-    result['side_rate_bits'] = result['side_rates'].astype(np.float64) / 32768.
-    result['psnrs_recon'] = psnrs_from_sses(result['sses'], w)
-    result['lambdas'] = np.array([hm_intra_lambda(q) for q in qps]) if c_lambdas is None else np.array(list(c_lambdas))
-    return result
+    return {name: out for (name, _), out in zip(outputs, outs)}
 
 
 def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoothing=0, sign_data_hiding=False, lambdas=None, device=None,
@@ -706,33 +693,23 @@ def rd_pass(intra_patterns, targets, candidate_predictions, qps, reference_smoot
     c_qps, c_lambdas = (ctypes.c_int * nq)(*qps), _check_lambdas(lambdas, nq, positive=bool(option) or bool(transform_skip))
     if not signalling and neighbour_modes is not None:
         raise ValueError('`neighbour_modes` is given without `signalling`.')
-    if signalling:
-        return _rd_pass_signal(patterns, targets, candidate, qps, smoothing, flag, option, c_qps, c_lambdas, neighbour_modes, device, codec,
-                               bool(transform_skip))
-    shapes = rd_pass_shapes(n, nq, w)
+    arrays, coding = (patterns, targets, candidate), (smoothing, c_qps, nq, c_lambdas, flag, option, int(bool(signalling)))
     L = _lib.lib()
-    if device is None or n == 0:                          # (no block: nothing to launch, the empty arrays)
-        outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
-        rc = L.pnn_rd_pass_codec_host(patterns.ctypes.data, patterns.shape[1], patterns.shape[2], targets.ctypes.data, w, n, candidate.ctypes.data,
-                                      smoothing, c_qps, nq, c_lambdas, flag, option, 0, None, None, number, *[o.ctypes.data for o in outs], None, None)
-        if rc != 0:
-            raise ValueError('pnn_rd_pass_host refused the arguments (patterns %dx%d, width %d).' % (patterns.shape[1], patterns.shape[2], w))
+    if not signalling:                                    # (the side outputs stay NULL)
+        result = _rd_pass_call(arrays, coding, (None, None), (number,), RD_PASS_OUTPUTS, rd_pass_shapes(n, nq, w), 2,
+                               L.pnn_rd_pass_codec_workspace_bytes, 'pnn_rd_pass_host', device)
     else:
-        import torch
-        dev = torch.device("cuda", device)
-        d_in = [torch.from_numpy(a).to(dev) for a in (patterns, targets, candidate)]
-        d_outs = [torch.zeros(int(np.prod(shape)) * np.dtype(dtype).itemsize, dtype=torch.uint8, device=dev)
-                  for (_, dtype), shape in zip(RD_PASS_OUTPUTS, shapes)]
-        nb_bytes = L.pnn_rd_pass_codec_workspace_bytes(w, n, nq, 0, number)
-        d_ws = torch.empty(max(nb_bytes, 8), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.pnn_rd_pass_codec_device(_context(device), w, d_in[0].data_ptr(), patterns.shape[1], patterns.shape[2], d_in[1].data_ptr(),
-                                                  n, d_in[2].data_ptr(), smoothing, c_qps, nq, c_lambdas, flag, option, 0, None, None, number,
-                                                  *[o.data_ptr() for o in d_outs], None, None, d_ws.data_ptr(), nb_bytes,
-                                                  ctypes.c_void_p(stream.cuda_stream)), _context(device))
-        outs = [o.cpu().numpy().view(dtype).reshape(shape) for o, (_, dtype), shape in zip(d_outs, RD_PASS_OUTPUTS, shapes)]   # (waits)
-    result = {name: out for (name, _), out in zip(RD_PASS_OUTPUTS, outs)}
+        left, above = (None, None) if neighbour_modes is None else neighbour_modes
+        with_35 = not number                              # a neighbour coded with 35 exists in the switch codec only
+        neighbours = (_neighbour_array(left, n, with_35, 'neighbour_modes[0]'), _neighbour_array(above, n, with_35, 'neighbour_modes[1]'))
+        outputs, shapes = RD_PASS_SIGNAL_OUTPUTS, rd_pass_signal_shapes(n, nq, w, codec)
+        if transform_skip:                                # the option behind the codec, one more output behind the others, a scratch function of its own
+            result = _rd_pass_call(arrays, coding, neighbours, (number, 1), outputs + (('best_transform_skip', np.uint8),), shapes + ((nq, n),), 0,
+                                   L.pnn_rd_pass_tskip_workspace_bytes, 'pnn_rd_pass_tskip_host', device)
+        else:
+            result = _rd_pass_call(arrays, coding, neighbours, (number,), outputs, shapes, 0, L.pnn_rd_pass_codec_workspace_bytes,
+                                   'pnn_rd_pass_signal_host', device)
+        result['side_rate_bits'] = result['side_rates'].astype(np.float64) / 32768.
     result['rate_bits'] = result['rates'].astype(np.float64) / 32768.
     result['psnrs_recon'] = psnrs_from_sses(result['sses'], w)
     result['lambdas'] = np.array([hm_intra_lambda(q) for q in qps]) if c_lambdas is None else np.array(list(c_lambdas))

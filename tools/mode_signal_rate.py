@@ -9,8 +9,8 @@
   split of SG from samples of its launches' own entries on the shapes SG gives them: HADS (the first-pass call asked for the costs, no
   list), TQ slots (nb_qps calls of the transform entry, one QP each, on the n (K + 3) slots with the slots' modes) and the rest --
   signal_list_kernel, the candidates and the decisions together, a difference, not timed alone.  With --parent-lib, a libpnn_hip.so
-  built from the parent commit joins the alternation for the untouched calls (FP, TQ PNN, TQ HEVC, RD): their medians here must lie
-  inside the min .. max spread of the parent's samples.
+  built from the parent commit joins the alternation for the calls whose kernels and launches are the parent's (FP, TQ PNN, TQ HEVC, RD
+  and SG itself): their medians here must lie inside the min .. max spread of the parent's samples.
 
     python tools/mode_signal_rate.py [--parent-lib /path/to/parent/libpnn_hip.so]          # on the GPU box
 """
@@ -29,7 +29,7 @@ from hevc_mode_hads_rate import blocks, sample  # noqa: E402
 
 SHAPES = ((8, 65536), (32, 8192))
 QPS = (22, 27, 32, 37)
-UNTOUCHED = ("fp", "tq_pnn", "tq_hevc", "rd")
+UNTOUCHED = ("fp", "tq_pnn", "tq_hevc", "rd", "sg")
 
 
 def main():
@@ -54,7 +54,8 @@ def main():
     parent = parent_ctx = None
     if args.parent_lib:
         parent = ctypes.CDLL(args.parent_lib)
-        for name in ("pnn_create_empty", "pnn_hevc_mode_hads_hm_device", "pnn_trquant_sdh_device", "pnn_rd_pass_rdoq_device"):
+        for name in ("pnn_create_empty", "pnn_hevc_mode_hads_hm_device", "pnn_trquant_sdh_device", "pnn_rd_pass_rdoq_device",
+                     "pnn_rd_pass_signal_device"):
             getattr(parent, name).restype, getattr(parent, name).argtypes = _lib.SIGNATURES[name]
         parent_ctx = ctypes.c_void_p()
         assert parent.pnn_create_empty(ctypes.byref(parent_ctx), ctypes.c_float(0.), 0) == 0
@@ -89,9 +90,9 @@ def main():
             slot_t, slot_c = d_t.repeat_interleave(slots, dim=0).contiguous(), d_c.repeat_interleave(slots, dim=0).contiguous()
             blocks_args = (w, d_p.data_ptr(), 2 * w + 1, 2 * w + 1, d_t.data_ptr(), n, d_c.data_ptr(), 0)
 
-            def sg():
-                return L.pnn_rd_pass_signal_device(ctx, *blocks_args, c_qps, nq, None, 0, 0, 1, d_l.data_ptr(), d_a.data_ptr(),
-                                                   *[o.data_ptr() for o in sg_outs], d_ws.data_ptr(), nb_sg, sp)
+            def sg(lib=L, c=ctx):
+                return lib.pnn_rd_pass_signal_device(c, *blocks_args, c_qps, nq, None, 0, 0, 1, d_l.data_ptr(), d_a.data_ptr(),
+                                                     *[o.data_ptr() for o in sg_outs], d_ws.data_ptr(), nb_sg, sp)
 
             def rd(lib=L, c=ctx):
                 return lib.pnn_rd_pass_rdoq_device(c, *blocks_args, c_qps, nq, None, 0, 0, *[o.data_ptr() for o in rd_outs], d_ws.data_ptr(), nb_rd, sp)
@@ -128,7 +129,7 @@ def main():
             if parent is not None:
                 calls.update({"parent_fp": lambda: fp(parent, parent_ctx), "parent_tq_pnn": lambda: tq(d_c, d_t, n, None, parent, parent_ctx),
                               "parent_tq_hevc": lambda: tq(d_c, d_t, n, d_modes.data_ptr(), parent, parent_ctx),
-                              "parent_rd": lambda: rd(parent, parent_ctx)})
+                              "parent_rd": lambda: rd(parent, parent_ctx), "parent_sg": lambda: sg(parent, parent_ctx)})
             times = {name: [] for name in calls}
             for i in range(args.warmup + args.reps):
                 order = list(calls)
