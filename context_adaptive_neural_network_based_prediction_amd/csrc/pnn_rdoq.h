@@ -28,6 +28,8 @@ constexpr long long kRdFactorMax = 1ll << 52;  // see consts()
 // HM's lambda of an I slice (TEncSlice::calculateLambda, GOP size 1, 8-bit, no modifier), the one home of the formula: pnn_hm_intra_lambda
 // returns it, and it is what RDOQ runs under when the caller hands no lambda
 inline double hm_intra_lambda(int qp) { return 0.57 * std::pow(2.0, (qp - 12) / 3.0); }
+// a lambda RDOQ, and the decision of transform skip, can run under: the one home of the check
+inline bool lambda_ok(double lambda) { return std::isfinite(lambda) && lambda > 0.; }
 
 // What a QP and a lambda turn into, computed in double on the host, in HM's operation order:
 //   err_scale: getErrScaleCoeffNoScalingList as setErrScaleCoeff leaves it -- 2^15 * 2^(-2 transformShift) / scale / scale / 1;

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
 // RDOQ's costs are doubles rounded once per operation (pnn_rdoq.h): nothing in this file may be contracted
@@ -36,6 +37,18 @@ bool unit_size_ok(int t) { return t == 4 || t == 8 || t == 16 || t == 32; }
 // 0, 1 or 2, and diagonal where the unit is above 8 x 8
 bool scan_ok(int scan, int t) { return scan >= 0 && scan <= 2 && (t <= 8 || scan == pnn::cabac::kScanDiag); }
 const char* const kBadScan = "The scan is not 0 (diagonal), 1 (horizontal) or 2 (vertical), or not diagonal above 8 x 8.\n";
+
+// log2_t (2 .. 5) as a compile-time L: f(std::integral_constant<int, L>()), the one dispatch to the templates over the unit size
+template <typename F>
+auto with_log2(int log2_t, F f)
+{
+    switch (log2_t) {
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 5>());
+    }
+}
 
 // M[k][x] of one unit size, dense
 struct Matrix {
@@ -125,12 +138,7 @@ void sign_hide_unit(int* levels, const int* coeffs, const int* delta_u, int scan
 }
 void sign_hide_unit(int log2_t, int* levels, const int* coeffs, const int* delta_u, int scan)
 {
-    switch (log2_t) {
-    case 2: sign_hide_unit<2>(levels, coeffs, delta_u, scan); break;
-    case 3: sign_hide_unit<3>(levels, coeffs, delta_u, scan); break;
-    case 4: sign_hide_unit<4>(levels, coeffs, delta_u, scan); break;
-    default: sign_hide_unit<5>(levels, coeffs, delta_u, scan); break;
-    }
+    with_log2(log2_t, [&](auto L) { sign_hide_unit<decltype(L)::value>(levels, coeffs, delta_u, scan); });
 }
 
 // RDOQ (pnn_rdoq.h): what one QP and lambda turn into at a unit size -- the constants and the bit estimates
@@ -143,17 +151,16 @@ struct Rdoq {
         uint8_t init[kNumCtx], cbf[2];
         for (int i = 0; i < kNumCtx; i++) init[i] = (uint8_t)init_state(qp, init_value(i));
         for (int i = 0; i < 2; i++) cbf[i] = (uint8_t)init_state(qp, pnn::rdoq::kCbfInit[i]);
-        int (*const word)(int, const uint8_t*, const uint8_t*, const int*) =
-            log2_t == 2 ? pnn::rdoq::est_bits_word<2> : log2_t == 3 ? pnn::rdoq::est_bits_word<3> : log2_t == 4 ? pnn::rdoq::est_bits_word<4>
-                                                                                                                  : pnn::rdoq::est_bits_word<5>;
         int* words = &e.ctx[0][0];
-        for (int i = 0; i < pnn::rdoq::kEstBitsWords; i++) words[i] = word(i, init, cbf, entropy_bits_table());
+        with_log2(log2_t, [&](auto L) {
+            for (int i = 0; i < pnn::rdoq::kEstBitsWords; i++) words[i] = pnn::rdoq::est_bits_word<decltype(L)::value>(i, init, cbf, entropy_bits_table());
+        });
     }
 };
 // the cbf context of the unit(s) of a block of width w: one transform unit of a 2N x 2N coding unit at 8, 16, 32; what HM reaches as N x N
 // at 4; the quadrants at 64 (this project's definition)
 int cbf_ctx_of_width(int w) { return w == 8 || w == 16 || w == 32 ? 1 : 0; }
-bool lambda_ok(double lambda) { return std::isfinite(lambda) && lambda > 0.; }
+using pnn::rdoq::lambda_ok;
 
 // xRateDistOptQuant of one unit: the levels (and those in front of RDOQ's own hiding), returns uiAbsSum
 template <int L>
@@ -170,12 +177,7 @@ int rdoq_unit(const int* coeffs, int scan, const QpConsts& q, const Rdoq& r, int
 }
 int rdoq_unit(int log2_t, const int* coeffs, int scan, const QpConsts& q, const Rdoq& r, int cbf_ctx, bool sdh, int* levels, int* before_hiding)
 {
-    switch (log2_t) {
-    case 2: return rdoq_unit<2>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding);
-    case 3: return rdoq_unit<3>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding);
-    case 4: return rdoq_unit<4>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding);
-    default: return rdoq_unit<5>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding);
-    }
+    return with_log2(log2_t, [&](auto L) { return rdoq_unit<decltype(L)::value>(coeffs, scan, q, r, cbf_ctx, sdh, levels, before_hiding); });
 }
 
 // quantise -> (hide signs) -> dequantise -> inverse of one unit's coefficients at one QP; the counts ADD into *nb_nonzero / *sum_abs.
@@ -225,19 +227,11 @@ uint64_t unit_rate(int log2_t, const int* levels, int scan, const InitStates& in
 {
     using namespace pnn::cabac;
     uint8_t state[kNumCtx];
-    if (sdh)
-        switch (log2_t) {
-        case 2: return pnn::cabac::unit_rate<2, true>(levels, scan, init.s, state, rom_tables());
-        case 3: return pnn::cabac::unit_rate<3, true>(levels, scan, init.s, state, rom_tables());
-        case 4: return pnn::cabac::unit_rate<4, true>(levels, scan, init.s, state, rom_tables());
-        default: return pnn::cabac::unit_rate<5, true>(levels, scan, init.s, state, rom_tables());
-        }
-    switch (log2_t) {
-    case 2: return pnn::cabac::unit_rate<2>(levels, scan, init.s, state, rom_tables());
-    case 3: return pnn::cabac::unit_rate<3>(levels, scan, init.s, state, rom_tables());
-    case 4: return pnn::cabac::unit_rate<4>(levels, scan, init.s, state, rom_tables());
-    default: return pnn::cabac::unit_rate<5>(levels, scan, init.s, state, rom_tables());
-    }
+    return with_log2(log2_t, [&](auto L) {
+        constexpr int kL = decltype(L)::value;
+        return sdh ? pnn::cabac::unit_rate<kL, true>(levels, scan, init.s, state, rom_tables())
+                   : pnn::cabac::unit_rate<kL>(levels, scan, init.s, state, rom_tables());
+    });
 }
 
 }  // namespace

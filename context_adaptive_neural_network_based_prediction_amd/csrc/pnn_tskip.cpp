@@ -27,7 +27,7 @@ namespace {
 using namespace pnn::trquant;
 namespace ts = pnn::tskip;
 
-bool lambda_ok(double lambda) { return std::isfinite(lambda) && lambda > 0.; }
+using pnn::rdoq::lambda_ok;
 
 // the skipped form of one unit at one QP: coefficients, levels (as dequantised), HM's uiAbsSum, the decoded residual
 int skipped_unit(const int* residual, int scan, int qp, bool sdh, bool rdoq, double lambda, int32_t* coeffs, int32_t* levels, int32_t* abs_sum,
@@ -171,8 +171,8 @@ extern "C" int pnn_trquant_tskip_host(const uint8_t* predictions, const uint8_t*
     return PNN_OK;
 }
 
-// ---- The second pass with transform skip (include/pnn_hip.h, "transform skip"): pnn_rd_pass.cpp's body with
-// signalling, which codes every slot through the coder below -- both forms, decided per slot under the slot's mode bits and the cbf bin ----
+// ---- The second pass with transform skip (include/pnn_hip.h, "transform skip"): pnn_rd_pass.cpp's pass with
+// signalling, whose record carries the coder below -- both forms, decided per slot under the slot's mode bits and the cbf bin ----
 namespace {
 int code_slots_both_forms(const uint8_t* pred, const uint8_t* targets, int n, const uint8_t* modes, int qp, uint32_t* sse, uint32_t* nonzero,
                           uint64_t* rate, int sign_data_hiding, int rdoq, double lambda, const uint32_t* mode_bits, uint8_t* ts_flag)
@@ -189,16 +189,15 @@ extern "C" int pnn_rd_pass_tskip_host(const uint8_t* patterns, int pattern_h, in
                                       double* best_cost, uint32_t* best_sse, uint64_t* best_rate, double* first_pass_costs, uint64_t* best_side_rate,
                                       uint8_t* best_ts_flag)
 {
-    const char* refusal = nullptr;
-    if (transform_skip != 0 && transform_skip != 1) refusal = "transform_skip is not 0 or 1.";
-    else if (transform_skip && width != ts::kWidth) refusal = "transform skip at a width other than 4.";
-    else if (codec != 0 && codec != 1) refusal = "the codec is not 0 (switch) or 1 (substitution).";
-    else if (!signalling) refusal = "the second pass with transform skip without signalling.";
-    for (int qi = 0; !refusal && transform_skip && lambdas && qps && qi < nb_qps && qi < 8; qi++)
-        if (!lambda_ok(lambdas[qi])) refusal = "transform skip with a lambda that is not finite or not above 0.";
-    if (refusal) { fprintf(stderr, "pnn_rd_pass_tskip_host: %s\n", refusal); return PNN_E_ARG; }
-    return pnn::rd_pass_host_with_coder("pnn_rd_pass_tskip_host", codec, patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps,
-                                        nb_qps, lambdas, sign_data_hiding, rdoq, left_modes, above_modes, cand_modes, cand_costs, best_mode, best_slot,
-                                        best_cost, best_sse, best_rate, first_pass_costs, best_side_rate,
-                                        transform_skip ? code_slots_both_forms : nullptr, best_ts_flag);
+    const char* entry = "pnn_rd_pass_tskip_host";
+    pnn::RdPassHostCall q{entry, patterns, pattern_h, pattern_w, targets, width, n, cand_pred, smoothing, qps, nb_qps, lambdas};
+    q.sign_data_hiding = sign_data_hiding; q.rdoq = rdoq; q.signalling = 1; q.codec = codec; q.left = left_modes; q.above = above_modes;
+    q.out = {cand_modes, cand_costs, best_mode, best_slot, best_cost, best_sse, best_rate, first_pass_costs, best_side_rate, best_ts_flag};
+    q.coder = transform_skip ? code_slots_both_forms : nullptr;
+    if (transform_skip != 0 && transform_skip != 1) return pnn::rd_pass_refuse(entry, "transform_skip is not 0 or 1.");
+    if (transform_skip && width != ts::kWidth) return pnn::rd_pass_refuse(entry, "transform skip at a width other than 4.");
+    if (codec != 0 && codec != 1) return pnn::rd_pass_refuse(entry, "the codec is not 0 (switch) or 1 (substitution).");
+    if (!signalling) return pnn::rd_pass_refuse(entry, "the second pass with transform skip without signalling.");
+    if (transform_skip && !q.given_lambdas_are(lambda_ok)) return pnn::rd_pass_refuse(entry, "transform skip with a lambda that is not finite or not above 0.");
+    return pnn::rd_pass_host_with_coder(q);
 }
