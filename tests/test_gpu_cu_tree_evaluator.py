@@ -7,6 +7,7 @@ import pytest
 
 from context_adaptive_neural_network_based_prediction_amd import evaluation
 from context_adaptive_neural_network_based_prediction_amd import intraprediction as ip
+from tests import cu_tree_cases
 from tests import util
 from tests.util import assert_same_dictionary
 
@@ -29,6 +30,23 @@ def leaves_of(scores):
         out[w] = (d['rd_pass_sses'], (d['rd_pass_rate_bits'] * 32768.).astype(np.uint64), (d['rd_pass_side_rate_bits'] * 32768.).astype(np.uint64),
                   d['rd_pass_modes'])
     return out
+
+
+# For the substitution codec from pairs the tree on these real leaves is also held to the independent restatement of
+# tests/cu_tree_cases.py, and the leaves themselves -- every width's rd_pass_sses, rd_pass_rate_bits, rd_pass_side_rate_bits and
+# rd_pass_modes -- to the second pass's host twin on the dictionary's own targets and PNN predictions and host-extracted patterns, over
+# all blocks of both CTUs (512 at w = 4: the twin takes a few hundredths of a second on them).
+TREE_KEYS = ("cu_depths", "part_nxn", "node_costs", "ctu_costs", "ctu_dists", "ctu_rates", "selected", "selected_pnn")
+LEAF_KEYS = {'rd_pass_sses': 'sses', 'rd_pass_rate_bits': 'rate_bits', 'rd_pass_side_rate_bits': 'side_rate_bits', 'rd_pass_modes': 'modes'}
+
+
+def assert_tree_is_the_restatement(got, leaves, pnn_mode, label):
+    """As tests/test_cu_tree.py holds the twin to the restatement, which takes rate plus side rate summed (cu_tree_cases.as_rd_pass_tuples
+    in reverse)"""
+    want = cu_tree_cases.restate({w: (d, r + side, m) for w, (d, r, side, m) in leaves.items()}, QPS, pnn_mode=pnn_mode)
+    for key in TREE_KEYS:
+        assert got[key].dtype == want[key].dtype and got[key].shape == want[key].shape, (label, key)
+        assert got[key].tobytes() == want[key].tobytes(), "%s %s: %d differing values" % (label, key, (got[key] != want[key]).sum())
 
 
 @pytest.mark.parametrize("codec, pairs", (('switch', False), ('substitution', True)))
@@ -57,6 +75,16 @@ def test_coding_tree_from_scores_equals_host_twin(codec, pairs):
         after = all_widths()
         for w in ip.WIDTHS:
             assert_same_dictionary(after[w][(0, 0)], before[w][(0, 0)], "%s width %d" % (codec, w))
+        if pairs:
+            assert_tree_is_the_restatement(got, leaves_of(before), pnn_mode, codec + " restated")
+            for w in ip.WIDTHS:                           # the tree's inputs: once more with the predictions kept, against the host twin
+                rows, cols = POSITIONS[w]
+                kept = score(channels, w, rows, cols, nets[w], util.MEAN, ((0, 0),), **dict(options, keep_predictions=True))[(0, 0)]
+                patterns = ip.extract_intra_patterns(channels[..., -1:], w, rows + w - 1, cols + w - 1, (0, 0))[..., 0]
+                host = ip.rd_pass(patterns, kept['targets_uint8'][..., 0], kept['predictions_pnn_uint8'][..., 0], QPS, reference_smoothing=2,
+                                  sign_data_hiding=True, rdoq=True, signalling=True, codec=codec)
+                assert_same_dictionary({k: kept[k] for k in LEAF_KEYS}, {k: host[v] for k, v in LEAF_KEYS.items()}, "%s leaves width %d" % (codec, w))
+                assert_same_dictionary({k: before[w][(0, 0)][k] for k in LEAF_KEYS}, {k: kept[k] for k in LEAF_KEYS}, "%s kept width %d" % (codec, w))
     finally:
         for net in nets.values():
             net.close()
