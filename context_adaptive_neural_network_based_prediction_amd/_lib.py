@@ -163,6 +163,11 @@ SIGNATURES = {
     "pnn_cu_tree_host": (ci, [ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, vp, vp, vp, vp, vp, ci] + [vp] * 8),
     "pnn_cu_tree_device": (ci, [vp, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, vp, vp, vp, vp, vp, ci] + [vp] * 9),
     "pnn_cu_tree_bins_host": (ci, [ci, vp]),
+    "pnn_cu_tree_picture_host": (ci, [ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, vp, ci] + [vp] * 10),
+    "pnn_cu_tree_picture_workspace_bytes": (ctypes.c_size_t, [ci, ci, ci, ci]),
+    "pnn_cu_tree_picture_device": (ci, [vp, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, vp, ci] + [vp] * 11 +
+                                   [ctypes.c_size_t, vp]),
+    "pnn_cu_tree_leaves_device": (ci, [vp, ci, ci, ci] + [vp] * 8),
     "pnn_last_call_stats": (ci,[vp, ctypes.POINTER(ci),ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

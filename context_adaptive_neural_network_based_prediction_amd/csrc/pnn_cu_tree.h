@@ -137,7 +137,17 @@ PNN_TQ_HD inline int selected_block(const Work& w, int z, int* leaf, int* count)
     return nxn ? 0 : 4 - d;
 }
 
-// The refusals both entries share (pnn_cu_tree_host, pnn_cu_tree_device): NULL, or the text of the first one that applies
+// The picture form (include/pnn_hip.h, "the coding tree over a picture"): edge cell e of a CTU -- e < 8 is left[y = e], else above[x =
+// e - 8] -- from the FINAL maps of the CTU left of it and of the CTU above it (NULL: there is none in the image): cell (7, y) of the
+// one, cell (x, 7) of the other.  The one place where a finished map becomes an edge, for twin and kernel alike.
+PNN_TQ_HD inline uint8_t edge_from_maps(const uint8_t* left_map, const uint8_t* above_map, int e)
+{
+    const uint8_t* map = e < 8 ? left_map : above_map;
+    return map ? map[e < 8 ? cell_of(7, e) : cell_of(e - 8, 7)] : (uint8_t)kNoDepth;
+}
+
+// The refusals every entry shares (pnn_cu_tree_host, pnn_cu_tree_device and the two picture entries): NULL, or the text of the first
+// one that applies
 inline const char* refusal(const int* qps, int nb_qps, const double* lambdas, int n_ctu, const uint32_t* const* dists, const uint64_t* const* rates,
                            const uint8_t* const* modes, int pnn_mode, bool any_output, bool wants_selected_pnn)
 {
@@ -153,6 +163,15 @@ inline const char* refusal(const int* qps, int nb_qps, const double* lambdas, in
     if (pnn_mode < 0 || pnn_mode > 255) return "pnn_mode does not belong to [0, 255]";
     if (wants_selected_pnn && !modes) return "selected_pnn without the modes";
     if (!any_output) return "every output is NULL";
+    return nullptr;
+}
+// The picture entries' grid, ahead of `refusal`: *n_ctu = n_images ctu_rows ctu_cols where that is an int
+inline const char* grid_refusal(int n_images, int ctu_rows, int ctu_cols, int* n_ctu)
+{
+    if (n_images < 1 || ctu_rows < 1 || ctu_cols < 1) return "fewer than one image, CTU row or CTU column";
+    const long long per_image = (long long)ctu_rows * ctu_cols;
+    if (per_image > 0x7fffffffLL || per_image * n_images > 0x7fffffffLL) return "the CTUs of the pictures do not fit an int";
+    *n_ctu = (int)(per_image * n_images);
     return nullptr;
 }
 inline const char* edge_refusal(const uint8_t* edge, size_t count)

@@ -1144,6 +1144,88 @@ int pnn_cu_tree_device(pnn_ctx* c, const int* qps, int nb_qps, const double* lam
     return PNN_OK;
 }
 
+// The coding tree over whole pictures: the depth maps every CTU's edges are gathered from, [nb_qps][n_ctu][64]
+// bytes -- the caller's cu_depths where given, else the caller's workspace; 0 for a grid the entry refuses.
+size_t pnn_cu_tree_picture_workspace_bytes(int nb_qps, int n_images, int ctu_rows, int ctu_cols)
+{
+    int n_ctu = 0;
+    if (nb_qps < 1 || nb_qps > cutree::kMaxQps || cutree::grid_refusal(n_images, ctu_rows, ctu_cols, &n_ctu)) return 0;
+    return (size_t)nb_qps * n_ctu * cutree::kCells;
+}
+
+// No caller edges, so nothing is read back: the four sum and count outputs are zeroed on the stream, then ctu_rows + ctu_cols - 1
+// launches of cu_tree_picture_kernel, one per anti-diagonal.
+int pnn_cu_tree_picture_device(pnn_ctx* c, const int* qps, int nb_qps, const double* lambdas, int n_images, int ctu_rows, int ctu_cols,
+                               const uint32_t* const* d_dists, const uint64_t* const* d_rates, const uint8_t* const* d_modes, int pnn_mode,
+                               uint8_t* d_cu_depths, uint8_t* d_part_nxn, double* d_node_costs, double* d_ctu_costs, uint64_t* d_ctu_dists,
+                               uint64_t* d_ctu_rates, uint32_t* d_selected, uint32_t* d_selected_pnn, uint64_t* d_image_dists,
+                               uint64_t* d_image_rates, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    const bool any = d_cu_depths || d_part_nxn || d_node_costs || d_ctu_costs || d_ctu_dists || d_ctu_rates || d_selected || d_selected_pnn ||
+                     d_image_dists || d_image_rates;
+    int n_ctu = 0;
+    const char* refusal = cutree::grid_refusal(n_images, ctu_rows, ctu_cols, &n_ctu);
+    if (!refusal) refusal = cutree::refusal(qps, nb_qps, lambdas, n_ctu, d_dists, d_rates, d_modes, pnn_mode, any, d_selected_pnn != nullptr);
+    if (refusal) return fail(c, PNN_E_ARG, "%s", refusal);
+    for (int k = 0; k < cutree::kWidths; k++)
+        if ((uintptr_t)d_dists[k] % 4 || (uintptr_t)d_rates[k] % 8) return fail(c, PNN_E_ARG, "a leaf array is not aligned to its element");
+    if ((uintptr_t)d_node_costs % 8 || (uintptr_t)d_ctu_costs % 8 || (uintptr_t)d_ctu_dists % 8 || (uintptr_t)d_ctu_rates % 8 ||
+        (uintptr_t)d_selected % 4 || (uintptr_t)d_selected_pnn % 4 || (uintptr_t)d_image_dists % 8 || (uintptr_t)d_image_rates % 8)
+        return fail(c, PNN_E_ARG, "an output is not aligned to its element");
+    const size_t need = pnn_cu_tree_picture_workspace_bytes(nb_qps, n_images, ctu_rows, ctu_cols);
+    if (!d_workspace || (uintptr_t)d_workspace % 16) return fail(c, PNN_E_ARG, "d_workspace is NULL or not aligned to 16 bytes");
+    if (workspace_bytes < need)
+        return fail(c, PNN_E_ARG, "the workspace has %zu bytes, pnn_cu_tree_picture_workspace_bytes asks for %zu", workspace_bytes, need);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    reset_stats(c);
+    CuTreeParams p;
+    for (int k = 0; k < cutree::kWidths; k++) { p.dist[k] = d_dists[k]; p.rate[k] = d_rates[k]; p.mode[k] = d_modes ? d_modes[k] : nullptr; }
+    p.left = nullptr; p.above = nullptr; p.n_ctu = n_ctu; p.nb_qps = nb_qps; p.pnn_mode = pnn_mode;
+    for (int i = 0; i < cutree::kMaxQps; i++) {
+        const int qp = qps[i < nb_qps ? i : 0];
+        p.lambda[i] = lambdas ? lambdas[i < nb_qps ? i : 0] : pnn_hm_intra_lambda(qp);
+        p.bits[i] = cutree::qp_bits(qp);
+    }
+    p.cu_depths = d_cu_depths ? d_cu_depths : (uint8_t*)d_workspace;          // the maps exist for the chaining either way
+    p.part_nxn = d_part_nxn; p.node_costs = d_node_costs; p.ctu_costs = d_ctu_costs; p.ctu_dists = d_ctu_dists;
+    p.ctu_rates = d_ctu_rates; p.selected = d_selected; p.selected_pnn = d_selected_pnn;
+    const CuTreePictureGrid g{n_images, ctu_rows, ctu_cols, 0, d_image_dists, d_image_rates};
+    if (d_selected) HIPCHK(c, hipMemsetAsync(d_selected, 0, (size_t)nb_qps * cutree::kWidths * 4, s));
+    if (d_selected_pnn) HIPCHK(c, hipMemsetAsync(d_selected_pnn, 0, (size_t)nb_qps * cutree::kWidths * 4, s));
+    if (d_image_dists) HIPCHK(c, hipMemsetAsync(d_image_dists, 0, (size_t)nb_qps * n_images * 8, s));
+    if (d_image_rates) HIPCHK(c, hipMemsetAsync(d_image_rates, 0, (size_t)nb_qps * n_images * 8, s));
+    HIPCHK(c, launch_cu_tree_picture(p, g, s));
+    c->stat_launches += ctu_rows + ctu_cols - 1;
+    return PNN_OK;
+}
+
+// One width's leaves of the coding tree from the device outputs of a second pass over the width's blocks: one launch, a copy (the tree
+// reads rate + side rate as one array, and leaf buffers of the caller's own outlive the score call's output buffer).
+int pnn_cu_tree_leaves_device(pnn_ctx* c, int width, int n, int nb_qps, const uint32_t* d_sses, const uint64_t* d_rates,
+                              const uint64_t* d_side_rates, const uint8_t* d_modes, uint32_t* d_dist, uint64_t* d_rate, uint8_t* d_mode,
+                              void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    int rc;
+    if ((rc = check_width(c, width))) return rc;
+    const int per_ctu = (64 / width) * (64 / width);
+    if (n < 1 || n % per_ctu) return fail(c, PNN_E_ARG, "%d blocks of width %d: not whole CTUs of %d", n, width, per_ctu);
+    if (nb_qps < 1 || nb_qps > cutree::kMaxQps) return fail(c, PNN_E_ARG, "the QPs are not 1 to %d", cutree::kMaxQps);
+    if (!d_sses || !d_rates || !d_side_rates || !d_modes || !d_dist || !d_rate || !d_mode) return fail(c, PNN_E_ARG, "an array is NULL");
+    if ((uintptr_t)d_sses % 4 || (uintptr_t)d_dist % 4 || (uintptr_t)d_rates % 8 || (uintptr_t)d_side_rates % 8 || (uintptr_t)d_rate % 8)
+        return fail(c, PNN_E_ARG, "an array is not aligned to its element");
+    HIPCHK(c, hipSetDevice(c->device));
+    reset_stats(c);
+    CuTreeLeavesParams p;
+    p.sses = d_sses; p.rates = d_rates; p.side_rates = d_side_rates; p.modes = d_modes; p.total = (long)nb_qps * n;
+    p.dist = d_dist; p.rate = d_rate; p.mode = d_mode;
+    HIPCHK(c, launch_cu_tree_leaves(p, (hipStream_t)stream));
+    c->stat_launches++;
+    return PNN_OK;
+}
+
 int pnn_score_f32_device(pnn_ctx* c, int width, const float* d_pred_f32, const uint8_t* d_channels, int images, int height,
                          int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, uint8_t* d_pred_u8,
                          uint32_t* d_sse, void* stream)

@@ -443,6 +443,21 @@ struct CuTreeParams {
     uint32_t* selected; uint32_t* selected_pnn;
 };
 hipError_t launch_cu_tree(const CuTreeParams& p, hipStream_t s);
+// The picture form: n_ctu = n_images ctu_rows ctu_cols CTUs in (image, CTU row, CTU column) order, left / above
+// of p NOT read: a CTU's edges are gathered from the maps p.cu_depths holds of the CTU left of it and of the one above it in the same
+// image (cutree::edge_from_maps), so p.cu_depths is REQUIRED (the entry points it into the caller's workspace where the caller asked
+// for no map).  launch_cu_tree_picture makes ctu_rows + ctu_cols - 1 launches on s, one per anti-diagonal r + c, each of (CTUs of the
+// diagonal x n_images, nb_qps) wavefronts: stream order makes the earlier diagonals' maps visible, and no workgroup waits on another.
+// image_dists / image_rates NULL or uint64 [nb_qps][n_images], ZEROED by the caller on the stream: the roots' D and F are added.
+struct CuTreePictureGrid { int n_images, ctu_rows, ctu_cols, diagonal; uint64_t* image_dists; uint64_t* image_rates; };
+hipError_t launch_cu_tree_picture(const CuTreeParams& p, const CuTreePictureGrid& g, hipStream_t s);
+// The leaves of one width from a second pass's outputs, each [total] = [nb_qps][n]: dist = sses, rate = rates + side_rates, mode =
+// modes.  A copy, four elements per lane; vector loads and stores where every array is aligned to 16 bytes (modes to 4), else scalar.
+struct CuTreeLeavesParams {
+    const uint32_t* sses; const uint64_t* rates; const uint64_t* side_rates; const uint8_t* modes; long total;
+    uint32_t* dist; uint64_t* rate; uint8_t* mode;
+};
+hipError_t launch_cu_tree_leaves(const CuTreeLeavesParams& p, hipStream_t s);
 
 // IPFCN-S, the evaluator's second competitor (pnn_ipfcns.hip).  Blocks b0 .. b0 + nb - 1 of images x positions (image-major): the
 // two groups of 8 reference lines at line origin (rows[pos], cols[pos]) of uint8 picture `img` [H][W] -- rows [r, r + 8) x columns

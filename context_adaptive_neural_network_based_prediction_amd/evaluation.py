@@ -484,11 +484,17 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
                  keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False,
                  transform_rdoq=False, rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False,
-                 transform_skip='off', rd_pass_transform_skip=False):
+                 transform_skip='off', rd_pass_transform_skip=False, _tree_leaves=None):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer.  Every option is an argument
-    of the one entry its call has (the smoothing; the mode pointer, the rate pointer and the flag), 0 or NULL when off."""
+    of the one entry its call has (the smoothing; the mode pointer, the rate pointer and the flag), 0 or NULL when off.
+    _tree_leaves (private to coding_tree_from_pictures; None: nothing changes, call for call): {'dist', 'rate', 'mode': torch tensors
+    on the predictor's device of [nb_qps, n] uint32 / uint64 / uint8 elements, 'keep': bool}.  Behind the second pass of each mask one
+    more call, pnn_cu_tree_leaves_device, writes the width's leaves of the coding tree into them from the outputs the pass left on the
+    device; with 'keep' False the mask's results are then neither downloaded nor returned (its value is None)."""
     w = width_target
+    if _tree_leaves is not None and not (rd_pass and rd_pass_signalling):
+        raise ValueError('`_tree_leaves` is given without the second pass with signalling.')
     if rd_pass_signalling and not rd_pass:
         raise ValueError('`rd_pass_signalling` is set without `rd_pass`.')
     if rd_pass_neighbour_modes is not None and not rd_pass_signalling:
@@ -593,6 +599,19 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                 _lib.check(L.pnn_rd_pass_mode_stats_device(
                     predictor.ctx, ptr['rd_pass_candidates'], signalling, intraprediction.rd_pass_slot_count(w, signalling, rd_pass_codec),
                     ptr['rd_pass_modes'], n, nb_qps, ptr['rd_pass_mode_stats'], stream), predictor.ctx)
+            if _tree_leaves is not None:                  # the coding tree's leaves of this width, device to device
+                _lib.check(L.pnn_cu_tree_leaves_device(
+                    predictor.ctx, w, n, nb_qps, ptr['rd_pass_sses'], ptr['rd_pass_rates'], ptr['rd_pass_side_rates'], ptr['rd_pass_modes'],
+                    _tree_leaves['dist'].data_ptr(), _tree_leaves['rate'].data_ptr(), _tree_leaves['mode'].data_ptr(), stream), predictor.ctx)
+        if _tree_leaves is not None and not _tree_leaves['keep']:
+            # No download, hence NO wait for the stream: this function returns, and d_out, d_scratch, d_planes and the positions go
+            # back to torch's caching allocator, while its launches may still be queued.  That is safe only because the allocator
+            # is stream-ordered and everything that follows -- the next width's calls, the tree, its download -- is issued on the
+            # SAME torch current stream of this device.  coding_tree_from_pictures must therefore run under one stream context from
+            # its first width to its download; a caller that switched torch.cuda.stream between widths would break this.  (c_qps
+            # and the other host arguments are read by the entries before they return.)
+            results[mask] = None
+            continue
         nb_down = (end['targets'] if first else begin['targets']) if keep_predictions else begin['predictions_pnn']
         out = d_out[:nb_down].cpu().numpy()               # (waits for the stream)
         view = {name: out[begin[name]:end[name]].view(dtype).reshape(shape) for name, dtype, shape in sections if end[name] <= out.size}
@@ -658,3 +677,65 @@ def coding_tree_from_scores(scores_by_width, left_depths=None, above_depths=None
                      d['rd_pass_modes'])
     pnn_mode = intraprediction.SUBSTITUTED_MODE if intraprediction.CODECS[codec] else intraprediction.NB_MODES
     return intraprediction.cu_tree(leaves, qps, None, left_depths, above_depths, pnn_mode, device)
+
+
+def coding_tree_from_pictures(channels_uint8, predictors_by_width, means_by_width, row_1st, col_1st, ctu_rows, ctu_cols, qps, codec='switch',
+                              pairs=False, keep_scores=False, reference_smoothing=0, transform_rate=False, transform_sign_hiding=False,
+                              transform_rdoq=False, rd_pass_transform_skip=False):
+    """From pictures to the pictures' coding tree (include/pnn_hip.h, "the coding tree over a picture"; intraprediction.cu_tree_picture)
+    without the leaves leaving the device: what a picture costs with the PNN in HM's search, per image and QP.
+    channels_uint8 [images, H, W, 1], or [images, H, W, 2] with pairs=True (score_masks_from_picture_pairs' planes); predictors_by_width
+    / means_by_width: {4: .., 8: .., 16: .., 32: .., 64: ..}, a PredictionNeuralNetwork and its training mean per width, all on one
+    device; (row_1st, col_1st): the top-left sample of the first CTU of a grid of ctu_rows x ctu_cols whole CTUs, the same in every
+    image -- at least 64 from the picture's top and left, and far enough from its bottom and right, for the 64-wide contexts; qps:
+    1 to 8 integers in [0, 51]; codec 'switch' or 'substitution'.  The other options are score_masks_from_pictures', given to every
+    width (rd_pass_transform_skip to width 4 alone, where it exists).  Everything is checked before anything touches the GPU.
+    Per width the calls score_masks_* make for mask (0, 0) with first_pass, rd_pass and rd_pass_signalling on the positions
+    ctu_block_positions(w, *ctu_grid(..)), then pnn_cu_tree_leaves_device from the second pass's device outputs into leaf buffers
+    kept here; then ONE pnn_cu_tree_picture_device call and ONE download, of the tree's outputs.  No neighbour modes are given to the
+    second passes (rd_pass_neighbour_modes None).  Returns cu_tree_picture's dictionary -- the mode that stands for the PNN is 35
+    under the switch codec, 18 under substitution; with keep_scores=True (dictionary, {w: mask (0, 0)'s dictionary of the width}),
+    the five also downloaded as score_masks_* would (without it nothing but the tree's outputs is).  Everything is issued on the
+    torch current stream of the predictors' device as it is when the call begins; nothing waits for it before the one download."""
+    if not isinstance(predictors_by_width, dict) or sorted(predictors_by_width) != list(intraprediction.WIDTHS):
+        raise ValueError('`predictors_by_width` is not a dictionary with the keys 4, 8, 16, 32 and 64.')
+    if not isinstance(means_by_width, dict) or sorted(means_by_width) != list(intraprediction.WIDTHS):
+        raise ValueError('`means_by_width` is not a dictionary with the keys 4, 8, 16, 32 and 64.')
+    if any(p is None for p in predictors_by_width.values()):
+        raise ValueError('a predictor is None.')
+    devices = {predictors_by_width[w].device for w in intraprediction.WIDTHS}
+    if len(devices) != 1:
+        raise ValueError('the five predictors are not on one device.')
+    if codec not in intraprediction.CODECS:
+        raise ValueError("`codec` is not 'switch' or 'substitution'.")
+    qps = intraprediction._check_qps(qps)
+    if not isinstance(channels_uint8, np.ndarray) or channels_uint8.ndim != 4 or channels_uint8.shape[3] != (2 if pairs else 1):
+        raise ValueError('`channels_uint8` is not an array [images, H, W, %d].' % (2 if pairs else 1))
+    n_images, height, width = channels_uint8.shape[:3]
+    ctu_rows, ctu_cols, n_images = intraprediction._check_ctu_grid(ctu_rows, ctu_cols, n_images)
+    ctu_row_1sts, ctu_col_1sts = intraprediction.ctu_grid(row_1st, col_1st, ctu_rows, ctu_cols)
+    positions = {w: intraprediction.ctu_block_positions(w, ctu_row_1sts, ctu_col_1sts) for w in intraprediction.WIDTHS}
+    for w in intraprediction.WIDTHS:
+        if positions[w][0].max() + 3 * w > height or positions[w][1].max() + 3 * w > width:
+            raise ValueError('the grid with its contexts of width %d does not lie inside the picture.' % w)
+    device = devices.pop()
+    nq, per_image = len(qps), ctu_rows * ctu_cols
+
+    import torch
+    dev = torch.device('cuda', device)
+    nb_planes = 2 if pairs else 1
+    held, scores = {}, {}
+    for w in intraprediction.WIDTHS:
+        n = n_images * per_image * (intraprediction.CTU_WIDTH // w) ** 2
+        held[w] = {'dist': torch.empty(nq * n, dtype=torch.int32, device=dev), 'rate': torch.empty(nq * n, dtype=torch.int64, device=dev),
+                   'mode': torch.empty(nq * n, dtype=torch.uint8, device=dev), 'keep': bool(keep_scores)}
+        result = _score_masks(channels_uint8, nb_planes, w, positions[w][0], positions[w][1], predictors_by_width[w], means_by_width[w],
+                              ((0, 0),), None, False, True, reference_smoothing, qps, transform_rate, transform_sign_hiding, True,
+                              transform_rdoq, True, None, codec, False, 'off', bool(rd_pass_transform_skip) and w == 4, _tree_leaves=held[w])
+        scores[w] = result[(0, 0)]
+    pnn_mode = intraprediction.SUBSTITUTED_MODE if intraprediction.CODECS[codec] else intraprediction.NB_MODES
+    wanted = [True] * len(intraprediction.CU_TREE_PICTURE_OUTPUTS)
+    leaf_pointers = [[held[w][name].data_ptr() for w in intraprediction.WIDTHS] for name in ('dist', 'rate', 'mode')]
+    outs = intraprediction._cu_tree_picture_device(device, leaf_pointers, True, qps, None, n_images, ctu_rows, ctu_cols, pnn_mode, wanted)
+    tree = intraprediction._cu_tree_picture_dictionary(outs, wanted, True, qps, None, n_images, ctu_rows, ctu_cols)
+    return (tree, scores) if keep_scores else tree

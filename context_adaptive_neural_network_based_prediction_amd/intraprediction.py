@@ -972,7 +972,12 @@ def cu_tree(leaves, qps, lambdas=None, left_depths=None, above_depths=None, pnn_
                                             ctypes.c_void_p(stream.cuda_stream)), _context(device))
         outs = [o.cpu().numpy()[:int(np.prod(shape)) * np.dtype(dtype).itemsize].view(dtype).reshape(shape)      # (waits for the stream)
                 for o, (_, dtype), shape in zip(d_outs, CU_TREE_OUTPUTS, shapes)]
-    result = {name: out for (name, _), out, want in zip(CU_TREE_OUTPUTS, outs, wanted) if want}
+    return _cu_tree_dictionary(CU_TREE_OUTPUTS, outs, wanted, with_modes, n_ctu, qps, c_lambdas)
+
+
+def _cu_tree_dictionary(outputs, outs, wanted, with_modes, n_ctu, qps, c_lambdas):
+    """The dictionary cu_tree and cu_tree_picture return, from the entry's outputs: the derived shares and the lambdas used join them."""
+    result = {name: out for (name, _), out, want in zip(outputs, outs, wanted) if want}
     selected = result['selected'].astype(np.float64)
     if with_modes:
         with np.errstate(invalid='ignore', divide='ignore'):
@@ -980,6 +985,116 @@ def cu_tree(leaves, qps, lambdas=None, left_depths=None, above_depths=None, pnn_
     result['area_share'] = selected * np.array([w * w for w in WIDTHS], np.float64) / float(n_ctu * CTU_WIDTH * CTU_WIDTH)
     result['lambdas'] = np.array([hm_intra_lambda(q) for q in qps]) if c_lambdas is None else np.array(list(c_lambdas))
     return result
+
+
+CU_TREE_PICTURE_OUTPUTS = CU_TREE_OUTPUTS + (('image_dists', np.uint64), ('image_rates', np.uint64))
+
+
+def cu_tree_picture_shapes(nb_qps, n_images, ctu_rows, ctu_cols):
+    """The shapes of CU_TREE_PICTURE_OUTPUTS, in the entries' order."""
+    return cu_tree_shapes(nb_qps, n_images * ctu_rows * ctu_cols) + ((nb_qps, n_images),) * 2
+
+
+def _check_ctu_grid(ctu_rows, ctu_cols, n_images=1):
+    for value, name in ((ctu_rows, 'ctu_rows'), (ctu_cols, 'ctu_cols'), (n_images, 'n_images')):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1:
+            raise ValueError('`%s` is not an integer >= 1.' % name)
+    if int(n_images) * int(ctu_rows) * int(ctu_cols) > 2 ** 31 - 1:
+        raise ValueError('the CTUs of the pictures do not fit an int.')
+    return int(ctu_rows), int(ctu_cols), int(n_images)
+
+
+def ctu_grid(row_1st, col_1st, ctu_rows, ctu_cols):
+    """The top-left samples of the ctu_rows x ctu_cols CTUs of a grid whose first CTU starts at sample (row_1st, col_1st), in raster
+    order -- the order of cu_tree_picture's CTUs inside an image -- as ctu_block_positions takes them.  Returns (ctu_row_1sts,
+    ctu_col_1sts), int64 [ctu_rows * ctu_cols]."""
+    ctu_rows, ctu_cols, _ = _check_ctu_grid(ctu_rows, ctu_cols)
+    for value, name in ((row_1st, 'row_1st'), (col_1st, 'col_1st')):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 0:
+            raise ValueError('`%s` is not an integer >= 0.' % name)
+    return (int(row_1st) + CTU_WIDTH * np.repeat(np.arange(ctu_rows, dtype=np.int64), ctu_cols),
+            int(col_1st) + CTU_WIDTH * np.tile(np.arange(ctu_cols, dtype=np.int64), ctu_rows))
+
+
+def _cu_tree_picture_device(device, leaf_pointers, with_modes, qps, c_lambdas, n_images, ctu_rows, ctu_cols, pnn_mode, wanted):
+    """pnn_cu_tree_picture_device on leaves that lie on `device` -- leaf_pointers: three lists (dist, rate, mode) of five device
+    addresses -- with every output in ONE buffer and one download of it.  Returns CU_TREE_PICTURE_OUTPUTS as numpy arrays."""
+    import torch
+    dev = torch.device("cuda", device)
+    nq = len(qps)
+    L = _lib.lib()
+    shapes = cu_tree_picture_shapes(nq, n_images, ctu_rows, ctu_cols)
+    begin, offset = [], 0
+    for (_, dtype), shape in zip(CU_TREE_PICTURE_OUTPUTS, shapes):            # each output at a multiple of 8 bytes
+        begin.append(offset)
+        offset += (int(np.prod(shape)) * np.dtype(dtype).itemsize + 7) // 8 * 8
+    nb_workspace = L.pnn_cu_tree_picture_workspace_bytes(nq, n_images, ctu_rows, ctu_cols)
+    pointers = ctypes.c_void_p * len(WIDTHS)
+    with torch.cuda.device(dev):
+        d_out = torch.zeros(offset, dtype=torch.uint8, device=dev)
+        d_workspace = torch.empty(nb_workspace, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _lib.check(L.pnn_cu_tree_picture_device(
+            _context(device), (ctypes.c_int * nq)(*qps), nq, c_lambdas, n_images, ctu_rows, ctu_cols, pointers(*leaf_pointers[0]),
+            pointers(*leaf_pointers[1]), pointers(*leaf_pointers[2]) if with_modes else None, int(pnn_mode),
+            *[d_out.data_ptr() + b if want else None for b, want in zip(begin, wanted)], d_workspace.data_ptr(), nb_workspace,
+            ctypes.c_void_p(stream.cuda_stream)), _context(device))
+        out = d_out.cpu().numpy()                         # (waits for the stream)
+    return [out[b:b + int(np.prod(shape)) * np.dtype(dtype).itemsize].view(dtype).reshape(shape).copy()
+            for b, (_, dtype), shape in zip(begin, CU_TREE_PICTURE_OUTPUTS, shapes)]
+
+
+def _cu_tree_picture_dictionary(outs, wanted, with_modes, qps, c_lambdas, n_images, ctu_rows, ctu_cols):
+    """cu_tree_picture's dictionary from the entry's ten outputs"""
+    result = _cu_tree_dictionary(CU_TREE_PICTURE_OUTPUTS, outs, wanted, with_modes, n_images * ctu_rows * ctu_cols, qps, c_lambdas)
+    samples = float(ctu_rows * ctu_cols * CTU_WIDTH * CTU_WIDTH)
+    result['image_rate_bits'] = result.pop('image_rates').astype(np.float64) / 32768.
+    result['psnr_images'] = 10. * np.log10(255. ** 2 / (result['image_dists'].astype(np.float64) / samples + 1.e-6))
+    result['bits_per_pixel_images'] = result['image_rate_bits'] / samples
+    return result
+
+
+def cu_tree_picture(leaves, qps, n_images, ctu_rows, ctu_cols, lambdas=None, pnn_mode=35, device=None):
+    """The coding tree over whole pictures as include/pnn_hip.h defines it ("the coding tree over a picture"; pnn_cu_tree_picture_host
+    / _device): cu_tree with every CTU's edges taken from the final maps of the CTU left of it and the CTU above it in the same
+    image and QP, as HM reads them inside one slice, instead of from the caller.
+    leaves, qps, lambdas, pnn_mode, device: as for cu_tree; the blocks of each width in (image, CTU row, CTU column, z-order) order --
+    what a second pass over ctu_block_positions(w, *ctu_grid(..)) returns --, n_images * ctu_rows * ctu_cols CTUs in all.
+    Returns cu_tree's dictionary and 'image_dists': uint64 [nb_qps, n_images] (the SSE of an image's CTUs under the chosen
+    partitions), 'image_rate_bits': float64 [nb_qps, n_images] (their rate in bits), 'psnr_images': float64 (10 log10(255^2 / (SSE /
+    (ctu_rows ctu_cols 4096) + 1e-6)), as psnrs_from_sses), 'bits_per_pixel_images': float64 (the bits over the same samples)."""
+    qps = _check_qps(qps)
+    nq = len(qps)
+    ctu_rows, ctu_cols, n_images = _check_ctu_grid(ctu_rows, ctu_cols, n_images)
+    if not isinstance(leaves, dict) or sorted(leaves) != list(WIDTHS):
+        raise ValueError('`leaves` is not a dictionary with the keys 4, 8, 16, 32 and 64.')
+    if isinstance(pnn_mode, (bool, np.bool_)) or not isinstance(pnn_mode, (int, np.integer)) or not 0 <= pnn_mode <= 255:
+        raise ValueError('`pnn_mode` is not an integer in [0, 255].')
+    arrays = [_cu_tree_leaf(leaves[w], w, nq) for w in WIDTHS]
+    n_ctu = n_images * ctu_rows * ctu_cols
+    if any(a[0].shape[1] != n_ctu * (CTU_WIDTH // w) ** 2 for a, w in zip(arrays, WIDTHS)):
+        raise ValueError('the leaves do not hold the blocks of n_images * ctu_rows * ctu_cols CTUs: n_ctu * (64 / w)^2 per width.')
+    with_modes = all(a[2] is not None for a in arrays)
+    c_lambdas = _check_lambdas(lambdas, nq)
+    shapes = cu_tree_picture_shapes(nq, n_images, ctu_rows, ctu_cols)
+    wanted = [with_modes or name != 'selected_pnn' for name, _ in CU_TREE_PICTURE_OUTPUTS]
+    if device is None:
+        pointers = ctypes.c_void_p * len(WIDTHS)
+        outs = [np.zeros(shape, dtype) for (_, dtype), shape in zip(CU_TREE_PICTURE_OUTPUTS, shapes)]
+        rc = _lib.lib().pnn_cu_tree_picture_host(
+            (ctypes.c_int * nq)(*qps), nq, c_lambdas, n_images, ctu_rows, ctu_cols, pointers(*[a[0].ctypes.data for a in arrays]),
+            pointers(*[a[1].ctypes.data for a in arrays]), pointers(*[a[2].ctypes.data for a in arrays]) if with_modes else None,
+            int(pnn_mode), *[o.ctypes.data if want else None for o, want in zip(outs, wanted)])
+        if rc != 0:
+            raise ValueError('pnn_cu_tree_picture_host refused the arguments.')
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        d_in = [[None if a is None else torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32
+                                                         else a).to(dev) for a in triple] for triple in arrays]
+        leaf_pointers = [[None if t[k] is None else t[k].data_ptr() for t in d_in] for k in range(3)]
+        outs = _cu_tree_picture_device(device, leaf_pointers, with_modes, qps, c_lambdas, n_images, ctu_rows, ctu_cols, pnn_mode, wanted)
+    return _cu_tree_picture_dictionary(outs, wanted, with_modes, qps, c_lambdas, n_images, ctu_rows, ctu_cols)
 
 
 def cu_tree_bins(qp):

@@ -1042,7 +1042,8 @@ int pnn_rd_pass_tskip_picture_pairs_device(pnn_ctx* ctx, int width, const uint8_
  *     > d], "left" the CU that covers the sample left of the node's top-left sample, "above" the one over it.  Inside the CTU the depth
  *     comes from an 8 x 8 map of minimum-CU cells into which a subtree writes its final depth when its root is decided; outside from
  *     left_depths / above_depths, uint8 [nb_qps][n_ctu][8], one cell per 8 samples along the edge (top to bottom, left to right),
- *     0 .. 3 or 255 = not available; NULL: nothing available.  No CTU's result is chained into the next CTU's edge.
+ *     0 .. 3 or 255 = not available; NULL: nothing available.  No CTU's result is chained into the next CTU's edge here: that is
+ *     "the coding tree over a picture" below.
  *   The three contexts start from the state an I slice of the QP begins with (initial values 139, 141, 157; part size 184).
  *   Where this differs from the tree (whole bits per CU, the counter's carried fraction, running contexts): DESIGN.md section 5q.
  * Outputs, each NULL or: cu_depths uint8 [nb_qps][n_ctu][64], the final map; part_nxn uint8 [nb_qps][n_ctu][64], 1 where the cell is
@@ -1070,6 +1071,47 @@ int pnn_cu_tree_device(pnn_ctx* ctx, const int* qps, int nb_qps, const double* l
                        double* d_ctu_costs, uint64_t* d_ctu_dists, uint64_t* d_ctu_rates, uint32_t* d_selected, uint32_t* d_selected_pnn,
                        void* stream);
 int pnn_cu_tree_bins_host(int qp, uint32_t* out);
+
+/* ---- the coding tree over a picture: the pass above with every CTU's edges taken from its neighbours' results.
+ *   Grid.  Per image the CTUs form a grid of ctu_rows x ctu_cols; every per-CTU array is in (image, CTU row, CTU column) order, so
+ *     n_ctu = n_images ctu_rows ctu_cols.  Leaves, bins, costs, tie rules, z-order and outputs are those of the coding tree above.
+ *   Edges, the only new rule.  left[y] of the CTU at (r, c) is the FINAL depth of cell (x = 7, y) of the CTU at (r, c - 1) of the same
+ *     image and QP, 255 (not available) at c = 0; above[x] is the final depth of cell (x, y = 7) of the CTU at (r - 1, c), 255 at
+ *     r = 0.  This is what TComDataCU::getPULeft / getPUAbove with their default arguments answer inside one slice and tile, which is
+ *     what the reference's configurations code.  Nothing crosses an image or a QP.
+ *   Order.  HM decides CTUs in raster order; only the CTU left of and the CTU above a CTU are read, so the CTUs of one anti-diagonal
+ *     r + c do not depend on each other.
+ *   The coding tree's other departures from HM stay: every bin starts from the state an I slice of the QP begins with (no running
+ *     contexts), fractions are summed exactly and shifted once per comparison (not HM's whole bits per CU with the counter's carried
+ *     fraction).  Whole CTUs only: no partial CTU at a picture's border.
+ * Outputs: the eight of pnn_cu_tree_host, and image_dists, image_rates, each NULL or uint64 [nb_qps][n_images]: the sums of the roots'
+ * chosen D and F (ctu_dists, ctu_rates) over the image's CTUs.
+ * PNN_E_ARG, before anything is written: those of pnn_cu_tree_host without the edges; n_images, ctu_rows or ctu_cols < 1; n_ctu not
+ * fitting an int.
+ * pnn_cu_tree_picture_device: the same on leaves in device memory, bit-identical; dists, rates and modes are HOST arrays of five device
+ * pointers.  The depth maps exist for the chaining whether or not cu_depths is given: without it they live in d_workspace, of
+ * pnn_cu_tree_picture_workspace_bytes bytes (nb_qps n_ctu 64; 0 for a grid the entry refuses) and aligned to 16 bytes, which is
+ * required either way.  Asynchronous on `stream`, no allocation on the device, nothing read back: the two count outputs and the two
+ * sums are zeroed on the stream, then ctu_rows + ctu_cols - 1 launches, one per anti-diagonal, each of (CTUs of the diagonal x
+ * n_images, nb_qps) wavefronts; stream order makes the earlier maps visible and no workgroup waits on another.  Also PNN_E_ARG,
+ * before any launch and with outputs and workspace untouched: an array not aligned to its element, a workspace that is NULL,
+ * misaligned or too small.
+ * pnn_cu_tree_leaves_device: the leaves of ONE width from the device outputs of a second pass over that width's n blocks (n a positive
+ * multiple of (64 / width)^2), each [nb_qps][n]: dist = sses, rate = rates + side_rates, mode = modes.  One launch, a copy.  PNN_E_ARG
+ * before it: a width not of the five, such an n, nb_qps outside 1 .. 8, a NULL array, one not aligned to its element. */
+int pnn_cu_tree_picture_host(const int* qps, int nb_qps, const double* lambdas, int n_images, int ctu_rows, int ctu_cols,
+                             const uint32_t* const* dists, const uint64_t* const* rates, const uint8_t* const* modes, int pnn_mode,
+                             uint8_t* cu_depths, uint8_t* part_nxn, double* node_costs, double* ctu_costs, uint64_t* ctu_dists,
+                             uint64_t* ctu_rates, uint32_t* selected, uint32_t* selected_pnn, uint64_t* image_dists, uint64_t* image_rates);
+size_t pnn_cu_tree_picture_workspace_bytes(int nb_qps, int n_images, int ctu_rows, int ctu_cols);
+int pnn_cu_tree_picture_device(pnn_ctx* ctx, const int* qps, int nb_qps, const double* lambdas, int n_images, int ctu_rows, int ctu_cols,
+                               const uint32_t* const* d_dists, const uint64_t* const* d_rates, const uint8_t* const* d_modes, int pnn_mode,
+                               uint8_t* d_cu_depths, uint8_t* d_part_nxn, double* d_node_costs, double* d_ctu_costs, uint64_t* d_ctu_dists,
+                               uint64_t* d_ctu_rates, uint32_t* d_selected, uint32_t* d_selected_pnn, uint64_t* d_image_dists,
+                               uint64_t* d_image_rates, void* d_workspace, size_t workspace_bytes, void* stream);
+int pnn_cu_tree_leaves_device(pnn_ctx* ctx, int width, int n, int nb_qps, const uint32_t* d_sses, const uint64_t* d_rates,
+                              const uint64_t* d_side_rates, const uint8_t* d_modes, uint32_t* d_dist, uint64_t* d_rate, uint8_t* d_mode,
+                              void* stream);
 
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */

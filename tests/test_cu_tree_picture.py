@@ -1,0 +1,246 @@
+"""The coding tree over whole pictures on the CPU (include/pnn_hip.h, "the coding tree over a picture"): the host
+twin pnn_cu_tree_picture_host against the existing pnn_cu_tree_host called CTU by CTU with edges cut from its own maps
+(tests/cu_tree_picture_cases.py), the conditions that keep the seeded cases from being vacuous, the known answers, every refusal,
+ctu_grid against a brute-force loop and the pinned workspace size."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from context_adaptive_neural_network_based_prediction_amd import _lib
+from context_adaptive_neural_network_based_prediction_amd import intraprediction as ip
+from tests import cu_tree_cases as cc
+from tests import cu_tree_picture_cases as pc
+
+WIDTHS = pc.WIDTHS
+POINTERS = ctypes.c_void_p * 5
+NAMES = [name for name, _ in ip.CU_TREE_PICTURE_OUTPUTS]
+
+
+@pytest.fixture(scope="module")
+def yardsticks():
+    """The yardstick's answer to every case, computed once"""
+    return {case[0]: pc.yardstick(pc.case_leaves(case), case[4], case[1], case[2], case[3], case[5]) for case in pc.CASES}
+
+
+def raw_host_call(leaves, qps, n_images, rows, cols, lambdas=None, pnn_mode=35, outputs=range(10), nq=None, drop=None, modes=True):
+    """pnn_cu_tree_picture_host with the outputs filled with 7 first; `drop` = (0 dists / 1 rates / 2 modes, width index or None)"""
+    nq_arrays = len(qps)
+    n_ctu = leaves[64][0].shape[1]
+    tables = [[leaves[w][k].ctypes.data if leaves[w][k] is not None else None for w in WIDTHS] for k in range(3)]
+    if drop is not None and drop[1] is not None:
+        tables[drop[0]][drop[1]] = None
+    tables = [None if (drop is not None and drop[0] == k and drop[1] is None) or (k == 2 and not modes) else POINTERS(*t)
+              for k, t in enumerate(tables)]
+    shapes = ip.cu_tree_shapes(nq_arrays, n_ctu) + ((nq_arrays, max(n_images, 1)),) * 2
+    outs = [np.full(shape, 7, dtype) for (_, dtype), shape in zip(ip.CU_TREE_PICTURE_OUTPUTS, shapes)]
+    c_lambdas = None if lambdas is None else (ctypes.c_double * len(lambdas))(*lambdas)
+    rc = _lib.lib().pnn_cu_tree_picture_host((ctypes.c_int * len(qps))(*qps), len(qps) if nq is None else nq, c_lambdas, n_images, rows, cols,
+                                             *tables, pnn_mode, *[o.ctypes.data if i in outputs else None for i, o in enumerate(outs)])
+    return rc, outs
+
+
+@pytest.mark.parametrize("case", pc.CASES, ids=[c[0] for c in pc.CASES])
+def test_picture_twin_equals_the_existing_entry_called_ctu_by_ctu(case, yardsticks):
+    name, n_images, rows, cols, qps, lambdas, modes = case
+    leaves, want = pc.case_leaves(case), yardsticks[name]
+    rc, outs = raw_host_call(leaves, qps, n_images, rows, cols, lambdas, outputs=range(10) if modes else [i for i in range(10) if i != 7],
+                             modes=modes)
+    assert rc == 0
+    for key, got in zip(NAMES, outs):
+        if key == "selected_pnn" and not modes:
+            assert (got == 7).all()
+            continue
+        assert got.dtype == want[key].dtype and got.shape == want[key].shape, (name, key)
+        assert got.tobytes() == want[key].tobytes(), "%s %s: %d differing values" % (name, key, (got != want[key]).sum())
+    nq = len(qps)
+    assert np.array_equal(outs[8], outs[4].reshape(nq, n_images, rows * cols).sum(axis=2, dtype=np.uint64))
+    assert np.array_equal(outs[9], outs[5].reshape(nq, n_images, rows * cols).sum(axis=2, dtype=np.uint64))
+    # the Python layer: the same bytes and the derived keys
+    got = ip.cu_tree_picture(cc.as_rd_pass_tuples(leaves), qps, n_images, rows, cols, lambdas)
+    for key in pc.TREE_KEYS + ("image_dists",):
+        if key in want:
+            assert got[key].tobytes() == want[key].tobytes(), (name, key)
+    assert ("selected_pnn" in got) == modes and ("frequency_selected_pnn" in got) == modes
+    samples = rows * cols * 4096.0
+    assert np.array_equal(got["image_rate_bits"], want["image_rates"].astype(np.float64) / 32768.0)
+    assert np.array_equal(got["psnr_images"], 10.0 * np.log10(255.0 ** 2 / (want["image_dists"].astype(np.float64) / samples + 1e-6)))
+    assert np.array_equal(got["bits_per_pixel_images"], got["image_rate_bits"] / samples)
+    assert got["psnr_images"].shape == (nq, n_images)
+    assert np.allclose(got["area_share"].sum(axis=1), 1.0)
+
+
+def test_one_ctu_equals_the_call_without_edges(yardsticks):
+    case = pc.CASES[0]
+    leaves = pc.case_leaves(case)
+    alone = ip.cu_tree(cc.as_rd_pass_tuples(leaves), case[4], case[5])
+    got = ip.cu_tree_picture(cc.as_rd_pass_tuples(leaves), case[4], 1, 1, 1, case[5])
+    for key in pc.TREE_KEYS + ("frequency_selected_pnn", "area_share", "lambdas"):
+        assert got[key].tobytes() == alone[key].tobytes(), key
+
+
+def test_rows_and_columns_are_not_exchangeable(yardsticks):
+    """The 2x3 leaves read as a 3x2 grid give another tree: a twin that mixed the two up would not pass the cases above"""
+    case = pc.CASES[5]
+    leaves = pc.case_leaves(case)
+    a = ip.cu_tree_picture(cc.as_rd_pass_tuples(leaves), case[4], 2, 2, 3, case[5])
+    b = ip.cu_tree_picture(cc.as_rd_pass_tuples(leaves), case[4], 2, 3, 2, case[5])
+    assert not np.array_equal(a["cu_depths"], b["cu_depths"])
+
+
+def test_the_cases_are_not_vacuous(yardsticks):
+    """The conditions, from the yardstick alone (the figures are written in tests/cu_tree_picture_cases.py)"""
+    differing, by_context, moved, area = pc.conditions()
+    print("differing %.4f, cross-CTU contexts %s, moved maps %s, area %s" % (differing, by_context, moved, area))
+    assert differing >= 0.05
+    assert (by_context >= 0.05).all(), by_context
+    assert len(moved) == sum(1 for case in pc.CASES if case[2] * case[3] > 1) and all(count >= 1 for count in moved.values()), moved
+    assert (area >= 0.05).all(), area
+
+
+def constant_ctus(dists, nq=1):
+    """{w: (dist, rate 0, None)} of len(dists) CTUs, CTU i with dists[i][w] at every block of width w"""
+    return {w: (np.concatenate([np.full((nq, (64 // w) ** 2), d[w], np.uint32) for d in dists], axis=1),
+                np.zeros((nq, len(dists) * (64 // w) ** 2), np.uint64), None) for w in WIDTHS}
+
+
+def run(leaves, qps, n_images, rows, cols, lambdas=None):
+    return ip.cu_tree_picture({w: (d, r, np.zeros_like(r), m) for w, (d, r, m) in leaves.items()}, qps, n_images, rows, cols, lambdas)
+
+
+@pytest.mark.parametrize("lambdas", [None, (0., 0.)])
+def test_all_zero_leaves_give_one_cu_everywhere(lambdas):
+    """D = F = 0: every CTU stays whole, so every edge holds depth 0, nothing is deeper than a node, and every context is 0"""
+    zero = dict.fromkeys(WIDTHS, 0)
+    got = run(constant_ctus([zero] * 12, 2), (22, 37), 2, 2, 3, lambdas)
+    assert (got["cu_depths"] == 0).all() and (got["part_nxn"] == 0).all()
+    assert np.array_equal(got["selected"], np.array([[0, 0, 0, 0, 12]] * 2, np.uint32))
+    assert (got["image_dists"] == 0).all() and got["image_dists"].shape == (2, 2)
+    for qi, qp in enumerate((22, 37)):                    # context 0 at every node: the unsplit cost is the bin of context 0, value 0
+        bins = ip.cu_tree_bins(qp)["split"]
+        lam = got["lambdas"][qi]
+        assert (got["node_costs"][qi, :, :21, 0] == lam * float(int(bins[0][0]) >> 15)).all()
+
+
+QP = 0
+DEEP = {4: 0, 8: 0, 16: 10 ** 6, 32: 10 ** 6, 64: 10 ** 6}          # every 8 x 8 CU kept: depth 3 in every cell
+
+
+def sensitive():
+    """A CTU whose root is decided by its neighbour, at lambda 1, with D = 0 below the root so that every node below it stays unsplit
+    (no distortion, fewer bits).  Alone every context is 0: the root costs D + (bin 0 of context 0) whole and (four such bins + bin 1
+    of context 0) split.  Beside a CTU of depth 3 along the whole shared edge the root and the two depth-1 children on that edge read
+    context 1: D + (bin 0 of context 1) whole and (two bins 0 of context 1 + two of context 0 + bin 1 of context 1) split.  A
+    deeper neighbour makes the CHILDREN's unsplit flags dearer by more than the root's: with D one above the alone tie the root
+    splits alone and stays whole beside the deep CTU.  The bins of QP 0 allow it (asserted)."""
+    bins = ip.cu_tree_bins(QP)["split"].astype(np.int64)
+    whole_alone, split_alone = int(bins[0][0]) >> 15, (4 * int(bins[0][0]) + int(bins[0][1])) >> 15
+    whole_beside, split_beside = int(bins[1][0]) >> 15, (2 * int(bins[1][0]) + 2 * int(bins[0][0]) + int(bins[1][1])) >> 15
+    d = split_alone - whole_alone + 1
+    assert d + whole_alone > split_alone and d + whole_beside <= split_beside, "the bins of QP %d do not allow the construction" % QP
+    return {4: 0, 8: 0, 16: 0, 32: 0, 64: d}
+
+
+@pytest.mark.parametrize("rows, cols", [(1, 2), (2, 1)])
+def test_a_deep_neighbour_flips_the_root_of_the_next_ctu(rows, cols):
+    alone = ip.cu_tree({w: (d, r, np.zeros_like(r), m) for w, (d, r, m) in constant_ctus([sensitive()]).items()}, (QP,), (1.,))
+    assert (alone["cu_depths"] == 1).all() and alone["node_costs"][0, 0, 0, 1] < alone["node_costs"][0, 0, 0, 0]
+    got = run(constant_ctus([DEEP, sensitive()]), (QP,), 1, rows, cols, (1.,))
+    assert (got["cu_depths"][0, 0] == 3).all()
+    assert (got["cu_depths"][0, 1] == 0).all() and not got["node_costs"][0, 1, 0, 1] < got["node_costs"][0, 1, 0, 0]
+    # the other way round the sensitive CTU comes first and sees nothing
+    got = run(constant_ctus([sensitive(), DEEP]), (QP,), 1, rows, cols, (1.,))
+    assert (got["cu_depths"][0, 0] == 1).all() and (got["cu_depths"][0, 1] == 3).all()
+
+
+@pytest.mark.parametrize("rows, cols", [(1, 2), (2, 1)])
+def test_an_images_last_ctu_does_not_reach_the_next_images_first(rows, cols):
+    got = run(constant_ctus([sensitive(), DEEP, sensitive(), DEEP]), (QP,), 2, rows, cols, (1.,))
+    assert (got["cu_depths"][0, 1] == 3).all() and (got["cu_depths"][0, 3] == 3).all()
+    assert (got["cu_depths"][0, 0] == 1).all()
+    assert (got["cu_depths"][0, 2] == 1).all(), "the second image's first CTU read the first image's last"
+    # the same four CTUs as ONE image of 1 x 4 or 4 x 1: now the third does read the second
+    one = run(constant_ctus([sensitive(), DEEP, sensitive(), DEEP]), (QP,), 1, 1 if rows == 1 else 4, 4 if rows == 1 else 1, (1.,))
+    assert (one["cu_depths"][0, 2] == 0).all()
+
+
+def test_a_qp_does_not_reach_the_next():
+    """Per QP the chain is its own: the picture at two QPs equals the two pictures at one QP each"""
+    case = pc.CASES[4]
+    leaves = pc.near_tie_leaves(12, (22, 37), None, 11)
+    both = ip.cu_tree_picture(cc.as_rd_pass_tuples(leaves), (22, 37), 2, 3, 2)
+    for qi, qp in enumerate((22, 37)):
+        single = ip.cu_tree_picture({w: tuple(None if a is None else a[qi:qi + 1] for a in t) for w, t in cc.as_rd_pass_tuples(leaves).items()},
+                                    (qp,), 2, 3, 2)
+        assert np.array_equal(both["cu_depths"][qi], single["cu_depths"][0]) and np.array_equal(both["image_dists"][qi], single["image_dists"][0])
+    assert case[2:4] == (3, 2)
+
+
+def zero_leaves(nq, n_ctu):
+    return {w: (np.zeros((nq, n_ctu * (64 // w) ** 2), np.uint32), np.zeros((nq, n_ctu * (64 // w) ** 2), np.uint64),
+                np.zeros((nq, n_ctu * (64 // w) ** 2), np.uint8)) for w in WIDTHS}
+
+
+REFUSALS = (dict(nq=0), dict(nq=9), dict(qps=(52,)), dict(qps=(-1,)), dict(n_images=0), dict(n_images=-2), dict(rows=0), dict(cols=0),
+            dict(cols=-1), dict(n_images=65536, rows=65536, cols=1), dict(n_images=1, rows=65536, cols=65536), dict(drop=(0, None)),
+            dict(drop=(1, None)), dict(drop=(0, 0)), dict(drop=(0, 4)), dict(drop=(1, 2)), dict(drop=(2, 3)), dict(lambdas=(float("nan"),)),
+            dict(lambdas=(float("inf"),)), dict(lambdas=(-0.5,)), dict(modes=False, outputs=(7,)), dict(modes=False, outputs=range(10)),
+            dict(outputs=()), dict(pnn_mode=256), dict(pnn_mode=-1))
+
+
+@pytest.mark.parametrize("arguments", REFUSALS, ids=[str(i) for i in range(len(REFUSALS))])
+def test_refusals(arguments):
+    base = dict(leaves=zero_leaves(1, 2), qps=(30,), n_images=1, rows=1, cols=2)
+    if arguments.get("nq") == 9:
+        base["qps"] = (30,) * 9
+        base["leaves"] = zero_leaves(9, 2)
+    base.update(arguments)
+    rc, outs = raw_host_call(**base)
+    assert rc == -1
+    assert all((o == 7).all() for o in outs), "a refused call wrote an output"
+
+
+def test_good_raw_calls_and_each_output_alone():
+    leaves = pc.near_tie_leaves(6, (22, 37), None, 5)
+    rc, all_outs = raw_host_call(leaves, (22, 37), 1, 2, 3)
+    assert rc == 0
+    for i in range(10):
+        rc, outs = raw_host_call(leaves, (22, 37), 1, 2, 3, outputs=(i,))
+        assert rc == 0 and outs[i].tobytes() == all_outs[i].tobytes(), NAMES[i]
+        assert all((o == 7).all() for k, o in enumerate(outs) if k != i)
+    assert raw_host_call(leaves, (22, 37), 1, 2, 3, modes=False, outputs=(8, 9))[0] == 0
+
+
+def test_python_layer_refuses_before_the_library():
+    leaves = cc.as_rd_pass_tuples(pc.near_tie_leaves(2, (30,), None, 1))
+    for arguments in (dict(n_images=0), dict(ctu_rows=0), dict(ctu_cols=2.0), dict(ctu_rows=True), dict(ctu_cols=3), dict(n_images=2),
+                      dict(qps=(22, 37)), dict(lambdas=(-1.,)), dict(pnn_mode=300)):
+        call = dict(leaves=leaves, qps=(30,), n_images=1, ctu_rows=1, ctu_cols=2)
+        call.update(arguments)
+        with pytest.raises(ValueError):
+            ip.cu_tree_picture(**call)
+    with pytest.raises(ValueError):
+        ip.cu_tree_picture({w: leaves[w] for w in (4, 8, 16, 32)}, (30,), 1, 1, 2)
+
+
+def test_ctu_grid_against_a_brute_force_loop():
+    for row_1st, col_1st, rows, cols in ((64, 64, 2, 2), (64, 128, 3, 2), (100, 72, 2, 3), (0, 0, 1, 1), (64, 64, 17, 30)):
+        got_rows, got_cols = ip.ctu_grid(row_1st, col_1st, rows, cols)
+        want = [(row_1st + 64 * r, col_1st + 64 * c) for r in range(rows) for c in range(cols)]
+        assert got_rows.dtype == np.int64 and got_cols.dtype == np.int64
+        assert list(zip(got_rows.tolist(), got_cols.tolist())) == want
+    # ready for ctu_block_positions: the 64-wide blocks' context corners are the CTUs' own corners minus 64
+    rows64, cols64 = ip.ctu_block_positions(64, *ip.ctu_grid(64, 128, 3, 2))
+    assert rows64.tolist() == [0, 0, 64, 64, 128, 128] and cols64.tolist() == [64, 128] * 3
+    for bad in ((64, 64, 0, 2), (64, 64, 2, -1), (-1, 64, 1, 1), (64, 6.5, 1, 1), (64, 64, 1.0, 1)):
+        with pytest.raises(ValueError):
+            ip.ctu_grid(*bad)
+
+
+def test_workspace_bytes_are_pinned():
+    size = _lib.lib().pnn_cu_tree_picture_workspace_bytes
+    assert size(1, 1, 1, 1) == 64
+    assert size(8, 2, 3, 2) == 8 * 12 * 64
+    assert size(4, 1, 17, 30) == 4 * 510 * 64
+    for refused in ((0, 1, 1, 1), (9, 1, 1, 1), (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 1, -1), (1, 65536, 65536, 1)):
+        assert size(*refused) == 0
