@@ -15,6 +15,14 @@ touches the CTU's left or top edge and a CTU lies beyond it:
     nodes that read a cross-CTU neighbour and get context 0, 1, 2:              15.8 %, 18.1 %, 6.7 %
     multi-CTU cases, (QP, CTU) maps that differ from the unchained decision:    1, 1, 5, 2, 14, 6 (in CASES' order)
     share of the selected area per width 4, 8, 16, 32, 64:                      15.7 %, 15.1 %, 15.0 %, 26.2 %, 28.0 %
+EXTRA_CASES (longer diagonals, one row, one column, three images) stand apart from these figures; their own floor and the seeds tried
+are written beside them.
+
+The evaluator's cases (tests/test_gpu_cu_tree_picture_evaluator.py) follow below: the 2 x 2 picture of one image, then EVALUATOR_CASES
+-- two images on a 1 x 2 and a 2 x 1 grid, and transform skip on the 2 x 2 grid -- with a yardstick built on the host image by image
+(host_leaves, tree_leaves_of_host, case_yardstick) and its floors (evaluator_floors: the edges count 2 / 2 / 6 of 8 (QP, CTU) pairs
+and 2.4 % / 3.6 % / 4.8 % of the nodes' contexts in A / B / the crossing; image 1 does not depend on image 0 and would if stacked; a
+transposition moves 1 (QP, CTU) pair in A and in B; the images differ; transform skip moves 2356 and 2383 width-4 leaf values).
 """
 import numpy as np
 
@@ -64,9 +72,22 @@ def near_tie_leaves(n_ctu, qps, lambdas=None, seed=SEED, modes=True, mu=MU, sigm
     return leaves
 
 
-def case_leaves(case, seed=SEED):
-    """{w: (dist, rate, modes or None)} of a case, in (image, CTU row, CTU column, z-order) order"""
+# The direct entry's further grids (tests/test_cu_tree_picture.py, tests/test_gpu_cu_tree_picture.py), kept apart from CASES: `conditions`
+# and the figures above are computed over CASES alone.  4x3: anti-diagonals of 1, 2, 3, 3, 2, 1 CTUs, three images; 1x5: every diagonal
+# holds one CTU and only left edges exist; 5x1: only above edges exist.
+EXTRA_CASES = (("4x3, three images, eight QPs, own lambdas", 3, 4, 3, EIGHT_QPS, OWN_LAMBDAS, True),
+               ("1x5, one image, one QP", 1, 1, 5, (32,), None, True),
+               ("5x1, two images, eight QPs, no modes", 2, 5, 1, EIGHT_QPS, None, False))
+# Their seeds, chosen per case on the CPU as SEED was: the first of 0, 1, ... at which the yardstick alone shows at least one (QP, CTU)
+# map that differs from the unchained decision (`moved_maps`; tests/test_cu_tree_picture.py asserts it).  Tried: seed 0 gives the 4x3 case 55 such maps of 288 and the 5x1 case 3 of 80; the 1x5 case, with one QP and four
+# CTUs that have a neighbour, keeps every map at seeds 0 .. 5 and moves 1 of its 5 at seed 6.
+EXTRA_SEEDS = {"4x3, three images, eight QPs, own lambdas": 0, "1x5, one image, one QP": 6, "5x1, two images, eight QPs, no modes": 0}
+
+
+def case_leaves(case, seed=None):
+    """{w: (dist, rate, modes or None)} of a case, in (image, CTU row, CTU column, z-order) order; the seed of an extra case is its own"""
     name, n_images, rows, cols, qps, lambdas, modes = case
+    seed = EXTRA_SEEDS.get(name, SEED) if seed is None else seed
     return near_tie_leaves(n_images * rows * cols, qps, lambdas, seed + len(name), modes)
 
 
@@ -122,6 +143,15 @@ def yardstick(leaves, qps, n_images, rows, cols, lambdas=None, pnn_mode=35, chai
     out["image_rates"] = out["ctu_rates"].reshape(nq, n_images, rows * cols).sum(axis=2, dtype=np.uint64)
     out["edges"] = (lefts, aboves)
     return out
+
+
+def moved_maps(case, seed=None):
+    """How many (QP, CTU) maps of a case differ between the chained yardstick and the unchained decision"""
+    name, n_images, rows, cols, qps, lambdas, _ = case
+    leaves = case_leaves(case, seed)
+    chained = yardstick(leaves, qps, n_images, rows, cols, lambdas)
+    alone = yardstick(leaves, qps, n_images, rows, cols, lambdas, chain=False)
+    return int((chained["cu_depths"] != alone["cu_depths"]).any(axis=2).sum())
 
 
 FIRST = {0: 0, 1: 1, 2: 5, 3: 21}
@@ -220,3 +250,134 @@ def evaluator_channels(pairs, seed):
     from tests import util
     pictures = util.pictures(2 if pairs else 1, SIDE, SIDE, seed)
     return np.ascontiguousarray(np.stack([pictures[0], pictures[1]], axis=-1)[None] if pairs else pictures[..., None])
+
+
+# ---- two images, grids that are not square, every codec / plane form (tests/test_gpu_cu_tree_picture_evaluator.py) ----
+# A and B are the smallest pictures that hold a 1 x 2 and a 2 x 1 grid from (64, 64) with the 64-wide contexts; `crossing` puts transform
+# skip on the 2 x 2 grid of the test above, which has both kinds of edge.  Width 4 has 1024 blocks per call in A and B, width 64 has 4.
+#
+# The floors (`evaluator_floors`, from the yardstick alone; the test asserts each) and the seeds.  For A and B the seeds 5300, 5301, ...
+# were tried in turn on an MI355X, the first that meets every floor kept.  What is scarce is a map with a depth beyond 1: exchanging
+# rows and columns shows only where a neighbour's last column and last row differ, and with seeded predictors most CTUs are one CU or
+# four.  A: 5714 -- none of 5300 .. 5713 (414 seeds) held a cell of depth 2, so none showed a transposition; 266 of them also gave
+# stacked images the node costs of separate ones (the last CTU of image 0 is one CU), 210 had no node cost that an edge moves, 123
+# gave both images the same maps.  B: 5304 -- 5300 .. 5303 met every floor but the transposition.  The crossing keeps SEEDS['switch'].
+# Measured at these seeds (floors, not figures to reproduce: a floor is "at least one", "differs" or "equal"):
+#                                                                        A          B          crossing
+#   (QP, CTU) pairs whose node costs the edges move                      2 of 8     2 of 8     6 of 8
+#   upper nodes of CTUs with a neighbour whose context the edges move    2.4 %      3.6 %      4.8 %
+#   (QP, CTU) pairs whose node costs differ with rows and columns
+#   exchanged                                                            1          1          (square grid)
+#   first CTU of image 1: node costs of absent edges / other ones
+#   with the images stacked as one grid of 1 x 4 (A), 4 x 1 (B)          yes / yes  yes / yes
+#   the two images' depth maps differ / their image_dists differ         yes / yes  yes / yes
+#   cells of depth 0, 1, 2 over both QPs                                 256 240 16 128 352 32 0 512 0
+#   width-4 leaf values (of 4 x 2 x blocks) that transform skip moves    2356       --         2383
+EVALUATOR_CASES = {
+    'A': dict(n_images=2, ctu_rows=1, ctu_cols=2, height=192, width=256, codec='switch', pairs=True, transform_skip=True, seed=5714),
+    'B': dict(n_images=2, ctu_rows=2, ctu_cols=1, height=256, width=192, codec='substitution', pairs=False, transform_skip=False, seed=5304),
+    'crossing': dict(n_images=1, ctu_rows=2, ctu_cols=2, height=SIDE, width=SIDE, codec='switch', pairs=False, transform_skip=True,
+                     seed=SEEDS['switch'])}
+LEAF_KEYS = {'rd_pass_sses': 'sses', 'rd_pass_rate_bits': 'rate_bits', 'rd_pass_side_rate_bits': 'side_rate_bits', 'rd_pass_modes': 'modes'}
+
+
+def case_positions(case):
+    """{w: (row_1sts, col_1sts)} of the case's grid from (ROW_1ST, COL_1ST), one image's blocks in (CTU, z-order) order"""
+    return {w: ip.ctu_block_positions(w, *ip.ctu_grid(ROW_1ST, COL_1ST, case['ctu_rows'], case['ctu_cols'])) for w in ip.WIDTHS}
+
+
+def case_channels(case, seed=None):
+    """[images, H, W, 1] different seeded pictures, or [images, H, W, 2] with pairs: further seeded pictures as the decoded planes"""
+    from tests import util
+    n = case['n_images']
+    pictures = util.pictures(2 * n if case['pairs'] else n, case['height'], case['width'], case['seed'] if seed is None else seed)
+    return np.ascontiguousarray(np.stack([pictures[:n], pictures[n:]], axis=-1) if case['pairs'] else pictures[..., None])
+
+
+def case_pnn_mode(case):
+    return 35 if case['codec'] == 'switch' else 18
+
+
+def case_score_options(case, w, keep_predictions):
+    """The options of score_masks_* that make the calls coding_tree_from_pictures makes for width w"""
+    return dict(OPTIONS, keep_predictions=keep_predictions, first_pass=True, transform_qps=EVALUATOR_QPS, rd_pass=True, rd_pass_signalling=True,
+                rd_pass_codec=case['codec'], rd_pass_transform_skip=case['transform_skip'] and w == 4)
+
+
+def host_leaves(case, channels, nets, transform_skip=None):
+    """{w: {'sses', 'rate_bits', 'side_rate_bits', 'modes': [nb_qps, images * blocks]}} from the second pass's HOST twin, image by
+    image: score_masks_* on each image ALONE gives the targets and the PNN's uint8 predictions, the patterns are cut on the host from
+    that image's context plane, intraprediction.rd_pass(device=None) decides; the images are then joined along the block axis.
+    Nothing here goes through a device call on more than one image, the second pass on the device or the picture entries of the tree."""
+    from context_adaptive_neural_network_based_prediction_amd import evaluation
+    from tests import util
+    score = evaluation.score_masks_from_picture_pairs if case['pairs'] else evaluation.score_masks_from_pictures
+    transform_skip = case['transform_skip'] if transform_skip is None else transform_skip
+    positions, out = case_positions(case), {}
+    for w in ip.WIDTHS:
+        rows, cols = positions[w]
+        per_image = []
+        for i in range(case['n_images']):
+            alone = channels[i:i + 1]
+            kept = score(alone, w, rows, cols, nets[w], util.MEAN, ((0, 0),), **case_score_options(case, w, True))[(0, 0)]
+            patterns = ip.extract_intra_patterns(alone[..., -1:], w, rows + w - 1, cols + w - 1, (0, 0))[..., 0]
+            host = ip.rd_pass(patterns, kept['targets_uint8'][..., 0], kept['predictions_pnn_uint8'][..., 0], EVALUATOR_QPS,
+                              reference_smoothing=OPTIONS['reference_smoothing'], sign_data_hiding=OPTIONS['transform_sign_hiding'],
+                              rdoq=OPTIONS['transform_rdoq'], signalling=True, codec=case['codec'], transform_skip=transform_skip and w == 4)
+            host['predictions_pnn_uint8'], host['targets_uint8'] = kept['predictions_pnn_uint8'], kept['targets_uint8']
+            per_image.append(host)
+        out[w] = {key: np.concatenate([h[key] for h in per_image], axis=1) for key in LEAF_KEYS.values()}
+        for key in ('predictions_pnn_uint8', 'targets_uint8'):
+            out[w][key] = np.concatenate([h[key] for h in per_image], axis=0)
+    return out
+
+
+def tree_leaves_of_host(host):
+    """{w: (dist, rate + side rate, modes)} as `yardstick` takes them, formed as leaves_of_scores forms the two rates"""
+    return {w: (h['sses'], (h['rate_bits'] * 32768.).astype(np.uint64) + (h['side_rate_bits'] * 32768.).astype(np.uint64), h['modes'])
+            for w, h in host.items()}
+
+
+def case_yardstick(case, leaves, **changes):
+    """`yardstick` on the case's leaves; changes: n_images / rows / cols / chain other than the case's own"""
+    arguments = dict(n_images=case['n_images'], rows=case['ctu_rows'], cols=case['ctu_cols'], pnn_mode=case_pnn_mode(case))
+    arguments.update(changes)
+    return yardstick(leaves, EVALUATOR_QPS, **arguments)
+
+
+def evaluator_floors(case, leaves, chained):
+    """What keeps an evaluator case from passing vacuously, from the yardstick alone.  Returns a dictionary:
+    'edges' -- (QP, CTU) pairs whose node costs differ between the chained yardstick and absent edges; 'context_share' -- the share of
+    the upper nodes of CTUs with a neighbour whose context differs from the one absent edges give (replay_contexts); and for two images
+    'first_of_image_1_alone' -- the first CTU of image 1 has the node costs absent edges give; 'stacked' -- and other ones when the
+    two images are stacked as ONE taller (one column) or wider (one row) grid; 'transposed' -- (QP, CTU) pairs whose node costs differ
+    with rows and columns exchanged; 'depth_maps_differ', 'image_dists_differ' -- between the two images."""
+    rows, cols, n_images = case['ctu_rows'], case['ctu_cols'], case['n_images']
+    per_image = rows * cols
+
+    def differing(other):
+        return int((chained['node_costs'] != other['node_costs']).any(axis=(2, 3)).sum())
+
+    alone = case_yardstick(case, leaves, chain=False)
+    lefts, aboves = chained['edges']
+    nodes = moved = 0
+    for qi in range(len(EVALUATOR_QPS)):
+        for ctu in range(n_images * per_image):
+            if ctu % per_image:
+                for _, ctx, ctx_absent, _ in replay_contexts(chained['node_costs'][qi, ctu], lefts[qi, ctu], aboves[qi, ctu]):
+                    nodes += 1
+                    moved += ctx != ctx_absent
+    floors = {'edges': differing(alone), 'context_share': moved / nodes,
+              'transposed': differing(case_yardstick(case, leaves, rows=cols, cols=rows))}
+    if n_images == 2:
+        first = per_image
+        stacked = case_yardstick(case, leaves, n_images=1, rows=rows * (2 if cols == 1 else 1), cols=cols * (2 if cols != 1 else 1))
+        floors['first_of_image_1_alone'] = bool(np.array_equal(chained['node_costs'][:, first], alone['node_costs'][:, first]))
+        floors['stacked'] = bool((chained['node_costs'][:, first] != stacked['node_costs'][:, first]).any())
+        floors['depth_maps_differ'] = bool((chained['cu_depths'][:, :per_image] != chained['cu_depths'][:, per_image:]).any())
+        floors['image_dists_differ'] = bool((chained['image_dists'][:, 0] != chained['image_dists'][:, 1]).any())
+    return floors
+
+
+def floors_hold(floors):
+    return all(bool(value) for value in floors.values())

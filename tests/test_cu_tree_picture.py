@@ -42,8 +42,31 @@ def raw_host_call(leaves, qps, n_images, rows, cols, lambdas=None, pnn_mode=35, 
 
 @pytest.mark.parametrize("case", pc.CASES, ids=[c[0] for c in pc.CASES])
 def test_picture_twin_equals_the_existing_entry_called_ctu_by_ctu(case, yardsticks):
+    assert_twin_is_the_yardstick(case, yardsticks[case[0]])
+
+
+@pytest.mark.parametrize("case", pc.EXTRA_CASES, ids=[c[0] for c in pc.EXTRA_CASES])
+def test_picture_twin_equals_the_yardstick_on_the_extra_cases(case):
+    """Anti-diagonals of up to three CTUs, a single row and a single column of five, three images; and the floor of each: at least one
+    (QP, CTU) map differs from the unchained decision (the seeds tried are written in tests/cu_tree_picture_cases.py)."""
+    name, n_images, rows, cols, qps, lambdas, _ = case
+    leaves = pc.case_leaves(case)
+    want = pc.yardstick(leaves, qps, n_images, rows, cols, lambdas)
+    assert_twin_is_the_yardstick(case, want)
+    alone = pc.yardstick(leaves, qps, n_images, rows, cols, lambdas, chain=False)
+    moved = int((want["cu_depths"] != alone["cu_depths"]).any(axis=2).sum())
+    print("%s: %d of %d (QP, CTU) maps differ from the unchained decision" % (name, moved, len(qps) * n_images * rows * cols))
+    assert moved >= 1 and moved == pc.moved_maps(case)
+    lefts, aboves = want["edges"]
+    if rows == 1:
+        assert (aboves == pc.NO_DEPTH).all() and (lefts[:, 1:] != pc.NO_DEPTH).all()
+    if cols == 1:
+        assert (lefts == pc.NO_DEPTH).all() and (aboves.reshape(len(qps), n_images, rows, 8)[:, :, 1:] != pc.NO_DEPTH).all()
+
+
+def assert_twin_is_the_yardstick(case, want):
     name, n_images, rows, cols, qps, lambdas, modes = case
-    leaves, want = pc.case_leaves(case), yardsticks[name]
+    leaves = pc.case_leaves(case)
     rc, outs = raw_host_call(leaves, qps, n_images, rows, cols, lambdas, outputs=range(10) if modes else [i for i in range(10) if i != 7],
                              modes=modes)
     assert rc == 0

@@ -1,7 +1,7 @@
 """The coding tree over whole pictures on the GPU: cu_tree_picture_kernel behind pnn_cu_tree_picture_device,
 called raw with every output and the workspace between guard bytes, at zero tolerance against the host twin pnn_cu_tree_picture_host
-(which tests/test_cu_tree_picture.py holds to the existing entry called CTU by CTU); cu_depths NULL (the maps in the workspace) and
-given; the launch count of an accepted call; every refusal before a launch, by the launch count, with outputs and workspace untouched;
+(which tests/test_cu_tree_picture.py holds to the existing entry called CTU by CTU), over CASES and EXTRA_CASES (anti-diagonals of up
+to three CTUs, one row and one column of five, three images); cu_depths NULL (the maps in the workspace) and given; the launch count of an accepted call; every refusal before a launch, by the launch count, with outputs and workspace untouched;
 intraprediction.cu_tree_picture(device=0) against device=None; cu_tree_leaves_kernel behind pnn_cu_tree_leaves_device against the numpy
 expression evaluation.coding_tree_from_scores builds its leaves with."""
 import ctypes
@@ -77,8 +77,9 @@ def device_call(leaves, qps, lambdas, n_images, rows, cols, modes, pnn_mode, wan
     return rc, outs, intact, bool((raw == GUARD).all())
 
 
-# every grid of the CPU cases, both image counts, 1 and 8 QPs, HM's lambda and the caller's, modes present and absent
-@pytest.mark.parametrize("case", pc.CASES, ids=[c[0] for c in pc.CASES])
+# every grid of the CPU cases, both image counts, 1 and 8 QPs, HM's lambda and the caller's, modes present and absent; the extra cases
+# add anti-diagonals of 1, 2, 3, 3, 2, 1 CTUs under three images, and one row and one column of five CTUs
+@pytest.mark.parametrize("case", pc.CASES + pc.EXTRA_CASES, ids=[c[0] for c in pc.CASES + pc.EXTRA_CASES])
 @pytest.mark.parametrize("maps_given", [True, False], ids=["cu_depths given", "cu_depths NULL"])
 def test_device_entry_equals_host_twin(case, maps_given):
     name, n_images, rows, cols, qps, lambdas, modes = case
@@ -149,8 +150,19 @@ def test_every_refusal_comes_before_a_launch():
 def test_leaves_entry_equals_the_numpy_expression(w, nq, offset):
     """n = one CTU's blocks.  `offset` moves every input one element on, off the 16-byte alignment of the vector path; at w = 64 and
     one QP the single element goes through the partial group."""
+    leaves_entry_equals_the_numpy_expression(w, nq, offset, (64 // w) ** 2)
+
+
+@pytest.mark.parametrize("w, nq", [(4, 8), (64, 1)])
+@pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "one element on"])
+def test_leaves_entry_over_three_ctus(w, nq, offset):
+    """n = three CTUs' blocks, as coding_tree_from_pictures calls the entry with every image's blocks at once: 768 blocks x 8 QPs at
+    w = 4 (6144 elements: six whole workgroups of 256 lanes x 4 elements) and 3 blocks x 1 QP at w = 64 (one partial group of three)."""
+    leaves_entry_equals_the_numpy_expression(w, nq, offset, 3 * (64 // w) ** 2)
+
+
+def leaves_entry_equals_the_numpy_expression(w, nq, offset, n):
     import torch
-    n = (64 // w) ** 2
     rng = np.random.default_rng(100 * w + nq)
     sses = rng.integers(0, 2 ** 32, nq * n + 1, dtype=np.uint64).astype(np.uint32)
     rates = rng.integers(0, 2 ** 40, nq * n + 1, dtype=np.uint64)
