@@ -168,6 +168,13 @@ SIGNATURES = {
     "pnn_cu_tree_picture_device": (ci, [vp, ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, vp, ci] + [vp] * 11 +
                                    [ctypes.c_size_t, vp]),
     "pnn_cu_tree_leaves_device": (ci, [vp, ci, ci, ci] + [vp] * 8),
+    # context availability and masks per block: the widest picture entries with two device arrays for the two ints
+    "pnn_hm_context_masks_host": (ci, [ci, ci, ci, vp, vp]),
+    "pnn_score_picture_pairs_masks_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pnn_first_pass_picture_pairs_masks_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]),
+    "pnn_rd_pass_picture_pairs_masks_device": (ci, [vp, ci, vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, ci, ctypes.POINTER(ci), ci,
+                                                    ctypes.POINTER(ctypes.c_double), ci, ci, ci, vp, vp, ci, ci] + [vp] * 11 +
+                                               [ctypes.c_size_t, vp]),
     "pnn_last_call_stats": (ci,[vp, ctypes.POINTER(ci),ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci)]),
     "pnn_launch_times": (ci, [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

@@ -56,10 +56,13 @@ int check_dense_blocks(pnn_ctx* c, int width, const uint8_t* d_patterns, int pat
     return n < 0 || (n > 0 && (!d_patterns || !d_targets)) ? fail(c, PNN_E_ARG, "bad batch size or input buffers") : PNN_OK;
 }
 
-PictureBlocks picture_blocks(const uint8_t* d_channels, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions)
+// d_mask_w / d_mask_h: the masks per position of the *_masks_ entries (include/pnn_hip.h, "masks per block"), NULL for the call's scalars
+PictureBlocks picture_blocks(const uint8_t* d_channels, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                             const uint8_t* d_mask_w = nullptr, const uint8_t* d_mask_h = nullptr)
 {
     PictureBlocks b;
     b.channels = d_channels; b.H = height; b.W = width_ch; b.rows = d_rows; b.cols = d_cols; b.positions = positions;
+    b.mask_w = d_mask_w; b.mask_h = d_mask_h;
     return b;
 }
 
@@ -91,6 +94,7 @@ int check_pair_geometry(pnn_ctx* c, int width, const BlockSource& b)
     int rc;
     if (!b.pic.channels != !b.target_channels)
         return fail(c, PNN_E_ARG, "one plane of the pair is NULL (%s)", b.pic.channels ? "d_target_channels" : "d_context_channels");
+    if (!b.pic.mask_w != !b.pic.mask_h) return fail(c, PNN_E_ARG, "one mask array is NULL (%s)", b.pic.mask_w ? "d_mask_h" : "d_mask_w");
     if ((rc = check_width(c, width)) || (rc = check_masks(c, width, b.mask_w, b.mask_h))) return rc;
     return check_sizes(c, b.images, b.pic.positions, b.pic.H, b.pic.W);
 }
@@ -102,19 +106,29 @@ int check_blocks(pnn_ctx* c, int width, const BlockSource& b)
 
 // The positions are read back once (the call waits for the stream) and checked before any launch: the span x span pixels at each of
 // them lie inside the picture.  `what` and `leaves` word the refusal: "position" / "context leaves" for the 3w contexts, "line origin" /
-// "lines leave" for the 2w + 8 reference lines of IPFCN-S.
-int check_positions(pnn_ctx* c, const PictureBlocks& pic, int span, const char* what, const char* leaves, hipStream_t s)
+// "lines leave" for the 2w + 8 reference lines of IPFCN-S.  Masks per position (mask_width > 0 and pic.mask_w set) come back in the same
+// wait and are checked behind the positions: each belongs to {0, 4, ..., mask_width}.
+int check_positions(pnn_ctx* c, const PictureBlocks& pic, int span, const char* what, const char* leaves, hipStream_t s, int mask_width = 0)
 {
+    const bool masks = mask_width > 0 && pic.mask_w && pic.mask_h;
     std::vector<int32_t> rows(pic.positions), cols(pic.positions);
+    std::vector<uint8_t> mask_w(masks ? pic.positions : 0), mask_h(masks ? pic.positions : 0);
     {
         PNN_UNSAFE_CALLS_GUARD;
         HIPCHK(c, hipMemcpyAsync(rows.data(), pic.rows, (size_t)pic.positions * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(cols.data(), pic.cols, (size_t)pic.positions * 4, hipMemcpyDeviceToHost, s));
+        if (masks) {
+            HIPCHK(c, hipMemcpyAsync(mask_w.data(), pic.mask_w, (size_t)pic.positions, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(mask_h.data(), pic.mask_h, (size_t)pic.positions, hipMemcpyDeviceToHost, s));
+        }
         HIPCHK(c, hipStreamSynchronize(s));
     }
     for (int i = 0; i < pic.positions; i++)
         if (rows[i] < 0 || cols[i] < 0 || (long)rows[i] + span > pic.H || (long)cols[i] + span > pic.W)
             return fail(c, PNN_E_ARG, "%s %d (%d, %d): the %dx%d %s the %dx%d picture", what, i, rows[i], cols[i], span, span, leaves, pic.H, pic.W);
+    for (int i = 0; masks && i < pic.positions; i++)
+        if (mask_w[i] > mask_width || mask_w[i] % 4 || mask_h[i] > mask_width || mask_h[i] % 4)
+            return fail(c, PNN_E_ARG, "masks (%d, %d) of position %d: both must belong to {0, 4, ..., %d}", mask_w[i], mask_h[i], i, mask_width);
     return PNN_OK;
 }
 
@@ -122,7 +136,7 @@ int check_positions(pnn_ctx* c, const PictureBlocks& pic, int span, const char* 
 int check_picture_blocks(pnn_ctx* c, int width, const PictureBlocks& pic, hipStream_t s)
 {
     if (!pic.channels || !pic.rows || !pic.cols) return fail(c, PNN_E_ARG, "NULL input buffers");
-    return check_positions(c, pic, 3 * width, "position", "context leaves", s);
+    return check_positions(c, pic, 3 * width, "position", "context leaves", s, width);
 }
 
 // The blocks of a 35-mode kernel, the fields its parameter structs share (pnn_kernels.h): the dense form has no picture, the picture
@@ -693,16 +707,18 @@ int pnn_score_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_conte
                                              stream);
 }
 
-int pnn_score_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
-                                      int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
-                                      int mask_h, int smoothing, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
-                                      uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
+// The one body of the score entries: the call's scalar masks (the *_masks_ entry passes 0, 0), or masks per position where the two
+// arrays are given.
+static int score_picture_pairs(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                               int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w, int mask_h,
+                               const uint8_t* d_mask_w, const uint8_t* d_mask_h, int smoothing, uint8_t* d_targets, uint8_t* d_pnn_u8,
+                               float* d_pnn_f32, uint32_t* d_pnn_sse, uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
 {
     if (!c) return PNN_E_ARG;
     int rc;
     const bool want_pnn = d_pnn_u8 || d_pnn_f32 || d_pnn_sse, want_hevc = d_hevc_mode || d_hevc_sse || d_hevc_pred;
     // contexts and intra patterns from the context plane, targets (hence both SSEs) from the target plane
-    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions);
+    const PictureBlocks pic = picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions, d_mask_w, d_mask_h);
     const PictureBlocks pic_tg = picture_blocks(d_target_channels, height, width_ch, d_rows, d_cols, positions);
     BlockSource blocks = picture_pair_blocks(pic, d_target_channels, images, mask_w, mask_h);
     if ((rc = check_pair_geometry(c, width, blocks)) ||
@@ -758,6 +774,26 @@ int pnn_score_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_co
     return PNN_OK;
 }
 
+int pnn_score_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                      int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
+                                      int mask_h, int smoothing, uint8_t* d_targets, uint8_t* d_pnn_u8, float* d_pnn_f32, uint32_t* d_pnn_sse,
+                                      uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred, void* stream)
+{
+    return score_picture_pairs(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols, positions, mask_w, mask_h,
+                               nullptr, nullptr, smoothing, d_targets, d_pnn_u8, d_pnn_f32, d_pnn_sse, d_hevc_mode, d_hevc_sse, d_hevc_pred, stream);
+}
+
+// ---- masks per block (include/pnn_hip.h, "masks per block") ----
+int pnn_score_picture_pairs_masks_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                         int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                         const uint8_t* d_mask_w, const uint8_t* d_mask_h, int smoothing, uint8_t* d_targets, uint8_t* d_pnn_u8,
+                                         float* d_pnn_f32, uint32_t* d_pnn_sse, uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred,
+                                         void* stream)
+{
+    return score_picture_pairs(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols, positions, 0, 0, d_mask_w,
+                               d_mask_h, smoothing, d_targets, d_pnn_u8, d_pnn_f32, d_pnn_sse, d_hevc_mode, d_hevc_sse, d_hevc_pred, stream);
+}
+
 int pnn_first_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
                                         int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w,
                                         int mask_h, const uint8_t* d_cand_pred, uint32_t* d_mode_hads, uint32_t* d_cand_hads,
@@ -768,15 +804,16 @@ int pnn_first_pass_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_
                                                   stream);
 }
 
-int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
-                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
-                                           int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, uint32_t* d_mode_hads,
-                                           uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
+// the one body of the first-pass entries from pictures: scalar masks or masks per position, as score_picture_pairs
+static int first_pass_picture_pairs(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                    int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w, int mask_h,
+                                    const uint8_t* d_mask_w, const uint8_t* d_mask_h, const uint8_t* d_cand_pred, int smoothing,
+                                    uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
 {
     if (!c) return PNN_E_ARG;
     int rc;
-    BlockSource blocks = picture_pair_blocks(picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions), d_target_channels,
-                                             images, mask_w, mask_h);
+    BlockSource blocks = picture_pair_blocks(picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions, d_mask_w, d_mask_h),
+                                             d_target_channels, images, mask_w, mask_h);
     if ((rc = check_pair_geometry(c, width, blocks)) || (rc = check_smoothing(c, smoothing)) ||
         (rc = check_hads_outputs(c, d_cand_pred, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs)) ||
         (rc = count_blocks(c, images, positions, &blocks.n))) return rc;
@@ -790,6 +827,25 @@ int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t*
     HIPCHK(c, launch_hevc_mode_hads(p, s));
     c->stat_launches++;
     return PNN_OK;
+}
+
+int pnn_first_pass_picture_pairs_hm_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                           int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, uint32_t* d_mode_hads,
+                                           uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs, void* stream)
+{
+    return first_pass_picture_pairs(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols, positions, mask_w,
+                                    mask_h, nullptr, nullptr, d_cand_pred, smoothing, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs, stream);
+}
+
+int pnn_first_pass_picture_pairs_masks_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                              int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                              const uint8_t* d_mask_w, const uint8_t* d_mask_h, const uint8_t* d_cand_pred, int smoothing,
+                                              uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs,
+                                              void* stream)
+{
+    return first_pass_picture_pairs(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols, positions, 0, 0,
+                                    d_mask_w, d_mask_h, d_cand_pred, smoothing, d_mode_hads, d_cand_hads, d_list_modes, d_list_costs, stream);
 }
 
 int pnn_trquant_device(pnn_ctx* c, int width, const uint8_t* d_predictions, const uint8_t* d_targets, int n, const int* qps, int nb_qps,
@@ -1050,6 +1106,25 @@ int pnn_rd_pass_tskip_device(pnn_ctx* c, int width, const uint8_t* d_patterns, i
     return rd_pass(c, q);
 }
 
+// the one body of the _tskip_ entries from picture pairs: scalar masks or masks per position, as score_picture_pairs
+static int rd_pass_tskip_picture_pairs(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                       int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions, int mask_w, int mask_h,
+                                       const uint8_t* d_mask_w, const uint8_t* d_mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps,
+                                       int nb_qps, const double* lambdas, int sign_data_hiding, int rdoq, int signalling, const uint8_t* d_left_modes,
+                                       const uint8_t* d_above_modes, int codec, int transform_skip, const RdPassOutputs& out, void* d_workspace,
+                                       size_t workspace_bytes, void* stream)
+{
+    if (!c) return PNN_E_ARG;
+    const BlockSource blocks = picture_pair_blocks(picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions, d_mask_w, d_mask_h),
+                                                   d_target_channels, images, mask_w, mask_h);
+    RdPassCall q = rd_pass_call(width, blocks, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding);
+    q.rdoq = rdoq; q.signalling = signalling; q.left = d_left_modes; q.above = d_above_modes; q.codec = codec;
+    q.transform_skip = transform_skip; q.tskip_entry = true;
+    q.out = out;
+    q.workspace = d_workspace; q.workspace_bytes = workspace_bytes; q.stream = (hipStream_t)stream;
+    return rd_pass(c, q);
+}
+
 int pnn_rd_pass_tskip_picture_pairs_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
                                            int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
                                            int mask_w, int mask_h, const uint8_t* d_cand_pred, int smoothing, const int* qps, int nb_qps,
@@ -1059,16 +1134,31 @@ int pnn_rd_pass_tskip_picture_pairs_device(pnn_ctx* c, int width, const uint8_t*
                                            uint64_t* d_best_rate, double* d_first_pass_costs, uint64_t* d_best_side_rate, uint8_t* d_best_ts_flag,
                                            void* d_workspace, size_t workspace_bytes, void* stream)
 {
-    if (!c) return PNN_E_ARG;
-    const BlockSource blocks = picture_pair_blocks(picture_blocks(d_context_channels, height, width_ch, d_rows, d_cols, positions),
-                                                   d_target_channels, images, mask_w, mask_h);
-    RdPassCall q = rd_pass_call(width, blocks, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding);
-    q.rdoq = rdoq; q.signalling = signalling; q.left = d_left_modes; q.above = d_above_modes; q.codec = codec;
-    q.transform_skip = transform_skip; q.tskip_entry = true;
-    q.out = {d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs, d_best_side_rate,
-             d_best_ts_flag};
-    q.workspace = d_workspace; q.workspace_bytes = workspace_bytes; q.stream = (hipStream_t)stream;
-    return rd_pass(c, q);
+    return rd_pass_tskip_picture_pairs(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols, positions, mask_w,
+                                       mask_h, nullptr, nullptr, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, signalling,
+                                       d_left_modes, d_above_modes, codec, transform_skip,
+                                       {d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs,
+                                        d_best_side_rate, d_best_ts_flag},
+                                       d_workspace, workspace_bytes, stream);
+}
+
+// The _tskip_ entry from picture pairs with masks per position in place of the call's two scalars.
+int pnn_rd_pass_picture_pairs_masks_device(pnn_ctx* c, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                           const uint8_t* d_mask_w, const uint8_t* d_mask_h, const uint8_t* d_cand_pred, int smoothing,
+                                           const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding, int rdoq, int signalling,
+                                           const uint8_t* d_left_modes, const uint8_t* d_above_modes, int codec, int transform_skip,
+                                           uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot,
+                                           double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs,
+                                           uint64_t* d_best_side_rate, uint8_t* d_best_ts_flag, void* d_workspace, size_t workspace_bytes,
+                                           void* stream)
+{
+    return rd_pass_tskip_picture_pairs(c, width, d_context_channels, d_target_channels, images, height, width_ch, d_rows, d_cols, positions, 0, 0,
+                                       d_mask_w, d_mask_h, d_cand_pred, smoothing, qps, nb_qps, lambdas, sign_data_hiding, rdoq, signalling,
+                                       d_left_modes, d_above_modes, codec, transform_skip,
+                                       {d_cand_modes, d_cand_costs, d_best_mode, d_best_slot, d_best_cost, d_best_sse, d_best_rate, d_first_pass_costs,
+                                        d_best_side_rate, d_best_ts_flag},
+                                       d_workspace, workspace_bytes, stream);
 }
 
 // The mode statistics of a second pass whose slot modes and winners are on the device: the output is zeroed on the stream, then one

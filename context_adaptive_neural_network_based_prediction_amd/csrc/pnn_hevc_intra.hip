@@ -132,12 +132,23 @@ __device__ inline size_t picture_corner(const PictureBlocks& pic, long b)
 // intra patterns, targets from their own array; true: both from pictures -- the reference samples from the context plane (p.pic.channels),
 // the targets from the target plane (p.pic_targets), which have one geometry and so share each block's offset `corner`.  For single
 // pictures the two pointers are equal.  NT: the threads of the calling workgroup (rd_candidates_kernel has 256).
-template <int W, int G, bool PIC, int NT = kThreads, typename Params>
+// MASKS (picture form only; p.pic.mask_w / mask_h set): every block is clamped with its OWN pw = 2w + 1 - mask_w[pos] and ph in place of
+// the call's p.pw / p.ph, kept per staged block in G ints of LDS beside the corners.  MASKS = false is the staging of the scalar
+// entries, instruction for instruction what it was before masks per block existed.
+template <int W, int G, bool PIC, bool MASKS, int NT = kThreads, typename Params>
 __device__ __forceinline__ void stage_blocks(const Params& p, long blk0, int tid, int* ref, uint8_t* tgt, size_t* corner)
 {
+    static_assert(PIC || !MASKS, "masks per block exist in the picture form only");
     constexpr int RS = 4 * W + 1, TS = W * W + 4;                 // LDS strides (odd in dwords: lanes of different blocks spread over banks)
+    __shared__ int last[MASKS ? G : 1];                           // MASKS: (pw - 1) | (ph - 1) << 16 of each staged block
     if (PIC) {
-        if (tid < G && blk0 + tid < p.N) corner[tid] = picture_corner(p.pic, blk0 + tid);
+        if (tid < G && blk0 + tid < p.N) {
+            corner[tid] = picture_corner(p.pic, blk0 + tid);
+            if (MASKS) {
+                const int pos = (int)((blk0 + tid) % p.pic.positions);
+                last[tid] = (2 * W - p.pic.mask_w[pos]) | (2 * W - p.pic.mask_h[pos]) << 16;
+            }
+        }
         __syncthreads();
     }
     for (int i = tid; i < G * RS; i += NT) {
@@ -146,7 +157,8 @@ __device__ __forceinline__ void stage_blocks(const Params& p, long blk0, int tid
         if (blk0 + g < p.N) {
             if (PIC) {                                 // the dense form's padding rule in picture coordinates: inside the block's 3w x 3w context square
                 const uint8_t* pat = p.pic.channels + corner[g] + (size_t)(W - 1) * p.pic.W + W - 1;
-                v = j >= 0 ? pat[min(j, p.pw - 1)] : pat[(size_t)min(-j, p.ph - 1) * p.pic.W];
+                const int pw1 = MASKS ? last[g] & 0xffff : p.pw - 1, ph1 = MASKS ? last[g] >> 16 : p.ph - 1;
+                v = j >= 0 ? pat[min(j, pw1)] : pat[(size_t)min(-j, ph1) * p.pic.W];
             } else {
                 const uint8_t* pat = p.patterns + (size_t)(blk0 + g) * p.ph * p.pw;
                 v = j >= 0 ? pat[min(j, p.pw - 1)] : pat[min(-j, p.ph - 1) * p.pw];
@@ -214,7 +226,7 @@ __device__ __forceinline__ void stage_smoothed(const int* ref, int* ref_s, int* 
     }
 }
 
-template <int W, bool PIC, bool SMOOTH>
+template <int W, bool PIC, bool SMOOTH, bool MASKS = false>
 __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBestModeParams p)
 {
     constexpr int R = W <= 8 ? W : 4, RG = W / R, G = 64 / RG;    // rows per lane, lanes per block, blocks per workgroup
@@ -230,7 +242,7 @@ __global__ __launch_bounds__(kThreads) void hevc_best_mode_kernel(const HevcBest
     const int tid = threadIdx.x;
     const long blk0 = (long)blockIdx.x * G;
 
-    stage_blocks<W, G, PIC>(p, blk0, tid, ref, tgt, corner);
+    stage_blocks<W, G, PIC, MASKS>(p, blk0, tid, ref, tgt, corner);
     for (int i = tid; i < G * 35; i += kThreads) sse[i] = 0;
     __syncthreads();
     stage_dc<W, G>(ref, dcv, tid);
@@ -312,7 +324,7 @@ __device__ __forceinline__ unsigned sub_block_hads(const uint8_t* tg, int by, in
 
 // The SATD twin of hevc_best_mode_kernel (same staging, same forms PIC).  Lane = (block g, sub-block sb) of the workgroup's G =
 // 64 / (w / T)^2 blocks; wave = one mode per round, so the mode is wave-uniform.  cost[g][0 .. 34] the modes, [35] the candidate.
-template <int W, bool PIC, bool SMOOTH>
+template <int W, bool PIC, bool SMOOTH, bool MASKS = false>
 __global__ __launch_bounds__(kThreads) void hevc_mode_hads_kernel(const HevcModeHadsParams p)
 {
     static_assert(!SMOOTH || W == 8 || W == 16 || W == 32, "no mode smooths at w = 4 and 64");
@@ -330,7 +342,7 @@ __global__ __launch_bounds__(kThreads) void hevc_mode_hads_kernel(const HevcMode
     const int tid = threadIdx.x;
     const long blk0 = (long)blockIdx.x * G;
 
-    stage_blocks<W, G, PIC>(p, blk0, tid, ref, tgt, corner);
+    stage_blocks<W, G, PIC, MASKS>(p, blk0, tid, ref, tgt, corner);
     if (p.cand_pred)
         for (int i = tid; i < G * W * W; i += kThreads) {
             const int g = i / (W * W), e = i % (W * W);
@@ -417,7 +429,7 @@ constexpr int kRdThreads = 256;
 // kernel derives nothing: it predicts them (cand_modes is not written).  Everything else is as it stands.
 // SUBST (with SLOTS): the substitution codec's K + 2 slots, in which mode 18 is the candidate's prediction and 35
 // does not occur.  Without it the statements are the ones they were.
-template <int W, bool PIC, bool SMOOTH, bool SLOTS = false, bool SUBST = false>
+template <int W, bool PIC, bool SMOOTH, bool SLOTS = false, bool SUBST = false, bool MASKS = false>
 __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandidatesParams p)
 {
     static_assert(!SMOOTH || W == 8 || W == 16 || W == 32, "no mode smooths at w = 4 and 64");
@@ -435,7 +447,7 @@ __global__ __launch_bounds__(kRdThreads) void rd_candidates_kernel(const RdCandi
     const int tid = threadIdx.x;
     const long blk0 = (long)blockIdx.x * G;
 
-    stage_blocks<W, G, PIC, kRdThreads>(p, blk0, tid, ref, tgt, corner);
+    stage_blocks<W, G, PIC, MASKS, kRdThreads>(p, blk0, tid, ref, tgt, corner);
     __syncthreads();
     stage_dc<W, G>(ref, dcv, tid);
     if (SMOOTH) stage_smoothed<W, G, kRdThreads>(ref, ref_s, strong, p.smoothing == 2, tid);
@@ -703,11 +715,13 @@ hipError_t launch_rd_candidates_substitution(const RdCandidatesParams& p, hipStr
     const int g = rd_candidates_blocks_per_workgroup(p.w);
     const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kRdThreads);
     const bool pic = p.patterns == nullptr;
-    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+    if (pic && (!p.pic.channels || !p.pic_targets || !p.pic.mask_w != !p.pic.mask_h)) return hipErrorInvalidValue;
+    const bool masks = pic && p.pic.mask_w;           // masks per position: the MASKS instantiation (the scalar entries keep theirs)
     if (!p.cand_pred || !p.list_modes || !p.slot_pred || !p.slot_targets) return hipErrorInvalidValue;
     if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
 #define PNN_RD_LAUNCH(W_, SMOOTH_) \
-    if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, true, true>), grid, block, 0, s, p); \
+    if (masks) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, true, true, true>), grid, block, 0, s, p); \
+    else if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, true, true>), grid, block, 0, s, p); \
     else hipLaunchKernelGGL((rd_candidates_kernel<W_, false, SMOOTH_, true, true>), grid, block, 0, s, p);
 #define PNN_RD_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_RD_LAUNCH(W_, true) } else { PNN_RD_LAUNCH(W_, false) }
     switch (p.w) {                                     // (width 64 writes each slot as its four quadrants, 32 x 32 blocks)
@@ -751,11 +765,13 @@ hipError_t launch_rd_candidates_slots(const RdCandidatesParams& p, hipStream_t s
     const int g = rd_candidates_blocks_per_workgroup(p.w);
     const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kRdThreads);
     const bool pic = p.patterns == nullptr;
-    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+    if (pic && (!p.pic.channels || !p.pic_targets || !p.pic.mask_w != !p.pic.mask_h)) return hipErrorInvalidValue;
+    const bool masks = pic && p.pic.mask_w;           // masks per position: the MASKS instantiation (the scalar entries keep theirs)
     if (!p.cand_pred || !p.list_modes || !p.slot_pred || !p.slot_targets) return hipErrorInvalidValue;
     if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
 #define PNN_RD_LAUNCH(W_, SMOOTH_) \
-    if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, true>), grid, block, 0, s, p); \
+    if (masks) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, true, false, true>), grid, block, 0, s, p); \
+    else if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, true>), grid, block, 0, s, p); \
     else hipLaunchKernelGGL((rd_candidates_kernel<W_, false, SMOOTH_, true>), grid, block, 0, s, p);
 #define PNN_RD_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_RD_LAUNCH(W_, true) } else { PNN_RD_LAUNCH(W_, false) }
     switch (p.w) {                                     // (width 64 writes each slot as its four quadrants, 32 x 32 blocks)
@@ -790,11 +806,13 @@ hipError_t launch_rd_candidates(const RdCandidatesParams& p, hipStream_t s)
     const int g = rd_candidates_blocks_per_workgroup(p.w);
     const dim3 grid((unsigned)((p.N + g - 1) / g)), block(kRdThreads);
     const bool pic = p.patterns == nullptr;
-    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+    if (pic && (!p.pic.channels || !p.pic_targets || !p.pic.mask_w != !p.pic.mask_h)) return hipErrorInvalidValue;
+    const bool masks = pic && p.pic.mask_w;           // masks per position: the MASKS instantiation (the scalar entries keep theirs)
     if (!p.cand_pred || !p.list_modes || !p.cand_modes || !p.slot_pred || !p.slot_targets) return hipErrorInvalidValue;
     if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
 #define PNN_RD_LAUNCH(W_, SMOOTH_) \
-    if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
+    if (masks) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_, false, false, true>), grid, block, 0, s, p); \
+    else if (pic) hipLaunchKernelGGL((rd_candidates_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
     else hipLaunchKernelGGL((rd_candidates_kernel<W_, false, SMOOTH_>), grid, block, 0, s, p);
 #define PNN_RD_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_RD_LAUNCH(W_, true) } else { PNN_RD_LAUNCH(W_, false) }
     switch (p.w) {                                     // at w = 4 and 64 no mode smooths: the one instantiation for every `smoothing`
@@ -827,10 +845,12 @@ hipError_t launch_hevc_best_mode(const HevcBestModeParams& p, hipStream_t s)
     const int rows_per_lane = p.w <= 8 ? p.w : 4, blocks_per_wg = 64 / (p.w / rows_per_lane);
     const dim3 grid((unsigned)((p.N + blocks_per_wg - 1) / blocks_per_wg)), block(kThreads);
     const bool pic = p.patterns == nullptr;
-    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+    if (pic && (!p.pic.channels || !p.pic_targets || !p.pic.mask_w != !p.pic.mask_h)) return hipErrorInvalidValue;
+    const bool masks = pic && p.pic.mask_w;           // masks per position: the MASKS instantiation (the scalar entries keep theirs)
     if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
 #define PNN_HEVC_LAUNCH(W_, SMOOTH_) \
-    if (pic) hipLaunchKernelGGL((hevc_best_mode_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
+    if (masks) hipLaunchKernelGGL((hevc_best_mode_kernel<W_, true, SMOOTH_, true>), grid, block, 0, s, p); \
+    else if (pic) hipLaunchKernelGGL((hevc_best_mode_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
     else hipLaunchKernelGGL((hevc_best_mode_kernel<W_, false, SMOOTH_>), grid, block, 0, s, p);
 #define PNN_HEVC_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_HEVC_LAUNCH(W_, true) } else { PNN_HEVC_LAUNCH(W_, false) }
     switch (p.w) {                                     // at w = 4 and 64 no mode smooths: the one instantiation for every `smoothing`
@@ -852,10 +872,12 @@ hipError_t launch_hevc_mode_hads(const HevcModeHadsParams& p, hipStream_t s)
     const int t = p.w == 4 ? 4 : 8, blocks_per_wg = 64 / ((p.w / t) * (p.w / t));
     const dim3 grid((unsigned)((p.N + blocks_per_wg - 1) / blocks_per_wg)), block(kThreads);
     const bool pic = p.patterns == nullptr;
-    if (pic && (!p.pic.channels || !p.pic_targets)) return hipErrorInvalidValue;
+    if (pic && (!p.pic.channels || !p.pic_targets || !p.pic.mask_w != !p.pic.mask_h)) return hipErrorInvalidValue;
+    const bool masks = pic && p.pic.mask_w;           // masks per position: the MASKS instantiation (the scalar entries keep theirs)
     if (p.smoothing < 0 || p.smoothing > 2) return hipErrorInvalidValue;
 #define PNN_HADS_LAUNCH(W_, SMOOTH_) \
-    if (pic) hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
+    if (masks) hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, true, SMOOTH_, true>), grid, block, 0, s, p); \
+    else if (pic) hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, true, SMOOTH_>), grid, block, 0, s, p); \
     else hipLaunchKernelGGL((hevc_mode_hads_kernel<W_, false, SMOOTH_>), grid, block, 0, s, p);
 #define PNN_HADS_LAUNCH_SMOOTH(W_) if (p.smoothing) { PNN_HADS_LAUNCH(W_, true) } else { PNN_HADS_LAUNCH(W_, false) }
     switch (p.w) {

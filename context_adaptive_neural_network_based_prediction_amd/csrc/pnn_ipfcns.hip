@@ -97,8 +97,9 @@ __global__ __launch_bounds__(256) void score_desc_kernel(const ScoreDescParams p
     TbDev d;
     d.origin = (img * p.pic.H + p.pic.rows[pos] + p.w) * p.pic.W + p.pic.cols[pos] + p.w;
     d.stride = p.pic.W;
-    d.above_mask = (uint32_t)((1ull << (units - p.mask_w / 4)) - 1ull);    // 64 bits: the count is 32 at w = 64 without a mask
-    d.left_units = units - p.mask_h / 4;
+    const int mask_w = p.pic.mask_w ? p.pic.mask_w[pos] : p.mask_w, mask_h = p.pic.mask_h ? p.pic.mask_h[pos] : p.mask_h;   // per position, or the call's
+    d.above_mask = (uint32_t)((1ull << (units - mask_w / 4)) - 1ull);      // 64 bits: the count is 32 at w = 64 without a mask
+    d.left_units = units - mask_h / 4;
     d.reserved = 0;
     p.tbs[bb] = d;
 }

@@ -293,8 +293,11 @@ hipError_t launch_block_cost(const BlockCostParams& p, hipStream_t s);
 // Blocks of the evaluator's pictures (pnn_score_pictures_device): uint8 pictures [images][H][W], context corners (rows[pos], cols[pos])
 // of `positions` positions, block b = image * positions + pos.  The block's 3w x 3w context square starts at its corner, its w x w
 // target at (row + w, col + w).  The caller has checked that every square lies inside the picture.
+// mask_w / mask_h: NULL (every block under the call's scalar masks) or uint8 [positions], the masks of the blocks at each POSITION, in
+// samples and checked by the caller; both or none.
 struct PictureBlocks {
     const uint8_t* channels; int H, W; const int32_t* rows; const int32_t* cols; int positions;
+    const uint8_t* mask_w; const uint8_t* mask_h;
 };
 
 // HEVC best intra mode (pnn_hevc_intra.hip): N intra patterns [N][ph][pw] (first row and column used) and targets [N][w][w], all uint8;
@@ -482,7 +485,7 @@ hipError_t launch_ipfcns_epilogue(const IpfcnsEpilogueParams& p, hipStream_t s);
 // epilogue's pic.channels is the target plane.  Positions and geometry are those of both.
 // Descriptors of the blocks' L-shaped contexts, as context.py builds them: origin = (image * H + row + w) * W + col + w (the target's
 // top-left pixel), stride = W, above_mask = 2^(units - mask_w / 4) - 1 (units = 2w / 4; all 32 bits at w = 64 without a mask),
-// left_units = units - mask_h / 4.
+// left_units = units - mask_h / 4.  mask_w / mask_h: the call's; with pic.mask_w / pic.mask_h set, the block's own, by its position.
 struct ScoreDescParams { PictureBlocks pic; long b0; int nb; int w; int mask_w, mask_h; TbDev* tbs; };
 hipError_t launch_score_desc(const ScoreDescParams& p, hipStream_t s);
 // Score epilogue: q = rint(clip(fl32(pred + mean), 0, 255)) (half to even) against the target read from the picture.  Each of u8

@@ -22,6 +22,8 @@ rd_pass=True (with first_pass and transform_qps) adds HM's second intra pass: th
 and the PNN (pnn_rd_pass_rdoq_picture_pairs_device: one more call per mask, the same download).
 Options travel as arguments: every call of the mask loop goes to the widest entry of its operation (*_hm_device, pnn_trquant_rdoq_device) with 0
 or NULL for an option that is off; the narrower entries of include/pnn_hip.h forward to these with those values: the same kernel launch.
+score_block_masks_from_pictures / _picture_pairs score every block under a mask of its OWN (the *_masks_device entries), and
+coding_tree_from_pictures(availability='hm') gives each block of the tree the masks HM's coding order leaves it.
 """
 import ctypes
 
@@ -322,6 +324,66 @@ def score_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, 
                         transform_rate, transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling, rd_pass_neighbour_modes, rd_pass_codec,
                         rd_pass_mode_stats, transform_skip, rd_pass_transform_skip)
 
+def _check_block_masks(width_target, row_1sts, masks_w, masks_h, rd_pass, rd_pass_signalling):
+    """The masks per block of score_block_masks_*: two integer arrays of row_1sts.size values in {0, 4, ..., width_target}; as uint8.
+    Also the one option the per-block entries lack: a second pass without signalling (the entry it extends has none either)."""
+    if rd_pass and not rd_pass_signalling:
+        raise ValueError('masks per block: `rd_pass` needs `rd_pass_signalling` (pnn_rd_pass_picture_pairs_masks_device has no form without).')
+    checked = []
+    for masks, name in ((masks_w, 'masks_w'), (masks_h, 'masks_h')):
+        masks = np.asarray(masks)
+        if not np.issubdtype(masks.dtype, np.integer):
+            raise TypeError('`%s.dtype` is not smaller than `numpy.integer` in type hierarchy.' % name)
+        if masks.size != np.asarray(row_1sts).size:
+            raise ValueError('`%s.size` is not equal to `row_1sts.size`.' % name)
+        if masks.size and (masks.min() < 0 or masks.max() > width_target or np.any(masks % 4)):
+            raise ValueError('`%s` has a value that does not belong to {0, 4, ..., `width_target`}.' % name)
+        checked.append(np.ascontiguousarray(masks.ravel(), dtype=np.uint8))
+    return tuple(checked)
+
+
+def score_block_masks_from_pictures(channels_uint8, width_target, row_1sts, col_1sts, predictor, mean_training, masks_w, masks_h,
+                                    keep_predictions=True, first_pass=False, reference_smoothing=0, transform_qps=(), transform_rate=False,
+                                    transform_sign_hiding=False, rd_pass=False, transform_rdoq=False, rd_pass_signalling=False,
+                                    rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False, transform_skip='off',
+                                    rd_pass_transform_skip=False):
+    """score_masks_from_pictures with a mask PER BLOCK instead of a list of masks for all blocks (include/pnn_hip.h, "masks per block"):
+    masks_w / masks_h, integer arrays [positions] with values in {0, 4, ..., width_target}, give the masks of the blocks at each
+    position, the same in every image -- intraprediction.hm_context_masks makes the ones HM's coding order leaves the blocks of a CTU
+    grid.  Returns ONE dictionary with the keys a mask's dictionary has: block b's entries are those the mask
+    (masks_w[pos], masks_h[pos]) gives it in score_masks_from_pictures, bit for bit; the frequencies and means run over the blocks as
+    they are.  One upload (pictures, positions and masks), the same calls -- the score call, the first pass and the second pass as
+    pnn_score_picture_pairs_masks_device, pnn_first_pass_picture_pairs_masks_device and pnn_rd_pass_picture_pairs_masks_device, the
+    transform coding unchanged --, one download.  The options are score_masks_from_pictures' but two: there is no net_ipfcns (IPFCN-S
+    has no masked form), and rd_pass=True needs rd_pass_signalling=True (ValueError otherwise: the second pass's entry has no form
+    without).  Every argument is checked before anything touches the GPU."""
+    w = width_target
+    if w not in intraprediction.WIDTHS:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    block_masks = _check_block_masks(w, row_1sts, masks_w, masks_h, rd_pass, rd_pass_signalling)
+    return _score_masks(channels_uint8, 1, w, row_1sts, col_1sts, predictor, mean_training, (), None, keep_predictions, first_pass,
+                        reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling,
+                        rd_pass_neighbour_modes, rd_pass_codec, rd_pass_mode_stats, transform_skip, rd_pass_transform_skip,
+                        _block_masks=block_masks)[None]
+
+
+def score_block_masks_from_picture_pairs(channels_pair_uint8, width_target, row_1sts, col_1sts, predictor, mean_training, masks_w, masks_h,
+                                         keep_predictions=True, first_pass=False, reference_smoothing=0, transform_qps=(), transform_rate=False,
+                                         transform_sign_hiding=False, rd_pass=False, transform_rdoq=False, rd_pass_signalling=False,
+                                         rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False, transform_skip='off',
+                                         rd_pass_transform_skip=False):
+    """score_block_masks_from_pictures on [images, H, W, 2] pairs (original, decoded), the planes used as score_masks_from_picture_pairs
+    uses them."""
+    w = width_target
+    if w not in intraprediction.WIDTHS:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    block_masks = _check_block_masks(w, row_1sts, masks_w, masks_h, rd_pass, rd_pass_signalling)
+    return _score_masks(channels_pair_uint8, 2, w, row_1sts, col_1sts, predictor, mean_training, (), None, keep_predictions, first_pass,
+                        reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass, transform_rdoq, rd_pass_signalling,
+                        rd_pass_neighbour_modes, rd_pass_codec, rd_pass_mode_stats, transform_skip, rd_pass_transform_skip,
+                        _block_masks=block_masks)[None]
+
+
 def _check_score_masks_arguments(ch, nb_planes, w, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
                                  reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False, transform_rdoq=False):
     """The argument checks of _score_masks, all before anything touches the GPU; the library is first used by the last, the predictor's mean.
@@ -484,15 +546,20 @@ def _dictionary_of_download(view, n, w, first_pass, reference_smoothing, transfo
 def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mean_training, tuples_width_height_masks, net_ipfcns,
                  keep_predictions, first_pass, reference_smoothing, transform_qps, transform_rate, transform_sign_hiding, rd_pass=False,
                  transform_rdoq=False, rd_pass_signalling=False, rd_pass_neighbour_modes=None, rd_pass_codec='switch', rd_pass_mode_stats=False,
-                 transform_skip='off', rd_pass_transform_skip=False, _tree_leaves=None):
+                 transform_skip='off', rd_pass_transform_skip=False, _tree_leaves=None, _block_masks=None):
     """The body of score_masks_from_pictures (nb_planes = 1) and score_masks_from_picture_pairs (2): the targets come from channel 0,
     everything a predictor reads from the last channel; with one plane the two are the same device buffer.  Every option is an argument
     of the one entry its call has (the smoothing; the mode pointer, the rate pointer and the flag), 0 or NULL when off.
     _tree_leaves (private to coding_tree_from_pictures; None: nothing changes, call for call): {'dist', 'rate', 'mode': torch tensors
     on the predictor's device of [nb_qps, n] uint32 / uint64 / uint8 elements, 'keep': bool}.  Behind the second pass of each mask one
     more call, pnn_cu_tree_leaves_device, writes the width's leaves of the coding tree into them from the outputs the pass left on the
-    device; with 'keep' False the mask's results are then neither downloaded nor returned (its value is None)."""
+    device; with 'keep' False the mask's results are then neither downloaded nor returned (its value is None).
+    _block_masks (private to score_block_masks_* and coding_tree_from_pictures; None: nothing changes, call for call): (masks_w, masks_h),
+    checked uint8 [positions] arrays.  The loop then runs ONCE, under the key None (tuples_width_height_masks must be empty), and the score
+    call, the first pass and the second pass go to the *_masks_device entries with the two arrays, uploaded once with everything else."""
     w = width_target
+    if _block_masks is not None and len(tuples_width_height_masks):
+        raise ValueError('`_block_masks` is given beside a list of masks.')
     if _tree_leaves is not None and not (rd_pass and rd_pass_signalling):
         raise ValueError('`_tree_leaves` is given without the second pass with signalling.')
     if rd_pass_signalling and not rd_pass:
@@ -525,6 +592,9 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     n_pos, nb_qps = rows.size, len(transform_qps)
     n = nb_images * n_pos
     L = _lib.lib()
+    per_block = _block_masks is not None
+    if per_block:                                         # one pass of the loop below, under the key None
+        masks = [None]
     signalling = int(bool(rd_pass_signalling))
     left, above = (None, None) if rd_pass_neighbour_modes is None else rd_pass_neighbour_modes
     left = intraprediction._neighbour_array(left, n, not codec, 'rd_pass_neighbour_modes[0]')
@@ -535,6 +605,8 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
     d_planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(ch, 3, 0))).to(dev)      # [planes, images, H, W]: one copy, one upload
     d_target_channels, d_context_channels = d_planes[0], d_planes[nb_planes - 1]
     d_rows, d_cols = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (rows, cols))
+    if per_block:                                         # both arrays in one upload, [2, positions]
+        d_block_masks = torch.from_numpy(np.stack([np.asarray(a, np.uint8).ravel() for a in _block_masks])).to(dev)
     sections, begin, end = _output_layout(n, w, first_pass, nb_qps, transform_rate, rd_pass, rd_pass_signalling, rd_pass_codec, rd_pass_mode_stats,
                                           skip, rd_skip)
     d_out = torch.empty(end['targets'], dtype=torch.uint8, device=dev)       # the last section
@@ -554,15 +626,17 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
         if mask in results:
             continue
         first = i == 0
+        # the blocks of every picture entry: the mask's two ints, or (per block) the two arrays in their place for the *_masks_ entries
         blocks = (predictor.ctx, w, d_context_channels.data_ptr(), d_target_channels.data_ptr(), nb_images, height, width,
-                  d_rows.data_ptr(), d_cols.data_ptr(), n_pos, mask[0], mask[1])
+                  d_rows.data_ptr(), d_cols.data_ptr(), n_pos) + \
+            ((d_block_masks[0].data_ptr(), d_block_masks[1].data_ptr()) if per_block else (mask[0], mask[1]))
         with torch.cuda.device(dev):
-            _lib.check(L.pnn_score_picture_pairs_hm_device(
+            _lib.check((L.pnn_score_picture_pairs_masks_device if per_block else L.pnn_score_picture_pairs_hm_device)(
                 *blocks, reference_smoothing, ptr['targets'] if first else None,
                 ptr['predictions_pnn'] if keep_predictions or first_pass or nb_qps else None, None, ptr['sses_pnn'], ptr['indices_hevc'],
                 ptr['sses_hevc'], ptr['predictions_hevc'] if keep_predictions or nb_qps else None, stream), predictor.ctx)
             if first_pass:                                # the PNN's uint8 predictions are on the device: candidate 35
-                _lib.check(L.pnn_first_pass_picture_pairs_hm_device(
+                _lib.check((L.pnn_first_pass_picture_pairs_masks_device if per_block else L.pnn_first_pass_picture_pairs_hm_device)(
                     *blocks, ptr['predictions_pnn'], reference_smoothing, ptr['hads_hevc_modes'], ptr['hads_pnn'], ptr['first_pass_list'],
                     ptr['first_pass_costs'], stream), predictor.ctx)
             for column, predictions in _CODED_COLUMNS if nb_qps else ():
@@ -581,7 +655,14 @@ def _score_masks(ch, nb_planes, width_target, row_1sts, col_1sts, predictor, mea
                     predictor.ctx, w, ptr[predictions], ptr['targets'], n, modes, c_qps, nb_qps, ptr['sses_recon_' + column],
                     ptr['nb_nonzero_levels_' + column], ptr['sum_abs_levels_' + column], None, ptr['rate_' + column] if transform_rate else None,
                     int(bool(transform_sign_hiding)), int(bool(transform_rdoq)), None, stream), predictor.ctx)
-            if rd_pass and rd_skip:                       # the second pass with transform skip: the codec entry's arguments and two more
+            if rd_pass and per_block:                     # masks per block: the one entry, transform skip as its option (0: the codec entry's launches)
+                _lib.check(L.pnn_rd_pass_picture_pairs_masks_device(
+                    *blocks, ptr['predictions_pnn'], reference_smoothing, c_qps, nb_qps, None, int(bool(transform_sign_hiding)),
+                    int(bool(transform_rdoq)), signalling, None if d_left is None else d_left.data_ptr(),
+                    None if d_above is None else d_above.data_ptr(), codec, rd_skip, *[ptr[name] for name in _RD_PASS_SECTIONS], None,
+                    ptr['rd_pass_side_rates'], ptr['rd_pass_best_transform_skip'] if rd_skip else None, d_scratch.data_ptr(), nb_scratch, stream),
+                    predictor.ctx)
+            elif rd_pass and rd_skip:                     # the second pass with transform skip: the codec entry's arguments and two more
                 _lib.check(L.pnn_rd_pass_tskip_picture_pairs_device(
                     *blocks, ptr['predictions_pnn'], reference_smoothing, c_qps, nb_qps, None, int(bool(transform_sign_hiding)),
                     int(bool(transform_rdoq)), signalling, None if d_left is None else d_left.data_ptr(),
@@ -681,7 +762,7 @@ def coding_tree_from_scores(scores_by_width, left_depths=None, above_depths=None
 
 def coding_tree_from_pictures(channels_uint8, predictors_by_width, means_by_width, row_1st, col_1st, ctu_rows, ctu_cols, qps, codec='switch',
                               pairs=False, keep_scores=False, reference_smoothing=0, transform_rate=False, transform_sign_hiding=False,
-                              transform_rdoq=False, rd_pass_transform_skip=False):
+                              transform_rdoq=False, rd_pass_transform_skip=False, availability='all'):
     """From pictures to the pictures' coding tree (include/pnn_hip.h, "the coding tree over a picture"; intraprediction.cu_tree_picture)
     without the leaves leaving the device: what a picture costs with the PNN in HM's search, per image and QP.
     channels_uint8 [images, H, W, 1], or [images, H, W, 2] with pairs=True (score_masks_from_picture_pairs' planes); predictors_by_width
@@ -696,7 +777,13 @@ def coding_tree_from_pictures(channels_uint8, predictors_by_width, means_by_widt
     second passes (rd_pass_neighbour_modes None).  Returns cu_tree_picture's dictionary -- the mode that stands for the PNN is 35
     under the switch codec, 18 under substitution; with keep_scores=True (dictionary, {w: mask (0, 0)'s dictionary of the width}),
     the five also downloaded as score_masks_* would (without it nothing but the tree's outputs is).  Everything is issued on the
-    torch current stream of the predictors' device as it is when the call begins; nothing waits for it before the one download."""
+    torch current stream of the predictors' device as it is when the call begins; nothing waits for it before the one download.
+    availability: 'all' -- every block reads its complete context, mask (0, 0), the calls above entry for entry -- or 'hm': every block
+    reads what HM's coding order leaves it (include/pnn_hip.h, "context availability"), each width's masks from
+    intraprediction.hm_context_masks(w, ctu_rows, ctu_cols) and its three picture calls the *_masks_device entries (score_block_masks_*'s
+    calls); keep_scores=True then returns the per-width dictionaries as score_block_masks_* would.  ValueError for any other name."""
+    if availability not in ('all', 'hm'):
+        raise ValueError("`availability` is not 'all' or 'hm'.")
     if not isinstance(predictors_by_width, dict) or sorted(predictors_by_width) != list(intraprediction.WIDTHS):
         raise ValueError('`predictors_by_width` is not a dictionary with the keys 4, 8, 16, 32 and 64.')
     if not isinstance(means_by_width, dict) or sorted(means_by_width) != list(intraprediction.WIDTHS):
@@ -729,10 +816,12 @@ def coding_tree_from_pictures(channels_uint8, predictors_by_width, means_by_widt
         n = n_images * per_image * (intraprediction.CTU_WIDTH // w) ** 2
         held[w] = {'dist': torch.empty(nq * n, dtype=torch.int32, device=dev), 'rate': torch.empty(nq * n, dtype=torch.int64, device=dev),
                    'mode': torch.empty(nq * n, dtype=torch.uint8, device=dev), 'keep': bool(keep_scores)}
+        block_masks = intraprediction.hm_context_masks(w, ctu_rows, ctu_cols) if availability == 'hm' else None
         result = _score_masks(channels_uint8, nb_planes, w, positions[w][0], positions[w][1], predictors_by_width[w], means_by_width[w],
-                              ((0, 0),), None, False, True, reference_smoothing, qps, transform_rate, transform_sign_hiding, True,
-                              transform_rdoq, True, None, codec, False, 'off', bool(rd_pass_transform_skip) and w == 4, _tree_leaves=held[w])
-        scores[w] = result[(0, 0)]
+                              () if availability == 'hm' else ((0, 0),), None, False, True, reference_smoothing, qps, transform_rate, transform_sign_hiding, True,
+                              transform_rdoq, True, None, codec, False, 'off', bool(rd_pass_transform_skip) and w == 4, _tree_leaves=held[w],
+                              _block_masks=block_masks)
+        scores[w] = result[None if availability == 'hm' else (0, 0)]
     pnn_mode = intraprediction.SUBSTITUTED_MODE if intraprediction.CODECS[codec] else intraprediction.NB_MODES
     wanted = [True] * len(intraprediction.CU_TREE_PICTURE_OUTPUTS)
     leaf_pointers = [[held[w][name].data_ptr() for w in intraprediction.WIDTHS] for name in ('dist', 'rate', 'mode')]

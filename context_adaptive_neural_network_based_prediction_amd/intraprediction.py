@@ -1016,6 +1016,25 @@ def ctu_grid(row_1st, col_1st, ctu_rows, ctu_cols):
             int(col_1st) + CTU_WIDTH * np.tile(np.arange(ctu_cols, dtype=np.int64), ctu_rows))
 
 
+def hm_context_masks(width_target, ctu_rows, ctu_cols):
+    """Context availability (include/pnn_hip.h, "context availability"; pnn_hm_context_masks_host): for every aligned block of width
+    `width_target` in a grid of ctu_rows x ctu_cols whole CTUs, the masks HM's z-scan coding order leaves it -- mask_w = 0 where the
+    above-right portion is coded before the block, else width_target; mask_h likewise for the below-left portion.  Returns (masks_w,
+    masks_h), uint8 [ctu_rows * ctu_cols * (64 / width_target)^2] in (CTU raster, z-order) order: the order of
+    ctu_block_positions(width_target, *ctu_grid(row_1st, col_1st, ctu_rows, ctu_cols)).  ValueError for a width outside the five or a
+    grid dimension that is not an integer >= 1."""
+    if width_target not in WIDTHS:
+        raise ValueError('`width_target` does not belong to {4, 8, 16, 32, 64}.')
+    ctu_rows, ctu_cols, _ = _check_ctu_grid(ctu_rows, ctu_cols)
+    count = ctu_rows * ctu_cols * (CTU_WIDTH // width_target) ** 2
+    if count > 2 ** 31 - 1:
+        raise ValueError('the blocks of the grid do not fit an int.')
+    masks_w, masks_h = np.empty(count, np.uint8), np.empty(count, np.uint8)
+    if _lib.lib().pnn_hm_context_masks_host(int(width_target), ctu_rows, ctu_cols, _address(masks_w), _address(masks_h)) != 0:
+        raise ValueError('pnn_hm_context_masks_host refused its arguments.')
+    return masks_w, masks_h
+
+
 def _cu_tree_picture_device(device, leaf_pointers, with_modes, qps, c_lambdas, n_images, ctu_rows, ctu_cols, pnn_mode, wanted):
     """pnn_cu_tree_picture_device on leaves that lie on `device` -- leaf_pointers: three lists (dist, rate, mode) of five device
     addresses -- with every output in ONE buffer and one download of it.  Returns CU_TREE_PICTURE_OUTPUTS as numpy arrays."""

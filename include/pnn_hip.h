@@ -1113,6 +1113,64 @@ int pnn_cu_tree_leaves_device(pnn_ctx* ctx, int width, int n, int nb_qps, const 
                               const uint64_t* d_side_rates, const uint8_t* d_modes, uint32_t* d_dist, uint64_t* d_rate, uint8_t* d_mode,
                               void* stream);
 
+/* ---- context availability: which of a block's above-right and below-left neighbours an encoder holds when it
+ * predicts the block, as HM-16.15 answers it (isAboveRightAvailable / isBelowLeftAvailable of TComPattern.cpp through getPUAboveRight /
+ * getPUBelowLeft of TComDataCU.cpp; one slice, one tile, constrained intra prediction off), written as the masks of the picture entries.
+ *   World.  The picture is the grid of R = ctu_rows x C = ctu_cols whole CTUs of 64, as for the tree's edges: nothing exists beyond the
+ *     grid's right and bottom edges.  A CTU is 16 x 16 units of 4 x 4 samples; z(x, y) is the z-order index of unit (x, y) of a CTU (bit
+ *     2 j of z is bit j of x, bit 2 j + 1 is bit j of y): the order in which the units of a CTU are coded.  CTUs are coded in raster order.
+ *   A block of width w, n = w / 4 units, at unit (x, y) of the CTU at (r, c); x and y are multiples of n.
+ *   Above-right, units (x + n .. x + 2 n - 1, y - 1):
+ *     x + n < 16, y > 0:  available iff z(x + n, y - 1) < z(x + n - 1, y)   (inside the CTU: coded before the block's top-right unit)
+ *     x + n < 16, y = 0:  available iff r > 0                               (the CTU above)
+ *     x + n = 16, y > 0:  not available                                     (the CTU to the right is coded later)
+ *     x + n = 16, y = 0:  available iff r > 0 and c + 1 < C                 (the above-right CTU; beyond the picture's right edge at c + 1 = C)
+ *   Below-left, units (x - 1, y + n .. y + 2 n - 1):
+ *     y + n = 16:         not available                                     (the CTU below or below-left is coded later, or the picture ends)
+ *     x > 0:              available iff z(x - 1, y + n) < z(x, y + n - 1)   (coded before the block's bottom-left unit)
+ *     x = 0:              available iff c > 0                               (the CTU to the left)
+ *   For an aligned block every unit of a portion has the portion's answer (all or nothing), and the answer does not depend on the
+ *     partition.  mask_w = 0 where the above-right portion is available, else w; mask_h likewise for the below-left portion: the masks
+ *     (in samples) of pnn_score_picture_pairs_device and its kin.
+ *   The one departure from HM: at the grid's first CTU row and column the above, corner and left portions are NOT masked -- the picture
+ *     entries read them from the plane, whose margin the caller provides; HM would substitute them, and the PNN has no form without
+ *     them.  The above-right of the first CTU row and the below-left of the first CTU column follow HM: absent.
+ * pnn_hm_context_masks_host: mask_w, mask_h uint8 [ctu_rows ctu_cols (64 / width)^2], CTUs in raster order, a CTU's blocks in z-order
+ * (the order of the coding tree's leaves).  PNN_E_ARG, nothing written: a width not of the five, ctu_rows or ctu_cols < 1, a number of
+ * blocks that does not fit an int, a NULL output.  tests/test_hm_context_masks.py pins it to HM's own answers. */
+int pnn_hm_context_masks_host(int width, int ctu_rows, int ctu_cols, uint8_t* mask_w, uint8_t* mask_h);
+
+/* ---- masks per block: the picture entries with the masks of every POSITION in place of the call's two scalars.
+ * Each entry is the widest existing entry of its operation -- pnn_score_picture_pairs_hm_device, pnn_first_pass_picture_pairs_hm_device,
+ * pnn_rd_pass_tskip_picture_pairs_device (transform_skip 0: the codec entry's launches) -- with `int mask_w, int mask_h` replaced by
+ * d_mask_w, d_mask_h: uint8 [positions] in device memory, in samples, the same for every image (block b = image positions + pos reads
+ * element pos).  Both NULL: nothing is masked.
+ * Contract: every output of block b has the bytes the existing entry gives that block when called with the scalar masks
+ * (d_mask_w[pos], d_mask_h[pos]); a block's bits do not depend on the other blocks of the call.  Same launches, same workspace
+ * functions, same order of checks as the entry each extends.
+ * PNN_E_ARG, before any launch and with the outputs untouched: exactly one of the two arrays NULL (checked with the planes); a mask
+ * outside {0, 4, .., width} -- the masks are read back with the positions, in the same single wait for the stream, and checked behind
+ * them.  The geometry check is the existing one: the whole 3 width square of every position lies inside the picture, masked or not. */
+int pnn_score_picture_pairs_masks_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels, int images,
+                                         int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                         const uint8_t* d_mask_w, const uint8_t* d_mask_h, int smoothing, uint8_t* d_targets, uint8_t* d_pnn_u8,
+                                         float* d_pnn_f32, uint32_t* d_pnn_sse, uint8_t* d_hevc_mode, uint32_t* d_hevc_sse, uint8_t* d_hevc_pred,
+                                         void* stream);
+int pnn_first_pass_picture_pairs_masks_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                              int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                              const uint8_t* d_mask_w, const uint8_t* d_mask_h, const uint8_t* d_cand_pred, int smoothing,
+                                              uint32_t* d_mode_hads, uint32_t* d_cand_hads, uint8_t* d_list_modes, uint32_t* d_list_costs,
+                                              void* stream);
+int pnn_rd_pass_picture_pairs_masks_device(pnn_ctx* ctx, int width, const uint8_t* d_context_channels, const uint8_t* d_target_channels,
+                                           int images, int height, int width_ch, const int32_t* d_rows, const int32_t* d_cols, int positions,
+                                           const uint8_t* d_mask_w, const uint8_t* d_mask_h, const uint8_t* d_cand_pred, int smoothing,
+                                           const int* qps, int nb_qps, const double* lambdas, int sign_data_hiding, int rdoq, int signalling,
+                                           const uint8_t* d_left_modes, const uint8_t* d_above_modes, int codec, int transform_skip,
+                                           uint8_t* d_cand_modes, double* d_cand_costs, uint8_t* d_best_mode, uint8_t* d_best_slot,
+                                           double* d_best_cost, uint32_t* d_best_sse, uint64_t* d_best_rate, double* d_first_pass_costs,
+                                           uint64_t* d_best_side_rate, uint8_t* d_best_ts_flag, void* d_workspace, size_t workspace_bytes,
+                                           void* stream);
+
 /* Per-launch accounting of the last *_device call (for bench.py's roofline object): number of tap-GEMM
  * launches and their algorithmic FLOPs (2 * M * K * N summed, padding excluded). */
 int pnn_last_call_stats(const pnn_ctx* ctx, int* n_gemm_launches, double* gemm_flops, int* n_launches);
